@@ -25,6 +25,13 @@ rows and queries iid N(0,1)^768 (`iid`: no IVF index reaches recall 0.95 on it, 
 the low-intrinsic-dimension mixture the first three rounds quoted (`latent32`: 1024 blobs in a 32-d latent space embedded in
 R^768) are separate legs.  `--data` picks the headline's model.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`,
+`config`; `recall_at_10`, `roofline` and `cpu_baseline` are null): its time outside the steps is the set-up alone.  Everything
+else below -- the recall check, the roofline pass, the 3-stream side measurement, the CPU baseline, every leg and, at N > 1, the
+replicated form beside the routed one and the sharded C4 family -- runs under --full.  --dump-outputs DIR writes what the last
+timed step returned (DIR/ids.npy as float64, DIR/distances.npy as float32; rank 0's batch at N > 1) before anything else runs
+on the device; every input is seeded, so two builds of the project can be compared output for output.
+
 Prints ONE JSON line on rank 0 (driver contract): a compact digest (< 6 KB, `compact_line`: the contract's keys, `roofline` and
 `cpu_baseline` without prose, one or two numbers per leg under `legs`).  The FULL object described below goes to bench_detail.json
 (beside bench.py and under gpurun_out/) and to stderr:
@@ -49,8 +56,8 @@ Prints ONE JSON line on rank 0 (driver contract): a compact digest (< 6 KB, `com
                    their own cpu_baseline.
 Every hbm fraction in the line prices the bytes the launches MOVE (fp16 shadow row + norm + id for the shadow pass, f32 rows for
 the canonical paths); MFMA-bound passes (exhaustive batches) are priced against the dense fp16 matrix peak.
-Every leg but the headline is skipped by --headline-only (profiler runs); --only LEG[,LEG] runs the named legs only; N > 1 runs
-the headline and the sharded C4 family (12.5M rows, 2048 lists, 8 probes PER RANK: at N = 8 that is BASELINE configs[3]).
+Under --full, every leg but the headline is skipped by --headline-only (profiler runs); --only LEG[,LEG] runs the named legs only;
+N > 1 runs the headline and the sharded C4 family (12.5M rows, 2048 lists, 8 probes PER RANK: at N = 8 that is BASELINE configs[3]).
 """
 import argparse
 import ctypes
@@ -350,6 +357,22 @@ def recall_at_k(got, gt, k):
     return float(np.mean([len(set(a) & set(b)) / k for a, b in zip(got.tolist(), gt.tolist())]))
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, ids, dis):
+    """--dump-outputs: one step's results (ids as float64, exact for every row id; distances as float32) as path/ids.npy and
+    path/distances.npy.  A step larger than DUMP_BYTES is sampled: the same seeded rows every run."""
+    ids, dis = ids.cpu().numpy(), dis.cpu().numpy()
+    rows = DUMP_BYTES // (ids.shape[1] * (8 + 4))
+    if ids.shape[0] > rows:
+        keep = np.sort(np.random.default_rng(0).choice(ids.shape[0], rows, replace=False))
+        ids, dis = ids[keep], dis[keep]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(path, "distances.npy"), dis.astype(np.float32))
+
+
 def leg(name, fn, out):
     """Optional legs never cost the bench line: a failure is recorded instead."""
     t = time.time()
@@ -378,15 +401,20 @@ def main():
                     help="independent batches in flight on one GPU: step i runs on HIP stream i %% streams (N = 1 only)")
     ap.add_argument("--data", default="blobs03", choices=("blobs03", "iid", "latent32", "mid"),
                     help="data model of the headline: SURVEY 8d's clustered variant (default), its iid one, or the 32-d latent mixture")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else this script measures and checks: recall@10, the roofline pass, the "
+                         "3-stream side measurement, the CPU baseline, the legs (N > 1: the replicated form, the sharded C4 family)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results to DIR/ids.npy (float64) and DIR/distances.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-concurrent", action="store_true", help="skip the 3-stream side measurement (kernel traces of the single-stream steps)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed steps + the roofline pass (profiler runs)")
+                    help="with --full: only the timed steps + the roofline pass (profiler runs)")
     ap.add_argument("--skip", default="", help="comma list of legs to skip: other_batches,latency,iid,blobs03,latent32,mid,target,c1,c3,c4,c5,cpu")
     ap.add_argument("--shard-mode", default="routed", choices=("routed", "replicated"),
                     help="N > 1: every rank brings its own batch and queries are routed to the ranks that own their lists (default), or "
                          "every rank works through the same batch (msvs_shard_search_device)")
-    ap.add_argument("--only", default="", help="comma list of legs to run (the others are skipped; the headline always runs)")
+    ap.add_argument("--only", default="", help="with --full: comma list of legs to run (the others are skipped; the headline always runs)")
     ap.add_argument("--c4-rows", type=int, default=12_500_000, help="rows per GPU of the C4 leg (100M / 8)")
     ap.add_argument("--big-rows", type=int, default=10_000_000, help="rows of the C3 / C5 legs")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -396,6 +424,8 @@ def main():
                     help="N > 1 ranks all on cuda:0 with a gloo transport under msvs_shard_search_device: exercises the N > 1 "
                          "code path of this script on a one-GPU box (not a measurement)")
     args = ap.parse_args()
+    if args.only and not args.full:
+        ap.error("--only picks legs of --full")
     skip = set(x for x in args.skip.split(",") if x)
     ALL_LEGS = ("other_batches", "latency", "iid", "blobs03", "latent32", "mid", "target", "c1", "c3", "c4", "c5", "cpu")
     if args.only:
@@ -481,7 +511,7 @@ def main():
     # --streams S: S independent batches in flight, each search on its own stream with its own result buffers (a server with S
     # worker streams): the small launches around one batch's list scan run beside the other batch's scan
     n_streams = max(1, args.streams) if world == 1 else 1
-    side_streams = 3 if world == 1 and n_streams == 1 and not args.no_concurrent else 0  # reported beside the headline (`concurrent_batches`), never as `value`
+    side_streams = 3 if args.full and world == 1 and n_streams == 1 and not args.no_concurrent else 0  # reported beside the headline (`concurrent_batches`), never as `value`
     xs = [torch.cuda.Stream() for _ in range(max(n_streams, side_streams))] if max(n_streams, side_streams) > 1 else []
     xs_out = [(torch.empty((B, k), device=dev, dtype=torch.int64), torch.empty((B, k), device=dev, dtype=torch.float32)) for _ in xs]
     multi = {"on": False, "n": n_streams}
@@ -551,6 +581,44 @@ def main():
         step(i)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        last = args.steps - 1  # (the buffers step(last) wrote, complete after the fence)
+        res = routed_slots[last % 3][:2] if routed else xs_out[last % n_streams] if n_streams > 1 else (out_ids, out_dis)
+        dump_outputs(args.dump_outputs, *res)
+    if world > 1:
+        t = torch.tensor([elapsed], device="cpu" if args.test_single_device else dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    qps = args.steps * B * (world if routed else 1) / elapsed
+
+    def head():
+        """The line's headline keys: the rate of the timed steps and what was timed."""
+        return {
+            "metric": "QPS at recall@10>=0.95, 1Mx768-d L2 top-10 (IVFFLAT nlist=1024 nprobe=%d)" % nprobe,
+            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak" if routed else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "IVFFLAT nlist=%d, %dx%d f32, L2, nprobe=%d, top-%d, batch %d queries/step "
+                                   "(BASELINE.json configs[1])" % (nlist, n, d, nprobe, k, B),
+                       "rows": n, "dim": d, "nlist": nlist, "nprobe": nprobe, "k": k, "batch": B,
+                       "parallelism": (("lists %% %d, ROUTED: a batch of %d queries per rank and step, coarse quantiser + pre-pruning at the home rank, "
+                                        "point-to-point exchange of the surviving (query, rank) pairs, local search, results back, merge at home "
+                                        "(msvs_shard_search_routed_device_async: two steps in flight); transport: %s" % (world, B, comm_kind)) if routed else
+                                       ("lists %% %d, coarse quantiser by query, probe (+ coarse distance word) and packed top-k all-gathers, "
+                                        "one stream-ordered call per batch (msvs_shard_search_device); transport: %s"
+                                        % (world, comm_kind))) if world > 1 else
+                                      ("single GPU" if n_streams == 1 else "single GPU, %d independent batches in flight on %d HIP streams" % (n_streams, n_streams)),
+                       "streams": n_streams, "data_model": data_desc},
+        }
+
+    if not args.full:
+        if rank == 0:
+            emit(dict(head(), setup_s=round(setup_s, 1)))
+        if world > 1:
+            comm.close()
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     multi["on"] = False  # (the profiled passes below run one batch at a time on the current stream)
     concurrent = None
     if side_streams:
@@ -568,11 +636,6 @@ def main():
         multi.update(on=False, n=n_streams)
         concurrent = {"streams": side_streams, "qps": round(args.steps * B / e1, 1), "ms_per_step": round(e1 / args.steps * 1e3, 4),
                       "note": "%d independent batches in flight on %d HIP streams, same steps; `value` is the single-stream rate" % (side_streams, side_streams)}
-    if world > 1:
-        t = torch.tensor([elapsed], device="cpu" if args.test_single_device else dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    qps = args.steps * B * (world if routed else 1) / elapsed
     multi_gpu = None
     if world > 1:
         # both forms side by side: the routed one (own batch per rank) and the replicated one (every rank works through the same batch)
@@ -1528,21 +1591,7 @@ def main():
                       "at_nprobe_32": {f: a32.get(f) for f in ("nprobe", "qps", "ms_per_step", "roofline_frac", "whole_step_frac", "pruned_pair_fraction",
                                                                "rows_read_per_step", "union_rows_per_step")}}
         out = {
-            "metric": "QPS at recall@10>=0.95, 1Mx768-d L2 top-10 (IVFFLAT nlist=1024 nprobe=%d)" % nprobe,
-            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak" if routed else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "IVFFLAT nlist=%d, %dx%d f32, L2, nprobe=%d, top-%d, batch %d queries/step "
-                                   "(BASELINE.json configs[1])" % (nlist, n, d, nprobe, k, B),
-                       "rows": n, "dim": d, "nlist": nlist, "nprobe": nprobe, "k": k, "batch": B,
-                       "parallelism": (("lists %% %d, ROUTED: a batch of %d queries per rank and step, coarse quantiser + pre-pruning at the home rank, "
-                                        "point-to-point exchange of the surviving (query, rank) pairs, local search, results back, merge at home "
-                                        "(msvs_shard_search_routed_device_async: two steps in flight); transport: %s" % (world, B, comm_kind)) if routed else
-                                       ("lists %% %d, coarse quantiser by query, probe (+ coarse distance word) and packed top-k all-gathers, "
-                                        "one stream-ordered call per batch (msvs_shard_search_device); transport: %s"
-                                        % (world, comm_kind))) if world > 1 else
-                                      ("single GPU" if n_streams == 1 else "single GPU, %d independent batches in flight on %d HIP streams" % (n_streams, n_streams)),
-                       "streams": n_streams, "data_model": data_desc},
+            **head(),
             "recall_at_10": None if recall is None else round(recall, 4),
             "p50_ms_batch1": extra.get("latency", {}).get("p50_us", 0) / 1e3 if "latency" in extra and "p50_us" in extra["latency"] else None,
             "roofline": roof,

@@ -5,6 +5,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -93,3 +95,47 @@ def test_emit_writes_detail_and_prints_one_line(tmp_path, capsys, monkeypatch):
     assert len(lines) == 1 and json.loads(lines[0])["value"] == out["value"]
     for p in (tmp_path / "bench_detail.json", tmp_path / "gpurun_out" / "bench_detail.json"):
         assert json.loads(p.read_text()) == out
+
+
+def test_dump_outputs_are_float_arrays_under_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    import bench
+
+    ids = torch.arange(40 * 10, dtype=torch.int64).reshape(40, 10)
+    dis = torch.rand((40, 10), generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / "all"), ids, dis)
+    i, d = np.load(tmp_path / "all" / "ids.npy"), np.load(tmp_path / "all" / "distances.npy")
+    assert i.dtype == np.float64 and d.dtype == np.float32 and (i == ids.numpy()).all() and (d == dis.numpy()).all()
+    # a step larger than the cap: the same seeded rows every time, whole rows of both arrays
+    monkeypatch.setattr(bench, "DUMP_BYTES", 16 * 10 * 12)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), ids, dis)
+    a, b = np.load(tmp_path / "a" / "ids.npy"), np.load(tmp_path / "b" / "ids.npy")
+    assert a.shape == (16, 10) and (a == b).all() and (a[:, 0] % 10 == 0).all()
+    rows = (a[:, 0] // 10).astype(np.int64)
+    assert (np.load(tmp_path / "a" / "distances.npy") == dis.numpy()[rows]).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line alone, and --dump-outputs writes the
+    last timed step's results."""
+    import subprocess
+
+    import numpy as np
+
+    rows, batch, k = 200000, 512, 10
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", str(rows),
+                        "--batch", str(batch), "--nlist", "256", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    got = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("{")][-1])
+    for key in CONTRACT:
+        assert key in got, key
+    assert got["steps"] == 3 and got["ms_per_step"] > 0 and got["value"] > 0 and got["dtype"] == "f32"
+    assert got["roofline"]["frac"] is None and got["cpu_baseline"]["value"] is None and got["legs"] == {}
+    i, d = np.load(tmp_path / "out" / "ids.npy"), np.load(tmp_path / "out" / "distances.npy")
+    assert i.shape == d.shape == (batch, k) and i.dtype == np.float64 and d.dtype == np.float32
+    assert ((i >= 0) & (i < rows)).all() and (np.diff(d, axis=1) >= 0).all()

@@ -551,7 +551,7 @@ def test_bench_n_gt_1_code_path_runs_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--rows", "200000", "--batch", "512", "--nlist", "256", "--c4-rows", "60000", "--test-single-device"],
+                        "--rows", "200000", "--batch", "512", "--nlist", "256", "--c4-rows", "60000", "--test-single-device", "--full"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [ln for ln in r.stdout.split("\n") if ln.startswith("{")][-1]
@@ -567,3 +567,24 @@ def test_bench_n_gt_1_code_path_runs_on_one_gpu():
     with open(os.path.join(root, "bench_detail.json")) as f:
         full = json.load(f)
     assert full["value"] == out["value"] and full["multi_gpu"]["routed"]["stage_ms_rank0"] == mg["routed"]["stage_ms_rank0"]
+
+
+@pytest.mark.gpu
+def test_bench_n_gt_1_plain_run_on_one_gpu(tmp_path):
+    """bench.py --gpus 2 without --full: the routed headline alone, rank 0's last batch dumped, and the ranks shut down cleanly."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                        "--rows", "200000", "--batch", "512", "--nlist", "256", "--test-single-device", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, env=env, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("{")][-1])
+    assert out["n_gpus"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0 and out["scaling"] == "weak" and out["legs"] == {}
+    ids = np.load(tmp_path / "ids.npy")
+    assert ids.shape == (512, 10) and ((ids >= 0) & (ids < 200000)).all()

@@ -3,7 +3,7 @@
 for rep in 1 2; do
 for t in "$@"; do
   cp ab_libs/libmsvs_$t.so myscaledb_amd/libmsvs.so
-  python bench.py --headline-only --steps 40 --warmup 10 --no-concurrent ${BENCH_ARGS} 2>/dev/null | python -c "
+  python bench.py --full --headline-only --steps 40 --warmup 10 --no-concurrent ${BENCH_ARGS} 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); r=d['roofline']
 det=json.load(open('bench_detail.json'))['roofline']['step_kernels_ms']
