@@ -42,6 +42,8 @@ namespace msvs
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int H_ROWS = 32;  // rows per shadow block (one wavefront's B operand)
 
@@ -82,6 +84,9 @@ struct H16Params
     uint32_t * sched;         // [8] work-queue cursors of this launch (zeroed by the caller)
     uint32_t group_appends;   // n: tiles of <= n queries append their survivors with one atomic per (wavefront, query) (0: one per record)
     uint32_t lazy_flush;      // 1: survivors stay in the wavefront's LDS stage from block to block and leave when it is full / at the end of the item
+    // int8 residual form (i8r): H holds int8 blocks of nch chunks of 128 elements, Qh the PAIR images ([q * nprobe + p][2 nch][8])
+    const float2 * side;      // [n] {s_x, |r_x|^2}
+    const float2 * pinfo;     // [nq * nprobe] {-2 s_q, |r_q|^2}
     uint64_t * stamps;        // nullable (option h16_stamps): [grid][H_STAMP_ITEMS][4] {item popped, tile resident, rows done, l << 32 | nvalid << 8}
                               // in wall_clock64 ticks (100 MHz), [grid][0][0] = items of the workgroup
 };
@@ -198,6 +203,268 @@ static __global__ void h16_build_kernel(const float * vecs, uint32_t ld, const i
     }
     H[i] = make_uint4(pack_h2(v0.x * scale, v0.y * scale), pack_h2(v0.z * scale, v0.w * scale),
                       pack_h2(v1.x * scale, v1.y * scale), pack_h2(v1.z * scale, v1.w * scale));
+}
+
+// ------------------------------------------------------------------------------------------ the int8 residual form (i8r)
+//
+// L2 IVFFLAT indexes whose rows sit close to their centroids store the shadow as int8 RESIDUALS instead: row x of list l is
+// r_x = x - c_l (exact in double), s_x = max |r_x,i| / 127, ix = rint(r_x / s_x) -- 1 B per element, half the bytes the scan
+// streams.  The layout is the fp16 one with 32 elements per step: a block = 32 rows, per 32-element step 1 KiB = 64 lanes x 16 B,
+// lane (r, h) holding elements 32 s + 16 h .. + 15 of row r, the B operand of v_mfma_i32_32x32x32_i8; a chunk = 4 steps = 128
+// elements = 4 KiB, so the register ring keeps the same bytes in flight and covers twice the reduction.  Per row the sideband
+// {s_x, |r_x|^2}.  A (query, list) pair is r_q = q - c_l split into TWO int8 images (h8_prep_pairs_kernel): hi = rint(r_q / s_q),
+// lo = rint((r_q - s_q hi) 256 / s_q); the scan multiplies both against the same row fragment (exact i32 sums) and forms
+//   a = fl(fl(fma(fl(-2 s_q s_x), fl(acc_hi + acc_lo / 256), |r_x|^2)) + |r_q|^2)
+// -- the same distance |x - q|^2 = |r_x - r_q|^2, with an error bound that scales with the RESIDUALS (set_error_model_i8r).
+
+constexpr int H8_CHUNK = 128; // elements per i8r chunk (4 KiB of a block, like an fp16 chunk)
+
+/// Largest beta_l (rows) and |r_q| / |q| (pairs) the i8r error model covers at dimension d (set_error_model_i8r).
+inline float i8r_limit(size_t d) { return (float)std::sqrt(((double)d + 8.0) / 6.0); }
+
+/// Sums of a wavefront in double.
+__device__ __forceinline__ double h8_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double h8_wave_max(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ int h8_q(const double v) // rint, clamped to the int8 range the error is measured against
+{
+    const double r = rint(v);
+    return (int)(r > 127.0 ? 127.0 : r < -127.0 ? -127.0 : r);
+}
+/// 16 consecutive elements (k0 .. k0 + 15, zero at and past ld) of a - b, exact in double.
+__device__ __forceinline__ void h8_load_diff(const float * a, const float * b, uint32_t k0, uint32_t ld, double (&d)[16])
+{
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+    {
+        float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
+        if (k0 + 4 * t < ld)
+        {
+            va = *reinterpret_cast<const float4 *>(a + k0 + 4 * t);
+            vb = *reinterpret_cast<const float4 *>(b + k0 + 4 * t);
+        }
+        d[4 * t + 0] = (double)va.x - (double)vb.x;
+        d[4 * t + 1] = (double)va.y - (double)vb.y;
+        d[4 * t + 2] = (double)va.z - (double)vb.z;
+        d[4 * t + 3] = (double)va.w - (double)vb.w;
+    }
+}
+__device__ __forceinline__ uint4 h8_pack(const int (&v)[16])
+{
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        w[i] = (uint32_t)(v[4 * i] & 255) | (uint32_t)(v[4 * i + 1] & 255) << 8 | (uint32_t)(v[4 * i + 2] & 255) << 16
+            | (uint32_t)(v[4 * i + 3] & 255) << 24;
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void h8_atomic_max_f(uint32_t * p, const float v) // v >= 0 (or +inf): float order = unsigned order
+{
+    const uint32_t bits = __float_as_uint(v);
+    if (bits > *reinterpret_cast<volatile uint32_t *>(p))
+        atomicMax(p, bits);
+}
+
+/// f32 list-major rows -> i8r shadow blocks + sideband; one wavefront per stored row (H zeroed by the caller: padding rows stay 0).
+/// list_ab[l] = {alpha_l, beta_l} as float bits (atomicMax; zeroed by the caller).
+static __global__ __launch_bounds__(256) void h8_build_kernel(const float * vecs, const float * cents, uint32_t ld, size_t n,
+                                                              const int64_t * list_off, uint32_t nlist, const uint32_t * hoff,
+                                                              uint32_t nch8, uint4 * H, float2 * side, uint32_t * list_ab)
+{
+    const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (r >= n)
+        return;
+    uint32_t lo = 0, hi = nlist;
+    while (hi - lo > 1)
+    {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (list_off[mid] <= (int64_t)r)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const uint32_t l = lo;
+    const float * x = vecs + r * ld;
+    const float * c = cents + (size_t)l * ld;
+    const uint32_t npc = nch8 * 8; // 16-element pieces per row
+    double mx = 0.0, rr = 0.0, xx = 0.0;
+    for (uint32_t t = lane; t < npc; t += 64)
+    {
+        double d[16];
+        h8_load_diff(x, c, 16 * t, ld, d);
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+        {
+            mx = fmax(mx, fabs(d[i]));
+            rr += d[i] * d[i];
+        }
+    }
+    for (uint32_t e = lane * 4; e < ld; e += 256)
+    {
+        const float4 v = *reinterpret_cast<const float4 *>(x + e);
+        xx += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    }
+    mx = h8_wave_max(mx);
+    rr = h8_wave_sum(rr);
+    xx = h8_wave_sum(xx);
+    const float sx = (float)(mx / 127.0);
+    const double inv = sx > 0.f ? 1.0 / (double)sx : 0.0;
+    const uint32_t rb = (uint32_t)(r - (size_t)list_off[l]);
+    const size_t blk = (size_t)hoff[l] + rb / H_ROWS;
+    double ee = 0.0;
+    for (uint32_t t = lane; t < npc; t += 64)
+    {
+        double d[16];
+        h8_load_diff(x, c, 16 * t, ld, d);
+        int v[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+        {
+            v[i] = h8_q(d[i] * inv);
+            const double e = d[i] - (double)sx * (double)v[i];
+            ee += e * e;
+        }
+        const uint32_t s = t >> 1, h = t & 1; // step of 32 elements, lane half
+        H[(blk * nch8 * 4 + s) * 64 + (rb % H_ROWS) + 32 * h] = h8_pack(v);
+    }
+    ee = h8_wave_sum(ee);
+    if (lane == 0)
+    {
+        const double ex = sqrt(ee) * (1.0 + 1e-6), nr = sqrt(rr), nx = sqrt(xx);
+        side[r] = make_float2(sx, (float)rr);
+        const float alpha = nx > 0.0 ? (float)(ex / nx * (1.0 + 1e-6)) : ex > 0.0 ? __uint_as_float(0x7f800000u) : 0.f;
+        const float beta = nx > 0.0 ? (float)((nr + ex) / nx * (1.0 + 1e-6)) : nr + ex > 0.0 ? __uint_as_float(0x7f800000u) : 0.f;
+        h8_atomic_max_f(list_ab + 2 * l, alpha);
+        h8_atomic_max_f(list_ab + 2 * l + 1, beta);
+    }
+}
+
+/// The (query, list) pairs of a list scan over the i8r shadow: one workgroup per query, its wavefronts take the probes that survived
+/// the pre-pruning (probes[q][p] >= 0).  Writes the pair's hi / lo images ([q * nprobe + p][2 nch8][8 pieces]: virtual chunk 2 c =
+/// hi of chunk c, 2 c + 1 = lo, piece j = elements 128 c + 16 j .. + 15 -- the fp16 query image's piece order), pinfo = {-2 s_q,
+/// fl(|r_q|^2 - off_p)} and qbound[q].  The coefficient of |x||q| in the error model of pair p (set_error_model_i8r) is
+///   C_p = alpha_l rho + beta_l e + 6.1 u beta_l h,  rho = |r_q| / |q|, e = E_q / |q|, h = s_q (|hi| + |lo| / 256) / |q|;
+/// it grows with the distance of the query from the list's centroid, and one bound per query -- the largest -- would be as loose
+/// as the query's farthest list.  So qbound[q] = min over the pairs of C_p, and every key of pair p is LOWERED by
+/// off_p = 2 (C_p - qbound[q]) X Q (X >= every |x|, Q >= |q|) through its |r_q|^2 term: then key - eps(qbound) <= key_p - eps(C_p)
+/// <= the true distance for every row, the one-sided bound the certificate relies on.  The second pruning stage reads a sample word
+/// as an UPPER bound too: qoff[q] = the largest off_p of the query widens it there (H16Prune::qoff).  +inf: a pair outside the
+/// model's range, the certificate then fails and the canonical fallback serves the query.  pc: [nq * nprobe] scratch for the C_p.
+static __global__ __launch_bounds__(256) void h8_prep_pairs_kernel(const float * Q, uint32_t nq, uint32_t ld, const float * cents,
+                                                                   const int32_t * probes, uint32_t nprobe, uint32_t nch8,
+                                                                   const float2 * list_ab, float lim, float xmax, uint4 * img,
+                                                                   float2 * pinfo, float * pc, float * qbound, float * qoff)
+{
+    __shared__ float wmin[4], wmax[4];
+    const uint32_t q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (q >= nq)
+        return;
+    const float * src = Q + (size_t)q * ld;
+    double qq = 0.0;
+    for (uint32_t e = lane * 4; e < ld; e += 256)
+    {
+        const float4 v = *reinterpret_cast<const float4 *>(src + e);
+        qq += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    }
+    const double nqn = sqrt(h8_wave_sum(qq));
+    const uint32_t npc = nch8 * 8;
+    float best = __uint_as_float(0x7f800000u), worst = 0.f;
+    for (uint32_t p = wave; p < nprobe; p += 4)
+    {
+        const int32_t l = probes[(size_t)q * nprobe + p];
+        if (l < 0)
+            continue;
+        const float * c = cents + (size_t)l * ld;
+        double mx = 0.0, dd = 0.0;
+        for (uint32_t t = lane; t < npc; t += 64)
+        {
+            double d[16];
+            h8_load_diff(src, c, 16 * t, ld, d);
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+            {
+                mx = fmax(mx, fabs(d[i]));
+                dd += d[i] * d[i];
+            }
+        }
+        mx = h8_wave_max(mx);
+        dd = h8_wave_sum(dd);
+        const float sq = (float)(mx / 127.0);
+        const double inv = sq > 0.f ? 1.0 / (double)sq : 0.0, s = (double)sq;
+        double ee = 0.0, hh = 0.0, ll = 0.0;
+        uint4 * const out = img + ((size_t)q * nprobe + p) * (2 * nch8) * 8;
+        for (uint32_t t = lane; t < npc; t += 64)
+        {
+            double d[16];
+            h8_load_diff(src, c, 16 * t, ld, d);
+            int vh[16], vl[16];
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+            {
+                vh[i] = h8_q(d[i] * inv);
+                const double rem = d[i] - s * (double)vh[i];
+                vl[i] = h8_q(rem * inv * 256.0);
+                const double e = rem - s * (double)vl[i] * (1.0 / 256.0);
+                ee += e * e;
+                hh += (double)(vh[i] * vh[i]);
+                ll += (double)(vl[i] * vl[i]);
+            }
+            const uint32_t ch = t >> 3, j = t & 7;
+            out[(2 * ch) * 8 + j] = h8_pack(vh);
+            out[(2 * ch + 1) * 8 + j] = h8_pack(vl);
+        }
+        ee = h8_wave_sum(ee);
+        hh = h8_wave_sum(hh);
+        ll = h8_wave_sum(ll);
+        if (lane == 0)
+        {
+            const float2 ab = list_ab[l];
+            const double rho = sqrt(dd) / nqn, e = sqrt(ee) * (1.0 + 1e-6) / nqn, hq = s * (sqrt(hh) + sqrt(ll) / 256.0) / nqn;
+            const double cq = ((double)ab.x * rho + (double)ab.y * e + 6.1 * ldexp(1.0, -24) * (double)ab.y * hq) * (1.0 + 1e-5);
+            const bool ok = nqn > 0.0 && rho + e <= (double)lim && (double)ab.y <= (double)lim && cq < 1e30;
+            const float c = ok ? (float)cq * (1.f + 1e-6f) : __uint_as_float(0x7f800000u);
+            pinfo[(size_t)q * nprobe + p] = make_float2(-2.f * sq, (float)dd); // (|r_q|^2 gets its offset below)
+            pc[(size_t)q * nprobe + p] = c;
+            best = fminf(best, c);
+            worst = fmaxf(worst, c);
+        }
+    }
+    if (lane == 0)
+    {
+        wmin[wave] = best;
+        wmax[wave] = worst;
+    }
+    __syncthreads();
+    const float cmin = fminf(fminf(wmin[0], wmin[1]), fminf(wmin[2], wmin[3]));
+    const float cmax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    const bool fine = cmax < 3.0e38f; // (a pair outside the model: the whole query goes to the fallback)
+    // X Q with X = sqrt(xmax) (xmax: the largest f32 row norm, within 1e-3 of the real one) and Q = |q|, both rounded up
+    const double xq = sqrt((double)xmax * 1.001) * nqn * (1.0 + 1e-6);
+    if (threadIdx.x == 0)
+    {
+        qbound[q] = fine ? cmin : __uint_as_float(0x7f800000u);
+        qoff[q] = fine ? (float)(2.0 * ((double)cmax - (double)cmin) * xq * (1.0 + 2e-3)) : 0.f;
+    }
+    for (uint32_t p = threadIdx.x; p < nprobe; p += blockDim.x)
+    {
+        if (probes[(size_t)q * nprobe + p] < 0)
+            continue;
+        const double off = fine ? 2.0 * ((double)pc[(size_t)q * nprobe + p] - (double)cmin) * xq * (1.0 + 1e-3) : 0.0;
+        float2 & pi = pinfo[(size_t)q * nprobe + p];
+        pi.y = (float)((double)pi.y - off); // fl(fl|r_q|^2 - off): two roundings of |r_q|^2 (set_error_model_i8r)
+    }
 }
 
 /// Queries -> fp16 image + per-query constants; one wavefront per query.
@@ -361,11 +628,12 @@ constexpr int H_RING = 4;    // row chunks per wavefront in registers (H_RING - 
 constexpr int H_STAGE = 64;  // survivor records a wavefront stages in LDS before one round of atomics
 constexpr uint32_t H_NONE = 0xFFFFFFFFu;
 
-/// LDS bytes of the scan kernel for a tile of 32 * ncb queries.
-inline size_t h16_lds_bytes(uint32_t ncb, uint32_t nch)
+/// LDS bytes of the scan kernel for a tile of 32 * ncb queries; nch = 128-byte chunks of a query's image (i8r: 2 per 128-element
+/// chunk, hi and lo -- 2 d bytes per query either way) and one more word per query (its pair's image).
+inline size_t h16_lds_bytes(uint32_t ncb, uint32_t nch, bool i8 = false)
 {
     const size_t tq = 32 * (size_t)ncb;
-    return tq * nch * 128 + 4 * tq * 4 + (size_t)H_NW * H_STAGE * 12 + 16;
+    return tq * nch * 128 + 4 * tq * 4 + (size_t)H_NW * H_STAGE * 12 + 16 + (i8 ? 4 * tq : 0);
 }
 
 /// A wavefront's share of a work item: shadow blocks blk0, blk0 + stride, ... < nblk of the list (32 rows each) against
@@ -392,7 +660,7 @@ __device__ __forceinline__ uint32_t h16_stream_cut(const uint32_t cut)
     return cut > f2ord(3.402823466e+38f) ? __float_as_uint(3.402823466e+38f) : __float_as_uint(ord2f(cut));
 }
 
-template <int METRIC, int NCBI, int RING = H_RING, int NRB = 1>
+template <int METRIC, int NCBI, int RING = H_RING, int NRB = 1, bool I8 = false>
 __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned char * qt /* tile */,
                                            const uint32_t chunk_stride, const float * m2_s, const float * qn_s,
                                            const uint32_t * thr_s, const uint32_t * qrow_s, uint32_t * stage, const uint32_t lane,
@@ -400,6 +668,7 @@ __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned c
                                            const uint32_t blk0, const uint32_t stride, const uint32_t nblk,
                                            const int64_t lbeg, const int64_t lend, const uint32_t tile_queries = 0xFFFFFFFFu)
 {
+    static_assert(!I8 || (NRB == 1 && METRIC == M_L2), "i8r: L2 list scan only");
     if (blk0 >= nblk)
         return;
     // (uniform: see flush.  Not in the two-row-block form -- exhaustive batches, tiles of 64+ queries: the extra code cost the kernel
@@ -493,7 +762,7 @@ __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned c
         const u32x4 * hp_next[NRB];
         int64_t row[NRB];
         bool ok[NRB];
-        float xn[NRB];
+        float xn[NRB], xs[NRB];
 #pragma unroll
         for (int rb = 0; rb < NRB; rb++)
         {
@@ -501,9 +770,16 @@ __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned c
             row[rb] = lbeg + (int64_t)(blk + rb) * H_ROWS + r32;
             ok[rb] = blk + rb < nblk && row[rb] < lend;
             xn[rb] = 0.f;
+            xs[rb] = 0.f;
             if (ok[rb])
             {
-                if (METRIC == M_L2)
+                if (I8)
+                {
+                    const float2 sd = a.side[row[rb]];
+                    xs[rb] = sd.x;
+                    xn[rb] = sd.y;
+                }
+                else if (METRIC == M_L2)
                     xn[rb] = a.xnorm[row[rb]];
                 if (a.alive)
                 {
@@ -512,16 +788,54 @@ __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned c
                 }
             }
         }
-        f32x16 acc[NRB][NCBI];
+        f32x16 acc[I8 ? 1 : NRB][NCBI];
+        i32x16 ach[I8 ? NCBI : 1], acl[I8 ? NCBI : 1]; // i8r: the hi and lo products (exact)
+        if (!I8)
+        {
 #pragma unroll
-        for (int rb = 0; rb < NRB; rb++)
+            for (int rb = 0; rb < NRB; rb++)
+#pragma unroll
+                for (int cb = 0; cb < NCBI; cb++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++)
+                        acc[rb][cb][r] = 0.f;
+        }
+        else
+        {
 #pragma unroll
             for (int cb = 0; cb < NCBI; cb++)
 #pragma unroll
                 for (int r = 0; r < 16; r++)
-                    acc[rb][cb][r] = 0.f;
+                {
+                    ach[cb][r] = 0;
+                    acl[cb][r] = 0;
+                }
+        }
         auto step = [&](const int u, const uint32_t c) {
-            const unsigned char * qb = qt + (size_t)c * chunk_stride;
+            const unsigned char * qb = qt + (size_t)(I8 ? 2 * c : c) * chunk_stride;
+            if (I8)
+            {
+                // 4 steps of 32 elements: the hi and lo fragments of the step (tile chunks 2 c and 2 c + 1, the fp16 piece offsets)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                {
+                    i32x4 fh[NCBI], fl[NCBI];
+#pragma unroll
+                    for (int cb = 0; cb < NCBI; cb++)
+                    {
+                        fh[cb] = *reinterpret_cast<const i32x4 *>(qb + cb * 4096 + aoff[j]);
+                        fl[cb] = *reinterpret_cast<const i32x4 *>(qb + chunk_stride + cb * 4096 + aoff[j]);
+                    }
+                    const i32x4 bf = __builtin_bit_cast(i32x4, ring[0][u][j]);
+#pragma unroll
+                    for (int cb = 0; cb < NCBI; cb++)
+                    {
+                        ach[cb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fh[cb], bf, ach[cb], 0, 0, 0);
+                        acl[cb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fl[cb], bf, acl[cb], 0, 0, 0);
+                    }
+                }
+                return;
+            }
             if (NRB >= 2)
             {
                 // exhaustive batches (two row blocks per wavefront): the A fragments of the NEXT reduction step (of the next chunk after
@@ -641,7 +955,14 @@ __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned c
                 {
                     bool pass;
                     float v;
-                    if (METRIC == M_L2)
+                    if (I8)
+                    {
+                        // fl(acc_hi + acc_lo / 256), fl(-2 s_q s_x): the roundings set_error_model_i8r counts
+                        const float accf = fmaf((float)acl[cb][4 * g4 + e], 0.00390625f, (float)ach[cb][4 * g4 + e]);
+                        v = __fadd_rn(fmaf(__fmul_rn(m2v[e], xs[rb]), accf, xq), qnv[e]);
+                        pass = v < __uint_as_float(cutv[e]);
+                    }
+                    else if (METRIC == M_L2)
                     {
                         v = __fadd_rn(fmaf(m2v[e], acc[rb][cb][4 * g4 + e], xq), qnv[e]);
                         pass = v < __uint_as_float(cutv[e]);
@@ -701,19 +1022,21 @@ __device__ __forceinline__ uint32_t h16_next_item(uint32_t * sched, const uint32
 /// the tile can (the last tile of a list; most tiles once the probe pruning has thinned the pairs) loads and multiplies only the
 /// column blocks it has queries for (round 4: the per-item stamps of option h16_stamps showed 61 % of the bench step's items
 /// holding <= 32 queries; 0.505 -> 0.475 ms).
-template <int METRIC, int NCB>
+template <int METRIC, int NCB, bool I8 = false>
 __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
 {
     constexpr uint32_t TQ = 32 * NCB;
     constexpr uint32_t NW = H_NW;
     const uint32_t nch = a.nch;
+    const uint32_t tnch = I8 ? 2 * nch : nch; // 128-byte chunks of a query's image in the tile
     unsigned char * const tile = msvs_smem; // [chunk][query][8 x 16 B]
-    float * const m2_s = reinterpret_cast<float *>(tile + (size_t)TQ * nch * 128);
+    float * const m2_s = reinterpret_cast<float *>(tile + (size_t)TQ * tnch * 128);
     float * const qn_s = m2_s + TQ;
     uint32_t * const thr_s = reinterpret_cast<uint32_t *>(qn_s + TQ);
     uint32_t * const qrow_s = thr_s + TQ;
     uint32_t * const stage_s = qrow_s + TQ; // [NW][3][H_STAGE]
     uint32_t * const item_s = stage_s + NW * 3 * H_STAGE;
+    uint32_t * const pimg_s = item_s + 4; // i8r: the pair (image) of every tile row
 
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t total = a.work_off[a.nlist];
@@ -771,7 +1094,9 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
             const uint32_t qp = a.pairs[v ? pb + tid : pe - 1];
             const uint32_t q = qp / a.nprobe;
             qrow_s[tid] = q;
-            const float2 qi = a.qinfo[q];
+            if (I8)
+                pimg_s[tid] = qp;
+            const float2 qi = I8 ? a.pinfo[qp] : a.qinfo[q];
             m2_s[tid] = qi.x;
             qn_s[tid] = qi.y;
             thr_s[tid] = h16_stream_cut<METRIC>(v ? a.qthr[q] : 0u); // padding queries of a short tile never pass
@@ -780,7 +1105,7 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
         // the tile: piece p = (chunk, query < tq_e, slot) holds piece slot ^ swizzle(query) of the query's chunk; LDS keeps the
         // full tile's strides (compile-time operand offsets in the stream), an item with fewer column blocks leaves rows unwritten
         {
-            const uint32_t npieces = tq_e * nch * 8;
+            const uint32_t npieces = tq_e * tnch * 8;
             for (uint32_t p0 = tid; p0 < npieces; p0 += 4 * 64 * NW)
             {
                 uint4 v[4]; // 4 loads in flight per thread; pieces past the end re-load the last one
@@ -791,7 +1116,7 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
                     const uint32_t pp = p0 + u * 64 * NW;
                     const uint32_t p = pp < npieces ? pp : npieces - 1;
                     const uint32_t slot = p & 7, qi = (p >> 3) % tq_e, c = (p >> 3) / tq_e;
-                    v[u] = a.Qh[((size_t)qrow_s[qi] * nch + c) * 8 + (slot ^ ((qi >> 1) & 7))];
+                    v[u] = a.Qh[((size_t)(I8 ? pimg_s[qi] : qrow_s[qi]) * tnch + c) * 8 + (slot ^ ((qi >> 1) & 7))];
                     at[u] = ((c * TQ + qi) * 8 + slot) * 16;
                 }
 #pragma unroll
@@ -808,7 +1133,7 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
         }
         uint32_t * const stage = stage_s + wave * 3 * H_STAGE;
 #define MSVS_H16_STREAM(N)                                                                                                         \
-    h16_stream<METRIC, N>(a, tile, TQ * 128, m2_s, qn_s, thr_s, qrow_s, stage, lane, nch, a.hoff[l], b_first + wave, NW, b_end, lbeg, lend, nvalid)
+    h16_stream<METRIC, N, H_RING, 1, I8>(a, tile, TQ * 128, m2_s, qn_s, thr_s, qrow_s, stage, lane, nch, a.hoff[l], b_first + wave, NW, b_end, lbeg, lend, nvalid)
         if constexpr (NCB == 1)
             MSVS_H16_STREAM(1);
         else if (ncb_e == 1)
@@ -838,9 +1163,12 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
 /// NQB = 2 (not instantiated any more): an item is TWO column blocks (64 probing queries; the plan is built with T = 64), every
 /// row fragment feeds two MFMAs, a quarter less operand traffic -- measured SLOWER (80 against 73 us per 4096-query step: 240
 /// VGPRs, and half of the second blocks are empty).  A short second block repeats the item's last pair and stores nothing.
-template <int METRIC, int NQB>
+/// I8 (i8r shadow, NQB = 1, L2): the A operands are the pairs' hi / lo images, two exact i32 products per row fragment, the scan's
+/// epilogue arithmetic.
+template <int METRIC, int NQB, bool I8 = false>
 __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
 {
+    static_assert(!I8 || (NQB == 1 && METRIC == M_L2), "i8r: one column block, L2");
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r32 = lane & 31, h = lane >> 5;
     const uint32_t nch = a.nch, total = a.work_off[a.nlist];
     for (uint32_t w = blockIdx.x * 4 + wave; w < total; w += gridDim.x * 4)
@@ -869,16 +1197,22 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
             const uint32_t slot = 32u * b + r32;
             qp[b] = a.pairs[pb + (slot < nvalid ? slot : nvalid - 1)];
             const uint32_t q = qp[b] / a.nprobe;
-            qi[b] = a.qinfo[q];
-            ap[b] = reinterpret_cast<const u32x4 *>(a.Qh) + (size_t)q * nch * 8 + h;
+            qi[b] = I8 ? a.pinfo[qp[b]] : a.qinfo[q];
+            ap[b] = reinterpret_cast<const u32x4 *>(a.Qh) + (size_t)(I8 ? qp[b] : q) * (I8 ? 2 * nch : nch) * 8 + h;
         }
         const u32x4 * const bp = reinterpret_cast<const u32x4 *>(a.H) + (size_t)a.hoff[l] * nch * 256 + lane;
         const int64_t row = lbeg + r32;
         bool ok = row < lend;
-        float xn = 0.f;
+        float xn = 0.f, xs = 0.f;
         if (ok)
         {
-            if (METRIC == M_L2)
+            if (I8)
+            {
+                const float2 sd = a.side[row];
+                xs = sd.x;
+                xn = sd.y;
+            }
+            else if (METRIC == M_L2)
                 xn = a.xnorm[row];
             if (a.alive)
             {
@@ -892,24 +1226,36 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
 #pragma unroll
             for (int r = 0; r < 16; r++)
                 acc[b][r] = 0.f;
-        u32x4 ar[2][NQB][4], br[2][4];
+        i32x16 ach = {}, acl = {};
+        u32x4 ar[2][NQB][4], al[2][I8 ? 4 : 1], br[2][4];
         auto load = [&](const int s, const uint32_t c) {
 #pragma unroll
             for (int j = 0; j < 4; j++)
             {
 #pragma unroll
                 for (int b = 0; b < NQB; b++)
-                    ar[s][b][j] = ap[b][(size_t)c * 8 + 2 * j];
+                    ar[s][b][j] = ap[b][(size_t)(I8 ? 2 * c : c) * 8 + 2 * j];
+                if (I8)
+                    al[s][j] = ap[0][(size_t)(2 * c + 1) * 8 + 2 * j];
                 br[s][j] = bp[(size_t)c * 256 + j * 64];
             }
         };
         auto mul = [&](const int s) {
 #pragma unroll
             for (int j = 0; j < 4; j++)
+            {
+                if (I8)
+                {
+                    const i32x4 bf = __builtin_bit_cast(i32x4, br[s][j]);
+                    ach = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, ar[s][0][j]), bf, ach, 0, 0, 0);
+                    acl = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, al[s][j]), bf, acl, 0, 0, 0);
+                    continue;
+                }
 #pragma unroll
                 for (int b = 0; b < NQB; b++)
                     acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, ar[s][b][j]),
                                                                     __builtin_bit_cast(half8, br[s][j]), acc[b], 0, 0, 0);
+            }
         };
         load(0, 0);
         const uint32_t last = nch - 1;
@@ -936,7 +1282,8 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
                 const int qidx = (i & 3) + 8 * (i >> 2) + 4 * (int)h; // lanes qidx and qidx + 32 hold the same query
                 const float m2 = __shfl(qi[b].x, qidx), qn = __shfl(qi[b].y, qidx);
                 const uint32_t pair = (uint32_t)__shfl((int)qp[b], qidx);
-                const float v = METRIC == M_L2 ? __fadd_rn(fmaf(m2, acc[b][i], xn), qn) : __fmul_rn(m2, acc[b][i]);
+                const float v = I8 ? __fadd_rn(fmaf(__fmul_rn(m2, xs), fmaf((float)acl[i], 0.00390625f, (float)ach[i]), xn), qn)
+                    : METRIC == M_L2 ? __fadd_rn(fmaf(m2, acc[b][i], xn), qn) : __fmul_rn(m2, acc[b][i]);
                 const uint64_t key = ok ? make_key<METRIC>(v, (uint32_t)row) : KEY_NONE;
                 if (32u * b + (uint32_t)qidx < nvalid)
                     a.sample_out[(size_t)pair * H_ROWS + r32] = (uint32_t)(key >> 32);
@@ -985,8 +1332,11 @@ struct H16Prune
     double c_dot, c_norm, c_canon; // the shadow passes' error model: rows ...
     double c_dot_c;                // ... and centroids (their table has its own measured rounding error: set_error_model_h16)
     const float * qrho;            // nullable [nq]: the query image's measured rounding error, added as qrho_scale{,_c} * qrho[q]
+    const float * qrho_x;          // nullable [nq]: the rows' share of it (fp16: the same array; i8r: the bound of set_error_model_i8r)
+    const float * qoff;            // nullable [nq] (i8r): the largest per-pair lowering of the query's keys -- a sample word w bounds
+                                   // a distance from above only as w + eps_x + 2 qoff (h8_prep_pairs_kernel)
     double qrho_scale, qrho_scale_c;
-    __device__ double cd_x(uint32_t q) const { return qrho ? c_dot + qrho_scale * (double)qrho[q] : c_dot; }
+    __device__ double cd_x(uint32_t q) const { return qrho_x ? c_dot + qrho_scale * (double)qrho_x[q] : c_dot; }
     __device__ double cd_c(uint32_t q) const { return qrho ? c_dot_c + qrho_scale_c * (double)qrho[q] : c_dot_c; }
     uint32_t k;
     float * upre;              // nullable [nq]: h16_preprune_kernel leaves its upper bound of the query's k-th best (real) distance,
@@ -1248,7 +1598,7 @@ __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t *
                 {
                     const double dc = sqrt(inner) * (1.0 - 1e-7), r = (double)pr.radius[l];
                     // the k-th best canonical distance is at most ak + 2 eps_x (k sample rows) and at most the pre-pruning's bound
-                    double kth = ak + 2.0 * eps_x;
+                    double kth = ak + 2.0 * eps_x + (pr.qoff ? 2.0 * (double)pr.qoff[q] : 0.0);
                     if (pr.upre && (double)pr.upre[q] < kth)
                         kth = (double)pr.upre[q];
                     if (dc > r)

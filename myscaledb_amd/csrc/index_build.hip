@@ -35,9 +35,58 @@ static float measure_shadow_rho(const float * rows, size_t n, uint32_t ld, float
     return rho >= 0.f && rho < 1.f ? rho : -1.f;
 }
 
+/// The int8 residual form of the list shadow (h16_scan_kernels.hpp, "i8r") when `form` asks for it (3) or allows it (1, auto).
+/// The bound of a query of list l is ~ alpha_l rho with rho = |q - c_l| / |q| ~ beta_l (set_error_model_i8r); the fp16 form's is
+/// c16 = 2 rho16 + 1.01 d 2^-23 (rho16: its measured rounding error of this table, the query's taken alike; set_error_model_h16).
+/// Auto takes i8r when at least 97 % of the rows sit in lists with alpha_l beta_l <= 3 c16: half the bytes for a bound that stays
+/// within a small factor of fp16's almost everywhere.  On rows close to their centroids (clustered data) the residual pays for
+/// the int8 rounding; on iid rows the residual is as long as the row (~15x looser than fp16), and a list that k-means left
+/// straddling two clusters has long residuals too -- queries there would lose their certificate.  Every list's beta must stay
+/// inside the error model's range.  True: ix.shadow holds the i8r blocks.
+static bool index_build_shadow_i8r(msvs_index & ix, int form, float rho, size_t nblocks, hipStream_t stream)
+{
+    ix.h8 = false;
+    ix.h8_side.release();
+    ix.h8_list.release();
+    if (form != 1 && form != 3)
+        return false;
+    if (ix.metric != MSVS_METRIC_L2 || !ix.centroids.p || !(rho >= 0.f))
+        return false;
+    const uint32_t nch8 = (uint32_t)ceil_div(ix.dim, (size_t)H8_CHUNK);
+    const size_t npieces = nblocks * (size_t)nch8 * 4 * 64;
+    DevBuf<uint4> H(npieces + 32768);
+    DevBuf<float2> side(ix.n), lab(ix.nlist);
+    MSVS_HIP(hipMemsetAsync(H.p, 0, H.n * sizeof(uint4), stream));
+    MSVS_HIP(hipMemsetAsync(lab.p, 0, ix.nlist * sizeof(float2), stream));
+    hipLaunchKernelGGL(h8_build_kernel, dim3((unsigned)ceil_div(ix.n, (size_t)4)), dim3(256), 0, stream, ix.vecs.p, ix.centroids.p, ix.ld,
+                       ix.n, ix.list_off.p, (uint32_t)ix.nlist, ix.hoff.p, nch8, H.p, side.p, reinterpret_cast<uint32_t *>(lab.p));
+    MSVS_HIP(hipGetLastError());
+    std::vector<float2> h_lab(ix.nlist);
+    MSVS_HIP(hipMemcpyAsync(h_lab.data(), lab.p, ix.nlist * sizeof(float2), hipMemcpyDeviceToHost, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    const double c16 = 2.0 * (double)rho + 1.01 * (double)round_up(ix.dim, H_CHUNK) * ldexp(1.0, -23);
+    bool in_range = true;
+    size_t good = 0;
+    for (size_t l = 0; l < ix.nlist; l++)
+    {
+        in_range = in_range && h_lab[l].y <= i8r_limit(ix.dim); // (NaN: out of range)
+        if ((double)h_lab[l].x * (double)h_lab[l].y <= 3.0 * c16)
+            good += (size_t)(ix.h_list_off[l + 1] - ix.h_list_off[l]);
+    }
+    if (form == 1 && !(in_range && (double)good >= 0.97 * (double)ix.n))
+        return false;
+    ix.shadow = std::move(H);
+    ix.h8_side = std::move(side);
+    ix.h8_list = std::move(lab);
+    ix.h8_nch = nch8;
+    ix.h8 = true;
+    return true;
+}
+
 static void index_build_shadow(msvs_index & ix, hipStream_t stream)
 {
     ix.shadow_ready = false;
+    ix.h8 = false;
     ix.h_rho = ix.c_rho = -1.f;
     if (ix.type == MSVS_INDEX_FLAT)
     {
@@ -155,22 +204,27 @@ static void index_build_shadow(msvs_index & ix, hipStream_t stream)
     ix.hoff.alloc(ix.nlist + 1);
     ix.list_mid32.alloc(ix.nlist);
     const size_t npieces = nblocks * (size_t)ix.h_nks * 64;
-    ix.shadow.alloc(npieces + 32768); // (+ 512 KiB of zeros past the last list)
-    MSVS_HIP(hipMemsetAsync(ix.shadow.p + npieces, 0, 32768 * sizeof(uint4), stream));
     MSVS_HIP(hipMemcpyAsync(d_blk.p, blk_list.data(), nblocks * 4, hipMemcpyHostToDevice, stream));
     MSVS_HIP(hipMemcpyAsync(ix.hoff.p, hoff.data(), (ix.nlist + 1) * 4, hipMemcpyHostToDevice, stream));
     MSVS_HIP(hipMemcpyAsync(ix.list_mid32.p, mid.data(), ix.nlist * 8, hipMemcpyHostToDevice, stream));
-    const size_t per_launch = (size_t)1 << 30; // pieces per launch (grid dimension limit)
-    for (size_t p0 = 0; p0 < npieces; p0 += per_launch)
-    {
-        const size_t m = std::min(per_launch, npieces - p0);
-        // p0 is a multiple of 2^30 pieces; the kernel indexes from the start of the shadow, so shift the base
-        hipLaunchKernelGGL(h16_build_kernel, dim3((unsigned)ceil_div(m, (size_t)256)), dim3(256), 0, stream, ix.vecs.p,
-                           ix.ld, ix.list_off.p, d_blk.p, ix.hoff.p, ix.h_nks, ix.h_scale, ix.shadow.p, p0, m);
-    }
-    MSVS_HIP(hipGetLastError());
-    MSVS_HIP(hipStreamSynchronize(stream));
+    // (the fp16 form's measured rounding error: its error model, and the yardstick of the auto rule for the i8r form)
     ix.h_rho = measure_shadow_rho(ix.vecs.p, ix.n, ix.ld, ix.h_scale, ix.h_inv_scale, stream);
+    const int form = options().h16_form != 0 ? (int)options().h16_form : ix.want_shadow;
+    if (!index_build_shadow_i8r(ix, form, ix.h_rho, nblocks, stream))
+    {
+        ix.shadow.alloc(npieces + 32768); // (+ 512 KiB of zeros past the last list)
+        MSVS_HIP(hipMemsetAsync(ix.shadow.p + npieces, 0, 32768 * sizeof(uint4), stream));
+        const size_t per_launch = (size_t)1 << 30; // pieces per launch (grid dimension limit)
+        for (size_t p0 = 0; p0 < npieces; p0 += per_launch)
+        {
+            const size_t m = std::min(per_launch, npieces - p0);
+            // p0 is a multiple of 2^30 pieces; the kernel indexes from the start of the shadow, so shift the base
+            hipLaunchKernelGGL(h16_build_kernel, dim3((unsigned)ceil_div(m, (size_t)256)), dim3(256), 0, stream, ix.vecs.p,
+                               ix.ld, ix.list_off.p, d_blk.p, ix.hoff.p, ix.h_nks, ix.h_scale, ix.shadow.p, p0, m);
+        }
+        MSVS_HIP(hipGetLastError());
+        MSVS_HIP(hipStreamSynchronize(stream));
+    }
     ix.shadow_ready = true;
     // the centroid table in the same form (one list of nlist rows = G blocks), if it fits the rows' scale
     ix.c_shadow_ready = false;

@@ -62,7 +62,7 @@ struct msvs_index
     float cnorm_max = 0.f;
     DevBuf<int64_t> list_mid; // nlist: end of the SAMPLE slice of list l = min(list_off[l] + 128, list_off[l+1])
     // fp16 shadow of the lists (h16_scan_kernels.hpp): the list scan of batched searches reads this instead of vecs
-    int want_shadow = 1;        // build parameter `shadow=0|1`
+    int want_shadow = 1;        // build parameter `shadow`: 0 none, 1 auto, 2 fp16, 3 int8 residual (L2 IVFFLAT; others: fp16)
     DevBuf<uint4> shadow;       // blocks of 32 rows in MFMA operand order
     DevBuf<uint32_t> hoff;      // nlist + 1: first block of list l
     DevBuf<int64_t> list_mid32; // nlist: end of block 0 of list l = min(list_off[l] + 32, list_off[l+1])
@@ -70,6 +70,12 @@ struct msvs_index
     float h_scale = 0.f, h_inv_scale = 0.f; // stored value = fp16(x * h_scale)
     float h_rho = -1.f, c_rho = -1.f; // measured max |x' - x| / |x| over the stored rows / the centroid shadow (h16_rho_kernel; < 0: unknown)
     bool shadow_ready = false;
+    // int8 RESIDUAL form of the list shadow (h16_scan_kernels.hpp, "i8r"): `shadow` then holds blocks of int8 x - c_l in the B operand
+    // order of v_mfma_i32_32x32x32_i8, h8_nch chunks of 128 elements per row
+    bool h8 = false;
+    uint32_t h8_nch = 0;
+    DevBuf<float2> h8_side;     // [n] {s_x, |x - c|^2} of stored row r (the stored value is s_x * int8)
+    DevBuf<float2> h8_list;     // [nlist] {alpha_l, beta_l}: max over the list's rows of E_x / |x| and (|x - c| + E_x) / |x| (set_error_model_i8r)
     // fp16 shadow of the CENTROID table (same scale, same block layout: ceil(nlist / 32) blocks) for the coarse quantiser of
     // batches, and the G-lists-of-one-block view the sample kernel walks it through
     DevBuf<uint4> c_shadow;

@@ -251,6 +251,11 @@ struct IvfSearchPlan
     bool mfma() const { return nqg != 0; }
 };
 
+/// 128-byte chunks of a query's image in the list scan's LDS tile: the fp16 image, or the hi and lo images of an i8r pair.
+static uint32_t h16_tile_nch(const msvs_index & ix) { return ix.h8 ? 2 * ix.h8_nch : ix.h_nch; }
+/// Scratch bytes of one (query, probe) pair of a list scan over the i8r shadow: its two images and its constants.
+static size_t i8r_pair_bytes(const msvs_index & ix) { return (size_t)ix.h8_nch * 256 + 12; }
+
 static IvfSearchPlan plan_ivf(const msvs_index & ix, size_t nq, size_t nprobe, uint32_t k, bool allow_pass = true)
 {
     IvfSearchPlan p{};
@@ -263,7 +268,7 @@ static IvfSearchPlan plan_ivf(const msvs_index & ix, size_t nq, size_t nprobe, u
         const int mode = allow_pass ? (int)options().ivf_pass : 0; // experiment knob: 0 = never, 2 = whenever eligible
         // row positions travel in the low word of the candidate keys: < 2^32 rows; NaN norms compare false
         // the shadow pass keeps a whole query tile in LDS: at least one column block of 32 queries must fit
-        const bool h16 = ix.shadow_ready && options().ivf_h16 != 0 && h16_lds_bytes(1, ix.h_nch) <= 160 * 1024;
+        const bool h16 = ix.shadow_ready && options().ivf_h16 != 0 && h16_lds_bytes(1, h16_tile_nch(ix), ix.h8) <= 160 * 1024;
         // k <= 40: 64 candidates; the shadow pass also serves 40 < k <= 128 with 256 (hybrid searches take a vector top-100)
         const bool eligible = (k <= 40 || (h16 && k <= 128 && options().h16_k128 != 0)) && ix.xnorm.p && ix.xnorm_max < 1e30f
             && ix.n <= 0xfffffff0ull;
@@ -279,7 +284,7 @@ static IvfSearchPlan plan_ivf(const msvs_index & ix, size_t nq, size_t nprobe, u
                 uint32_t ncb = (uint32_t)std::min<size_t>(4, std::max<size_t>(2, ceil_div(2 * ceil_div(pairs, nlist), (size_t)32)));
                 if (options().h16_ncb >= 1)
                     ncb = (uint32_t)std::min(4.0, options().h16_ncb);
-                while (ncb > 1 && h16_lds_bytes(ncb, ix.h_nch) > 160 * 1024)
+                while (ncb > 1 && h16_lds_bytes(ncb, h16_tile_nch(ix), ix.h8) > 160 * 1024)
                     ncb--;
                 p.h_ncb = ncb;
             }
@@ -414,7 +419,8 @@ static size_t index_search_scratch(const msvs_index & ix, size_t nq, uint32_t k,
         need += nq * (p.h16 ? (size_t)p.h_cap : big_cand_cap(nprobe, p.seg_max)) * 8
             + nq * (size_t)p.kc * 8 + nq * 32 + 8192
             + fallback_cap(nq, nprobe, p.seg_max1, k) * nprobe * (size_t)p.seg_max1 * k * 8
-            + (p.h16 ? nq * ((size_t)ix.h_nch * 128 + 8 + 4 + 4) + 2048 + nq * nprobe * H_ROWS * 4 + 4 * ix.nlist + 4096 : 0);
+            + (p.h16 ? nq * ((size_t)ix.h_nch * 128 + 8 + 4 + 4) + 2048 + nq * nprobe * H_ROWS * 4 + 4 * ix.nlist + 4096 : 0)
+            + (p.h16 && ix.h8 ? nq * nprobe * i8r_pair_bytes(ix) + nq * 8 + 2048 : 0); // i8r: the pairs' images, constants, the bound
     else
         need += nq * nprobe * (size_t)p.seg_max * k * 8;
     return need;
@@ -1088,6 +1094,35 @@ static void set_error_model_h16(RerankParams & rp, size_t dim, float rho_table, 
     rp.c_canon = scale * 32.0 * ldexp(1.0, -24);
 }
 
+/// Error model of the int8 residual shadow (h16_scan_kernels.hpp, "i8r"), u = 2^-24.  Row x of list l is stored as s_x ix with
+/// r_x = x - c_l, E_x = |r_x - s_x ix| (exact differences in double, h8_build_kernel); the pair (q, l) as s_q (hi + lo / 256) with
+/// r_q = q - c_l, E_q = |r_q - s_q (hi + lo / 256)| (h8_prep_pairs_kernel).  With A = |r_x|^2 + |r_q|^2 - 2 s_x s_q (acc_hi + acc_lo / 256)
+/// (exact integer sums) and D = |x - q|^2 = |r_x - r_q|^2:
+///   |A - D| = 2 |<r_x, r_q> - <r~_x, r~_q>| <= 2 (E_x |r_q| + |r~_x| E_q),  |r~_x| <= |r_x| + E_x;
+/// the scan's a = fl(fl(fma(fl(-2 s_q s_x), fl(acc_hi + acc_lo / 256), fl|r_x|^2)) + fl|r_q|^2) adds, with H_q = s_q (|hi| + |lo| / 256)
+/// >= |acc_hi| s_q / |ix| + |acc_lo| s_q / (256 |ix|) (Cauchy-Schwarz; conversions, the combine, the product, the fma, the sum and the
+/// rounded norms -- |r_q|^2 twice: to f32, and after h8_prep_pairs_kernel's offset below -- each <= u relative):
+///   |a - A| <= 12.1 u |r~_x| H_q + 3.1 u |r_x|^2 + 3.1 u |r_q|^2.  In the consumers' form
+/// eps = 2 c_dot(q) |x||q| + c_norm (|x|^2 + |q|^2) + canonical terms: with per-list alpha_l = max E_x / |x|,
+/// beta_l = max (|r_x| + E_x) / |x| (build) and per pair rho = |r_q| / |q|, e = E_q / |q|, h = H_q / |q|,
+///   |a - D| <= 2 C_p |x||q| + 3.1 u (beta_l^2 |x|^2 + rho^2 |q|^2),   C_p = alpha_l rho + beta_l e + 6.05 u beta_l h,
+/// and the last term is within c_norm (|x|^2 + |q|^2) = 1.05 (d + 8) u (...) -- with room for the offset's rounding -- as long as
+/// beta_l, rho + e <= i8r_limit(d) = sqrt((d + 8) / 6) (outside that the query's bound is +inf: canonical fallback).
+/// C_p grows with the query's distance from the list's centroid.  The consumers take ONE coefficient per query, c_dot(q) = qbound[q]
+/// = min over its pairs of C_p, and the keys of every other pair are lowered by off_p >= 2 (C_p - qbound[q]) |x||q| (h8_prep_pairs_kernel):
+/// key - eps(qbound) <= D for every row of every pair -- the lower bound the re-rank certificate and its early exit, the second chance,
+/// the cut and the fallback rest on.  The one consumer that reads a sample key as an UPPER bound, the second pruning stage, widens
+/// it by twice the query's largest lowering (H16Prune::qoff); the returned ids and distances are the canonical ones.
+static void set_error_model_i8r(RerankParams & rp, size_t dim, const float * qbound)
+{
+    const double scale = 1.05 * options().ivf_eps_scale;
+    rp.qrho = qbound;
+    rp.qrho_scale = scale;
+    rp.c_dot = 0.0;
+    rp.c_norm = scale * ((double)dim + 8.0) * ldexp(1.0, -24);
+    rp.c_canon = scale * 32.0 * ldexp(1.0, -24);
+}
+
 /// The same model for the kernels that bound sample / centroid words (H16Prune): the rows' table and the centroid table each
 /// with its own measured rounding error.
 /// remote_words: the coarse words were computed by ANOTHER rank's centroid shadow and query images (ProbeWords::given): its measured
@@ -1103,20 +1138,21 @@ static void set_prune_error_model(H16Prune & pr, const msvs_index & ix, const fl
     pr.c_norm = ex.c_norm;
     pr.c_canon = ex.c_canon;
     pr.qrho = ex.qrho;
+    pr.qrho_x = ex.qrho;
     pr.qrho_scale = ex.qrho_scale;
     pr.qrho_scale_c = ec.qrho_scale;
 }
 
-template <int METRIC, int NCB>
+template <int METRIC, int NCB, bool I8 = false>
 static void h16_launch(uint32_t grid, size_t lds, const H16Params & a, hipStream_t stream)
 {
     // more than 64 KiB of dynamic LDS needs the attribute raised once per kernel
     static std::once_flag once;
     std::call_once(once, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&h16_scan_kernel<METRIC, NCB>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&h16_scan_kernel<METRIC, NCB, I8>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
-    hipLaunchKernelGGL((h16_scan_kernel<METRIC, NCB>), dim3(grid), dim3(64 * H_NW), lds, stream, a);
+    hipLaunchKernelGGL((h16_scan_kernel<METRIC, NCB, I8>), dim3(grid), dim3(64 * H_NW), lds, stream, a);
 }
 
 template <int METRIC>
@@ -1128,6 +1164,18 @@ static void h16_dispatch(uint32_t ncb, uint32_t grid, size_t lds, const H16Param
         case 2: h16_launch<METRIC, 2>(grid, lds, a, stream); break;
         case 3: h16_launch<METRIC, 3>(grid, lds, a, stream); break;
         default: h16_launch<METRIC, 4>(grid, lds, a, stream); break;
+    }
+}
+
+/// The list scan over the int8 residual shadow (L2 only).
+static void h8_dispatch(uint32_t ncb, uint32_t grid, size_t lds, const H16Params & a, hipStream_t stream)
+{
+    switch (ncb)
+    {
+        case 1: h16_launch<M_L2, 1, true>(grid, lds, a, stream); break;
+        case 2: h16_launch<M_L2, 2, true>(grid, lds, a, stream); break;
+        case 3: h16_launch<M_L2, 3, true>(grid, lds, a, stream); break;
+        default: h16_launch<M_L2, 4, true>(grid, lds, a, stream); break;
     }
 }
 
@@ -1204,6 +1252,7 @@ struct H16Last
     uint32_t cap = 0;
     size_t nq = 0;
     hipStream_t stream = nullptr;
+    const float * qbound = nullptr; // i8r: the queries' coefficients of |x||q| (set_error_model_i8r)
 };
 static thread_local H16Last g_h16_last;
 
@@ -1325,16 +1374,33 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     uint32_t * failq = scr.take<uint32_t>(nq);
     if (!prep_done)
         prep(H16PrepAux{});
+    // i8r: the images of the (query, list) pairs the pre-pruning left, their constants and every query's error bound
+    uint4 * pimg = nullptr;
+    float2 * pinfo = nullptr;
+    float * qbound = nullptr, * qoff = nullptr;
+    if (ix.h8)
+    {
+        pimg = scr.take<uint4>(nq * nprobe * (size_t)ix.h8_nch * 16 + 64);
+        pinfo = scr.take<float2>(nq * nprobe);
+        qbound = scr.take<float>(nq);
+        qoff = scr.take<float>(nq);
+        float * pc = scr.take<float>(nq * nprobe);
+        ProfileScope prof("ivf_prep_pairs", stream);
+        hipLaunchKernelGGL(h8_prep_pairs_kernel, dim3((unsigned)nq), dim3(256), 0, stream, dq, (uint32_t)nq, ld, ix.centroids.p, plan_probes,
+                           (uint32_t)nprobe, ix.h8_nch, ix.h8_list.p, i8r_limit(ix.dim), ix.xnorm_max, pimg, pinfo, pc, qbound, qoff);
+    }
     // (no fill of `sample`: the sample launch writes all 32 words of every pair whose list has rows, and the cut kernels
     // take a pair whose list is empty as 32 missing rows)
     H16Params a{};
     a.H = ix.shadow.p;
     a.hoff = ix.hoff.p;
     a.nks = ix.h_nks;
-    a.nch = ix.h_nch;
-    a.Qh = qh;
+    a.nch = ix.h8 ? ix.h8_nch : ix.h_nch;
+    a.Qh = ix.h8 ? pimg : qh;
     a.qinfo = qinfo;
     a.xnorm = ix.xnorm.p;
+    a.side = ix.h8_side.p;
+    a.pinfo = pinfo;
     a.list_off = ix.list_off.p;
     a.ids = ix.row_ids.p;
     a.alive = d_alive;
@@ -1351,7 +1417,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     a.cand_cap = pl.h_cap;
     a.sample_out = sample;
     // persistent workgroups pulling work items from per-XCD queues: one per CU (the tile takes most of the LDS)
-    const size_t lds = h16_lds_bytes(pl.h_ncb, ix.h_nch);
+    const size_t lds = h16_lds_bytes(pl.h_ncb, h16_tile_nch(ix), ix.h8);
     const uint32_t per_cu = (uint32_t)std::min<size_t>(2, std::max<size_t>(1, (160 * 1024) / lds));
     const uint32_t grid = options().h16_grid >= 1 ? (uint32_t)options().h16_grid : device_cu_count() * per_cu;
     H16Prune pr{};
@@ -1359,7 +1425,9 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         ProfileScope prof("ivf_sample_scan", stream);
         a.work_off = pa.work_off;
         const uint32_t sgrid = device_cu_count() * 8; // one wavefront per (list, 32-query column block), grid-stride
-        if (scan_metric(m) == M_IP)
+        if (ix.h8)
+            hipLaunchKernelGGL((h16_sample_kernel<M_L2, 1, true>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
+        else if (scan_metric(m) == M_IP)
             hipLaunchKernelGGL((h16_sample_kernel<M_IP, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
         else
             hipLaunchKernelGGL((h16_sample_kernel<M_L2, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
@@ -1372,6 +1440,16 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
             if (prune2)
             {
                 set_prune_error_model(pr, ix, qrho, !prepared.coarse_words && prepared.probe_words != nullptr);
+                if (ix.h8)
+                {
+                    // the rows' words come from the i8r shadow: its bound, widened by the keys' lowering where a word is an upper bound
+                    RerankParams ex{};
+                    set_error_model_i8r(ex, ix.dim, qbound);
+                    pr.c_dot = ex.c_dot;
+                    pr.qrho_x = ex.qrho;
+                    pr.qrho_scale = ex.qrho_scale;
+                    pr.qoff = qoff;
+                }
                 pr.coarse_words = prepared.coarse_words;
                 pr.npad = prepared.coarse_npad;
                 pr.probe_words = prepared.coarse_words ? nullptr : prepared.probe_words;
@@ -1447,14 +1525,16 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
                 a.stamps = g_h16_stamps.p;
                 g_h16_stamp_grid = grid;
             }
-            if (scan_metric(m) == M_IP)
+            if (ix.h8)
+                h8_dispatch(pl.h_ncb, grid, lds, a, stream);
+            else if (scan_metric(m) == M_IP)
                 h16_dispatch<M_IP>(pl.h_ncb, grid, lds, a, stream);
             else
                 h16_dispatch<M_L2>(pl.h_ncb, grid, lds, a, stream);
         }
     }
     MSVS_HIP(hipGetLastError());
-    g_h16_last = H16Last{partial, qstate + nq, pl.h_cap, nq, stream};
+    g_h16_last = H16Last{partial, qstate + nq, pl.h_cap, nq, stream, qbound};
     launch_cand_select(partial, qstate + nq, qstate, pl.h_cap, (uint32_t)nq, pl.kc, cand, bound, stream);
     RerankParams rp{};
     rp.Y = reinterpret_cast<const float4 *>(ix.vecs.p);
@@ -1469,7 +1549,10 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     rp.out_ids = d_ids;
     rp.out_dis = d_dis;
     rp.cosine = ix.metric == MSVS_METRIC_COSINE;
-    set_error_model_h16(rp, ix.dim, ix.h_rho, qrho);
+    if (ix.h8)
+        set_error_model_i8r(rp, ix.dim, qbound);
+    else
+        set_error_model_h16(rp, ix.dim, ix.h_rho, qrho);
     rp.xmax = ix.xnorm_max;
     rp.failq = failq;
     rp.nfail = nfail;
@@ -1571,7 +1654,9 @@ void index_search_device(const msvs_index & ix, const float * d_queries /* nq x 
                          const int32_t * given_probes, int32_t * probes_only, const SearchView * view, ProbeWords words)
 {
     const size_t np_eff = ix.type == MSVS_INDEX_IVFFLAT ? std::max<size_t>(1, std::min(nprobe, std::max<size_t>(ix.nlist, 1))) : 1;
-    const size_t sub = std::max<size_t>(256, ((size_t)1 << 21) / np_eff);
+    // (an i8r index keeps the images of a sub-batch's pairs: at most ~384 MB of them)
+    const size_t max_pairs = ix.h8 ? std::min<size_t>((size_t)1 << 21, ((size_t)384 << 20) / i8r_pair_bytes(ix)) : (size_t)1 << 21;
+    const size_t sub = std::max<size_t>(256, max_pairs / np_eff);
     if (nq <= sub)
         return index_search_device_one(ix, d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, given_probes,
                                        probes_only, view, words);
@@ -2244,6 +2329,35 @@ extern "C" __attribute__((visibility("default"))) int msvs_debug_coarse_words(ui
         MSVS_HIP(hipStreamSynchronize(c.stream));
         MSVS_HIP(hipMemcpy(out, c.words, nq * npad * 4, hipMemcpyDeviceToHost));
         g_coarse_last = CoarseLast{};
+    });
+}
+
+/// Tests only: the form of an index's list shadow (0: none, 2: fp16, 3: int8 residual).
+extern "C" __attribute__((visibility("default"))) int msvs_debug_shadow_form(const msvs_index_t * ix)
+{
+    return !ix->shadow_ready ? 0 : ix->h8 ? 3 : 2;
+}
+
+/// Tests only: the i8r error model of this thread's last shadow list scan -- per query the coefficient of |x||q| (qbound, times
+/// the margin: c_dot of the consumers' eps), c_norm and c_canon.  *ran = 1 when the last pass ran over an i8r shadow.
+extern "C" __attribute__((visibility("default"))) int msvs_debug_i8r_bound(size_t dim, size_t nq, double * c_dot_out, double * c_norm,
+                                                                          double * c_canon, int * ran)
+{
+    return guarded([&] {
+        const H16Last & h = g_h16_last;
+        *ran = 0;
+        if (!h.qbound || h.nq != nq)
+            return;
+        std::vector<float> b(nq);
+        MSVS_HIP(hipStreamSynchronize(h.stream));
+        MSVS_HIP(hipMemcpy(b.data(), h.qbound, nq * 4, hipMemcpyDeviceToHost));
+        RerankParams rp{};
+        set_error_model_i8r(rp, dim, nullptr);
+        for (size_t q = 0; q < nq; q++)
+            c_dot_out[q] = rp.c_dot + rp.qrho_scale * (double)b[q];
+        *c_norm = rp.c_norm;
+        *c_canon = rp.c_canon;
+        *ran = 1;
     });
 }
 
