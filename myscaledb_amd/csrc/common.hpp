@@ -218,6 +218,9 @@ struct Options
     double h16_group_appends = 32; // shadow passes: tiles of at most this many queries append their survivors with one atomic per (wavefront, query) (0: one per record)
     double h16_feedback = 1;  // shadow list scan: the second pruning stage is skipped while the last search of the index (same batch shape) came out of the
                               // pre-pruning with too few pairs for it to pay (0: decided from nq * nprobe alone, as before round 6)
+    double h8_pairs = 1;      // i8r list scan: the pair images by one wavefront per pair of the plan (h8_pairs_wave_kernel) for batches of more than 8192
+                              // (query, probe) words; 0: always a workgroup per query (h8_prep_pairs_kernel); 2: always a wavefront per pair
+    double h8_pairs_grid = 0; // ... its grid in workgroups of 4 wavefronts (0: 4 per CU; tests: a grid smaller than the pairs)
     double h16_prune = 1;     // shadow list scan (L2): drop (query, list) pairs that provably cannot hold one of the query's k nearest rows when the lists are probed by more than a tile of queries (0: off, 2: always)
     double coarse_gemm_tq = 64; // coarse_gemm_kernel: queries per workgroup tile (64 or 128)
     double coarse_gemm_tc = 128; // ... and centroids (64 or 128)

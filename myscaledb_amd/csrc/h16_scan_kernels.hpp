@@ -87,7 +87,12 @@ struct H16Params
     // int8 residual form (i8r): H holds int8 blocks of nch chunks of 128 elements, Qh the PAIR images ([q * nprobe + p][2 nch][8])
     const float2 * side;      // [n] {s_x, |r_x|^2}
     const float2 * pinfo;     // [nq * nprobe] {-2 s_q, |r_q|^2}
-    uint64_t * stamps;        // nullable (option h16_stamps): [grid][H_STAMP_ITEMS][4] {item popped, tile resident, rows done, l << 32 | nvalid << 8}
+    // ... as h8_pairs_wave_kernel leaves it, |r_q|^2 WITHOUT the pair's offset: the readers apply it (h8_pair_info).  pc = nullptr
+    // (h8_prep_pairs_kernel, option h8_pairs = 0): pinfo carries the offset already
+    const float * pc;         // [nq * nprobe] C_p
+    const uint32_t * qmm;     // [2 nq] the query's {min, max} of C_p (h8_cmin / float bits)
+    const double * qxq;       // [nq] X Q
+    uint64_t * stamps;       // nullable (option h16_stamps): [grid][H_STAMP_ITEMS][4] {item popped, tile resident, rows done, l << 32 | nvalid << 8}
                               // in wall_clock64 ticks (100 MHz), [grid][0][0] = items of the workgroup
 };
 constexpr uint32_t H_STAMP_ITEMS = 64;
@@ -464,6 +469,204 @@ static __global__ __launch_bounds__(256) void h8_prep_pairs_kernel(const float *
         const double off = fine ? 2.0 * ((double)pc[(size_t)q * nprobe + p] - (double)cmin) * xq * (1.0 + 1e-3) : 0.0;
         float2 & pi = pinfo[(size_t)q * nprobe + p];
         pi.y = (float)((double)pi.y - off); // fl(fl|r_q|^2 - off): two roundings of |r_q|^2 (set_error_model_i8r)
+    }
+}
+
+// The same images, constants and bounds with ONE WAVEFRONT PER PAIR (h8_pairs_wave_kernel; option h8_pairs = 0 keeps the kernel
+// above).  After the pre-pruning a query keeps ~1 of its 32 probes: a workgroup per query left three of its four wavefronts idle
+// behind a barrier and walked the operands three times, 38 us for work the device does in a few.  Here the wavefronts of a fixed
+// grid stride over the plan's pair list (grouped by list: neighbours read the same centroid row), the differences are loaded once
+// and stay in registers, and nothing waits for another wavefront: min / max of C_p over a query's pairs are atomics on two words
+// per query, and the readers form what the barrier used to make ready --
+//   qmm[2 q] = 0x7f800000 - bits(min C_p), qmm[2 q + 1] = bits(max C_p)   (C_p >= 0 or +inf: unsigned order = float order; both
+//   grow under atomicMax, and the ZERO a preceding launch leaves there is "no pair yet": min = +inf, max = 0),
+//   qxq[q] = X Q in double, pc[pair] = C_p, pinfo[pair].y = fl(|r_q|^2) without the offset;
+// h8_pair_info applies fl(fl|r_q|^2 - off_p) where the sample and the main launch read a pair's constants, h8_query_bound gives
+// qbound / qoff (the cut kernels store them for the re-rank: H8Finish).  Same expressions, same roundings, same bits.
+
+__device__ __forceinline__ float h8_cmin(const uint32_t w) { return __uint_as_float(0x7f800000u - w); }
+
+/// pinfo of pair qp of query q as the scan wants it.
+__device__ __forceinline__ float2 h8_pair_info(const float2 * pinfo, const float * pc, const uint32_t * qmm, const double * qxq,
+                                               const uint32_t qp, const uint32_t q)
+{
+    float2 pi = pinfo[qp];
+    if (pc)
+    {
+        const float cmin = h8_cmin(qmm[2 * q]), cmax = __uint_as_float(qmm[2 * q + 1]);
+        const bool fine = cmax < 3.0e38f; // (a pair outside the model: the whole query goes to the fallback)
+        const double xq = qxq[q];
+        const double off = fine ? 2.0 * ((double)pc[qp] - (double)cmin) * xq * (1.0 + 1e-3) : 0.0;
+        pi.y = (float)((double)pi.y - off); // fl(fl|r_q|^2 - off): two roundings of |r_q|^2 (set_error_model_i8r)
+    }
+    return pi;
+}
+
+/// qbound[q] and qoff[q] from the per-query words.  A query without any pair (nothing wrote qxq[q]): +inf and -inf, what
+/// h8_prep_pairs_kernel leaves for it (no key of such a query exists to be bounded).
+__device__ __forceinline__ void h8_query_bound(const uint32_t * qmm, const double * qxq, const uint32_t q, float & qbound, float & qoff)
+{
+    const uint32_t wmin = qmm[2 * q], wmax = qmm[2 * q + 1];
+    const float cmin = h8_cmin(wmin), cmax = __uint_as_float(wmax);
+    const bool fine = cmax < 3.0e38f;
+    qbound = fine ? cmin : __uint_as_float(0x7f800000u);
+    if (wmin == 0 && wmax == 0)
+        qoff = __uint_as_float(0xff800000u);
+    else
+        qoff = fine ? (float)(2.0 * ((double)cmax - (double)cmin) * qxq[q] * (1.0 + 2e-3)) : 0.f;
+}
+
+/// What a launch between the pair kernel and the re-rank finishes on its way (one wavefront per query: the cut kernels): the
+/// per-query arrays the re-rank, the second pruning stage and msvs_debug_i8r_bound read.  qmm = nullptr: nothing to do.
+struct H8Finish
+{
+    const uint32_t * qmm = nullptr;
+    const double * qxq = nullptr;
+    float * qbound = nullptr, * qoff = nullptr;
+};
+
+struct H8PairsParams
+{
+    const float * Q;          // [nq] rows of ld floats
+    const float * cents;      // [nlist] rows of ld floats
+    const int32_t * probes;   // [nq * nprobe] the plan's input (-1: no pair)
+    const uint32_t * pairs;   // the plan: pair indices q * nprobe + p grouped by list, ...
+    const uint32_t * pair_off; // ... pair_off[nlist] of them
+    const int64_t * whole_off; // [nlist + 1] the plan drops the pairs of lists without rows (IvfPlanParams::whole_off)
+    const float2 * list_ab;
+    uint32_t nq, ld, nprobe, nlist, nch8;
+    float lim, xmax;
+    uint4 * img;
+    float2 * pinfo;
+    float * pc;
+    uint32_t * qmm;
+    double * qxq;
+};
+
+// 16-element pieces per lane whose differences stay in registers between the reductions and the quantisation (32 VGPRs each): all
+// of them up to d = 2048; the pieces past that are loaded a second time.
+constexpr int H8_HOLD = 2;
+
+/// One pair: the arithmetic of h8_prep_pairs_kernel's probe loop, lane-to-piece map (t = lane, lane + 64, ...) and reduction order
+/// included, over operands read once.  |q|^2 keeps its own sweep (float4 groups strided by 256 elements): folding it into the pieces
+/// would change the order of its f64 sum; its loads are in flight together with the pieces'.
+__device__ __forceinline__ void h8_pair_wave(const H8PairsParams & a, const uint32_t pair, const uint32_t lane)
+{
+    const uint32_t qp = (uint32_t)__builtin_amdgcn_readfirstlane((int)pair); // (the same in every lane: scalar address arithmetic)
+    const uint32_t q = qp / a.nprobe, ld = a.ld;
+    const int32_t l = __builtin_amdgcn_readfirstlane(a.probes[qp]);
+    const float * src = a.Q + (size_t)q * ld;
+    const float * c = a.cents + (size_t)l * ld;
+    const uint32_t npc = a.nch8 * 8;
+    double d[H8_HOLD][16];
+#pragma unroll
+    for (int u = 0; u < H8_HOLD; u++)
+        if (lane + 64 * u < npc)
+            h8_load_diff(src, c, 16 * (lane + 64 * u), ld, d[u]);
+    double qq = 0.0;
+    for (uint32_t e = lane * 4; e < ld; e += 256)
+    {
+        const float4 v = *reinterpret_cast<const float4 *>(src + e);
+        qq += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    }
+    double mx = 0.0, dd = 0.0;
+#pragma unroll
+    for (int u = 0; u < H8_HOLD; u++)
+        if (lane + 64 * u < npc)
+        {
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+            {
+                mx = fmax(mx, fabs(d[u][i]));
+                dd += d[u][i] * d[u][i];
+            }
+        }
+    for (uint32_t t = lane + 64 * H8_HOLD; t < npc; t += 64)
+    {
+        double e[16];
+        h8_load_diff(src, c, 16 * t, ld, e);
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+        {
+            mx = fmax(mx, fabs(e[i]));
+            dd += e[i] * e[i];
+        }
+    }
+    const double nqn = sqrt(h8_wave_sum(qq));
+    mx = h8_wave_max(mx);
+    dd = h8_wave_sum(dd);
+    const float sq = (float)(mx / 127.0);
+    const double inv = sq > 0.f ? 1.0 / (double)sq : 0.0, s = (double)sq;
+    double ee = 0.0, hh = 0.0, ll = 0.0;
+    uint4 * const out = a.img + (size_t)qp * (2 * a.nch8) * 8;
+    auto quantise = [&](const uint32_t t, const double (&r)[16]) {
+        int vh[16], vl[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+        {
+            vh[i] = h8_q(r[i] * inv);
+            const double rem = r[i] - s * (double)vh[i];
+            vl[i] = h8_q(rem * inv * 256.0);
+            const double e = rem - s * (double)vl[i] * (1.0 / 256.0);
+            ee += e * e;
+            hh += (double)(vh[i] * vh[i]);
+            ll += (double)(vl[i] * vl[i]);
+        }
+        const uint32_t ch = t >> 3, j = t & 7;
+        out[(2 * ch) * 8 + j] = h8_pack(vh);
+        out[(2 * ch + 1) * 8 + j] = h8_pack(vl);
+    };
+#pragma unroll
+    for (int u = 0; u < H8_HOLD; u++)
+        if (lane + 64 * u < npc)
+            quantise(lane + 64 * u, d[u]);
+    for (uint32_t t = lane + 64 * H8_HOLD; t < npc; t += 64)
+    {
+        double e[16];
+        h8_load_diff(src, c, 16 * t, ld, e);
+        quantise(t, e);
+    }
+    ee = h8_wave_sum(ee);
+    hh = h8_wave_sum(hh);
+    ll = h8_wave_sum(ll);
+    if (lane == 0)
+    {
+        const float2 ab = a.list_ab[l];
+        const double rho = sqrt(dd) / nqn, e = sqrt(ee) * (1.0 + 1e-6) / nqn, hq = s * (sqrt(hh) + sqrt(ll) / 256.0) / nqn;
+        const double cq = ((double)ab.x * rho + (double)ab.y * e + 6.1 * ldexp(1.0, -24) * (double)ab.y * hq) * (1.0 + 1e-5);
+        const bool ok = nqn > 0.0 && rho + e <= (double)a.lim && (double)ab.y <= (double)a.lim && cq < 1e30;
+        const float cp = ok ? (float)cq * (1.f + 1e-6f) : __uint_as_float(0x7f800000u);
+        a.pinfo[qp] = make_float2(-2.f * sq, (float)dd);
+        a.pc[qp] = cp;
+        // X Q with X = sqrt(xmax) (xmax: the largest f32 row norm, within 1e-3 of the real one) and Q = |q|, both rounded up (every
+        // pair of the query stores the same value)
+        a.qxq[q] = sqrt((double)a.xmax * 1.001) * nqn * (1.0 + 1e-6);
+        const uint32_t bits = __float_as_uint(cp);
+        atomicMax(a.qmm + 2 * q, 0x7f800000u - bits);
+        atomicMax(a.qmm + 2 * q + 1, bits);
+    }
+}
+
+/// grid: any size, 4 wavefronts per block.  The pair count comes from the plan on the device (pair_off[nlist]).  The pairs the plan
+/// dropped -- probed lists without rows: a shard's foreign lists, an empty list -- have no key, but h8_prep_pairs_kernel counts their
+/// C_p (0 or +inf: alpha = beta = 0) in the query's minimum and maximum: a sweep over the probe words finds them, 64 per
+/// wavefront and step, and gives each the same treatment.
+static __global__ __launch_bounds__(256) void h8_pairs_wave_kernel(const H8PairsParams a)
+{
+    const uint32_t lane = threadIdx.x & 63, w0 = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+    const uint32_t npairs = a.pair_off[a.nlist];
+    for (uint32_t i = w0; i < npairs; i += nw)
+        h8_pair_wave(a, a.pairs[i], lane);
+    const uint32_t nall = a.nq * a.nprobe;
+    for (uint32_t base = w0 * 64; base < nall; base += nw * 64)
+    {
+        const int32_t l = base + lane < nall ? a.probes[base + lane] : -1;
+        uint64_t m = __ballot(l >= 0 && !(a.whole_off[l + 1] > a.whole_off[l]));
+        while (m)
+        {
+            h8_pair_wave(a, base + (uint32_t)__builtin_ctzll(m), lane);
+            m &= m - 1;
+        }
     }
 }
 
@@ -1096,7 +1299,7 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
             qrow_s[tid] = q;
             if (I8)
                 pimg_s[tid] = qp;
-            const float2 qi = I8 ? a.pinfo[qp] : a.qinfo[q];
+            const float2 qi = I8 ? h8_pair_info(a.pinfo, a.pc, a.qmm, a.qxq, qp, q) : a.qinfo[q];
             m2_s[tid] = qi.x;
             qn_s[tid] = qi.y;
             thr_s[tid] = h16_stream_cut<METRIC>(v ? a.qthr[q] : 0u); // padding queries of a short tile never pass
@@ -1197,7 +1400,7 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
             const uint32_t slot = 32u * b + r32;
             qp[b] = a.pairs[pb + (slot < nvalid ? slot : nvalid - 1)];
             const uint32_t q = qp[b] / a.nprobe;
-            qi[b] = I8 ? a.pinfo[qp[b]] : a.qinfo[q];
+            qi[b] = I8 ? h8_pair_info(a.pinfo, a.pc, a.qmm, a.qxq, qp[b], q) : a.qinfo[q];
             ap[b] = reinterpret_cast<const u32x4 *>(a.Qh) + (size_t)(I8 ? qp[b] : q) * (I8 ? 2 * nch : nch) * 8 + h;
         }
         const u32x4 * const bp = reinterpret_cast<const u32x4 *>(a.H) + (size_t)a.hoff[l] * nch * 256 + lane;
@@ -1515,8 +1718,21 @@ static __global__ __launch_bounds__(BLOCK) void h16_preprune_kernel(const int32_
 template <int NW>
 __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t * qprobes, const int64_t * list_off, uint32_t nprobe,
                                            uint32_t target, uint32_t * qthr, uint32_t * qcnt, uint64_t * dst, uint32_t cap,
-                                           uint32_t lane, uint32_t * hist, uint32_t q, const H16Prune & pr)
+                                           uint32_t lane, uint32_t * hist, uint32_t q, const H16Prune & pr, const H8Finish & fin)
 {
+    // i8r pairs from h8_pairs_wave_kernel: the query's bound and its largest lowering are formed here, for this kernel's own bound
+    // arithmetic below (pr.qrho_x / pr.qoff are then not read) and, stored, for the re-rank
+    float fin_qb = 0.f, fin_qo = 0.f;
+    if (fin.qmm)
+    {
+        h8_query_bound(fin.qmm, fin.qxq, q, fin_qb, fin_qo);
+        if (lane == 0)
+        {
+            fin.qbound[q] = fin_qb;
+            fin.qoff[q] = fin_qo;
+        }
+    }
+    auto cd_x = [&]() -> double { return fin.qmm ? pr.c_dot + pr.qrho_scale * (double)fin_qb : pr.cd_x(q); };
     const uint32_t n = nprobe * H_ROWS;
     uint32_t word[NW];
     int64_t lbeg[NW]; // start of the list word u belongs to (lane-dependent: i / 32)
@@ -1590,7 +1806,7 @@ __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t *
                 ; // no coarse value for this probe: kept
             else if (pr.ip == 0)
             {
-                const double eps_x = 2.0 * pr.cd_x(q) * sx * sq + pr.c_norm * (sx * sx + sq * sq) + (pr.c_canon + 4e-7) * (sx + sq) * (sx + sq) + 1e-30;
+                const double eps_x = 2.0 * cd_x() * sx * sq + pr.c_norm * (sx * sx + sq * sq) + (pr.c_canon + 4e-7) * (sx + sq) * (sx + sq) + 1e-30;
                 const double eps_c = 2.0 * cdc * sc * sq + pr.c_norm * (sc * sc + sq * sq) + (pr.c_canon + 4e-7) * (sc + sq) * (sc + sq) + 1e-30;
                 const double ak = (double)ord2f(uw), ac = cval;
                 const double inner = ac - 2.0 * eps_c;
@@ -1598,7 +1814,7 @@ __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t *
                 {
                     const double dc = sqrt(inner) * (1.0 - 1e-7), r = (double)pr.radius[l];
                     // the k-th best canonical distance is at most ak + 2 eps_x (k sample rows) and at most the pre-pruning's bound
-                    double kth = ak + 2.0 * eps_x + (pr.qoff ? 2.0 * (double)pr.qoff[q] : 0.0);
+                    double kth = ak + 2.0 * eps_x + (fin.qmm ? 2.0 * (double)fin_qo : pr.qoff ? 2.0 * (double)pr.qoff[q] : 0.0);
                     if (pr.upre && (double)pr.upre[q] < kth)
                         kth = (double)pr.upre[q];
                     if (dc > r)
@@ -1611,7 +1827,7 @@ __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t *
                 // value >= ipk, hence a canonical one >= ipk - eps_x: the k-th best canonical value of the query is at least that.
                 // A row x of list l has <q, x> = <q, c> + <q, x - c> <= <q, c> + |q| r_l, the coarse pass knows <q, c> to within
                 // eps_c (twice: approximate -> canonical -> real), a canonical value exceeds the real one by <= c_canon |x||q| <= eps_x
-                const double eps_x = (pr.cd_x(q) + pr.c_canon) * sx * sq + 1e-30, eps_c = (cdc + pr.c_canon + 4e-7) * sc * sq + 1e-30;
+                const double eps_x = (cd_x() + pr.c_canon) * sx * sq + 1e-30, eps_c = (cdc + pr.c_canon + 4e-7) * sc * sq + 1e-30;
                 const double ipk = (double)ord2f(~uw), ipc = cval;
                 const double ub = ipc + 2.0 * eps_c + sq * (double)pr.radius[l] * (1.0 + 1e-6);
                 keep = !(ub < ipk - 2.0 * eps_x);
@@ -1621,7 +1837,7 @@ __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t *
                 // cosine index: the words order inner products (larger is better).  ||q - c||^2 = |q|^2 + |c|^2 - 2 <q, c> from the
                 // coarse pass's <q, c> and the (f32, fma-accumulated: relative error c_norm) norms; a row x of the list has
                 // ||q - x|| >= ||q - c|| - r_l, i.e. <q, x> <= (|q|^2 + |x|^2 - (||q - c|| - r_l)^2) / 2
-                const double eps_x = (pr.cd_x(q) + pr.c_canon) * sx * sq + 1e-30, eps_c = (cdc + pr.c_canon + 4e-7) * sc * sq + 1e-30;
+                const double eps_x = (cd_x() + pr.c_canon) * sx * sq + 1e-30, eps_c = (cdc + pr.c_canon + 4e-7) * sc * sq + 1e-30;
                 const double ipk = (double)ord2f(~uw), ipc = cval;
                 const double cn = (double)pr.cnorm[l];
                 const double d2 = (double)qn * (1.0 - pr.c_norm) + cn * (1.0 - pr.c_norm) - 2.0 * (ipc + eps_c);
@@ -1674,7 +1890,7 @@ static __global__ __launch_bounds__(BLOCK) void h16_sample_thr_wave_kernel(const
                                                                             const int64_t * list_off, uint32_t nq, uint32_t nprobe,
                                                                             uint32_t target, uint32_t * qthr, uint32_t * qcnt,
                                                                             uint64_t * partial, uint32_t cap, int radix,
-                                                                            const H16Prune pr)
+                                                                            const H16Prune pr, const H8Finish fin)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[BLOCK / WAVE][256];
     const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1685,23 +1901,26 @@ static __global__ __launch_bounds__(BLOCK) void h16_sample_thr_wave_kernel(const
     const int32_t * qp = probes + (size_t)q * nprobe;
     uint64_t * dst = partial + (size_t)q * cap;
     if (nprobe <= 8)
-        h16_sample_thr_wave<4>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr);
+        h16_sample_thr_wave<4>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr, fin);
     else if (nprobe <= 16)
-        h16_sample_thr_wave<8>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr);
+        h16_sample_thr_wave<8>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr, fin);
     else if (nprobe <= 32)
-        h16_sample_thr_wave<16>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr);
+        h16_sample_thr_wave<16>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr, fin);
     else
-        h16_sample_thr_wave<32>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr);
+        h16_sample_thr_wave<32>(src, qp, list_off, nprobe, target, qthr + q, qcnt + q, dst, cap, lane, hist, q, pr, fin);
 }
 
 static __global__ __launch_bounds__(BLOCK) void h16_sample_thr_kernel(const uint32_t * sample, const int32_t * probes,
                                                                        const int64_t * list_off, uint32_t nq,
                                                                        uint32_t nprobe, uint32_t target, uint32_t * qthr,
-                                                                       uint32_t * qcnt, uint64_t * partial, uint32_t cap)
+                                                                       uint32_t * qcnt, uint64_t * partial, uint32_t cap,
+                                                                       const H8Finish fin)
 {
     const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= nq)
         return;
+    if (fin.qmm && lane == 0)
+        h8_query_bound(fin.qmm, fin.qxq, q, fin.qbound[q], fin.qoff[q]);
     const uint32_t * src = sample + (size_t)q * nprobe * H_ROWS;
     const uint32_t n = nprobe * H_ROWS;
     // R and S

@@ -420,7 +420,8 @@ static size_t index_search_scratch(const msvs_index & ix, size_t nq, uint32_t k,
             + nq * (size_t)p.kc * 8 + nq * 32 + 8192
             + fallback_cap(nq, nprobe, p.seg_max1, k) * nprobe * (size_t)p.seg_max1 * k * 8
             + (p.h16 ? nq * ((size_t)ix.h_nch * 128 + 8 + 4 + 4) + 2048 + nq * nprobe * H_ROWS * 4 + 4 * ix.nlist + 4096 : 0)
-            + (p.h16 && ix.h8 ? nq * nprobe * i8r_pair_bytes(ix) + nq * 8 + 2048 : 0); // i8r: the pairs' images, constants, the bound
+            + (p.h16 && ix.h8 ? nq * nprobe * i8r_pair_bytes(ix) + nq * 8 + 2048 + nq * 16 + 512 : 0); // i8r: the pairs' images, constants, the bound;
+                                                                                              // the per-query min / max words (counters) and X Q of h8_pairs_wave_kernel
     else
         need += nq * nprobe * (size_t)p.seg_max * k * 8;
     return need;
@@ -1256,6 +1257,18 @@ struct H16Last
 };
 static thread_local H16Last g_h16_last;
 
+/// Words of the list scan's counter block that h8_pairs_wave_kernel's per-query minimum and maximum take (zeroed with the counters);
+/// 0: the batch takes h8_prep_pairs_kernel.  Small batches keep the workgroup-per-query kernel: their launches are latency chains of
+/// a few microseconds each, the old kernel has as many workgroups as queries there, and the offset the readers form on their way
+/// costs more than the reshaped launch saves (measured, 32 probes: 16 queries 125 -> 128 us, 64 queries 166 -> 170 us, 256 equal,
+/// 4096 queries 473 -> 457 us).  Option h8_pairs = 2: the wavefront-per-pair kernel whatever the batch (tests).
+constexpr size_t H8_PAIRS_WAVE_MIN = 8192;
+static size_t h8_query_words(const msvs_index & ix, size_t nq, size_t nprobe)
+{
+    const bool wave = options().h8_pairs == 2 || (options().h8_pairs != 0 && nq * nprobe > H8_PAIRS_WAVE_MIN);
+    return ix.h8 && wave ? 2 * nq : 0;
+}
+
 /// List scan of a batch over the fp16 shadow: sample launch -> cut -> main launch -> candidate select -> canonical
 /// re-rank + certificate -> canonical fallback for the queries without one (h16_scan_kernels.hpp).
 static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const float * dq, size_t nq, uint32_t k,
@@ -1275,7 +1288,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     pp.nlist = (uint32_t)ix.nlist;
     pp.rows_per_block = 0x7fffffffu; // one segment per non-empty row range
     pp.T = 32 * pl.h_ncb;
-    const size_t n_counters = 4 * ix.nlist + 2 + 16; // two plans (cnt, fill each), nfail, 16 queue cursors, nfail2
+    // two plans (cnt, fill each), nfail, 16 queue cursors, nfail2; i8r: the pair kernel's two words per query (h8_pairs_wave_kernel)
+    const size_t n_qmm = h8_query_words(ix, nq, nprobe), n_counters = 4 * ix.nlist + 2 + 16 + n_qmm;
     const bool zeroed = prepared.qh && prepared.counters && prepared.n_counters >= n_counters;
     uint32_t * counters = zeroed ? prepared.counters : scr.take<uint32_t>(n_counters);
     pp.cnt = counters;
@@ -1283,6 +1297,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     uint32_t * nfail = counters + 2 * ix.nlist;
     uint32_t * sched = nfail + 1; // 8 work-queue cursors per launch
     uint32_t * nfail2 = sched + 16; // queries still without a certificate after the second chance
+    uint32_t * qmm = nfail2 + 1;    // [n_qmm]: behind the 18 words the fused plan clears, so that it clears these as well
     pp.pair_off = scr.take<uint32_t>(ix.nlist + 1);
     pp.work_off = scr.take<uint32_t>(ix.nlist + 1);
     pp.pairs = scr.take<uint32_t>(nq * nprobe);
@@ -1312,7 +1327,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         if (ivf_plan_fused(pp)) // (a small batch: the one-launch plan needs no zeroed counts and clears nfail / the cursors / nfail2 itself)
         {
             pp.zero = nfail;
-            pp.nzero = 18;
+            pp.nzero = 18 + (uint32_t)n_qmm;
         }
         else if (!prep_done)
         {
@@ -1378,6 +1393,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     uint4 * pimg = nullptr;
     float2 * pinfo = nullptr;
     float * qbound = nullptr, * qoff = nullptr;
+    const float * pair_pc = nullptr;
+    H8Finish fin{};
     if (ix.h8)
     {
         pimg = scr.take<uint4>(nq * nprobe * (size_t)ix.h8_nch * 16 + 64);
@@ -1386,8 +1403,40 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         qoff = scr.take<float>(nq);
         float * pc = scr.take<float>(nq * nprobe);
         ProfileScope prof("ivf_prep_pairs", stream);
-        hipLaunchKernelGGL(h8_prep_pairs_kernel, dim3((unsigned)nq), dim3(256), 0, stream, dq, (uint32_t)nq, ld, ix.centroids.p, plan_probes,
-                           (uint32_t)nprobe, ix.h8_nch, ix.h8_list.p, i8r_limit(ix.dim), ix.xnorm_max, pimg, pinfo, pc, qbound, qoff);
+        if (n_qmm)
+        {
+            // one wavefront per pair of the plan; the cut kernel below finishes qbound / qoff (H8Finish)
+            H8PairsParams hp{};
+            hp.Q = dq;
+            hp.cents = ix.centroids.p;
+            hp.probes = plan_probes;
+            hp.pairs = pp.pairs;
+            hp.pair_off = pp.pair_off;
+            hp.whole_off = pp.whole_off;
+            hp.list_ab = ix.h8_list.p;
+            hp.nq = (uint32_t)nq;
+            hp.ld = ld;
+            hp.nprobe = (uint32_t)nprobe;
+            hp.nlist = (uint32_t)ix.nlist;
+            hp.nch8 = ix.h8_nch;
+            hp.lim = i8r_limit(ix.dim);
+            hp.xmax = ix.xnorm_max;
+            hp.img = pimg;
+            hp.pinfo = pinfo;
+            hp.pc = pc;
+            hp.qmm = qmm;
+            hp.qxq = scr.take<double>(nq);
+            fin.qmm = qmm;
+            fin.qxq = hp.qxq;
+            fin.qbound = qbound;
+            fin.qoff = qoff;
+            const uint32_t pgrid = options().h8_pairs_grid >= 1 ? (uint32_t)options().h8_pairs_grid : device_cu_count() * 4;
+            hipLaunchKernelGGL(h8_pairs_wave_kernel, dim3(pgrid), dim3(256), 0, stream, hp);
+        }
+        else
+            hipLaunchKernelGGL(h8_prep_pairs_kernel, dim3((unsigned)nq), dim3(256), 0, stream, dq, (uint32_t)nq, ld, ix.centroids.p, plan_probes,
+                               (uint32_t)nprobe, ix.h8_nch, ix.h8_list.p, i8r_limit(ix.dim), ix.xnorm_max, pimg, pinfo, pc, qbound, qoff);
+        pair_pc = n_qmm ? pc : nullptr;
     }
     // (no fill of `sample`: the sample launch writes all 32 words of every pair whose list has rows, and the cut kernels
     // take a pair whose list is empty as 32 missing rows)
@@ -1401,6 +1450,9 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     a.xnorm = ix.xnorm.p;
     a.side = ix.h8_side.p;
     a.pinfo = pinfo;
+    a.pc = pair_pc;
+    a.qmm = fin.qmm;
+    a.qxq = fin.qxq;
     a.list_off = ix.list_off.p;
     a.ids = ix.row_ids.p;
     a.alive = d_alive;
@@ -1468,12 +1520,12 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
             }
             hipLaunchKernelGGL(h16_sample_thr_wave_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(BLOCK), 0, stream,
                                sample, plan_probes, ix.list_off.p, (uint32_t)nq, (uint32_t)nprobe, pl.h_mth, qstate,
-                               qstate + nq, partial, pl.h_cap, options().wave_select == 3 ? 0 : 1, pr);
+                               qstate + nq, partial, pl.h_cap, options().wave_select == 3 ? 0 : 1, pr, fin);
         }
         else
             hipLaunchKernelGGL(h16_sample_thr_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(BLOCK), 0, stream,
                                sample, plan_probes, ix.list_off.p, (uint32_t)nq, (uint32_t)nprobe, pl.h_mth, qstate,
-                               qstate + nq, partial, pl.h_cap);
+                               qstate + nq, partial, pl.h_cap, fin);
     }
     if (pr.on())
     {
@@ -1482,7 +1534,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         p2.zero = nullptr;
         p2.nzero = 0;
         p2.probes = pr.out_probes;
-        p2.cnt = counters + 2 * ix.nlist + 18;
+        p2.cnt = counters + 2 * ix.nlist + 18 + n_qmm;
         p2.fill = p2.cnt + ix.nlist;
         p2.pair_off = scr.take<uint32_t>(ix.nlist + 1);
         p2.work_off = scr.take<uint32_t>(ix.nlist + 1);
@@ -1744,7 +1796,7 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
     }
     // 1. coarse quantiser: exact top-nprobe of the centroids (canonical arithmetic, so probes match the oracle)
     H16Queries prepared{};
-    prepared.n_counters = (uint32_t)(4 * ix.nlist + 2 + 16); // the shadow list scan's counters (h16_list_scan)
+    prepared.n_counters = (uint32_t)(4 * ix.nlist + 2 + 16 + h8_query_words(ix, nq, nprobe)); // the shadow list scan's counters (h16_list_scan)
     prepared.counters = scr.take<uint32_t>(prepared.n_counters);
     int32_t * d_probes = probes_only ? probes_only : scr.take<int32_t>(nq * nprobe);
     if (given_probes)
