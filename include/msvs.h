@@ -154,7 +154,12 @@ typedef struct msvs_index msvs_index_t;
 /* params: "key=value" pairs separated by ',' or a flat JSON object, e.g. "ncentroids=1024" /
  * {"ncentroids":"1024"}.  IVFFLAT build params: ncentroids (default 1024), kmeans_iters (10),
  * train_sample (ncentroids*64), seed (1234).  Sharding for multi-GPU: shard_rank / shard_world
- * (lists with list_id % shard_world == shard_rank are kept on this device). */
+ * (lists with list_id % shard_world == shard_rank are kept on this device).
+ * shadow (1): the second, compact copy of the rows the batched list scan streams -- 0 none, 1 auto (L2 IVFFLAT: int8
+ * residuals where the rows sit close to their centroids, else fp16; every other index fp16), 2 fp16, 3 int8 residuals (L2
+ * IVFFLAT only; others fp16), 4 int8 residuals whatever the metric of an IVFFLAT index (L2: the same as 3), 5 auto over
+ * every metric (L2: the rule of 1; inner product and cosine: int8 residuals when every list is inside the error model's
+ * range and >= 97 % of the rows sit in lists whose rounding bound is within 3x fp16's).  Results never depend on it. */
 MSVS_API int msvs_index_create(int index_type, int metric, size_t dim, const char * params, msvs_index_t ** out);
 MSVS_API void msvs_index_free(msvs_index_t * index);
 

@@ -198,7 +198,7 @@ struct Options
     double rerank_fused = 1;  // shadow list scan: the second chance runs inside the re-rank launch, by the block of the query that failed (0: a launch of its own)
     double rerank_second = 1; // queries whose first certificate fails get their whole candidate buffer re-ranked before the canonical scan
     double h16_segs = 1;      // shadow list scan: lists cut into row segments on the device so that a launch has ~4 items per workgroup; 0: one item per (list, tile)
-    double h16_form = 0;      // IVF list shadow form of the NEXT build: 0 = the index's `shadow` parameter, 2 = fp16, 3 = int8 residual (i8r)
+    double h16_form = 0;      // IVF list shadow form of the NEXT build: 0 = the index's `shadow` parameter, 2 = fp16, 3 = int8 residual (i8r; L2), 4 = i8r whatever the metric, 5 = auto over every metric
     double h16_rho = 1;       // fp16 shadow passes: error bound from the MEASURED rounding error of the stored rows and of each query image; 0: the worst case per element
     double flat_h16 = 1;      // FLAT batches through the index's fp16 shadow (h16_flat_kernel); 0: the split-bf16 pass over the f32 rows; 3: one row block per wavefront
     double flat_ncb = 0;      // FLAT shadow pass: column blocks per tile (0: by batch size)

@@ -85,8 +85,9 @@ struct H16Params
     uint32_t group_appends;   // n: tiles of <= n queries append their survivors with one atomic per (wavefront, query) (0: one per record)
     uint32_t lazy_flush;      // 1: survivors stay in the wavefront's LDS stage from block to block and leave when it is full / at the end of the item
     // int8 residual form (i8r): H holds int8 blocks of nch chunks of 128 elements, Qh the PAIR images ([q * nprobe + p][2 nch][8])
+    // under L2, the QUERY images ([q][2 nch][8]) under inner product and cosine (h8_ip_prep_kernel)
     const float2 * side;      // [n] {s_x, |r_x|^2}
-    const float2 * pinfo;     // [nq * nprobe] {-2 s_q, |r_q|^2}
+    const float2 * pinfo;     // [nq * nprobe] L2: {-2 s_q, |r_q|^2}; inner product, cosine: {s_q, <q, c_l> + the pair's offset} (pc = nullptr)
     // ... as h8_pairs_wave_kernel leaves it, |r_q|^2 WITHOUT the pair's offset: the readers apply it (h8_pair_info).  pc = nullptr
     // (h8_prep_pairs_kernel, option h8_pairs = 0): pinfo carries the offset already
     const float * pc;         // [nq * nprobe] C_p
@@ -670,6 +671,187 @@ static __global__ __launch_bounds__(256) void h8_pairs_wave_kernel(const H8Pairs
     }
 }
 
+// ------------------------------------------------------------------------------------------ i8r under inner product and cosine
+//
+// <q, x> = <q, c_l> + <q, r_x>: the row side is the residual shadow above, unchanged; the QUERY side is q itself (cosine: the
+// normalised query), split into hi = rint(q / s_q), lo = rint((q - s_q hi) 256 / s_q) with s_q = max |q_i| / 127 -- ONE image per
+// query for every list it probes (an inner-product search prunes next to nothing: images per pair would write and read back more
+// bytes than the form saves).  What stays per pair is one constant, qc_p = <q, c_l> summed in double (+ the pair's offset), and
+// the scan forms
+//   v = fl(fma(fl(s_q s_x), fl(acc_hi + acc_lo / 256), qc_p))
+// -- the inner product, keyed like the fp16 form's (~f2ord(v)).  The coefficient of |x||q| in the error of pair p
+// (set_error_model_i8r) is
+//   C_p = alpha_l + beta_l e + 3.1 u beta_l h + u (4.1 + 2.02 beta_l),   e = E_q / |q|, h = s_q (|hi| + |lo| / 256) / |q|, u = 2^-24:
+// no factor rho -- it does not shrink with the query's distance from the centroid and varies with the list through alpha_l only.
+// qbound[q] = min over the query's pairs (with rows) of C_p; the keys of every other pair are RAISED by off_p = (C_p - qbound[q]) X Q
+// through qc_p, so that key + eps(qbound) >= key_p + eps(C_p) >= the true product for every row: the one-sided bound the
+// certificate uses under inner product.  qoff[q] = the largest off_p: a sample word bounds a product from BELOW only as
+// w - eps_x - 2 qoff (H16Prune::qoff).  +inf: a zero or non-finite query, a list outside the model's range -- canonical fallback.
+
+struct H8IpParams
+{
+    const float * Q;           // [nq] rows of ld floats (cosine: normalised)
+    const float * cents;       // [nlist] rows of ld floats
+    const int32_t * probes;    // [nq * nprobe] (-1: no pair)
+    const int64_t * whole_off; // [nlist + 1]: a list without rows has no key and does not count in the minimum
+    const float2 * list_ab;
+    uint32_t nq, ld, nprobe, nch8;
+    float lim, xmax;
+    uint4 * img;               // [nq][2 nch8][8 pieces]: virtual chunk 2 c = hi of chunk c, 2 c + 1 = lo (the pair images' order)
+    float2 * pinfo;            // [nq * nprobe] {s_q, fl(fl<q, c_l> + off_p)}
+    float * pc;                // [nq * nprobe] C_p
+    float * qbound, * qoff;    // [nq]
+};
+
+/// 16 consecutive floats (k0 .. k0 + 15, zero at and past ld).
+__device__ __forceinline__ void h8_load16(const float * a, uint32_t k0, uint32_t ld, float (&v)[16])
+{
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+    {
+        float4 va = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (k0 + 4 * t < ld)
+            va = *reinterpret_cast<const float4 *>(a + k0 + 4 * t);
+        v[4 * t + 0] = va.x;
+        v[4 * t + 1] = va.y;
+        v[4 * t + 2] = va.z;
+        v[4 * t + 3] = va.w;
+    }
+}
+
+/// One wavefront per query: its hi / lo images, then the constants of its pairs, one f64 dot product against the centroid each (the
+/// query's first 2048 elements stay in registers; the centroid rows come out of L2: the table is a few MB), then the offsets.  A
+/// pair's words are written and read back by the same lane (p mod 64): program order, no fence.
+static __global__ __launch_bounds__(256) void h8_ip_prep_kernel(const H8IpParams a)
+{
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= a.nq)
+        return;
+    const uint32_t ld = a.ld, npc = a.nch8 * 8, nprobe = a.nprobe;
+    const float * src = a.Q + (size_t)q * ld;
+    float qv[H8_HOLD][16];
+#pragma unroll
+    for (int u = 0; u < H8_HOLD; u++)
+        h8_load16(src, lane + 64 * u < npc ? 16 * (lane + 64 * u) : ld, ld, qv[u]); // (past the last piece: zeros)
+    double mx = 0.0, qq = 0.0;
+#pragma unroll
+    for (int u = 0; u < H8_HOLD; u++)
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+        {
+            mx = fmax(mx, fabs((double)qv[u][i]));
+            qq += (double)qv[u][i] * (double)qv[u][i];
+        }
+    for (uint32_t t = lane + 64 * H8_HOLD; t < npc; t += 64)
+    {
+        float v[16];
+        h8_load16(src, 16 * t, ld, v);
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+        {
+            mx = fmax(mx, fabs((double)v[i]));
+            qq += (double)v[i] * (double)v[i];
+        }
+    }
+    mx = h8_wave_max(mx);
+    const double nqn = sqrt(h8_wave_sum(qq));
+    const float sq = (float)(mx / 127.0);
+    const double inv = sq > 0.f ? 1.0 / (double)sq : 0.0, s = (double)sq;
+    double ee = 0.0, hh = 0.0, ll = 0.0;
+    uint4 * const out = a.img + (size_t)q * (2 * a.nch8) * 8;
+    auto quantise = [&](const uint32_t t, const float (&r)[16]) {
+        int vh[16], vl[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+        {
+            vh[i] = h8_q((double)r[i] * inv);
+            const double rem = (double)r[i] - s * (double)vh[i];
+            vl[i] = h8_q(rem * inv * 256.0);
+            const double e = rem - s * (double)vl[i] * (1.0 / 256.0);
+            ee += e * e;
+            hh += (double)(vh[i] * vh[i]);
+            ll += (double)(vl[i] * vl[i]);
+        }
+        const uint32_t ch = t >> 3, j = t & 7;
+        out[(2 * ch) * 8 + j] = h8_pack(vh);
+        out[(2 * ch + 1) * 8 + j] = h8_pack(vl);
+    };
+#pragma unroll
+    for (int u = 0; u < H8_HOLD; u++)
+        if (lane + 64 * u < npc)
+            quantise(lane + 64 * u, qv[u]);
+    for (uint32_t t = lane + 64 * H8_HOLD; t < npc; t += 64)
+    {
+        float v[16];
+        h8_load16(src, 16 * t, ld, v);
+        quantise(t, v);
+    }
+    ee = h8_wave_sum(ee);
+    hh = h8_wave_sum(hh);
+    ll = h8_wave_sum(ll);
+    const double e = sqrt(ee) * (1.0 + 1e-6) / nqn, hq = s * (sqrt(hh) + sqrt(ll) / 256.0) / nqn, u24 = ldexp(1.0, -24);
+    float best = __uint_as_float(0x7f800000u), worst = 0.f; // (the same in every lane: the butterfly sums are)
+    for (uint32_t p = 0; p < nprobe; p++)
+    {
+        const uint32_t qp = q * nprobe + p;
+        const int32_t l = __builtin_amdgcn_readfirstlane(a.probes[qp]);
+        if (l < 0 || !(a.whole_off[l + 1] > a.whole_off[l]))
+            continue;
+        const float * c = a.cents + (size_t)l * ld;
+        double dot = 0.0;
+#pragma unroll
+        for (int u = 0; u < H8_HOLD; u++)
+            if (lane + 64 * u < npc)
+            {
+                float cv[16];
+                h8_load16(c, 16 * (lane + 64 * u), ld, cv);
+#pragma unroll
+                for (int i = 0; i < 16; i++)
+                    dot = fma((double)qv[u][i], (double)cv[i], dot);
+            }
+        for (uint32_t t = lane + 64 * H8_HOLD; t < npc; t += 64)
+        {
+            float v[16], cv[16];
+            h8_load16(src, 16 * t, ld, v);
+            h8_load16(c, 16 * t, ld, cv);
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+                dot = fma((double)v[i], (double)cv[i], dot);
+        }
+        dot = h8_wave_sum(dot);
+        const float2 ab = a.list_ab[l];
+        const double al = (double)ab.x, be = (double)ab.y;
+        const double cq = (al + be * e + 3.1 * u24 * be * hq + u24 * (4.1 + 2.02 * be)) * (1.0 + 1e-5);
+        const bool ok = nqn > 0.0 && nqn < 1e30 && be <= (double)a.lim && cq <= 1.0 && fabs(dot) < 1e30; // (NaN: false)
+        const float cp = ok ? (float)cq * (1.f + 1e-6f) : __uint_as_float(0x7f800000u);
+        if (lane == (p & 63))
+        {
+            a.pinfo[qp] = make_float2(sq, (float)dot); // (qc_p gets its offset below)
+            a.pc[qp] = cp;
+        }
+        best = fminf(best, cp);
+        worst = fmaxf(worst, cp);
+    }
+    const bool fine = worst < 3.0e38f; // (a pair outside the model: the whole query goes to the fallback)
+    // X Q with X = sqrt(xmax) (xmax: the largest f32 row norm, within 1e-3 of the real one) and Q = |q|, both rounded up
+    const double xq = sqrt((double)a.xmax * 1.001) * nqn * (1.0 + 1e-6);
+    if (lane == 0)
+    {
+        a.qbound[q] = fine ? best : __uint_as_float(0x7f800000u);
+        // (no pair with rows: best = +inf, no key exists to be offset -- 0, not inf - inf)
+        a.qoff[q] = fine && best < 3.0e38f ? (float)(((double)worst - (double)best) * xq * (1.0 + 2e-3)) : 0.f;
+    }
+    for (uint32_t p = lane; p < nprobe; p += 64)
+    {
+        const uint32_t qp = q * nprobe + p;
+        const int32_t l = a.probes[qp];
+        if (l < 0 || !(a.whole_off[l + 1] > a.whole_off[l]))
+            continue;
+        const double off = fine ? ((double)a.pc[qp] - (double)best) * xq * (1.0 + 1e-3) : 0.0;
+        a.pinfo[qp].y = (float)((double)a.pinfo[qp].y + off); // fl(fl<q, c> + off): two roundings of <q, c> (set_error_model_i8r)
+    }
+}
+
 /// Queries -> fp16 image + per-query constants; one wavefront per query.
 /// qnorm[q] = |q|^2: taken as given, or (compute_norm) computed here with row_sqnorm16_kernel's arithmetic -- 16 lanes,
 /// fma chains, the DPP row tree -- so one launch serves where there were three (norms, a copy of them, this).  It is
@@ -871,7 +1053,7 @@ __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned c
                                            const uint32_t blk0, const uint32_t stride, const uint32_t nblk,
                                            const int64_t lbeg, const int64_t lend, const uint32_t tile_queries = 0xFFFFFFFFu)
 {
-    static_assert(!I8 || (NRB == 1 && METRIC == M_L2), "i8r: L2 list scan only");
+    static_assert(!I8 || NRB == 1, "i8r: one row block per wavefront");
     if (blk0 >= nblk)
         return;
     // (uniform: see flush.  Not in the two-row-block form -- exhaustive batches, tiles of 64+ queries: the extra code cost the kernel
@@ -1162,8 +1344,17 @@ __device__ __forceinline__ void h16_stream(const H16Params & a, const unsigned c
                     {
                         // fl(acc_hi + acc_lo / 256), fl(-2 s_q s_x): the roundings set_error_model_i8r counts
                         const float accf = fmaf((float)acl[cb][4 * g4 + e], 0.00390625f, (float)ach[cb][4 * g4 + e]);
-                        v = __fadd_rn(fmaf(__fmul_rn(m2v[e], xs[rb]), accf, xq), qnv[e]);
-                        pass = v < __uint_as_float(cutv[e]);
+                        if (METRIC == M_L2)
+                        {
+                            v = __fadd_rn(fmaf(__fmul_rn(m2v[e], xs[rb]), accf, xq), qnv[e]);
+                            pass = v < __uint_as_float(cutv[e]);
+                        }
+                        else
+                        {
+                            // inner product / cosine: fl(fma(fl(s_q s_x), accf, qc_p)), the fp16 form's sign and word
+                            v = fmaf(__fmul_rn(m2v[e], xs[rb]), accf, qnv[e]);
+                            pass = v > -3.402823466e+38f && ~f2ord(v) < cutv[e];
+                        }
                     }
                     else if (METRIC == M_L2)
                     {
@@ -1319,7 +1510,8 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
                     const uint32_t pp = p0 + u * 64 * NW;
                     const uint32_t p = pp < npieces ? pp : npieces - 1;
                     const uint32_t slot = p & 7, qi = (p >> 3) % tq_e, c = (p >> 3) / tq_e;
-                    v[u] = a.Qh[((size_t)(I8 ? pimg_s[qi] : qrow_s[qi]) * tnch + c) * 8 + (slot ^ ((qi >> 1) & 7))];
+                    // (i8r: the image of the PAIR under L2, of the QUERY under inner product and cosine)
+                    v[u] = a.Qh[((size_t)(I8 && METRIC == M_L2 ? pimg_s[qi] : qrow_s[qi]) * tnch + c) * 8 + (slot ^ ((qi >> 1) & 7))];
                     at[u] = ((c * TQ + qi) * 8 + slot) * 16;
                 }
 #pragma unroll
@@ -1366,12 +1558,12 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
 /// NQB = 2 (not instantiated any more): an item is TWO column blocks (64 probing queries; the plan is built with T = 64), every
 /// row fragment feeds two MFMAs, a quarter less operand traffic -- measured SLOWER (80 against 73 us per 4096-query step: 240
 /// VGPRs, and half of the second blocks are empty).  A short second block repeats the item's last pair and stores nothing.
-/// I8 (i8r shadow, NQB = 1, L2): the A operands are the pairs' hi / lo images, two exact i32 products per row fragment, the scan's
+/// I8 (i8r shadow, NQB = 1): the A operands are the hi / lo images of the pairs (L2) or of the queries (inner product, cosine), two exact i32 products per row fragment, the scan's
 /// epilogue arithmetic.
 template <int METRIC, int NQB, bool I8 = false>
 __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
 {
-    static_assert(!I8 || (NQB == 1 && METRIC == M_L2), "i8r: one column block, L2");
+    static_assert(!I8 || NQB == 1, "i8r: one column block");
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r32 = lane & 31, h = lane >> 5;
     const uint32_t nch = a.nch, total = a.work_off[a.nlist];
     for (uint32_t w = blockIdx.x * 4 + wave; w < total; w += gridDim.x * 4)
@@ -1401,7 +1593,7 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
             qp[b] = a.pairs[pb + (slot < nvalid ? slot : nvalid - 1)];
             const uint32_t q = qp[b] / a.nprobe;
             qi[b] = I8 ? h8_pair_info(a.pinfo, a.pc, a.qmm, a.qxq, qp[b], q) : a.qinfo[q];
-            ap[b] = reinterpret_cast<const u32x4 *>(a.Qh) + (size_t)(I8 ? qp[b] : q) * (I8 ? 2 * nch : nch) * 8 + h;
+            ap[b] = reinterpret_cast<const u32x4 *>(a.Qh) + (size_t)(I8 && METRIC == M_L2 ? qp[b] : q) * (I8 ? 2 * nch : nch) * 8 + h;
         }
         const u32x4 * const bp = reinterpret_cast<const u32x4 *>(a.H) + (size_t)a.hoff[l] * nch * 256 + lane;
         const int64_t row = lbeg + r32;
@@ -1485,7 +1677,8 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
                 const int qidx = (i & 3) + 8 * (i >> 2) + 4 * (int)h; // lanes qidx and qidx + 32 hold the same query
                 const float m2 = __shfl(qi[b].x, qidx), qn = __shfl(qi[b].y, qidx);
                 const uint32_t pair = (uint32_t)__shfl((int)qp[b], qidx);
-                const float v = I8 ? __fadd_rn(fmaf(__fmul_rn(m2, xs), fmaf((float)acl[i], 0.00390625f, (float)ach[i]), xn), qn)
+                const float v = I8 && METRIC != M_L2 ? fmaf(__fmul_rn(m2, xs), fmaf((float)acl[i], 0.00390625f, (float)ach[i]), qn)
+                    : I8 ? __fadd_rn(fmaf(__fmul_rn(m2, xs), fmaf((float)acl[i], 0.00390625f, (float)ach[i]), xn), qn)
                     : METRIC == M_L2 ? __fadd_rn(fmaf(m2, acc[b][i], xn), qn) : __fmul_rn(m2, acc[b][i]);
                 const uint64_t key = ok ? make_key<METRIC>(v, (uint32_t)row) : KEY_NONE;
                 if (32u * b + (uint32_t)qidx < nvalid)
@@ -1830,7 +2023,8 @@ __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t *
                 const double eps_x = (cd_x() + pr.c_canon) * sx * sq + 1e-30, eps_c = (cdc + pr.c_canon + 4e-7) * sc * sq + 1e-30;
                 const double ipk = (double)ord2f(~uw), ipc = cval;
                 const double ub = ipc + 2.0 * eps_c + sq * (double)pr.radius[l] * (1.0 + 1e-6);
-                keep = !(ub < ipk - 2.0 * eps_x);
+                // (i8r: the keys of a query's other lists are raised -- a sample word bounds from below only after twice the largest offset)
+                keep = !(ub < ipk - 2.0 * eps_x - (pr.qoff ? 2.0 * (double)pr.qoff[q] : 0.0));
             }
             else
             {
@@ -1847,7 +2041,7 @@ __device__ inline void h16_sample_thr_wave(const uint32_t * src, const int32_t *
                     if (dc > r)
                     {
                         const double ub = 0.5 * (((double)qn + (double)pr.xmax) * (1.0 + pr.c_norm) - (dc - r) * (dc - r) * (1.0 - 1e-7));
-                        keep = !(ub < ipk - 2.0 * eps_x);
+                        keep = !(ub < ipk - 2.0 * eps_x - (pr.qoff ? 2.0 * (double)pr.qoff[q] : 0.0));
                     }
                 }
             }

@@ -43,15 +43,21 @@ static float measure_shadow_rho(const float * rows, size_t n, uint32_t ld, float
 /// the int8 rounding; on iid rows the residual is as long as the row (~15x looser than fp16), and a list that k-means left
 /// straddling two clusters has long residuals too -- queries there would lose their certificate.  Every list's beta must stay
 /// inside the error model's range.  True: ix.shadow holds the i8r blocks.
+/// Inner-product and cosine indexes (cosine: the residual of the normalised stored row) take the form only when asked with the
+/// values that name every metric: 4 (i8r whatever the metric; L2: the same as 3) and 5 (auto over every metric; L2: the rule of 1).
+/// Their bound is C_p ~ alpha_l + beta_l e (set_error_model_i8r: no factor rho, e ~ 1e-5 of a query image), so the auto rule reads
+/// alpha_l alone: every beta_l in range and at least 97 % of the rows in lists with alpha_l <= 3 c16.  3 and 1 keep them fp16.
 static bool index_build_shadow_i8r(msvs_index & ix, int form, float rho, size_t nblocks, hipStream_t stream)
 {
     ix.h8 = false;
     ix.h8_side.release();
     ix.h8_list.release();
-    if (form != 1 && form != 3)
+    if (form != 1 && form != 3 && form != 4 && form != 5)
         return false;
-    if (ix.metric != MSVS_METRIC_L2 || !ix.centroids.p || !(rho >= 0.f))
+    const bool l2 = ix.metric == MSVS_METRIC_L2;
+    if ((!l2 && form != 4 && form != 5) || !ix.centroids.p || !(rho >= 0.f))
         return false;
+    const bool automatic = form == 1 || form == 5;
     const uint32_t nch8 = (uint32_t)ceil_div(ix.dim, (size_t)H8_CHUNK);
     const size_t npieces = nblocks * (size_t)nch8 * 4 * 64;
     DevBuf<uint4> H(npieces + 32768);
@@ -70,10 +76,10 @@ static bool index_build_shadow_i8r(msvs_index & ix, int form, float rho, size_t 
     for (size_t l = 0; l < ix.nlist; l++)
     {
         in_range = in_range && h_lab[l].y <= i8r_limit(ix.dim); // (NaN: out of range)
-        if ((double)h_lab[l].x * (double)h_lab[l].y <= 3.0 * c16)
+        if ((double)h_lab[l].x * (l2 ? (double)h_lab[l].y : 1.0) <= 3.0 * c16)
             good += (size_t)(ix.h_list_off[l + 1] - ix.h_list_off[l]);
     }
-    if (form == 1 && !(in_range && (double)good >= 0.97 * (double)ix.n))
+    if (automatic && !(in_range && (double)good >= 0.97 * (double)ix.n))
         return false;
     ix.shadow = std::move(H);
     ix.h8_side = std::move(side);

@@ -62,7 +62,8 @@ struct msvs_index
     float cnorm_max = 0.f;
     DevBuf<int64_t> list_mid; // nlist: end of the SAMPLE slice of list l = min(list_off[l] + 128, list_off[l+1])
     // fp16 shadow of the lists (h16_scan_kernels.hpp): the list scan of batched searches reads this instead of vecs
-    int want_shadow = 1;        // build parameter `shadow`: 0 none, 1 auto, 2 fp16, 3 int8 residual (L2 IVFFLAT; others: fp16)
+    int want_shadow = 1;        // build parameter `shadow`: 0 none, 1 auto (L2), 2 fp16, 3 int8 residual (L2 IVFFLAT; others: fp16), 4 int8 residual (every
+                                // metric of IVFFLAT), 5 auto over every metric
     DevBuf<uint4> shadow;       // blocks of 32 rows in MFMA operand order
     DevBuf<uint32_t> hoff;      // nlist + 1: first block of list l
     DevBuf<int64_t> list_mid32; // nlist: end of block 0 of list l = min(list_off[l] + 32, list_off[l+1])

@@ -253,8 +253,10 @@ struct IvfSearchPlan
 
 /// 128-byte chunks of a query's image in the list scan's LDS tile: the fp16 image, or the hi and lo images of an i8r pair.
 static uint32_t h16_tile_nch(const msvs_index & ix) { return ix.h8 ? 2 * ix.h8_nch : ix.h_nch; }
-/// Scratch bytes of one (query, probe) pair of a list scan over the i8r shadow: its two images and its constants.
-static size_t i8r_pair_bytes(const msvs_index & ix) { return (size_t)ix.h8_nch * 256 + 12; }
+/// Scratch bytes of one (query, probe) pair of a list scan over the i8r shadow: its constants and, under L2, its two images ...
+static size_t i8r_pair_bytes(const msvs_index & ix) { return (ix.metric == MSVS_METRIC_L2 ? (size_t)ix.h8_nch * 256 : 0) + 12; }
+/// ... and of one query: under inner product and cosine the two images belong to the query (h8_ip_prep_kernel).
+static size_t i8r_query_bytes(const msvs_index & ix) { return ix.metric == MSVS_METRIC_L2 ? 0 : (size_t)ix.h8_nch * 256; }
 
 static IvfSearchPlan plan_ivf(const msvs_index & ix, size_t nq, size_t nprobe, uint32_t k, bool allow_pass = true)
 {
@@ -420,7 +422,7 @@ static size_t index_search_scratch(const msvs_index & ix, size_t nq, uint32_t k,
             + nq * (size_t)p.kc * 8 + nq * 32 + 8192
             + fallback_cap(nq, nprobe, p.seg_max1, k) * nprobe * (size_t)p.seg_max1 * k * 8
             + (p.h16 ? nq * ((size_t)ix.h_nch * 128 + 8 + 4 + 4) + 2048 + nq * nprobe * H_ROWS * 4 + 4 * ix.nlist + 4096 : 0)
-            + (p.h16 && ix.h8 ? nq * nprobe * i8r_pair_bytes(ix) + nq * 8 + 2048 + nq * 16 + 512 : 0); // i8r: the pairs' images, constants, the bound;
+            + (p.h16 && ix.h8 ? nq * nprobe * i8r_pair_bytes(ix) + nq * i8r_query_bytes(ix) + nq * 8 + 2048 + nq * 16 + 512 : 0); // i8r: the pairs' images, constants, the bound;
                                                                                               // the per-query min / max words (counters) and X Q of h8_pairs_wave_kernel
     else
         need += nq * nprobe * (size_t)p.seg_max * k * 8;
@@ -1114,6 +1116,27 @@ static void set_error_model_h16(RerankParams & rp, size_t dim, float rho_table, 
 /// key - eps(qbound) <= D for every row of every pair -- the lower bound the re-rank certificate and its early exit, the second chance,
 /// the cut and the fallback rest on.  The one consumer that reads a sample key as an UPPER bound, the second pruning stage, widens
 /// it by twice the query's largest lowering (H16Prune::qoff); the returned ids and distances are the canonical ones.
+///
+/// INNER PRODUCT and COSINE (cosine: rows and queries normalised).  The rows are the same residuals; the query side
+/// is q ITSELF as s_q (hi + lo / 256) =: q~ with E_q = |q - q~| (h8_ip_prep_kernel, exact differences in double), and
+///   P = <q, x> = <q, c_l> + <q, r_x>,   I = s_x s_q (acc_hi + acc_lo / 256) = <q~, r~_x> (exact integer sums):
+///   |I - <q, r_x>| = |<q~ - q, r~_x> + <q, r~_x - r_x>| <= E_q (|r_x| + E_x) + |q| E_x <= (beta_l e + alpha_l) |x||q|,  e = E_q / |q|.
+/// The scan's v = fl(fma(fl(s_q s_x), accf, qc_p)), accf = fl(fl(acc_lo) / 256 + fl(acc_hi)), qc_p = fl(fl(<q, c_l>) + off_p), adds:
+///   the conversions and the combine: |accf - (acc_hi + acc_lo / 256)| <= 2.01 u (|acc_hi| + |acc_lo| / 256) (an i32 sum of d products
+///     of int8 can exceed 2^24: each conversion rounds once, the fma once more); the scale product one more u: together
+///     <= 3.02 u s_x s_q (|acc_hi| + |acc_lo| / 256) <= 3.02 u |r~_x| H_q <= 3.02 u beta_l h |x||q| (Cauchy-Schwarz as above, h = H_q / |q|);
+///   <q, c_l>: summed in double (d 2^-53 |q||c_l|: inside the margins), rounded to f32 once and once more with the offset:
+///     <= 2.01 u |c_l||q|, and |c_l| <= |x| + |r_x| <= (1 + beta_l) |x| for every row of the list -- no further per-list quantity;
+///   the fma's own rounding: u |v| <= u (|P| + C_p |x||q| + off_p) <= 2 u |x||q| + u off_p as long as C_p <= 1 (beyond: +inf).
+///   C_p = alpha_l + beta_l e + 3.1 u beta_l h + u (4.1 + 2.02 beta_l)  -- the leading terms measured, no rho: the bound does not shrink
+/// with the query's distance from the centroid, and eps = (c_dot(q) + c_canon) |x||q| is the consumers' inner-product form as it stands.
+/// beta_l <= i8r_limit(d) as for L2 (the rounding terms stay ~1e-6); a zero or non-finite query: +inf.
+/// One coefficient per query again: c_dot(q) = qbound[q] = min over its pairs of C_p, and the key of every other pair is RAISED by
+/// off_p = 1.001 (C_p - qbound[q]) X Q >= (C_p - qbound[q]) |x||q| + the roundings of off_p itself (u off_p twice, above):
+/// key + eps(qbound) >= P for every row of every pair -- under inner product the certificate, its early exit, the second chance and
+/// the cut reject a row only on key + eps < something, so the one-sided bound is what they rest on.  The second pruning stage reads
+/// the k-th sample key as a LOWER bound of a product: it takes off twice the query's largest raising (H16Prune::qoff).
+/// The constants the consumers read are the same for both metrics: c_dot comes per query, c_norm is not used under inner product.
 static void set_error_model_i8r(RerankParams & rp, size_t dim, const float * qbound)
 {
     const double scale = 1.05 * options().ivf_eps_scale;
@@ -1168,15 +1191,16 @@ static void h16_dispatch(uint32_t ncb, uint32_t grid, size_t lds, const H16Param
     }
 }
 
-/// The list scan over the int8 residual shadow (L2 only).
+/// The list scan over the int8 residual shadow (M_IP: inner-product and cosine indexes, query images).
+template <int METRIC>
 static void h8_dispatch(uint32_t ncb, uint32_t grid, size_t lds, const H16Params & a, hipStream_t stream)
 {
     switch (ncb)
     {
-        case 1: h16_launch<M_L2, 1, true>(grid, lds, a, stream); break;
-        case 2: h16_launch<M_L2, 2, true>(grid, lds, a, stream); break;
-        case 3: h16_launch<M_L2, 3, true>(grid, lds, a, stream); break;
-        default: h16_launch<M_L2, 4, true>(grid, lds, a, stream); break;
+        case 1: h16_launch<METRIC, 1, true>(grid, lds, a, stream); break;
+        case 2: h16_launch<METRIC, 2, true>(grid, lds, a, stream); break;
+        case 3: h16_launch<METRIC, 3, true>(grid, lds, a, stream); break;
+        default: h16_launch<METRIC, 4, true>(grid, lds, a, stream); break;
     }
 }
 
@@ -1266,7 +1290,7 @@ constexpr size_t H8_PAIRS_WAVE_MIN = 8192;
 static size_t h8_query_words(const msvs_index & ix, size_t nq, size_t nprobe)
 {
     const bool wave = options().h8_pairs == 2 || (options().h8_pairs != 0 && nq * nprobe > H8_PAIRS_WAVE_MIN);
-    return ix.h8 && wave ? 2 * nq : 0;
+    return ix.h8 && ix.metric == MSVS_METRIC_L2 && wave ? 2 * nq : 0; // (inner product, cosine: h8_ip_prep_kernel needs no words)
 }
 
 /// List scan of a batch over the fp16 shadow: sample launch -> cut -> main launch -> candidate select -> canonical
@@ -1397,13 +1421,35 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     H8Finish fin{};
     if (ix.h8)
     {
-        pimg = scr.take<uint4>(nq * nprobe * (size_t)ix.h8_nch * 16 + 64);
+        const bool per_query = ix.metric != MSVS_METRIC_L2; // inner product, cosine: one image per query, one constant per pair
+        pimg = scr.take<uint4>((per_query ? nq : nq * nprobe) * (size_t)ix.h8_nch * 16 + 64);
         pinfo = scr.take<float2>(nq * nprobe);
         qbound = scr.take<float>(nq);
         qoff = scr.take<float>(nq);
         float * pc = scr.take<float>(nq * nprobe);
         ProfileScope prof("ivf_prep_pairs", stream);
-        if (n_qmm)
+        if (per_query)
+        {
+            H8IpParams hp{};
+            hp.Q = dq; // (cosine: normalised by the caller)
+            hp.cents = ix.centroids.p;
+            hp.probes = plan_probes;
+            hp.whole_off = pp.whole_off;
+            hp.list_ab = ix.h8_list.p;
+            hp.nq = (uint32_t)nq;
+            hp.ld = ld;
+            hp.nprobe = (uint32_t)nprobe;
+            hp.nch8 = ix.h8_nch;
+            hp.lim = i8r_limit(ix.dim);
+            hp.xmax = ix.xnorm_max;
+            hp.img = pimg;
+            hp.pinfo = pinfo;
+            hp.pc = pc;
+            hp.qbound = qbound;
+            hp.qoff = qoff;
+            hipLaunchKernelGGL(h8_ip_prep_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, hp);
+        }
+        else if (n_qmm)
         {
             // one wavefront per pair of the plan; the cut kernel below finishes qbound / qoff (H8Finish)
             H8PairsParams hp{};
@@ -1477,7 +1523,9 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         ProfileScope prof("ivf_sample_scan", stream);
         a.work_off = pa.work_off;
         const uint32_t sgrid = device_cu_count() * 8; // one wavefront per (list, 32-query column block), grid-stride
-        if (ix.h8)
+        if (ix.h8 && scan_metric(m) == M_IP)
+            hipLaunchKernelGGL((h16_sample_kernel<M_IP, 1, true>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
+        else if (ix.h8)
             hipLaunchKernelGGL((h16_sample_kernel<M_L2, 1, true>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
         else if (scan_metric(m) == M_IP)
             hipLaunchKernelGGL((h16_sample_kernel<M_IP, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
@@ -1577,8 +1625,10 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
                 a.stamps = g_h16_stamps.p;
                 g_h16_stamp_grid = grid;
             }
-            if (ix.h8)
-                h8_dispatch(pl.h_ncb, grid, lds, a, stream);
+            if (ix.h8 && scan_metric(m) == M_IP)
+                h8_dispatch<M_IP>(pl.h_ncb, grid, lds, a, stream);
+            else if (ix.h8)
+                h8_dispatch<M_L2>(pl.h_ncb, grid, lds, a, stream);
             else if (scan_metric(m) == M_IP)
                 h16_dispatch<M_IP>(pl.h_ncb, grid, lds, a, stream);
             else
@@ -1707,7 +1757,9 @@ void index_search_device(const msvs_index & ix, const float * d_queries /* nq x 
 {
     const size_t np_eff = ix.type == MSVS_INDEX_IVFFLAT ? std::max<size_t>(1, std::min(nprobe, std::max<size_t>(ix.nlist, 1))) : 1;
     // (an i8r index keeps the images of a sub-batch's pairs: at most ~384 MB of them)
-    const size_t max_pairs = ix.h8 ? std::min<size_t>((size_t)1 << 21, ((size_t)384 << 20) / i8r_pair_bytes(ix)) : (size_t)1 << 21;
+    // (under inner product and cosine the images are per query: a query costs its images and np_eff pairs' constants)
+    const size_t max_pairs = ix.h8 ? std::min<size_t>((size_t)1 << 21, ((size_t)384 << 20) * np_eff / (np_eff * i8r_pair_bytes(ix) + i8r_query_bytes(ix)))
+                                   : (size_t)1 << 21;
     const size_t sub = std::max<size_t>(256, max_pairs / np_eff);
     if (nq <= sub)
         return index_search_device_one(ix, d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, given_probes,
