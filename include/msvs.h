@@ -112,6 +112,32 @@ struct msvs_io;
 MSVS_API int msvs_bin_index_serialize_io(const msvs_bin_index_t * index, const struct msvs_io * io);
 MSVS_API int msvs_bin_index_load_io(const struct msvs_io * io, msvs_bin_index_t ** out);
 
+/* The PARTITIONED form of the binary index (the partition scan of BinaryMSTG): ncentroids bit vectors (k-majority centroids) and
+ * the rows grouped by list, searched by probing the nprobe nearest lists.  Integer popcounts throughout:
+ *   - the coarse distance is Hamming for both index metrics; a row belongs to the list with the smallest (distance, list id);
+ *     inside a list the rows are in ascending label order;
+ *   - a query probes the first min(nprobe, ncentroids) lists by (Hamming distance to the centroid, list id); the result is the
+ *     first k alive rows of those lists by (metric distance, label), unfilled slots id -1 / FLT_MAX;  k <= MSVS_MAX_K.
+ * create_ivf: params "ncentroids=N[,niter=I]" (defaults 1024, 10; parsed like msvs_index_create's).  The index is NOT READY
+ * (add and search return MSVS_ERR_NOT_READY) until it has centroids from train, set_centroids or a loaded file.
+ * train: seeds = ncentroids rows at evenly spaced positions (no RNG), then niter rounds of exact assignment + per-bit majority vote
+ * (a bit is set iff 2 * ones > members; an empty list keeps its centroid); deterministic; n < ncentroids -> MSVS_ERR_INVALID_ARGUMENT.
+ * set_centroids: nlist must equal ncentroids.  num_lists: 0 for a flat index.
+ * search_params: params "nprobe=P" (NULL / "": 1, the float IVFFLAT default); msvs_bin_index_search on a partitioned index is
+ * search_params with the default; on a flat index nprobe is ignored.
+ * export: list-major (centroids ncentroids * nbytes, ncentroids + 1 offsets, rows, labels) like msvs_index_export; NULL outputs
+ * are skipped.
+ * Files: a flat index writes version 1 exactly as before; a partitioned one writes version 2 (ncentroids in the header's reserved
+ * words, the centroids after the rows); rows and labels stay in insertion order, the lists are rebuilt from the centroids. */
+MSVS_API int msvs_bin_index_create_ivf(size_t nbytes, int metric, const char * params, msvs_bin_index_t ** out);
+MSVS_API int msvs_bin_index_train(msvs_bin_index_t * index, const uint8_t * rows, size_t n);
+MSVS_API int msvs_bin_index_set_centroids(msvs_bin_index_t * index, const uint8_t * centroids, size_t nlist);
+MSVS_API size_t msvs_bin_index_num_lists(const msvs_bin_index_t * index);
+MSVS_API int msvs_bin_index_search_params(const msvs_bin_index_t * index, const uint8_t * x, size_t nx, size_t k, const char * params,
+                                          const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_bin_index_export(const msvs_bin_index_t * index, uint8_t * centroids, int64_t * list_off, uint8_t * rows,
+                                   int64_t * labels);
+
 /* Resident blocks for the brute-force path: the GPU analogue of VICacheManager / VIWithMeta
  * (src/VectorIndex/Cache/VICacheObject.h:40-162) for the dense block a mark of a part turns into
  * (MergeTreeVSManager.cpp:1380-1392).  msvs_knn_f32 moves that block over PCIe on every query; here it is uploaded

@@ -34,6 +34,8 @@ SYMBOLS = [
     "msvs_index_load_io", "msvs_index_version", "msvs_index_resource_usage", "msvs_knn_bin",
     "msvs_cache_create", "msvs_cache_free", "msvs_block_upload", "msvs_block_lookup", "msvs_block_release", "msvs_block_info", "msvs_bin_index_create", "msvs_bin_index_free",
     "msvs_bin_index_add", "msvs_bin_index_num_data", "msvs_bin_index_search", "msvs_bin_index_serialize_io", "msvs_bin_index_load_io",
+    "msvs_bin_index_create_ivf", "msvs_bin_index_train", "msvs_bin_index_set_centroids", "msvs_bin_index_num_lists",
+    "msvs_bin_index_search_params", "msvs_bin_index_export",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
     "msvs_comm_free", "msvs_comm_all_reduce_u64", "msvs_comm_rank", "msvs_comm_size", "msvs_shard_search_device", "msvs_shard_search_device_async", "msvs_shard_search_drain", "msvs_shard_search_routed_device",
@@ -187,12 +189,26 @@ def knn_bin(x, y, k, metric, alive=None):
 
 
 class BinIndex:
-    """msvs_bin_index_t: BinaryFLAT over rows resident on the device (labels = ids given at add, filter indexed by label)."""
+    """msvs_bin_index_t: BinaryFLAT over rows resident on the device (labels = ids given at add, filter indexed by label);
+    with params ("ncentroids=N[,niter=I]") the partitioned form: centroids + list-major rows, searched by probing."""
 
-    def __init__(self, nbytes, metric):
+    def __init__(self, nbytes, metric, params=None, _handle=None):
         self._h = C.c_void_p()
         self.nbytes = int(nbytes)
-        _check(lib().msvs_bin_index_create(C.c_size_t(nbytes), int(metric), C.byref(self._h)))
+        if _handle is not None:
+            self._h = _handle
+        elif params is None:
+            _check(lib().msvs_bin_index_create(C.c_size_t(nbytes), int(metric), C.byref(self._h)))
+        else:
+            _check(lib().msvs_bin_index_create_ivf(C.c_size_t(nbytes), int(metric), params.encode(), C.byref(self._h)))
+
+    def train(self, rows):
+        rows = np.ascontiguousarray(rows, np.uint8).reshape(-1, self.nbytes)
+        _check(lib().msvs_bin_index_train(self._h, _p(rows, C.c_uint8), C.c_size_t(rows.shape[0])))
+
+    def set_centroids(self, centroids):
+        c = np.ascontiguousarray(centroids, np.uint8).reshape(-1, self.nbytes)
+        _check(lib().msvs_bin_index_set_centroids(self._h, _p(c, C.c_uint8), C.c_size_t(c.shape[0])))
 
     def add(self, rows, ids=None):
         rows = np.ascontiguousarray(rows, np.uint8).reshape(-1, self.nbytes)
@@ -207,14 +223,47 @@ class BinIndex:
         lib().msvs_bin_index_num_data.restype = C.c_size_t
         return lib().msvs_bin_index_num_data(self._h)
 
-    def search(self, x, k, alive=None):
+    @property
+    def num_lists(self):
+        """0 for a flat index."""
+        lib().msvs_bin_index_num_lists.restype = C.c_size_t
+        return lib().msvs_bin_index_num_lists(self._h)
+
+    def search(self, x, k, alive=None, params=None, nbits=None):
+        """params: "nprobe=P" (partitioned index; None = msvs_bin_index_search); alive: bool over labels, nbits: how many of
+        them the filter covers (default all of `alive`): labels at or beyond nbits are dead."""
         x = np.ascontiguousarray(x, np.uint8).reshape(-1, self.nbytes)
         ids = np.empty((x.shape[0], k), np.int64)
         dis = np.empty((x.shape[0], k), np.float32)
         bits = None if alive is None else pack_bits(alive)
-        _check(lib().msvs_bin_index_search(self._h, _p(x, C.c_uint8), C.c_size_t(x.shape[0]), C.c_size_t(k), _p(bits, C.c_uint64),
-                                           C.c_size_t(0 if alive is None else len(alive)), _p(ids, C.c_int64), _p(dis, C.c_float)))
+        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
+        if params is None:
+            _check(lib().msvs_bin_index_search(self._h, _p(x, C.c_uint8), C.c_size_t(x.shape[0]), C.c_size_t(k), _p(bits, C.c_uint64),
+                                               nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        else:
+            _check(lib().msvs_bin_index_search_params(self._h, _p(x, C.c_uint8), C.c_size_t(x.shape[0]), C.c_size_t(k), params.encode(),
+                                                      _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
         return ids, dis
+
+    def export(self):
+        """Partitioned index -> (centroids [nlist, nbytes], list offsets [nlist + 1], rows and labels in list-major order)."""
+        n, nl = self.num_data, self.num_lists
+        cent = np.empty((nl, self.nbytes), np.uint8)
+        off = np.empty(nl + 1, np.int64)
+        rows = np.empty((n, self.nbytes), np.uint8)
+        labels = np.empty(n, np.int64)
+        _check(lib().msvs_bin_index_export(self._h, _p(cent, C.c_uint8), _p(off, C.c_int64), _p(rows, C.c_uint8), _p(labels, C.c_int64)))
+        return cent, off, rows, labels
+
+    def serialize_io(self, store):
+        """msvs_bin_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""
+        _check(lib().msvs_bin_index_serialize_io(self._h, C.byref(_DictIO(store).io)))
+
+    @classmethod
+    def load_io(cls, store, nbytes, metric):
+        h = C.c_void_p()
+        _check(lib().msvs_bin_index_load_io(C.byref(_DictIO(store).io), C.byref(h)))
+        return cls(nbytes, metric, _handle=h)
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:

@@ -7,6 +7,7 @@
 #include <mutex>
 #include <vector>
 
+#include "bin_ivf_kernels.hpp"
 #include "bin_kernels.hpp"
 #include "device_ops.hpp"
 #include "io_stream.hpp"
@@ -44,6 +45,103 @@ static void bin_dispatch_g(uint32_t g, const BinParams & a, hipStream_t stream)
             break;
         default:
             bin_dispatch_r<METRIC, 16>(a, stream);
+            break;
+    }
+}
+
+/// lanes per row: one 16-byte word each per step
+static uint32_t bin_lanes(uint32_t ld16)
+{
+    uint32_t g = 1;
+    while (g < 16 && g * 2 <= ld16)
+        g *= 2;
+    return g;
+}
+
+constexpr uint32_t BIN_IVF_T = 8;                     // queries per tile of the list scan (4 beyond k = 64)
+constexpr size_t BIN_ASSIGN_LDS = (size_t)48 << 10;   // centroid tile of the assign kernel
+
+/// rows (or queries) against the centroids: best[n] (list of the smallest (distance, id)) and / or dist[n][nlist].
+static void launch_bin_assign(const unsigned char * dy, const unsigned char * dc, size_t n, size_t nlist, uint32_t ld16, uint32_t * best,
+                              uint32_t * dist, hipStream_t stream)
+{
+    if (n == 0 || nlist == 0)
+        return;
+    ProfileScope prof("bin_ivf_coarse", stream);
+    const uint32_t g = bin_lanes(ld16);
+    BinAssignParams a{};
+    a.Y = reinterpret_cast<const uint4 *>(dy);
+    a.C = reinterpret_cast<const uint4 *>(dc);
+    a.n = (uint32_t)n;
+    a.nlist = (uint32_t)nlist;
+    a.ld16 = ld16;
+    a.tile = (uint32_t)std::max<size_t>(1, std::min(nlist, BIN_ASSIGN_LDS / ((size_t)ld16 * 16)));
+    a.best = best;
+    a.dist = dist;
+    const dim3 grid((unsigned)ceil_div(n, (size_t)(BLOCK / g)));
+    const size_t lds = (size_t)a.tile * ld16 * 16;
+    switch (g)
+    {
+        case 1:
+            hipLaunchKernelGGL((bin_assign_kernel<1>), grid, dim3(BLOCK), lds, stream, a);
+            break;
+        case 2:
+            hipLaunchKernelGGL((bin_assign_kernel<2>), grid, dim3(BLOCK), lds, stream, a);
+            break;
+        case 4:
+            hipLaunchKernelGGL((bin_assign_kernel<4>), grid, dim3(BLOCK), lds, stream, a);
+            break;
+        case 8:
+            hipLaunchKernelGGL((bin_assign_kernel<8>), grid, dim3(BLOCK), lds, stream, a);
+            break;
+        default:
+            hipLaunchKernelGGL((bin_assign_kernel<16>), grid, dim3(BLOCK), lds, stream, a);
+            break;
+    }
+    MSVS_HIP(hipGetLastError());
+}
+
+template <int METRIC, int G>
+static void bin_ivf_dispatch_r(uint32_t grid, const BinIvfParams & a, hipStream_t stream)
+{
+    const bool reg = a.ld16 == (uint32_t)G;
+    if (a.k <= 64)
+    {
+        const size_t lds = (size_t)BIN_IVF_T * a.ld16 * 16 + (size_t)5 * a.k * 8;
+        if (reg)
+            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T, 1, true>), dim3(grid), dim3(BLOCK), lds, stream, a);
+        else
+            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T, 1, false>), dim3(grid), dim3(BLOCK), lds, stream, a);
+    }
+    else
+    {
+        const size_t lds = (size_t)(BIN_IVF_T / 2) * a.ld16 * 16 + (size_t)5 * a.k * 8;
+        if (reg)
+            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T / 2, 4, true>), dim3(grid), dim3(BLOCK), lds, stream, a);
+        else
+            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T / 2, 4, false>), dim3(grid), dim3(BLOCK), lds, stream, a);
+    }
+}
+
+template <int METRIC>
+static void bin_ivf_dispatch_g(uint32_t g, uint32_t grid, const BinIvfParams & a, hipStream_t stream)
+{
+    switch (g)
+    {
+        case 1:
+            bin_ivf_dispatch_r<METRIC, 1>(grid, a, stream);
+            break;
+        case 2:
+            bin_ivf_dispatch_r<METRIC, 2>(grid, a, stream);
+            break;
+        case 4:
+            bin_ivf_dispatch_r<METRIC, 4>(grid, a, stream);
+            break;
+        case 8:
+            bin_ivf_dispatch_r<METRIC, 8>(grid, a, stream);
+            break;
+        default:
+            bin_ivf_dispatch_r<METRIC, 16>(grid, a, stream);
             break;
     }
 }
@@ -159,20 +257,222 @@ struct msvs_bin_index
 {
     size_t nbytes = 0;
     int metric = MSVS_METRIC_HAMMING;
-    std::vector<uint8_t> rows;   // host copy: n x nbytes (the serialised form)
+    std::vector<uint8_t> rows;   // host copy: n x nbytes (the serialised form), insertion order
     std::vector<int64_t> labels; // n
+    // the partitioned form (msvs_bin_index_create_ivf): ncentroids > 0; the centroids come from train / set_centroids / load
+    size_t ncentroids = 0;          // 0: the flat index
+    int niter = 10;                 // rounds of majority Lloyd in train
+    std::vector<uint8_t> centroids; // ncentroids x nbytes, empty until the index is ready
     mutable std::mutex mu;
     /// The rows as a search reads them, on ONE device: n x round_up(nbytes, 16) + labels, uploaded at the first search (on that
     /// device) after an add.  Searches hold the image through a shared_ptr while they scan: an add that comes in meanwhile
     /// replaces the map entry, the buffers go when the last scan that uses them is done.
+    /// Partitioned: the rows are LIST-MAJOR (list = smallest (Hamming distance to the centroid, list id), assigned on the device;
+    /// ascending label inside a list), rebuilt from the centroids here -- the host copy and the files stay in insertion order.
     struct Image
     {
         DevBuf<unsigned char> rows;
         DevBuf<uint32_t> labels;
         size_t n = 0;
+        DevBuf<unsigned char> cent;  // nlist x round_up(nbytes, 16)
+        DevBuf<int64_t> list_off;    // nlist + 1
+        std::vector<int64_t> h_off;  // the same on the host
+        std::vector<uint32_t> perm;  // storage position -> insertion position
+        size_t nlist = 0, max_len = 0;
     };
     mutable std::map<int, std::shared_ptr<Image>> images; // by device; cleared by add
+    bool partitioned() const { return ncentroids != 0; }
+    bool ready() const { return !partitioned() || !centroids.empty(); }
 };
+
+/// n host rows of nbytes -> n device rows of ldb bytes (zero padded)
+static void bin_upload_padded(unsigned char * d, const uint8_t * h, size_t n, size_t nbytes, size_t ldb, hipStream_t stream)
+{
+    if (n == 0)
+        return;
+    if (ldb != nbytes)
+        MSVS_HIP(hipMemsetAsync(d, 0, n * ldb, stream));
+    MSVS_HIP(hipMemcpy2DAsync(d, ldb, h, nbytes, nbytes, n, hipMemcpyHostToDevice, stream));
+}
+
+/// The image of the calling thread's device, built if an add (or new centroids) dropped it.
+static std::shared_ptr<msvs_bin_index::Image> bin_image(const msvs_bin_index * ix, hipStream_t stream)
+{
+    const size_t ldb = round_up(ix->nbytes, (size_t)16);
+    int dev = 0;
+    MSVS_HIP(hipGetDevice(&dev));
+    // the row count is read and the upload made under ONE lock: an add between the two would otherwise leave rows that
+    // are never searched; the image is per device (a search thread bound to another GPU gets its own copy)
+    std::lock_guard<std::mutex> lk(ix->mu);
+    auto & slot = ix->images[dev];
+    if (slot)
+        return slot;
+    const size_t n = ix->labels.size();
+    auto fresh = std::make_shared<msvs_bin_index::Image>();
+    fresh->n = n;
+    fresh->rows.alloc(std::max<size_t>(n, 1) * ldb);
+    fresh->labels.alloc(std::max<size_t>(n, 1));
+    MSVS_HIP(hipMemsetAsync(fresh->rows.p, 0, std::max<size_t>(n, 1) * ldb, stream));
+    std::vector<uint32_t> l32(std::max<size_t>(n, 1));
+    if (!ix->partitioned())
+    {
+        if (n)
+        {
+            MSVS_HIP(hipMemcpy2DAsync(fresh->rows.p, ldb, ix->rows.data(), ix->nbytes, ix->nbytes, n, hipMemcpyHostToDevice, stream));
+            for (size_t i = 0; i < n; i++)
+                l32[i] = (uint32_t)ix->labels[i];
+            MSVS_HIP(hipMemcpyAsync(fresh->labels.p, l32.data(), n * 4, hipMemcpyHostToDevice, stream));
+        }
+        MSVS_HIP(hipStreamSynchronize(stream)); // l32 is about to go
+        slot = fresh;
+        return slot;
+    }
+    if (!ix->ready())
+        fail(MSVS_ERR_NOT_READY, "the partitioned binary index has no centroids yet");
+    const size_t nlist = ix->ncentroids;
+    fresh->nlist = nlist;
+    fresh->cent.alloc(nlist * ldb);
+    fresh->list_off.alloc(nlist + 1);
+    fresh->h_off.assign(nlist + 1, 0);
+    fresh->perm.resize(n);
+    MSVS_HIP(hipMemsetAsync(fresh->cent.p, 0, nlist * ldb, stream));
+    bin_upload_padded(fresh->cent.p, ix->centroids.data(), nlist, ix->nbytes, ldb, stream);
+    if (n)
+    {
+        // exact assignment on the device over the rows in insertion order (they sit in the image's own buffer for that), ...
+        std::vector<uint32_t> list(n);
+        {
+            DevBuf<uint32_t> d_best(n);
+            MSVS_HIP(hipMemcpy2DAsync(fresh->rows.p, ldb, ix->rows.data(), ix->nbytes, ix->nbytes, n, hipMemcpyHostToDevice, stream));
+            launch_bin_assign(fresh->rows.p, fresh->cent.p, n, nlist, (uint32_t)(ldb / 16), d_best.p, nullptr, stream);
+            MSVS_HIP(hipMemcpyAsync(list.data(), d_best.p, n * 4, hipMemcpyDeviceToHost, stream));
+            MSVS_HIP(hipStreamSynchronize(stream));
+        }
+        // ... then list-major by (list, label, insertion position) on the host, and the permuted rows go up
+        std::vector<std::pair<uint64_t, uint32_t>> order(n);
+        for (size_t i = 0; i < n; i++)
+        {
+            if (list[i] >= nlist)
+                fail(MSVS_ERR_DEVICE, "internal: row %zu was assigned to list %u of %zu", i, list[i], nlist);
+            order[i] = {(uint64_t)list[i] << 32 | (uint32_t)ix->labels[i], (uint32_t)i};
+            fresh->h_off[list[i] + 1]++;
+        }
+        std::sort(order.begin(), order.end());
+        for (size_t l = 0; l < nlist; l++)
+        {
+            fresh->max_len = std::max<size_t>(fresh->max_len, (size_t)fresh->h_off[l + 1]);
+            fresh->h_off[l + 1] += fresh->h_off[l];
+        }
+        std::vector<uint8_t> lm(n * ldb, 0);
+        for (size_t i = 0; i < n; i++)
+        {
+            const uint32_t src = order[i].second;
+            fresh->perm[i] = src;
+            l32[i] = (uint32_t)ix->labels[src];
+            memcpy(lm.data() + i * ldb, ix->rows.data() + (size_t)src * ix->nbytes, ix->nbytes);
+        }
+        MSVS_HIP(hipMemcpyAsync(fresh->rows.p, lm.data(), n * ldb, hipMemcpyHostToDevice, stream));
+        MSVS_HIP(hipMemcpyAsync(fresh->labels.p, l32.data(), n * 4, hipMemcpyHostToDevice, stream));
+        MSVS_HIP(hipStreamSynchronize(stream)); // lm, l32 are about to go
+    }
+    MSVS_HIP(hipMemcpyAsync(fresh->list_off.p, fresh->h_off.data(), (nlist + 1) * 8, hipMemcpyHostToDevice, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    slot = fresh;
+    return slot;
+}
+
+/// Coarse probe, plan, list scan and merge over a partitioned image; x, alive_bits, ids, dis on the HOST.
+static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbytes, int metric, const uint8_t * x, size_t nx, size_t k,
+                                 size_t nprobe, const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis, hipStream_t stream)
+{
+    const uint32_t ld16 = (uint32_t)ceil_div(nbytes, (size_t)16);
+    const size_t ldb = (size_t)ld16 * 16;
+    const uint32_t g = bin_lanes(ld16);
+    const size_t nlist = img.nlist, P = std::min(nprobe, nlist);
+    // row segments: at most ~8 per list (the longest one), at least 2048 rows each, whole wavefront steps
+    const size_t rows_step = 4 * (64 / g);
+    const size_t want_rpb = options().bin_ivf_rpb >= 1 ? (size_t)options().bin_ivf_rpb : std::max<size_t>(2048, ceil_div(img.max_len, (size_t)8));
+    const uint32_t rpb = (uint32_t)std::min<size_t>(round_up(want_rpb, rows_step), 0x40000000u);
+    const size_t seg_max = std::max<size_t>(1, ceil_div(img.max_len, (size_t)rpb));
+    // queries per round: the partial lists of a round stay below 256 MB and its pairs in 31 bits
+    const size_t per_q = P * seg_max * k * 8 + nlist * 4 + P * 8 + ldb + k * 12;
+    const size_t chunk = std::max<size_t>(1, std::min({nx, ((size_t)256 << 20) / per_q, (size_t)0x7fffffff / (P * seg_max)}));
+    const size_t words = alive_bits ? std::max<size_t>(1, ceil_div(nbits, (size_t)64)) : 0;
+    Scratch & scr = scratch_for(stream);
+    scr.reserve(chunk * per_q + (nlist + 1) * 16 + words * 8 + 16 * 256, stream);
+    unsigned char * dq = scr.take<unsigned char>(chunk * ldb);
+    uint32_t * dist = scr.take<uint32_t>(chunk * nlist);
+    int32_t * probes = scr.take<int32_t>(chunk * P);
+    uint32_t * pairs = scr.take<uint32_t>(chunk * P);
+    uint32_t * cnt_fill = scr.take<uint32_t>(2 * nlist);
+    uint32_t * pair_off = scr.take<uint32_t>(nlist + 1);
+    uint32_t * work_off = scr.take<uint32_t>(nlist + 1);
+    uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * k);
+    int64_t * d_ids = scr.take<int64_t>(chunk * k);
+    float * d_dis = scr.take<float>(chunk * k);
+    uint64_t * d_alive = words ? scr.take<uint64_t>(words) : nullptr;
+    if (words)
+        MSVS_HIP(hipMemcpyAsync(d_alive, alive_bits, words * 8, hipMemcpyHostToDevice, stream));
+    for (size_t q0 = 0; q0 < nx; q0 += chunk)
+    {
+        const size_t nq = std::min(chunk, nx - q0);
+        bin_upload_padded(dq, x + q0 * nbytes, nq, nbytes, ldb, stream);
+        launch_bin_assign(dq, img.cent.p, nq, nlist, ld16, nullptr, dist, stream);
+        hipLaunchKernelGGL(bin_probe_select_kernel, dim3((unsigned)nq), dim3(BLOCK), 0, stream, dist, (uint32_t)nlist, (uint32_t)P, ld16 * 128u, probes);
+        MSVS_HIP(hipGetLastError());
+        MSVS_HIP(hipMemsetAsync(cnt_fill, 0, 2 * nlist * 4, stream));
+        MSVS_HIP(hipMemsetAsync(partial, 0xff, nq * P * seg_max * k * 8, stream)); // KEY_NONE: (pair, segment) slots without rows
+        IvfPlanParams pp{};
+        pp.probes = probes;
+        pp.list_off = img.list_off.p;
+        pp.n_pairs = (uint32_t)(nq * P);
+        pp.nlist = (uint32_t)nlist;
+        pp.rows_per_block = rpb;
+        pp.T = k <= 64 ? BIN_IVF_T : BIN_IVF_T / 2;
+        pp.cnt = cnt_fill;
+        pp.fill = cnt_fill + nlist;
+        pp.pair_off = pair_off;
+        pp.work_off = work_off;
+        pp.pairs = pairs;
+        launch_ivf_plan(pp, stream);
+        BinIvfParams a{};
+        a.Y = reinterpret_cast<const uint4 *>(img.rows.p);
+        a.Q = reinterpret_cast<const uint4 *>(dq);
+        a.alive = d_alive;
+        a.labels = img.labels.p;
+        a.nbits = (uint32_t)std::min<size_t>(nbits, 0xffffffffu);
+        a.ld16 = ld16;
+        a.k = (uint32_t)k;
+        a.nprobe = (uint32_t)P;
+        a.nlist = (uint32_t)nlist;
+        a.rows_per_block = rpb;
+        a.seg_max = (uint32_t)seg_max;
+        a.list_off = img.list_off.p;
+        a.pair_off = pair_off;
+        a.work_off = work_off;
+        a.pairs = pairs;
+        a.partial = partial;
+        {
+            ProfileScope prof("bin_ivf_scan", stream);
+            const uint32_t grid = (uint32_t)std::min<size_t>(2048, nq * P * seg_max);
+            if (metric == MSVS_METRIC_HAMMING)
+                bin_ivf_dispatch_g<B_HAMMING>(g, grid, a, stream);
+            else
+                bin_ivf_dispatch_g<B_JACCARD>(g, grid, a, stream);
+            MSVS_HIP(hipGetLastError());
+        }
+        MergeParams m{};
+        m.partial = partial;
+        m.n_lists = (uint32_t)(P * seg_max);
+        m.k = (uint32_t)k;
+        m.out_ids = d_ids;
+        m.out_dis = d_dis;
+        launch_merge(M_L2, m, (uint32_t)nq, stream);
+        MSVS_HIP(hipMemcpyAsync(ids + q0 * k, d_ids, nq * k * 8, hipMemcpyDeviceToHost, stream));
+        MSVS_HIP(hipMemcpyAsync(dis + q0 * k, d_dis, nq * k * 4, hipMemcpyDeviceToHost, stream));
+    }
+    MSVS_HIP(hipStreamSynchronize(stream));
+}
 
 extern "C" int msvs_bin_index_create(size_t nbytes, int metric, msvs_bin_index_t ** out)
 {
@@ -187,7 +487,119 @@ extern "C" int msvs_bin_index_create(size_t nbytes, int metric, msvs_bin_index_t
     });
 }
 
+/// what the list scan's LDS stage holds: a tile of queries + the merge lists of the largest k
+static bool bin_ivf_fits(size_t nbytes)
+{
+    return BIN_IVF_T * round_up(nbytes, (size_t)16) + (size_t)5 * MSVS_MAX_K * 8 <= SCAN_LDS_BUDGET;
+}
+
+extern "C" int msvs_bin_index_create_ivf(size_t nbytes, int metric, const char * params, msvs_bin_index_t ** out)
+{
+    return guarded([&] {
+        if (!out)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "out is null");
+        *out = nullptr;
+        bin_check_args(nbytes, 1, metric);
+        if (!bin_ivf_fits(nbytes))
+            fail(MSVS_ERR_INVALID_ARGUMENT, "binary vectors of %zu bytes are too long for the partitioned index", nbytes);
+        auto p = parse_params(params);
+        const long nc = param_int(p, "ncentroids", 1024), niter = param_int(p, "niter", 10);
+        if (nc < 1 || nc > 0x7fffffffl || niter < 0)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "bad ncentroids / niter");
+        std::unique_ptr<msvs_bin_index> ix(new msvs_bin_index);
+        ix->nbytes = nbytes;
+        ix->metric = metric;
+        ix->ncentroids = (size_t)nc;
+        ix->niter = (int)niter;
+        *out = ix.release();
+    });
+}
+
 extern "C" void msvs_bin_index_free(msvs_bin_index_t * ix) { delete ix; }
+
+extern "C" size_t msvs_bin_index_num_lists(const msvs_bin_index_t * ix) { return ix ? ix->ncentroids : 0; }
+
+extern "C" int msvs_bin_index_set_centroids(msvs_bin_index_t * ix, const uint8_t * centroids, size_t nlist)
+{
+    return guarded([&] {
+        if (!ix || !centroids)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null index / centroids");
+        if (!ix->partitioned() || nlist != ix->ncentroids)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "%zu centroids given, the index has ncentroids = %zu", nlist, ix->ncentroids);
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->centroids.assign(centroids, centroids + nlist * ix->nbytes);
+        ix->images.clear(); // the lists are rebuilt from the new centroids at the next search
+    });
+}
+
+extern "C" int msvs_bin_index_train(msvs_bin_index_t * ix, const uint8_t * rows, size_t n)
+{
+    return guarded([&] {
+        if (!ix || (n && !rows))
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null index / rows");
+        if (!ix->partitioned())
+            fail(MSVS_ERR_INVALID_ARGUMENT, "a flat binary index is not trained");
+        const size_t nlist = ix->ncentroids, nbytes = ix->nbytes;
+        if (n < nlist)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "%zu training rows for %zu centroids", n, nlist);
+        if (n > 0xfffffff0ull)
+            fail(MSVS_ERR_ID_RANGE, "more training rows than the u32 range");
+        // seeds: rows at fixed, evenly spaced positions (no RNG: the same input trains the same centroids)
+        std::vector<uint8_t> cent(nlist * nbytes);
+        for (size_t l = 0; l < nlist; l++)
+            memcpy(cent.data() + l * nbytes, rows + (l * n / nlist) * nbytes, nbytes);
+        if (ix->niter > 0)
+        {
+            hipStream_t stream = thread_stream();
+            const size_t ldb = round_up(nbytes, (size_t)16);
+            const uint32_t ld16 = (uint32_t)(ldb / 16), words = ld16 * 4;
+            DevBuf<unsigned char> dy(n * ldb), dc(nlist * ldb);
+            DevBuf<uint32_t> d_list(n), d_votes(nlist * (size_t)words * 32 + nlist);
+            uint32_t * d_ones = d_votes.p, * d_members = d_votes.p + nlist * (size_t)words * 32;
+            std::vector<uint32_t> votes(d_votes.n);
+            MSVS_HIP(hipMemsetAsync(dc.p, 0, nlist * ldb, stream));
+            bin_upload_padded(dy.p, rows, n, nbytes, ldb, stream);
+            for (int it = 0; it < ix->niter; it++)
+            {
+                // exact assignment and the per-bit vote counts on the device, the majority (2 * ones > members) here
+                bin_upload_padded(dc.p, cent.data(), nlist, nbytes, ldb, stream);
+                launch_bin_assign(dy.p, dc.p, n, nlist, ld16, d_list.p, nullptr, stream);
+                MSVS_HIP(hipMemsetAsync(d_votes.p, 0, d_votes.bytes(), stream));
+                {
+                    ProfileScope prof("bin_ivf_vote", stream);
+                    const size_t threads = n * words;
+                    hipLaunchKernelGGL(bin_vote_kernel, dim3((unsigned)ceil_div(threads, (size_t)256)), dim3(256), 0, stream,
+                                       reinterpret_cast<const uint32_t *>(dy.p), d_list.p, n, words, d_ones, d_members);
+                    MSVS_HIP(hipGetLastError());
+                }
+                MSVS_HIP(hipMemcpyAsync(votes.data(), d_votes.p, d_votes.bytes(), hipMemcpyDeviceToHost, stream));
+                MSVS_HIP(hipStreamSynchronize(stream));
+                const uint32_t * members = votes.data() + nlist * (size_t)words * 32;
+                bool changed = false;
+                for (size_t l = 0; l < nlist; l++)
+                {
+                    if (members[l] == 0)
+                        continue; // an empty list keeps its centroid
+                    const uint32_t * ones = votes.data() + l * (size_t)words * 32;
+                    for (size_t b = 0; b < nbytes; b++)
+                    {
+                        uint8_t v = 0;
+                        for (int bit = 0; bit < 8; bit++)
+                            if (2 * (uint64_t)ones[b * 8 + bit] > members[l])
+                                v |= (uint8_t)(1u << bit);
+                        changed |= v != cent[l * nbytes + b];
+                        cent[l * nbytes + b] = v;
+                    }
+                }
+                if (!changed)
+                    break; // a fixed point: further rounds repeat it
+            }
+        }
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->centroids.swap(cent);
+        ix->images.clear();
+    });
+}
 
 extern "C" int msvs_bin_index_add(msvs_bin_index_t * ix, const uint8_t * rows, const int64_t * ids, size_t n)
 {
@@ -195,6 +607,8 @@ extern "C" int msvs_bin_index_add(msvs_bin_index_t * ix, const uint8_t * rows, c
         if (!ix || (n && !rows))
             fail(MSVS_ERR_INVALID_ARGUMENT, "null index / rows");
         std::lock_guard<std::mutex> lk(ix->mu);
+        if (!ix->ready())
+            fail(MSVS_ERR_NOT_READY, "the partitioned binary index has no centroids yet (train / set_centroids)");
         const size_t base = ix->labels.size();
         if (base + n > 0xfffffff0ull)
             fail(MSVS_ERR_ID_RANGE, "more rows than the u32 label range");
@@ -203,8 +617,9 @@ extern "C" int msvs_bin_index_add(msvs_bin_index_t * ix, const uint8_t * rows, c
             const int64_t id = ids ? ids[i] : (int64_t)(base + i);
             if (id < 0 || id > 0xfffffff0ll)
                 fail(MSVS_ERR_ID_RANGE, "id %lld does not fit the u32 label range", (long long)id);
-            ix->labels.push_back(id);
         }
+        for (size_t i = 0; i < n; i++)
+            ix->labels.push_back(ids ? ids[i] : (int64_t)(base + i));
         ix->rows.insert(ix->rows.end(), rows, rows + n * ix->nbytes);
         ix->images.clear(); // (scans in flight keep theirs alive)
     });
@@ -212,50 +627,78 @@ extern "C" int msvs_bin_index_add(msvs_bin_index_t * ix, const uint8_t * rows, c
 
 extern "C" size_t msvs_bin_index_num_data(const msvs_bin_index_t * ix) { return ix ? ix->labels.size() : 0; }
 
+static void bin_index_search(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, size_t nprobe, const uint64_t * alive_bits,
+                             size_t nbits, int64_t * ids, float * dis)
+{
+    bin_check_args(ix->nbytes, k, ix->metric);
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (!ix->ready())
+            fail(MSVS_ERR_NOT_READY, "the partitioned binary index has no centroids yet (train / set_centroids)");
+    }
+    if (nx == 0 || k == 0)
+        return;
+    if (!x || !ids || !dis)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
+    hipStream_t stream = thread_stream();
+    const std::shared_ptr<msvs_bin_index::Image> img = bin_image(ix, stream);
+    if (ix->partitioned())
+        bin_ivf_search_image(*img, ix->nbytes, ix->metric, x, nx, k, nprobe, alive_bits, nbits, ids, dis, stream);
+    else
+        bin_search_rows(img->rows.p, img->labels.p, img->n, ix->nbytes, x, nx, k, ix->metric, alive_bits, nbits, ids, dis, stream);
+}
+
 extern "C" int msvs_bin_index_search(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, const uint64_t * alive_bits,
                                      size_t nbits, int64_t * ids, float * dis)
 {
     return guarded([&] {
         if (!ix)
             fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
-        bin_check_args(ix->nbytes, k, ix->metric);
-        if (nx == 0 || k == 0)
-            return;
-        if (!x || !ids || !dis)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
-        hipStream_t stream = thread_stream();
-        const size_t ldb = round_up(ix->nbytes, (size_t)16);
-        int dev = 0;
-        MSVS_HIP(hipGetDevice(&dev));
-        std::shared_ptr<msvs_bin_index::Image> img;
+        bin_index_search(ix, x, nx, k, 1, alive_bits, nbits, ids, dis);
+    });
+}
+
+extern "C" int msvs_bin_index_search_params(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, const char * params,
+                                            const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return guarded([&] {
+        if (!ix)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
+        auto p = parse_params(params);
+        for (const auto & kv : p)
+            if (kv.first != "nprobe")
+                fail(MSVS_ERR_INVALID_ARGUMENT, "unknown search parameter `%s`", kv.first.c_str());
+        const long nprobe = param_int(p, "nprobe", 1); // (the float IVFFLAT default)
+        if (nprobe < 1)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "nprobe must be >= 1");
+        bin_index_search(ix, x, nx, k, (size_t)nprobe, alive_bits, nbits, ids, dis);
+    });
+}
+
+extern "C" int msvs_bin_index_export(const msvs_bin_index_t * ix, uint8_t * centroids, int64_t * list_off, uint8_t * rows, int64_t * labels)
+{
+    return guarded([&] {
+        if (!ix)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
+        if (!ix->partitioned())
+            fail(MSVS_ERR_INVALID_ARGUMENT, "a flat binary index has no lists to export");
+        // (the image holds the list structure: it is built here if no search has done so since the last add)
+        const std::shared_ptr<msvs_bin_index::Image> img = bin_image(ix, thread_stream());
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (img->n > ix->labels.size() || ix->centroids.size() != img->nlist * ix->nbytes)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the index changed during the export");
+        if (centroids)
+            memcpy(centroids, ix->centroids.data(), ix->centroids.size());
+        if (list_off)
+            memcpy(list_off, img->h_off.data(), (img->nlist + 1) * 8);
+        for (size_t i = 0; i < img->n; i++)
         {
-            // the row count is read and the upload made under ONE lock: an add between the two would otherwise leave rows that
-            // are never searched; the image is per device (a search thread bound to another GPU gets its own copy)
-            std::lock_guard<std::mutex> lk(ix->mu);
-            auto & slot = ix->images[dev];
-            if (!slot)
-            {
-                const size_t n = ix->labels.size();
-                auto fresh = std::make_shared<msvs_bin_index::Image>();
-                fresh->n = n;
-                fresh->rows.alloc(std::max<size_t>(n, 1) * ldb);
-                fresh->labels.alloc(std::max<size_t>(n, 1));
-                MSVS_HIP(hipMemsetAsync(fresh->rows.p, 0, std::max<size_t>(n, 1) * ldb, stream));
-                if (n)
-                {
-                    MSVS_HIP(hipMemcpy2DAsync(fresh->rows.p, ldb, ix->rows.data(), ix->nbytes, ix->nbytes, n, hipMemcpyHostToDevice, stream));
-                    std::vector<uint32_t> l32(n);
-                    for (size_t i = 0; i < n; i++)
-                        l32[i] = (uint32_t)ix->labels[i];
-                    MSVS_HIP(hipMemcpyAsync(fresh->labels.p, l32.data(), n * 4, hipMemcpyHostToDevice, stream));
-                    MSVS_HIP(hipStreamSynchronize(stream)); // l32 is about to go
-                }
-                MSVS_HIP(hipStreamSynchronize(stream));
-                slot = fresh;
-            }
-            img = slot;
+            const size_t src = img->perm[i];
+            if (rows)
+                memcpy(rows + i * ix->nbytes, ix->rows.data() + src * ix->nbytes, ix->nbytes);
+            if (labels)
+                labels[i] = ix->labels[src];
         }
-        bin_search_rows(img->rows.p, img->labels.p, img->n, ix->nbytes, x, nx, k, ix->metric, alive_bits, nbits, ids, dis, stream);
     });
 }
 
@@ -264,10 +707,11 @@ namespace
 struct BinHeader // 48 bytes, little endian
 {
     char magic[8]; // "MSVSBIN1"
-    uint32_t version;
+    uint32_t version; // 1: flat; 2: partitioned -- nlist / ncent below, the centroids after the rows
     int32_t metric;
     uint64_t nbytes, n;
-    uint64_t reserved[2];
+    uint64_t nlist; // version 2: ncentroids (version 1: reserved, 0)
+    uint64_t ncent; // version 2: centroids in the file, 0 (not trained yet) or nlist (version 1: reserved, 0)
 };
 }
 
@@ -281,13 +725,17 @@ extern "C" int msvs_bin_index_serialize_io(const msvs_bin_index_t * ix, const ms
             IoStream f(io, "data_bin", 1);
             BinHeader h{};
             memcpy(h.magic, "MSVSBIN1", 8);
-            h.version = 1;
+            h.version = ix->partitioned() ? 2 : 1;
             h.metric = ix->metric;
             h.nbytes = ix->nbytes;
             h.n = ix->labels.size();
+            h.nlist = ix->ncentroids;
+            h.ncent = ix->centroids.size() / ix->nbytes;
             f.write(&h, sizeof(h));
             if (!ix->rows.empty())
                 f.write(ix->rows.data(), ix->rows.size());
+            if (!ix->centroids.empty())
+                f.write(ix->centroids.data(), ix->centroids.size());
             f.finish();
         }
         {
@@ -301,6 +749,20 @@ extern "C" int msvs_bin_index_serialize_io(const msvs_bin_index_t * ix, const ms
     });
 }
 
+/// total bytes of a file section in pieces: the buffer grows with what has really been read, so a corrupt or truncated file
+/// ends in MSVS_ERR_IO (a short read) instead of an allocation sized by an untrusted header
+static void bin_read_grow(IoStream & f, std::vector<uint8_t> & v, size_t total)
+{
+    const size_t piece = (size_t)64 << 20;
+    for (size_t got = 0; got < total;)
+    {
+        const size_t m = std::min(piece, total - got);
+        v.resize(got + m);
+        f.read(v.data() + got, m);
+        got += m;
+    }
+}
+
 extern "C" int msvs_bin_index_load_io(const msvs_io_t * io, msvs_bin_index_t ** out)
 {
     return guarded([&] {
@@ -311,22 +773,22 @@ extern "C" int msvs_bin_index_load_io(const msvs_io_t * io, msvs_bin_index_t ** 
             IoStream f(io, "data_bin", 0);
             BinHeader h{};
             f.read(&h, sizeof(h));
-            if (memcmp(h.magic, "MSVSBIN1", 8) != 0 || h.version != 1 || h.nbytes == 0 || h.nbytes > 65536 || h.n > 0xfffffff0ull
-                || (h.metric != MSVS_METRIC_HAMMING && h.metric != MSVS_METRIC_JACCARD))
+            if (memcmp(h.magic, "MSVSBIN1", 8) != 0 || (h.version != 1 && h.version != 2) || h.nbytes == 0 || h.nbytes > 65536
+                || h.n > 0xfffffff0ull || (h.metric != MSVS_METRIC_HAMMING && h.metric != MSVS_METRIC_JACCARD))
                 fail(MSVS_ERR_IO, "corrupt msvs binary index header");
+            if (h.version == 2 && (h.nlist == 0 || h.nlist > 0x7fffffffull || (h.ncent != 0 && h.ncent != h.nlist) || !bin_ivf_fits(h.nbytes)))
+                fail(MSVS_ERR_IO, "corrupt msvs binary index header (lists)");
             ix->nbytes = h.nbytes;
             ix->metric = h.metric;
             // the header is untrusted: the rows arrive in pieces and the buffer grows with what has really been read, so a corrupt
             // or truncated file ends in MSVS_ERR_IO (a short read) instead of a 2.8e14-byte allocation
             if (h.nbytes != 0 && h.n > SIZE_MAX / h.nbytes) // (n <= 0xfffffff0 and nbytes <= 65536 above: cannot wrap in 64 bits -- kept explicit)
                 fail(MSVS_ERR_IO, "corrupt msvs binary index header");
-            const size_t total = (size_t)h.n * (size_t)h.nbytes, piece = (size_t)64 << 20;
-            for (size_t got = 0; got < total;)
+            bin_read_grow(f, ix->rows, (size_t)h.n * (size_t)h.nbytes);
+            if (h.version == 2)
             {
-                const size_t m = std::min(piece, total - got);
-                ix->rows.resize(got + m);
-                f.read(ix->rows.data() + got, m);
-                got += m;
+                ix->ncentroids = (size_t)h.nlist;
+                bin_read_grow(f, ix->centroids, (size_t)h.ncent * (size_t)h.nbytes); // (< 2^31 * 2^16)
             }
             // (the labels are sized by the id list's own count below, piece by piece like the rows -- not by the header)
         }
