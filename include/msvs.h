@@ -53,10 +53,12 @@ enum msvs_metric { MSVS_METRIC_L2 = 0, MSVS_METRIC_IP = 1, MSVS_METRIC_COSINE = 
 enum msvs_index_type { MSVS_INDEX_FLAT = 0, MSVS_INDEX_IVFFLAT = 1 };
 enum msvs_mem { MSVS_MEM_HOST = 0, MSVS_MEM_DEVICE = 1 };
 
-/* largest k (and nprobe) one device top-k pass supports (what msvs_index_search_device accepts) */
+/* largest k (and nprobe) one device top-k pass supports; the limit of the binary, sharded and routed searches */
 #define MSVS_MAX_K 256
-/* largest k of the host-pointer entry points: beyond MSVS_MAX_K they run exact rounds of MSVS_MAX_K per query,
- * each excluding the rows already returned (covers the reference's k + deleted-rows over-fetch and LIMIT 1000) */
+/* largest k of msvs_index_search[_filter][_device], msvs_knn_f32, the BM25 entries and msvs_hybrid_fuse_device: beyond
+ * MSVS_MAX_K they run exact rounds of MSVS_MAX_K ranks, each excluding the rows already returned (covers the reference's
+ * k + deleted-rows over-fetch, LIMIT 1000 and the 3 x LIMIT candidates of a hybrid search).  The vector searches run their
+ * rounds one query at a time; the BM25 entries over the whole batch at once.  Beyond it: MSVS_ERR_UNSUPPORTED_K. */
 #define MSVS_MAX_K_ROUNDS 4096
 
 MSVS_API const char * msvs_last_error(void);
@@ -213,7 +215,8 @@ MSVS_API int msvs_index_search(const msvs_index_t * index, const float * queries
                                const char * params, const uint64_t * alive_bits, size_t nbits, int64_t * ids,
                                float * dis);
 /* Same with DEVICE pointers, enqueued on `hip_stream` (hipStream_t, NULL = default stream) without host
- * synchronisation: the form a GPU-resident host pipeline (and bench.py) uses. */
+ * synchronisation: the form a GPU-resident host pipeline (and bench.py) uses.  k <= MSVS_MAX_K_ROUNDS; beyond MSVS_MAX_K the
+ * call runs the host entry's exact rounds, query by query, stream-ordered like the rest. */
 MSVS_API int msvs_index_search_device(const msvs_index_t * index, const float * d_queries, size_t nq, int k,
                                       int nprobe, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
                                       float * d_dis, void * hip_stream);
@@ -340,6 +343,7 @@ MSVS_API void msvs_comm_free(msvs_comm_t * comm);
 MSVS_API int msvs_comm_all_reduce_u64(const msvs_comm_t * comm, uint64_t * values, size_t n, void * hip_stream);
 MSVS_API int msvs_comm_rank(const msvs_comm_t * comm);
 MSVS_API int msvs_comm_size(const msvs_comm_t * comm);
+/* (The sharded and routed searches keep k <= MSVS_MAX_K: no rounds across ranks.) */
 MSVS_API int msvs_shard_search_device(const msvs_index_t * shard, const msvs_comm_t * comm, const float * d_queries,
                                       size_t nq, int k, int nprobe, const uint64_t * d_alive_bits, size_t nbits,
                                       int64_t * d_ids, float * d_dis, void * hip_stream);
@@ -405,7 +409,8 @@ MSVS_API int msvs_merge_topk_device_strided(const int64_t * d_ids, size_t ids_pa
  * (src/VectorIndex/Utils/HybridSearchUtils.cpp:164-300) as MergeTreeHybridSearchManager::hybridSearch applies them to ONE
  * part's vector and text results.  Inputs are the device searches' output arrays: query q's vector rows d_vec_dis /
  * d_vec_ids[q * kv ...] (best first; the first id < 0 ends the list), its text rows d_txt_scores / d_txt_ids[q * kt ...];
- * kv, kt <= 256.  fusion_type: 0 = RRF (score = sum of 1 / (fusion_k + rank), fusion_k 0 = 60), 1 = RSF (fusion_weight *
+ * kv, kt, topk <= MSVS_MAX_K_ROUNDS (lists of at most 256 rows: every entry compares itself with every other; longer ones: a hash
+ * table of the text labels and a sort of the fused rows, one workgroup per query either way).  fusion_type: 0 = RRF (score = sum of 1 / (fusion_k + rank), fusion_k 0 = 60), 1 = RSF (fusion_weight *
  * normalised text score + (1 - fusion_weight) * normalised vector score, vector_scan_direction -1: larger is better).
  * Outputs [nq][topk]: fused scores descending, ties by ascending label; label -1 / score 0 past d_n_out[q] rows.  Same
  * arithmetic, same order, same bits as msvs_host_hybrid_search_batch (include/msvs_host.h).  Stream-ordered, no host sync. */
@@ -438,7 +443,9 @@ MSVS_API void msvs_postings_free(msvs_postings_t * postings);
 MSVS_API int msvs_postings_set_alive(msvs_postings_t * postings, const uint64_t * alive_bits, size_t nbits);
 /* qterms/df: the query's term ids and their TABLE-level document frequencies (TANTIVY::Statistics.docs_freq,
  * src/VectorIndex/Processors/ReadWithHybridSearch.cpp:89-209); total_docs / total_tokens likewise.
- * Output: up to k (row id, score) best-first (score desc, row asc); *n_out = number written. */
+ * Output: up to k (row id, score) best-first (score desc, row asc); *n_out = number written.  k <= MSVS_MAX_K_ROUNDS (all
+ * BM25 entries; beyond MSVS_MAX_K: exact rounds of MSVS_MAX_K ranks over the whole batch, each continuing behind the last
+ * (score, row) of the one before). */
 MSVS_API int msvs_bm25_search(const msvs_postings_t * postings, const uint32_t * qterms, const uint64_t * df,
                               size_t num_qterms, uint64_t total_docs, uint64_t total_tokens,
                               const uint64_t * alive_bits, size_t nbits, size_t k, uint64_t * row_ids, float * scores,
@@ -483,6 +490,7 @@ MSVS_API int msvs_filter_to_bits(const msvs_filter_t * f, uint64_t * bits_out);
 MSVS_API void msvs_filter_free(msvs_filter_t * f);
 MSVS_API int msvs_index_search_filter(const msvs_index_t * index, const float * queries, size_t nq, int k, const char * params,
                                       const msvs_filter_t * filter, int64_t * ids, float * dis);
+/* (both: k <= MSVS_MAX_K_ROUNDS; beyond MSVS_MAX_K exact rounds over the filter's bit test, as msvs_index_search) */
 MSVS_API int msvs_index_search_filter_device(const msvs_index_t * index, const float * d_queries, size_t nq, int k, int nprobe,
                                              const msvs_filter_t * filter, int64_t * d_ids, float * d_dis, void * hip_stream);
 

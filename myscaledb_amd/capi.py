@@ -14,6 +14,7 @@ METRIC_L2, METRIC_IP, METRIC_COSINE, METRIC_HAMMING, METRIC_JACCARD = 0, 1, 2, 3
 INDEX_FLAT, INDEX_IVFFLAT = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 MAX_K = 256
+MAX_K_ROUNDS = 4096  # MSVS_MAX_K_ROUNDS: the BM25, device-fusion and (non-sharded, non-binary) vector searches go this far in exact rounds
 METRICS = {"L2": METRIC_L2, "IP": METRIC_IP, "Cosine": METRIC_COSINE, "COSINE": METRIC_COSINE, "cosine": METRIC_COSINE}
 
 OK, ERR_INVALID_ARGUMENT, ERR_NOT_IMPLEMENTED, ERR_DEVICE, ERR_OOM, ERR_NOT_READY, ERR_UNSUPPORTED_K, ERR_ID_RANGE, \

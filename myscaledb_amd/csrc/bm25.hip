@@ -307,6 +307,23 @@ std::shared_ptr<msvs_postings::RecSet> records_for(const msvs_postings & ps, con
 
 static __global__ void bm25_nop_kernel() {}
 
+/// One round of the rank-window search (k > MSVS_MAX_K, bm25_chunk_device): the round's merged keys, [nq][MSVS_MAX_K] ascending and
+/// KEY_NONE-padded, go to columns [col0, col0 + n) of the [nq][k] outputs, and the round's LAST key becomes the query's continuation
+/// key -- KEY_NONE when the round came back short: the query is finished, later rounds offer nothing and its tail stays "no hit".
+static __global__ __launch_bounds__(MSVS_MAX_K) void bm25_round_scatter_kernel(const uint64_t * keys, uint32_t k, uint32_t col0, uint32_t n,
+                                                                              int64_t * out_ids, float * out_scores, uint64_t * after)
+{
+    const uint32_t q = blockIdx.x, i = threadIdx.x;
+    const uint64_t key = keys[(size_t)q * MSVS_MAX_K + i];
+    if (i < n)
+    {
+        out_ids[(size_t)q * k + col0 + i] = key == KEY_NONE ? -1 : (int64_t)(uint32_t)key;
+        out_scores[(size_t)q * k + col0 + i] = key_value<M_IP>(key);
+    }
+    if (i == MSVS_MAX_K - 1)
+        after[q] = key;
+}
+
 /// Documents per sub-range for a batch whose densest query has `rho` postings per document: that query's windows are single
 /// sub-ranges ~3/4 full.  From 2048 on a multiple of the skip table's stretch (BM25_SKIP_DOCS): the bounds of the frequent terms are
 /// then table entries (bm25_bounds8_kernel reads no posting for them).
@@ -331,6 +348,10 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
 {
     const size_t f0 = qoff[0], n_flat = qoff[nq] - f0, nf1 = std::max<size_t>(n_flat, 1), nc = ps.num_fields * 256;
     const float K1 = 1.2f;
+    // k beyond one wavefront top-k list: exact rounds of MSVS_MAX_K ranks over the whole chunk (below, the `!emit` branch); the
+    // per-chunk lists are kl wide either way
+    const bool rounds = k > MSVS_MAX_K;
+    const size_t kl = rounds ? (size_t)MSVS_MAX_K : k;
     // two kernels share this flow: the wave-private streaming scorer (default) and the block scorer it replaced (knob)
     const bool wave = options().bm25_wave != 0;
     // ... and, for batches of sparse terms, the posting-as-unit scorer (bm25p_kernels.hpp).  Its sub-range size follows the
@@ -358,7 +379,8 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
             all_postings += sum;
             rho = std::max(rho, (double)sum / (double)std::max<size_t>(ps.num_docs, 1));
         }
-        if (rho > 0.125 && options().bm25_posting != 2) // 2: always (tests: every sub-range of a frequent term is split)
+        // 2: always (tests: every sub-range of a frequent term is split); the rounds run on the record scorers whatever the density
+        if (rho > 0.125 && options().bm25_posting != 2 && !rounds)
             posting = false;
         else
         {
@@ -378,7 +400,8 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
                                                     std::max<size_t>(1, (size_t)n_blocks * nq / 8192));
     const uint32_t n_chunks = wave ? (uint32_t)ceil_div((size_t)n_blocks, (size_t)spi) : n_blocks;
     // long corpora: sample -> cut -> emit -> select (+ exact fallback); short ones: per-chunk top-k lists, one merge
-    const bool emit = n_chunks >= (wave ? 32u : 64u) && ps.num_docs >= 500000 && options().bm25_emit != 0;
+    // (the rounds are exact by construction: the cut and the candidate buffer of the emit flow were sized for k <= 256)
+    const bool emit = n_chunks >= (wave ? 32u : 64u) && ps.num_docs >= 500000 && options().bm25_emit != 0 && !rounds;
     const uint32_t cand_cap = options().bm25_cand_cap > 0 ? (uint32_t)std::min<double>(options().bm25_cand_cap, BM25_CAND_CAP) : BM25_CAND_CAP;
     unsigned long long * stat_fail = bm25_fail_counter();
     // posting scorer, EMIT pass: items of about equal postings (a uniform spread of a term over the documents assumed), twice
@@ -386,6 +409,8 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     const uint32_t cus = bm25_cu_count();
     // the record scorer (bm25r_kernel) when the posting set has its score-ready records for this call's statistics
     const bool recs = posting && d_rec != nullptr;
+    if (rounds && !recs)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds %d: the rank-window rounds need the record scorers", k, MSVS_MAX_K);
     const bool big_slots = options().bm25_slots >= 16384;
     // ... and its lean form (bm25l_kernels.hpp) when no query of the chunk has more than four terms
     bool lean = recs && options().bm25_lean != 0;
@@ -522,14 +547,17 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
             }
     }
     Scratch & scr = scratch_for(stream);
-    scr.reserve(nq * (size_t)n_chunks * k * 8 + nf1 * (size_t)(n_blocks + 1) * 16 + blob_bytes
+    scr.reserve(nq * (size_t)n_chunks * kl * 8 + (rounds ? nq * (kl + 1) * 8 + 512 : 0) + nf1 * (size_t)(n_blocks + 1) * 16 + blob_bytes
                     + (emit ? nq * ((size_t)(n_sb + 1) * cut_m * 8 + (size_t)BM25_CAND_CAP * 8 + 16) : 0) + nq * 8 + 256 + 65536,
                 stream);
     Bm25Params a{};
     unsigned char * d_blob = scr.take<unsigned char>(blob_bytes);
     int64_t * d_bounds = scr.take<int64_t>(nf1 * (n_blocks + 1));
     int64_t * d_bounds_hi = scr.take<int64_t>(nf1 * (n_blocks + 1));
-    uint64_t * partial = scr.take<uint64_t>(nq * (size_t)n_chunks * k);
+    uint64_t * partial = scr.take<uint64_t>(nq * (size_t)n_chunks * kl);
+    uint64_t * round_keys = rounds ? scr.take<uint64_t>(nq * kl) : nullptr; // a round's merged keys ...
+    uint64_t * d_after = rounds ? scr.take<uint64_t>(nq) : nullptr;         // ... and the continuation key of every query
+    bool after_mode = false; // launch_topk: the BM25_TOPK_AFTER form of the record scorers
     memcpy(blob_pinned, blob, blob_bytes);
     // the tables go to the device with the bounds launch (bm25_bounds8_kernel) when there is one, else with a copy kernel of their own;
     // the first scorer launch behind them tells the host that the pinned slot is free again (Bm25Params::slot_done)
@@ -586,6 +614,19 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
                 if (recs)
                 {
                     Bm25RParams rp{w, d_rec};
+                    if (after_mode)
+                    {
+                        // instantiations of their own: the ones that serve k <= 256 (below) are untouched
+                        rp.after = d_after;
+                        if (lean)
+                            hipLaunchKernelGGL((bm25l_kernel<BM25_TOPK_AFTER, 4, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
+                        else if (big_slots)
+                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK_AFTER, 4, 16384>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
+                        else
+                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK_AFTER, 4, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
+                        MSVS_HIP(hipGetLastError());
+                        return;
+                    }
 #define MSVS_BM25R(RR) \
     do \
     { \
@@ -673,15 +714,36 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     if (!emit)
     {
         a.partial = partial;
-        a.kk = (uint32_t)k;
-        launch_topk(a, n_chunks, 1, nq, spi, n_chunks);
+        a.kk = (uint32_t)kl;
         MergeParams m{};
         m.partial = partial;
         m.n_lists = n_chunks;
-        m.k = (uint32_t)k;
-        m.out_ids = d_ids;
-        m.out_dis = d_scores;
-        launch_merge(M_IP, m, (uint32_t)nq, stream);
+        m.k = (uint32_t)kl;
+        if (!rounds)
+        {
+            launch_topk(a, n_chunks, 1, nq, spi, n_chunks);
+            m.out_ids = d_ids;
+            m.out_dis = d_scores;
+            launch_merge(M_IP, m, (uint32_t)nq, stream);
+            return;
+        }
+        // Rank windows.  Keys are unique per query (the document id is their low word), so "ranks 256 r .. 256 r + 255 of query q" are
+        // the 256 smallest keys strictly greater than the last key of round r - 1: every round is the exact path again -- per-chunk
+        // lists, one merge -- over the documents behind the query's continuation key, for the whole chunk of queries at once.  The
+        // bounds and tables above are shared by all rounds.  Round 0 starts from key 0, which admits every key (no score makes it:
+        // make_key turns NaN into KEY_NONE); a query whose round came back short continues from KEY_NONE, which admits none.
+        after_mode = true;
+        m.mode = 2;
+        m.out_keys = round_keys;
+        MSVS_HIP(hipMemsetAsync(d_after, 0, nq * 8, stream));
+        for (size_t done = 0; done < k; done += kl)
+        {
+            launch_topk(a, n_chunks, 1, nq, spi, n_chunks);
+            launch_merge(M_IP, m, (uint32_t)nq, stream);
+            hipLaunchKernelGGL(bm25_round_scatter_kernel, dim3((unsigned)nq), dim3(MSVS_MAX_K), 0, stream, round_keys, (uint32_t)k, (uint32_t)done,
+                               (uint32_t)std::min(kl, k - done), d_ids, d_scores, d_after);
+            MSVS_HIP(hipGetLastError());
+        }
         return;
     }
     if (!fills_ride)
@@ -820,8 +882,14 @@ void bm25_batch_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
                        int operator_or, const uint64_t * d_alive, size_t nbits, size_t k, int64_t * d_ids, float * d_scores,
                        hipStream_t stream)
 {
-    if (k > MSVS_MAX_K)
-        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the device top-k limit %d", k, MSVS_MAX_K);
+    if (k > MSVS_MAX_K_ROUNDS)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the limit %d", k, MSVS_MAX_K_ROUNDS);
+    // beyond one top-k list: exact rank-window rounds on the record scorers (bm25_chunk_device).  The knobs that select another scorer
+    // keep the old limit.
+    const bool rounds = k > MSVS_MAX_K;
+    if (rounds && (options().bm25_wave == 0 || options().bm25_posting == 0 || options().bm25_rec == 0))
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds %d, which only the record scorers serve: not with option %s = 0", k, MSVS_MAX_K,
+             options().bm25_wave == 0 ? "bm25_wave" : options().bm25_posting == 0 ? "bm25_posting" : "bm25_rec");
     if (total_docs == 0)
         fail(MSVS_ERR_INVALID_ARGUMENT, "total_docs is zero");
     // tantivy Bm25Weight (bm25.rs): K1 = 1.2, B = 0.75, all f32
@@ -887,13 +955,16 @@ void bm25_batch_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
         const size_t formula = bm25_sub_docs_for(rho);
         const size_t sub_p = options().bm25_sub_docs >= 16 ? (size_t)options().bm25_sub_docs : formula;
         // no chunk can be denser than the batch: all of them take the posting scorer, or some may keep the dense accumulator
-        sub_ub = rho <= 0.125 || options().bm25_posting == 2 ? sub_p : std::min<size_t>(BW_DOCS, sub_p);
+        // (the rounds of k > MSVS_MAX_K always do)
+        sub_ub = rho <= 0.125 || options().bm25_posting == 2 || rounds ? sub_p : std::min<size_t>(BW_DOCS, sub_p);
     }
     const size_t n_blocks = std::max<size_t>(1, ceil_div(ps.num_docs, sub_ub));
     // per query: candidate slots + ~4 terms of sub-range bounds (the per-chunk lists are ~8192 x k keys for the whole batch); chunks
     // of queries sized so that this stays under 1 GB (round 5: 256 MB cut a 1024-query batch over 10M documents into 6 chunks of
     // seven launches each)
-    const size_t per_q = (size_t)BM25_CAND_CAP * 8 + 4 * 16 * (n_blocks + 1) + 64 * k * 8 + 64
+    // (k > MSVS_MAX_K: the lists of a round are MSVS_MAX_K wide, plus the round's merged keys and the continuation key)
+    const size_t kl = std::min<size_t>(k, MSVS_MAX_K);
+    const size_t per_q = (size_t)BM25_CAND_CAP * 8 + 4 * 16 * (n_blocks + 1) + 64 * kl * 8 + (rounds ? (kl + 1) * 8 : 0) + 64
         + (options().bm25_wave != 0 ? 0 : ceil_div(ps.num_docs, (size_t)BM25_DOCS) * k * 8); // the block scorer: a list per block
     const size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)1024 << 20) / per_q));
     for (size_t q0 = 0; q0 < nq; q0 += chunk)

@@ -137,8 +137,11 @@ __device__ __forceinline__ void lds_barrier()
 enum
 {
     BM25_TOPK = 0,
-    BM25_EMIT = 1
+    BM25_EMIT = 1,
+    BM25_TOPK_AFTER = 2 // record scorers only (bm25r / bm25l): TOPK over the keys strictly behind a per-query continuation key
 };
+/// TOPK and its continuation form share everything but the admission test.
+constexpr bool bm25_topk_mode(int mode) { return mode == BM25_TOPK || mode == BM25_TOPK_AFTER; }
 
 /// grid (document blocks, Y); dynamic LDS (TOPK only): 5 * kk * 8 bytes for the block merge.
 ///

@@ -145,6 +145,9 @@ __global__ __launch_bounds__(64 * BP_WAVES, BL_WAVES_PER_SIMD) void bm25l_kernel
             const float c = ck == KEY_NONE ? 0.f : key_value<M_IP>(ck); // fewer than m sample hits: everything passes
             cut = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(c)));
         }
+        uint64_t after_q = 0; // BM25_TOPK_AFTER: the query's continuation key (uniform; Bm25RParams::after)
+        if (MODE == BM25_TOPK_AFTER)
+            after_q = readlane64(ar.after[q], 0);
         WaveTopK<R> top;
         top.init();
         // ---- per-term state.  In lanes (step jl, term tl) for the generator, in scalar registers for the rows
@@ -165,9 +168,9 @@ __global__ __launch_bounds__(64 * BP_WAVES, BL_WAVES_PER_SIMD) void bm25l_kernel
         auto group_of = [&](const uint32_t t) -> uint32_t { return (uint32_t)(gpack >> (16 * t)) & 0xffffu; };
         // what leaves a window, one key per lane: offered to the item's list (TOPK), or staged with its query (EMIT)
         auto out_one = [&](const bool ok, const uint64_t key) {
-            if (MODE == BM25_TOPK)
+            if (bm25_topk_mode(MODE))
             {
-                top.offer(ok ? key : KEY_NONE, p.kk, lane);
+                top.offer(ok && (MODE != BM25_TOPK_AFTER || key > after_q) ? key : KEY_NONE, p.kk, lane);
                 return;
             }
             const uint64_t m = __ballot(ok);
@@ -192,9 +195,9 @@ __global__ __launch_bounds__(64 * BP_WAVES, BL_WAVES_PER_SIMD) void bm25l_kernel
             len += dpp32<0xB1>(len);
             len += dpp32<0x4E>(len);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)len);
-            if (total == 0 || s_begin >= s_end)
+            if (total == 0 || s_begin >= s_end || (MODE == BM25_TOPK_AFTER && after_q == KEY_NONE))
             {
-                if (MODE == BM25_TOPK)
+                if (bm25_topk_mode(MODE))
                     top.store(p.partial + ((size_t)slot * a.lists + ci) * p.kk, p.kk, lane);
                 continue; // nothing of this query in the item
             }
@@ -464,14 +467,16 @@ __global__ __launch_bounds__(64 * BP_WAVES, BL_WAVES_PER_SIMD) void bm25l_kernel
                     const uint32_t t = (tpk >> (2 * r)) & 3u;
                     ok = ok && group_of(t) == full;
                 }
-                if (MODE == BM25_TOPK && ok && p.alive) // (EMIT tests the few records that pass the cut below)
+                if (MODE == BM25_TOPK_AFTER && ok) // (before the floor below: it counts the records that can still be offered)
+                    ok = make_key<M_IP>(s_r[r], rb[r].x) > after_q;
+                if (bm25_topk_mode(MODE) && ok && p.alive) // (EMIT tests the few records that pass the cut below)
                     ok = rb[r].x < p.nbits && ((p.alive[rb[r].x >> 6] >> (rb[r].x & 63)) & 1);
                 pass_r[r] = ok;
                 any = any || ok;
             }
             // TOPK, the item's list not full yet: the kk-th largest of the 64 lanes' BEST scores is a floor -- kk records at or
             // above it exist -- and what lies below it cannot be among the window's kk best
-            if (MODE == BM25_TOPK && top.thr == KEY_NONE)
+            if (bm25_topk_mode(MODE) && top.thr == KEY_NONE)
             {
                 float best = -1.f; // scores are >= 0
 #pragma unroll
@@ -493,7 +498,7 @@ __global__ __launch_bounds__(64 * BP_WAVES, BL_WAVES_PER_SIMD) void bm25l_kernel
                         pass_r[r] = pass_r[r] && !(s_r[r] < floor_s);
                 }
             }
-            if (MODE == BM25_TOPK || __ballot(any))
+            if (bm25_topk_mode(MODE) || __ballot(any))
             {
 #pragma unroll
                 for (uint32_t r = 0; r < BP_RMAX; r++)
@@ -586,7 +591,7 @@ __global__ __launch_bounds__(64 * BP_WAVES, BL_WAVES_PER_SIMD) void bm25l_kernel
             issue(loA, hiA, totA, rbA, wvA, tpA);
             process(totB, rbB, wvB, tpB);
         }
-        if (MODE == BM25_TOPK)
+        if (bm25_topk_mode(MODE))
             top.store(p.partial + ((size_t)slot * a.lists + ci) * p.kk, p.kk, lane);
     }
     if (MODE == BM25_EMIT)

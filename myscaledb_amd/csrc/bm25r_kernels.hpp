@@ -32,6 +32,10 @@ struct Bm25RParams
 {
     Bm25WParams w;
     const uint2 * rec; // [postings] (doc, bits of tf / (tf + cache[field][fieldnorm[doc]]))
+    // BM25_TOPK_AFTER (the rank-window rounds of k > MSVS_MAX_K, bm25.hip): [nq] continuation keys -- only keys strictly greater
+    // (= worse: later in the ranking) than after[q] are offered; 0 admits every key, KEY_NONE none (the query is finished).  Last
+    // member: the kernel arguments of the other modes keep their offsets.
+    const uint64_t * after = nullptr;
 };
 
 /// rec[p] = (doc, tfn) for every posting.  term_field != nullptr: the posting's term (and so its text column) by a binary search
@@ -186,6 +190,9 @@ __global__ __launch_bounds__(64 * BP_WAVES, 4) void bm25r_kernel(const Bm25RPara
             const float c = ck == KEY_NONE ? 0.f : key_value<M_IP>(ck); // fewer than m sample hits: everything passes
             cut = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(c)));
         }
+        uint64_t after_q = 0; // BM25_TOPK_AFTER: the query's continuation key (uniform)
+        if (MODE == BM25_TOPK_AFTER)
+            after_q = readlane64(ar.after[q], 0);
         // lane t = term t of the query (<= 64 terms)
         const bool has_term = lane < nt;
         const uint32_t jt = j0 + (has_term ? lane : 0);
@@ -200,9 +207,9 @@ __global__ __launch_bounds__(64 * BP_WAVES, 4) void bm25r_kernel(const Bm25RPara
         top.init();
         // what leaves a window, one key per lane: offered to the item's list (TOPK), or staged with its query (EMIT)
         auto out_one = [&](const bool ok, const uint64_t key) {
-            if (MODE == BM25_TOPK)
+            if (bm25_topk_mode(MODE))
             {
-                top.offer(ok ? key : KEY_NONE, p.kk, lane);
+                top.offer(ok && (MODE != BM25_TOPK_AFTER || key > after_q) ? key : KEY_NONE, p.kk, lane);
                 return;
             }
             const uint64_t m = __ballot(ok);
@@ -231,6 +238,8 @@ __global__ __launch_bounds__(64 * BP_WAVES, 4) void bm25r_kernel(const Bm25RPara
             }
             else
                 W = 0; // nothing of this query in the item
+            if (MODE == BM25_TOPK_AFTER && after_q == KEY_NONE)
+                W = 0; // the query is finished: an empty list
             W = (uint32_t)__builtin_amdgcn_readfirstlane((int)W);
         }
         // ---- the window generator (bm25p_kernel's loop head as a function: it runs one window AHEAD of the scoring)
@@ -398,13 +407,15 @@ __global__ __launch_bounds__(64 * BP_WAVES, 4) void bm25r_kernel(const Bm25RPara
                 const uint32_t t = (tp[r >> 2] >> (8 * (r & 3))) & 0xffu;
                 bool ok = !(a.dbg & 4) && r * 64 + lane < tot && !((flags >> r) & 1u) && (p.operator_or || (tfb[t] >> 8) == full)
                     && (MODE != BM25_EMIT || s_r[r] >= cut);
-                if (MODE == BM25_TOPK && ok && p.alive) // (EMIT tests the few records that pass the cut below)
+                if (MODE == BM25_TOPK_AFTER && ok) // (before the floor below: it counts the records that can still be offered)
+                    ok = make_key<M_IP>(s_r[r], rb[r].x) > after_q;
+                if (bm25_topk_mode(MODE) && ok && p.alive) // (EMIT tests the few records that pass the cut below)
                     ok = rb[r].x < p.nbits && ((p.alive[rb[r].x >> 6] >> (rb[r].x & 63)) & 1);
                 passbits |= (ok ? 1u : 0u) << r;
             }
             // TOPK, the item's list not full yet: the kk-th largest of the 64 lanes' BEST scores is a floor -- kk records at or
             // above it exist -- and what lies below it cannot be among the window's kk best
-            if (MODE == BM25_TOPK && top.thr == KEY_NONE)
+            if (bm25_topk_mode(MODE) && top.thr == KEY_NONE)
             {
                 float best = -1.f; // scores are >= 0
 #pragma unroll
@@ -427,7 +438,7 @@ __global__ __launch_bounds__(64 * BP_WAVES, 4) void bm25r_kernel(const Bm25RPara
                             passbits &= ~(1u << r);
                 }
             }
-            if (MODE == BM25_TOPK || __ballot(passbits != 0))
+            if (bm25_topk_mode(MODE) || __ballot(passbits != 0))
             {
 #pragma unroll
                 for (uint32_t r = 0; r < BP_RMAX; r++)
@@ -563,7 +574,7 @@ __global__ __launch_bounds__(64 * BP_WAVES, 4) void bm25r_kernel(const Bm25RPara
             issue(lwA, lenA, totA, rbA, tpA);
             process(totB, rbB, tpB);
         }
-        if (MODE == BM25_TOPK)
+        if (bm25_topk_mode(MODE))
             top.store(p.partial + ((size_t)slot * a.lists + ci) * p.kk, p.kk, lane);
     }
     if (MODE == BM25_EMIT)

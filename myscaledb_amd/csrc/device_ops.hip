@@ -56,7 +56,7 @@ namespace
 /// Every arena of the calling host thread, keyed by (device, stream).
 struct ThreadArenas
 {
-    std::map<std::pair<int, hipStream_t>, Scratch> scratch, staging, aux, shard, view, route;
+    std::map<std::pair<int, hipStream_t>, Scratch> scratch, staging, aux, shard, view, route, rounds;
 };
 thread_local ThreadArenas t_arenas;
 
@@ -74,12 +74,13 @@ Scratch & shard_for(hipStream_t stream) { return arena_in(t_arenas.shard, stream
 Scratch & staging_for(hipStream_t stream) { return arena_in(t_arenas.staging, stream); }
 Scratch & view_for(hipStream_t stream) { return arena_in(t_arenas.view, stream); }
 Scratch & route_for(hipStream_t stream) { return arena_in(t_arenas.route, stream); }
+Scratch & rounds_for(hipStream_t stream) { return arena_in(t_arenas.rounds, stream); }
 
 size_t release_thread_arenas()
 {
     size_t freed = 0;
     (void)hipDeviceSynchronize(); // nothing enqueued may still use them
-    for (auto * m : {&t_arenas.scratch, &t_arenas.staging, &t_arenas.aux, &t_arenas.shard, &t_arenas.view, &t_arenas.route})
+    for (auto * m : {&t_arenas.scratch, &t_arenas.staging, &t_arenas.aux, &t_arenas.shard, &t_arenas.view, &t_arenas.route, &t_arenas.rounds})
     {
         for (auto & kv : *m)
             freed += kv.second.buf.n;

@@ -47,6 +47,8 @@ Scratch & shard_for(hipStream_t stream);
 Scratch & route_for(hipStream_t stream); // the routed sharded search's exchange buffers (shard.hip)
 /// ... and one for the compacted view of a filtered search and small per-filter counters.
 Scratch & view_for(hipStream_t stream);
+/// ... and one for the private filter bitmap of a search in rounds (k > MSVS_MAX_K, search_entry.hip: index_search_rounds).
+Scratch & rounds_for(hipStream_t stream);
 /// Host -> device hand-over of a SMALL block that already sits in pinned host memory (query batches of the host-pointer calls, a BM25
 /// batch's tables): a copy KERNEL that streams it over the link (nontemporal 16-byte loads) instead of hipMemcpyAsync.  The runtime's
 /// copy is a blit surrounded by barrier packets: ~10 us of idle device before and after it in the kernel trace

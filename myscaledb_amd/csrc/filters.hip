@@ -250,13 +250,15 @@ extern "C" int msvs_index_search_filter_device(const msvs_index_t * ix, const fl
             fail(MSVS_ERR_INVALID_ARGUMENT, "null index/filter/buffer or negative k");
         if (nq == 0 || k == 0)
             return;
-        check_k((size_t)k);
         hipStream_t stream = as_stream(hip_stream);
         const auto meta = ix->get_meta();
         size_t eff_bits = filter->nbits;
         const uint64_t * eff = effective_filter(*ix, meta.get(), filter->bits.p, filter->nbits, &eff_bits, stream);
-        index_search_filtered(*ix, d_queries, nq, (uint32_t)k, (size_t)std::max(nprobe, 0), eff, eff_bits, filter->count, d_ids, d_dis,
-                              stream);
+        if ((size_t)k > MSVS_MAX_K) // exact rounds over the bit test (search_entry.hip); the compacted view serves one pass only
+            index_search_rounds(*ix, d_queries, nq, (size_t)k, (size_t)std::max(nprobe, 1), eff, eff_bits, d_ids, d_dis, stream);
+        else
+            index_search_filtered(*ix, d_queries, nq, (uint32_t)k, (size_t)std::max(nprobe, 0), eff, eff_bits, filter->count, d_ids, d_dis,
+                                  stream);
         apply_row_ids_map(meta.get(), d_ids, nq * (size_t)k, stream);
     });
 }
@@ -270,7 +272,8 @@ extern "C" int msvs_index_search_filter(const msvs_index_t * ix, const float * q
             fail(MSVS_ERR_INVALID_ARGUMENT, "null index/filter/buffer or negative k");
         if (nq == 0 || k == 0)
             return;
-        check_k((size_t)k);
+        if ((size_t)k > MSVS_MAX_K_ROUNDS)
+            fail(MSVS_ERR_UNSUPPORTED_K, "k = %d exceeds the limit %d", k, MSVS_MAX_K_ROUNDS);
         auto p = parse_params(params);
         for (const auto & kv : p)
             if (kv.first != "nprobe")

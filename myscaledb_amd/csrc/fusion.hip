@@ -13,6 +13,13 @@
 // up in the other list (LDS, <= 256 compares); an entry is the OWNER of its label when it is the vector entry, or a text
 // entry without a vector partner; owners rank themselves against each other by (score desc, label asc) and write themselves
 // to their output slot.  The lists hold distinct labels each (row ids of one search).
+//
+// Longer lists (up to FUSE_LONG_MAX = MSVS_MAX_K_ROUNDS rows each: a hybrid search asks both sides for 3 x LIMIT candidates) take
+// hybrid_fuse_long_kernel: the same arithmetic in the same order, but the all-pairs compares (4096 x 4096) give way to a hash table
+// of the text labels for the partner and a bitonic sort of the owners for the ranks.
+#include <algorithm>
+#include <mutex>
+
 #include "device_ops.hpp"
 
 #pragma clang fp contract(off)
@@ -20,7 +27,10 @@
 namespace msvs
 {
 
-constexpr uint32_t FUSE_MAX = 256; // entries per list (MSVS_MAX_K)
+constexpr uint32_t FUSE_MAX = 256; // entries per list (MSVS_MAX_K) of hybrid_fuse_kernel
+constexpr uint32_t FUSE_LONG_MAX = MSVS_MAX_K_ROUNDS; // ... of hybrid_fuse_long_kernel
+constexpr uint32_t FUSE_LONG_THREADS = 1024;
+constexpr uint64_t FUSE_NO_LABEL = ~0ull; // (labels are row ids >= 0)
 
 struct FuseParams
 {
@@ -160,6 +170,156 @@ static __global__ __launch_bounds__(2 * FUSE_MAX) void hybrid_fuse_kernel(const 
     }
 }
 
+/// The rank order of the output: descending fused score, ties by ascending label; an empty slot sorts behind every entry.
+__device__ __forceinline__ bool fuse_before(const uint64_t la, const float sa, const uint64_t lb, const float sb)
+{
+    if (la == FUSE_NO_LABEL || lb == FUSE_NO_LABEL)
+        return lb == FUSE_NO_LABEL && la != FUSE_NO_LABEL;
+    return sa > sb || (sa == sb && la < lb);
+}
+
+/// Lists of up to FUSE_LONG_MAX rows: one workgroup per query, both lists in LDS (entry i of the vector list at i, of the text list at
+/// P + i, P = the power of two at or above the longer list).
+///   1. list lengths (the first id < 0 ends a list) by an LDS minimum; labels and per-list values as in hybrid_fuse_kernel;
+///   2. the text labels go into an open-addressing hash table (2 P slots: at most half full); every vector entry looks its label up,
+///      adds its partner's value in the prescribed order and takes the partner out of the ranking;
+///   3. the owners (label, fused score) are sorted in place by fuse_before (bitonic, 2 P entries); the first topk leave.
+/// Dynamic LDS sized by P (fuse_long_lds_bytes: 33 P bytes -- 16.5 KB for the 300-row lists of a LIMIT 100 hybrid search, 132 of the
+/// 160 KB at 4096 rows) and min(P, 1024) threads, so that short lists share a CU.
+inline size_t fuse_long_lds_bytes(uint32_t P) { return (size_t)P * (2 * 8 + 2 * 4 + 2 * 4 + 1); }
+
+static __global__ __launch_bounds__(FUSE_LONG_THREADS) void hybrid_fuse_long_kernel(const FuseParams p, const uint32_t P)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char fuse_smem[];
+    uint64_t * const s_label = reinterpret_cast<uint64_t *>(fuse_smem);       // [2 P]
+    float * const s_value = reinterpret_cast<float *>(s_label + 2 * P);       // [2 P]
+    uint32_t * const s_tab = reinterpret_cast<uint32_t *>(s_value + 2 * P);   // [2 P] text entry + 1 (0: empty)
+    uint8_t * const s_taken = reinterpret_cast<uint8_t *>(s_tab + 2 * P);     // [P] text entry has a vector partner
+    __shared__ uint32_t s_n[3];                                               // nv, nt, owners
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, nthreads = blockDim.x;
+    const int64_t * vi = p.vec_ids + (size_t)q * p.kv, * ti = p.txt_ids + (size_t)q * p.kt;
+    const float * vs = p.vec_dis + (size_t)q * p.kv, * ts = p.txt_scores + (size_t)q * p.kt;
+    const uint32_t N = 2 * P, tmask = N - 1;
+    if (tid == 0)
+    {
+        s_n[0] = p.kv;
+        s_n[1] = p.kt;
+        s_n[2] = 0;
+    }
+    for (uint32_t i = tid; i < N; i += nthreads)
+        s_tab[i] = 0;
+    for (uint32_t i = tid; i < P; i += nthreads)
+        s_taken[i] = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < P; i += nthreads)
+    {
+        if (i < p.kv && !(vi[i] > -1))
+            atomicMin(&s_n[0], i);
+        if (i < p.kt && !(ti[i] > -1))
+            atomicMin(&s_n[1], i);
+    }
+    __syncthreads();
+    const uint32_t nv = s_n[0], nt = s_n[1];
+    // labels and values; the text labels enter the table
+    for (uint32_t i = tid; i < P; i += nthreads)
+    {
+        uint64_t lv = FUSE_NO_LABEL, lt = FUSE_NO_LABEL;
+        float xv = 0.f, xt = 0.f;
+        const float r = __fdiv_rn(1.0f, (float)(p.fusion_k + (uint64_t)(i + 1)));
+        if (i < nv)
+        {
+            lv = (uint64_t)vi[i];
+            if (!p.rsf)
+                xv = r;
+            else
+            {
+                const float n = fuse_norm(vs[i], vs[0], vs[nv - 1]);
+                const float w1 = __fsub_rn(1.0f, p.weight);
+                xv = p.direction == -1 ? __fmul_rn(n, w1) : __fmul_rn(__fsub_rn(1.0f, n), w1);
+            }
+        }
+        if (i < nt)
+        {
+            lt = (uint64_t)ti[i];
+            xt = p.rsf ? __fmul_rn(fuse_norm(ts[i], ts[0], ts[nt - 1]), p.weight) : r;
+            uint32_t h = (uint32_t)((lt * 0x9E3779B97F4A7C15ull) >> 40) & tmask;
+            while (atomicCAS(&s_tab[h], 0u, i + 1) != 0u) // (at most nt <= P of the 2 P slots are ever taken: an empty one is found)
+                h = (h + 1) & tmask;
+        }
+        s_label[i] = lv;
+        s_value[i] = xv;
+        s_label[P + i] = lt;
+        s_value[P + i] = xt;
+    }
+    __syncthreads();
+    // the vector entries: RRF (0 + vector) + text; RSF: text assigns, vector adds
+    uint32_t owners = 0;
+    for (uint32_t i = tid; i < nv; i += nthreads)
+    {
+        const uint64_t label = s_label[i];
+        const float value = s_value[i];
+        int partner = -1;
+        uint32_t h = (uint32_t)((label * 0x9E3779B97F4A7C15ull) >> 40) & tmask;
+        for (uint32_t e = s_tab[h]; e != 0u; h = (h + 1) & tmask, e = s_tab[h])
+            if (s_label[P + e - 1] == label)
+            {
+                partner = (int)(e - 1);
+                break;
+            }
+        float score;
+        if (p.rsf)
+            score = partner >= 0 ? __fadd_rn(s_value[P + partner], value) : __fadd_rn(0.0f, value);
+        else
+            score = partner >= 0 ? __fadd_rn(__fadd_rn(0.0f, value), s_value[P + partner]) : __fadd_rn(0.0f, value);
+        if (partner >= 0)
+            s_taken[partner] = 1;
+        s_value[i] = score; // (the vector half: nobody reads it in this phase)
+        owners++;
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < nt; i += nthreads)
+    {
+        if (s_taken[i])
+            s_label[P + i] = FUSE_NO_LABEL;
+        else
+        {
+            s_value[P + i] = p.rsf ? s_value[P + i] : __fadd_rn(0.0f, s_value[P + i]);
+            owners++;
+        }
+    }
+    if (owners)
+        atomicAdd(&s_n[2], owners);
+    __syncthreads();
+    // bitonic sort of the 2 P (label, score) entries, best first
+    for (uint32_t k2 = 2; k2 <= N; k2 <<= 1)
+        for (uint32_t j = k2 >> 1; j > 0; j >>= 1)
+        {
+            for (uint32_t t = tid; t < P; t += nthreads)
+            {
+                const uint32_t a = 2 * j * (t / j) + (t & (j - 1)), b = a + j;
+                const bool up = (a & k2) == 0;
+                const uint64_t la = s_label[a], lb = s_label[b];
+                const float sa = s_value[a], sb = s_value[b];
+                if (up ? fuse_before(lb, sb, la, sa) : fuse_before(la, sa, lb, sb))
+                {
+                    s_label[a] = lb;
+                    s_label[b] = la;
+                    s_value[a] = sb;
+                    s_value[b] = sa;
+                }
+            }
+            __syncthreads();
+        }
+    const uint32_t n = s_n[2] < p.topk ? s_n[2] : p.topk;
+    if (tid == 0)
+        p.n_out[q] = n;
+    for (uint32_t r = tid; r < p.topk; r += nthreads)
+    {
+        p.out_scores[(size_t)q * p.topk + r] = r < n ? s_value[r] : 0.f;
+        p.out_labels[(size_t)q * p.topk + r] = r < n ? (int64_t)s_label[r] : -1;
+    }
+}
+
 }
 
 using namespace msvs;
@@ -174,8 +334,8 @@ extern "C" int msvs_hybrid_fuse_device(int fusion_type, const float * d_vec_dis,
             return;
         if (!d_vec_dis || !d_vec_ids || !d_txt_scores || !d_txt_ids || !d_out_scores || !d_out_labels || !d_n_out || topk == 0)
             fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer or topk = 0");
-        if (kv > FUSE_MAX || kt > FUSE_MAX || topk > 2 * FUSE_MAX)
-            fail(MSVS_ERR_UNSUPPORTED_K, "the device fusion takes lists of at most %u rows", FUSE_MAX);
+        if (kv > FUSE_LONG_MAX || kt > FUSE_LONG_MAX || topk > FUSE_LONG_MAX)
+            fail(MSVS_ERR_UNSUPPORTED_K, "the device fusion takes lists and a topk of at most %u rows", FUSE_LONG_MAX);
         if (fusion_type != 0 && fusion_type != 1)
             fail(MSVS_ERR_INVALID_ARGUMENT, "fusion_type: 0 = RRF, 1 = RSF");
         FuseParams p{};
@@ -194,7 +354,21 @@ extern "C" int msvs_hybrid_fuse_device(int fusion_type, const float * d_vec_dis,
         p.out_scores = d_out_scores;
         p.out_labels = d_out_labels;
         p.n_out = d_n_out;
-        hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nq), dim3(2 * FUSE_MAX), 0, reinterpret_cast<hipStream_t>(hip_stream), p);
+        if (kv <= FUSE_MAX && kt <= FUSE_MAX && topk <= 2 * FUSE_MAX)
+            hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nq), dim3(2 * FUSE_MAX), 0, reinterpret_cast<hipStream_t>(hip_stream), p);
+        else
+        {
+            uint32_t P = 2 * FUSE_MAX;
+            while (P < std::max(kv, kt))
+                P *= 2;
+            static std::once_flag once; // more than 64 KiB of dynamic LDS needs the attribute raised once
+            std::call_once(once, [] {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hybrid_fuse_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)fuse_long_lds_bytes(FUSE_LONG_MAX));
+            });
+            hipLaunchKernelGGL(hybrid_fuse_long_kernel, dim3((unsigned)nq), dim3(std::min(P, FUSE_LONG_THREADS)), fuse_long_lds_bytes(P),
+                               reinterpret_cast<hipStream_t>(hip_stream), p, P);
+        }
         MSVS_HIP(hipGetLastError());
     });
 }

@@ -241,6 +241,9 @@ void index_search_filtered(const msvs_index & ix, const float * d_queries, size_
 /// exact rounds for large k.
 int index_search_host_call(const msvs_index_t * ix, const float * queries, size_t nq, int k, const char * params,
                            const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+/// MSVS_MAX_K < k <= MSVS_MAX_K_ROUNDS, device pointers (search_entry.hip): exact rounds of MSVS_MAX_K ranks, one query at a time.
+void index_search_rounds(const msvs_index & ix, const float * d_queries, size_t nq, size_t k, size_t nprobe, const uint64_t * eff,
+                         size_t eff_bits, int64_t * d_ids, float * d_dis, hipStream_t stream);
 /// Canonical merge of nparts partial top-k lists per query (shard.hip); strides in elements between the parts' [nq][k] arrays.
 void merge_topk_device(const int64_t * d_ids, size_t ids_stride, const float * d_dis, size_t dis_stride, size_t nparts, size_t nq,
                        size_t k, int metric, int64_t * d_out_ids, float * d_out_dis, hipStream_t stream);

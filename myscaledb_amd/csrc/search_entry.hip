@@ -412,6 +412,49 @@ void flat_few_search_host(const msvs_index & ix, const float * queries, size_t n
 }
 }
 
+namespace msvs
+{
+/// k beyond one wavefront top-k pass (MSVS_MAX_K < k <= MSVS_MAX_K_ROUNDS), all pointers on the device: rounds of MSVS_MAX_K per
+/// query, each round excluding the rows already returned through a private copy of the filter bitmap (exact: round r returns ranks
+/// 256r .. 256r+255).  `eff` is the effective filter (nullable); the ids are the index's own (apply_row_ids_map comes after).  The
+/// host-pointer search and the device entries share it.  One query at a time: batch-wide rounds, as the BM25 side runs them
+/// (bm25.hip), are not built for the vector search.  The round bitmap lives in an arena of its own (rounds_for): everything is enqueued
+/// on `stream`, nothing waits for the device once the arena has its size.
+void index_search_rounds(const msvs_index & ix, const float * d_queries, size_t nq, size_t k, size_t nprobe, const uint64_t * eff,
+                         size_t eff_bits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+{
+    if (!ix.ready)
+        fail(MSVS_ERR_NOT_READY, "index is not ready");
+    if (k > MSVS_MAX_K_ROUNDS)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the limit %d", k, MSVS_MAX_K_ROUNDS);
+    const bool eff_filtered = eff != nullptr;
+    const size_t idspace = std::max<size_t>(eff_filtered ? eff_bits : 0, (size_t)ix.max_id + 1);
+    const size_t bw = ceil_div(idspace, 64);
+    Scratch & rs = rounds_for(stream);
+    rs.reserve(bw * 8 + 256, stream);
+    const DevView<uint64_t> bm{rs.take<uint64_t>(bw)};
+    for (size_t q = 0; q < nq; q++)
+    {
+        if (eff_filtered)
+        {
+            MSVS_HIP(hipMemsetAsync(bm.p, 0, bw * 8, stream));
+            MSVS_HIP(hipMemcpyAsync(bm.p, eff, std::max<size_t>(1, ceil_div(eff_bits, (size_t)64)) * 8, hipMemcpyDeviceToDevice, stream));
+        }
+        else
+            MSVS_HIP(hipMemsetAsync(bm.p, 0xFF, bw * 8, stream));
+        for (size_t done = 0; done < k; done += MSVS_MAX_K)
+        {
+            const uint32_t kr = (uint32_t)std::min<size_t>(MSVS_MAX_K, k - done);
+            int64_t * oi = d_ids + q * k + done;
+            index_search_device(ix, d_queries + q * ix.dim, 1, kr, nprobe, bm.p, eff_filtered ? eff_bits : idspace, oi,
+                                d_dis + q * k + done, stream);
+            hipLaunchKernelGGL(clear_bits_kernel, dim3(1), dim3(256), 0, stream, bm.p, oi, kr);
+            MSVS_HIP(hipGetLastError());
+        }
+    }
+}
+}
+
 extern "C" int msvs_index_search_device(const msvs_index_t * ix, const float * d_queries, size_t nq, int k, int nprobe,
                                         const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
                                         void * hip_stream)
@@ -422,7 +465,9 @@ extern "C" int msvs_index_search_device(const msvs_index_t * ix, const float * d
         const auto meta = ix->get_meta();
         size_t eff_bits = nbits;
         const uint64_t * eff = effective_filter(*ix, meta.get(), d_alive_bits, nbits, &eff_bits, as_stream(hip_stream));
-        if (k > 0 && lat_eligible(*ix, nq, (size_t)k, (size_t)std::max(nprobe, 0)) && ix->ld == ix->dim && ix->metric != MSVS_METRIC_COSINE)
+        if ((size_t)k > MSVS_MAX_K)
+            index_search_rounds(*ix, d_queries, nq, (size_t)k, (size_t)std::max(nprobe, 1), eff, eff_bits, d_ids, d_dis, as_stream(hip_stream));
+        else if (k > 0 && lat_eligible(*ix, nq, (size_t)k, (size_t)std::max(nprobe, 0)) && ix->ld == ix->dim && ix->metric != MSVS_METRIC_COSINE)
             // a few scan-ready queries: two launches (latency_kernels.hpp)
             lat_launch(*ix, lat_ctx(as_stream(hip_stream)), d_queries, nq, (uint32_t)k, (size_t)std::max(nprobe, 0), eff, eff_bits, d_ids,
                        d_dis, nullptr, 0, as_stream(hip_stream));
@@ -545,33 +590,7 @@ int index_search_host_call(const msvs_index_t * ix, const float * queries, size_
         else if ((size_t)k <= MSVS_MAX_K)
             index_search_device(*ix, dq.p, nq, (uint32_t)k, (size_t)nprobe, eff, eff_bits, d_ids.p, d_dis.p, stream);
         else
-        {
-            // k beyond one wavefront top-k pass: rounds of MSVS_MAX_K per query, each round excluding the rows already
-            // returned through a private copy of the filter bitmap (exact: round r returns ranks 256r .. 256r+255)
-            const size_t idspace = std::max<size_t>(eff_filtered ? eff_bits : 0, (size_t)ix->max_id + 1);
-            const size_t bw = ceil_div(idspace, 64);
-            DevBuf<uint64_t> bm(bw);
-            for (size_t q = 0; q < nq; q++)
-            {
-                if (eff_filtered)
-                {
-                    MSVS_HIP(hipMemsetAsync(bm.p, 0, bw * 8, stream));
-                    MSVS_HIP(hipMemcpyAsync(bm.p, eff, std::max<size_t>(1, ceil_div(eff_bits, (size_t)64)) * 8,
-                                            hipMemcpyDeviceToDevice, stream));
-                }
-                else
-                    MSVS_HIP(hipMemsetAsync(bm.p, 0xFF, bw * 8, stream));
-                for (size_t done = 0; done < (size_t)k; done += MSVS_MAX_K)
-                {
-                    const uint32_t kr = (uint32_t)std::min<size_t>(MSVS_MAX_K, (size_t)k - done);
-                    int64_t * oi = d_ids.p + q * (size_t)k + done;
-                    index_search_device(*ix, dq.p + q * ix->dim, 1, kr, (size_t)nprobe, bm.p, eff_filtered ? eff_bits : idspace,
-                                        oi, d_dis.p + q * (size_t)k + done, stream);
-                    hipLaunchKernelGGL(clear_bits_kernel, dim3(1), dim3(256), 0, stream, bm.p, oi, kr);
-                    MSVS_HIP(hipGetLastError());
-                }
-            }
-        }
+            index_search_rounds(*ix, dq.p, nq, (size_t)k, (size_t)nprobe, eff, eff_bits, d_ids.p, d_dis.p, stream);
         apply_row_ids_map(meta.get(), d_ids.p, nq * (size_t)k, stream);
         MSVS_HIP(hipMemcpyAsync(ids, d_ids.p, nq * (size_t)k * 8, hipMemcpyDeviceToHost, stream));
         MSVS_HIP(hipMemcpyAsync(dis, d_dis.p, nq * (size_t)k * 4, hipMemcpyDeviceToHost, stream));
