@@ -140,6 +140,59 @@ MSVS_API int msvs_bin_index_search_params(const msvs_bin_index_t * index, const 
 MSVS_API int msvs_bin_index_export(const msvs_bin_index_t * index, uint8_t * centroids, int64_t * list_off, uint8_t * rows,
                                    int64_t * labels);
 
+/* IVFSQ -- an inverted-file index of Float32 vectors that keeps 8-bit residual codes ONLY (no f32 row survives build): dim bytes
+ * (padded to 16) + a u32 label per row.  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All arithmetic
+ * is f32 with separately rounded operations (fl), no fma, IEEE division:
+ *   - contents: nlist centroids c_l; ONE quantiser vmin[j], vmax[j] per dimension, step[j] = fl(fl(vmax[j] - vmin[j]) / 255);
+ *     per row its list, label and dim codes; rows inside a list in ascending label order;
+ *   - stored row x: the row as fed (L2, IP) or the normalised row (cosine; msvs_normalize_f32's arithmetic);
+ *   - encode in list l: r = fl(x_j - c_lj), t = fl(fl(r - vmin[j]) / step[j]), code = min(255, max(0, rint(t))) (ties to even),
+ *     0 where step[j] == 0; rows outside the trained range are clamped;
+ *   - decode: x^_j = fl(c_lj + fl(vmin[j] + fl(float(code) * step[j])));
+ *   - search = the IVFFLAT search of the decoded rows: the canonical exact top-min(nprobe, nlist) lists by (distance to the
+ *     centroid, list id), every alive row of them scored with the canonical scan arithmetic over x^, top-k by (distance, label),
+ *     unfilled slots -1 and the metric's neutral value; cosine normalises the query, searches with IP and reports fl(1 - ip) in
+ *     every slot; the filter is indexed by label.  The search over what the index stores is exact; the quantiser is lossy.
+ *   - a row is assigned to its nearest centroid by L2 (L2 indexes) or by inner product (IP and cosine), as msvs_index_add does.
+ * create: params as msvs_index_create's for IVFFLAT (ncentroids, kmeans_iters, train_sample, seed, ...).  dim is bounded by the
+ *   scan's LDS stage (round_up(dim, 16) <= 2240), checked here and at load.
+ * train: the IVFFLAT k-means over the rows, then vmin / vmax = exact minimum / maximum of the residuals of ALL n training rows
+ *   against their assigned centroids; the same input gives the same bits.  set_codebook: centroids and quantiser from the caller.
+ *   (vmin / vmax must be finite with vmax >= vmin: MSVS_ERR_INVALID_ARGUMENT otherwise).  Both must precede add
+ *   (MSVS_ERR_NOT_READY from add before either).
+ * add: any number of chunks before build; rows are encoded as they arrive, only codes, lists and labels are staged.  ids: labels
+ *   in [0, 2^32 - 1) (MSVS_ERR_ID_RANGE otherwise), NULL = staging order; labels are expected to be distinct, as for
+ *   msvs_index_add (a repeated label is not rejected).
+ * search (host pointers): params "nprobe=P" (default 1).  search_device: device pointers, enqueued on hip_stream without host
+ *   synchronisation.  k <= MSVS_MAX_K and min(nprobe, nlist) <= MSVS_MAX_K (MSVS_ERR_UNSUPPORTED_K); k = 0 or nq = 0 is a no-op;
+ *   before build: MSVS_ERR_NOT_READY.
+ * export: centroids nlist * dim, vmin / vmax dim each, nlist + 1 offsets, codes n * dim in NATURAL column order, labels n; any
+ *   output may be NULL.
+ * memory_usage after build <= n * (round_up(dim, 16) + 8) + the centroids, quantiser and offsets + 4096 bytes.
+ * Files "sq_data" / "sq_ids" through the caller's stream openers (a built index only); load validates sizes, offsets, labels and
+ * a checksum of each header: a corrupt or truncated file is MSVS_ERR_IO. */
+typedef struct msvs_sq_index msvs_sq_index_t;
+MSVS_API int msvs_sq_index_create(int metric, size_t dim, const char * params, msvs_sq_index_t ** out);
+MSVS_API void msvs_sq_index_free(msvs_sq_index_t * index);
+MSVS_API int msvs_sq_index_train(msvs_sq_index_t * index, const float * x, size_t n, int mem);
+MSVS_API int msvs_sq_index_set_codebook(msvs_sq_index_t * index, const float * centroids, size_t nlist, const float * vmin,
+                                        const float * vmax, int mem);
+MSVS_API int msvs_sq_index_add(msvs_sq_index_t * index, const float * x, const int64_t * ids, size_t n, int mem);
+MSVS_API int msvs_sq_index_build(msvs_sq_index_t * index);
+MSVS_API int msvs_sq_index_ready(const msvs_sq_index_t * index);
+MSVS_API size_t msvs_sq_index_num_data(const msvs_sq_index_t * index);
+MSVS_API size_t msvs_sq_index_num_lists(const msvs_sq_index_t * index);
+MSVS_API size_t msvs_sq_index_memory_usage(const msvs_sq_index_t * index);
+MSVS_API int msvs_sq_index_search(const msvs_sq_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
+                                  const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_sq_index_search_device(const msvs_sq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t nprobe,
+                                         const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                         void * hip_stream);
+MSVS_API int msvs_sq_index_export(const msvs_sq_index_t * index, float * centroids, float * vmin, float * vmax, int64_t * list_off,
+                                  uint8_t * codes, int64_t * ids);
+MSVS_API int msvs_sq_index_serialize_io(const msvs_sq_index_t * index, const struct msvs_io * io);
+MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t ** out);
+
 /* Resident blocks for the brute-force path: the GPU analogue of VICacheManager / VIWithMeta
  * (src/VectorIndex/Cache/VICacheObject.h:40-162) for the dense block a mark of a part turns into
  * (MergeTreeVSManager.cpp:1380-1392).  msvs_knn_f32 moves that block over PCIe on every query; here it is uploaded

@@ -37,6 +37,9 @@ SYMBOLS = [
     "msvs_bin_index_add", "msvs_bin_index_num_data", "msvs_bin_index_search", "msvs_bin_index_serialize_io", "msvs_bin_index_load_io",
     "msvs_bin_index_create_ivf", "msvs_bin_index_train", "msvs_bin_index_set_centroids", "msvs_bin_index_num_lists",
     "msvs_bin_index_search_params", "msvs_bin_index_export",
+    "msvs_sq_index_create", "msvs_sq_index_free", "msvs_sq_index_train", "msvs_sq_index_set_codebook", "msvs_sq_index_add",
+    "msvs_sq_index_build", "msvs_sq_index_ready", "msvs_sq_index_num_data", "msvs_sq_index_num_lists", "msvs_sq_index_memory_usage",
+    "msvs_sq_index_search", "msvs_sq_index_search_device", "msvs_sq_index_export", "msvs_sq_index_serialize_io", "msvs_sq_index_load_io",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
     "msvs_comm_free", "msvs_comm_all_reduce_u64", "msvs_comm_rank", "msvs_comm_size", "msvs_shard_search_device", "msvs_shard_search_device_async", "msvs_shard_search_drain", "msvs_shard_search_routed_device",
@@ -271,6 +274,112 @@ class BinIndex:
             _lib.msvs_bin_index_free.argtypes = [C.c_void_p]
             _lib.msvs_bin_index_free.restype = None
             _lib.msvs_bin_index_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class SqIndex:
+    """msvs_sq_index_t: the IVFSQ index -- coarse centroids, one per-dimension 8-bit quantiser of the residuals, and per row its
+    list, label and dim code bytes (no f32 row is kept).  params as Index's for IVFFLAT ("ncentroids=N,kmeans_iters=I,...")."""
+
+    def __init__(self, metric, dim, params="", _handle=None):
+        self.metric, self.dim = int(metric), int(dim)
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            _check(lib().msvs_sq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
+
+    def _size(self, name):
+        fn = getattr(lib(), name)
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_void_p]
+        return fn(self._h)
+
+    def train(self, x):
+        x = _f32(x).reshape(-1, self.dim)
+        _check(lib().msvs_sq_index_train(self._h, _p(x, C.c_float), C.c_size_t(x.shape[0]), MEM_HOST))
+
+    def set_codebook(self, centroids, vmin, vmax):
+        c = _f32(centroids).reshape(-1, self.dim)
+        lo, hi = _f32(vmin).reshape(self.dim), _f32(vmax).reshape(self.dim)
+        _check(lib().msvs_sq_index_set_codebook(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(lo, C.c_float), _p(hi, C.c_float),
+                                                MEM_HOST))
+
+    def add(self, x, ids=None):
+        x = _f32(x).reshape(-1, self.dim)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int64)
+        _check(lib().msvs_sq_index_add(self._h, _p(x, C.c_float), _p(ids, C.c_int64), C.c_size_t(x.shape[0]), MEM_HOST))
+
+    def build(self):
+        _check(lib().msvs_sq_index_build(self._h))
+
+    @property
+    def ready(self):
+        lib().msvs_sq_index_ready.argtypes = [C.c_void_p]
+        return bool(lib().msvs_sq_index_ready(self._h))
+
+    @property
+    def num_data(self):
+        return self._size("msvs_sq_index_num_data")
+
+    @property
+    def num_lists(self):
+        return self._size("msvs_sq_index_num_lists")
+
+    @property
+    def memory_usage(self):
+        return self._size("msvs_sq_index_memory_usage")
+
+    def search(self, queries, k, params="", alive=None, nbits=None):
+        """params: "nprobe=P"; alive: bool over labels, nbits: how many of them the filter covers (default all of `alive`)."""
+        q = _f32(queries).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), np.int64)
+        dis = np.empty((q.shape[0], k), np.float32)
+        bits = None if alive is None else pack_bits(alive)
+        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
+        _check(lib().msvs_sq_index_search(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), params.encode(),
+                                          _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        return ids, dis
+
+    def search_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """All arguments are raw device addresses (ints); enqueues on `stream` and returns immediately."""
+        _check(lib().msvs_sq_index_search_device(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(nprobe),
+                                                 C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
+                                                 C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
+                                                 C.c_void_p(int(stream)) if stream else None))
+
+    def export(self, with_lists=True):
+        """-> (centroids [nlist, dim], vmin [dim], vmax [dim], list offsets [nlist + 1], codes [n, dim] u8 in natural column order,
+        labels [n]) in list-major order; with_lists=False (an index not built yet): the codebook only, None for the rest."""
+        nl, d = self.num_lists, self.dim
+        cent = np.empty((nl, d), np.float32)
+        lo, hi = np.empty(d, np.float32), np.empty(d, np.float32)
+        off = codes = labels = None
+        if with_lists:
+            n = self.num_data
+            off, codes, labels = np.empty(nl + 1, np.int64), np.empty((n, d), np.uint8), np.empty(n, np.int64)
+        _check(lib().msvs_sq_index_export(self._h, _p(cent, C.c_float), _p(lo, C.c_float), _p(hi, C.c_float), _p(off, C.c_int64),
+                                          _p(codes, C.c_uint8), _p(labels, C.c_int64)))
+        return cent, lo, hi, off, codes, labels
+
+    def serialize_io(self, store):
+        """msvs_sq_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""
+        _check(lib().msvs_sq_index_serialize_io(self._h, C.byref(_DictIO(store).io)))
+
+    @classmethod
+    def load_io(cls, store, metric, dim):
+        h = C.c_void_p()
+        _check(lib().msvs_sq_index_load_io(C.byref(_DictIO(store).io), C.byref(h)))
+        return cls(metric, dim, _handle=h)
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.msvs_sq_index_free.argtypes = [C.c_void_p]
+            _lib.msvs_sq_index_free.restype = None
+            _lib.msvs_sq_index_free(self._h)
             self._h = None
 
     __del__ = close

@@ -259,6 +259,7 @@ struct Options
     double pinned_fetch = 1;     // small host -> device hand-overs out of pinned memory by a copy kernel instead of hipMemcpyAsync (device_ops.hpp: fetch_from_pinned)
     double pinned_fetch_max = 1048576; // ... up to this many bytes
     double bin_ivf_rpb = 0;     // partitioned binary index: rows per work item of the list scan (0 = planned: <= ~8 segments per list, >= 2048 rows; tests: small segments)
+    double sq_ivf_rpb = 0;      // IVFSQ index: rows per work item of the list scan (0 = planned, as bin_ivf_rpb; tests: several segments per short list)
     double route_self_rccl = 0; // routed sharded search over an RCCL communicator: a rank's OWN piece also travels through ncclSend / ncclRecv (to itself, grouped)
                                 // instead of a device copy -- lets one rank on a 1-GPU box execute the point-to-point group path (tests)
 };

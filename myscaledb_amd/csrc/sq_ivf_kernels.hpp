@@ -1,0 +1,327 @@
+// sq_ivf_kernels.hpp -- device code of the IVFSQ index (sq_index.hip): 8-bit residual codes are ALL the index keeps of a row.
+//
+//   quantiser : one per index, vmin[j] / step[j] per dimension, step = fl(fl(vmax - vmin) / 255);
+//   encode    : r = fl(x - c_l), t = fl(fl(r - vmin) / step), code = min(255, max(0, rint(t))), 0 where step == 0;
+//   decode    : x^ = fl(c_l + fl(vmin + fl(float(code) * step)));
+//   search    : the canonical arithmetic of scan_rows (scan_kernels.hpp) over the DECODED rows -- a 16-lane group owns a row, lane g
+//               owns float4 columns g, g + 16, ...; only the origin of the row operand differs (decoded in registers instead of
+//               loaded), so ids and distances are those of oracle.ivf_search over the decoded matrix, bit for bit.
+//
+// Stored row: ldc = round_up(dim, 16) bytes.  Inside every whole block of 256 columns the bytes are permuted so that the 16 bytes at
+// offset 256 b + 16 g are the four float4 columns 64 b + g, + 16, + 32, + 48 of lane g (one 16-byte load = four of the lane's own
+// columns, in its accumulation order); the tail (ldc mod 256 bytes) stays in natural order and a lane reads one 32-bit word per
+// column there.  sq_stored_pos is the map, used by the encoder and undone by the export.
+#pragma once
+
+#include "scan_kernels.hpp"
+
+namespace msvs
+{
+
+/// byte of natural column j (< ldc) inside a stored row of ldc bytes
+__host__ __device__ inline uint32_t sq_stored_pos(uint32_t j, uint32_t ldc)
+{
+    if (j >= (ldc & ~255u))
+        return j;
+    const uint32_t c = (j & 255u) >> 2; // float4 column inside the block
+    return (j & ~255u) + ((c & 15u) << 4) + ((c >> 4) << 2) + (j & 3u);
+}
+
+// ------------------------------------------------------------------------------------------ range of the training residuals
+
+/// omin[j] / omax[j] = min / max over the rows of f2ord(fl(x_j - c_lj)) (ordered-float atomics; omin starts at 0xFFFFFFFF, omax at 0).
+/// A block takes `rows_per_block` rows, thread t the columns t, t + 256, ...: one pair of atomics per (block, column).
+static __global__ __launch_bounds__(BLOCK) void sq_range_kernel(const float * X, const int32_t * list, const float * C, size_t n, uint32_t d,
+                                                                uint32_t ld, uint32_t rows_per_block, uint32_t * omin, uint32_t * omax)
+{
+    const size_t r0 = (size_t)blockIdx.x * rows_per_block;
+    const size_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+    for (uint32_t j = threadIdx.x; j < d; j += BLOCK)
+    {
+        uint32_t lo = 0xFFFFFFFFu, hi = 0;
+        for (size_t r = r0; r < r1; r++)
+        {
+            const float v = __fsub_rn(X[r * ld + j], C[(size_t)list[r] * ld + j]);
+            if (v == v) // (a NaN has no place in a range)
+            {
+                const uint32_t o = f2ord(v);
+                lo = o < lo ? o : lo;
+                hi = o > hi ? o : hi;
+            }
+        }
+        if (lo <= hi)
+        {
+            atomicMin(&omin[j], lo);
+            atomicMax(&omax[j], hi);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------ encode
+
+/// codes[r][sq_stored_pos(j)] = code of column j of row r against the centroid of list[r]; columns d .. ldc - 1 are 0.
+/// One thread per (row, natural column).
+static __global__ __launch_bounds__(BLOCK) void sq_encode_kernel(const float * X, const int32_t * list, const float * C, const float * vmin,
+                                                                 const float * step, size_t n, uint32_t d, uint32_t ld, uint32_t ldc,
+                                                                 uint8_t * codes)
+{
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n * ldc)
+        return;
+    const size_t r = i / ldc;
+    const uint32_t j = (uint32_t)(i - r * ldc);
+    float code = 0.f;
+    if (j < d)
+    {
+        const float st = step[j];
+        if (st != 0.f)
+        {
+            const float res = __fsub_rn(X[r * ld + j], C[(size_t)list[r] * ld + j]);
+            const float t = __fdiv_rn(__fsub_rn(res, vmin[j]), st);
+            code = fminf(255.f, fmaxf(0.f, rintf(t))); // rintf: to nearest, ties to even
+        }
+    }
+    codes[r * ldc + sq_stored_pos(j, ldc)] = (uint8_t)code;
+}
+
+/// dst[pos[i]] = src[i] for rows of ld16 16-byte words (the staged chunks into their list-major places)
+static __global__ void sq_scatter_rows_kernel(const uint4 * src, uint4 * dst, const uint32_t * pos, size_t n, uint32_t ld16)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * ld16)
+        return;
+    const size_t r = i / ld16;
+    dst[(size_t)pos[r] * ld16 + (i - r * ld16)] = src[i];
+}
+
+// ------------------------------------------------------------------------------------------ list scan
+
+struct SqIvfParams
+{
+    const uint4 * codes;     // rows, list-major, ld4 / 4 uint4 each (stored order)
+    const uint32_t * labels; // label of row r
+    const uint64_t * alive;  // nullable filter bitmap over labels
+    const float4 * Q;        // queries, ld4 float4 each (zero padded)
+    const float4 * cent;     // [nlist][ld4]
+    const float4 * vmin, * step; // [ld4], zero padded
+    uint64_t * partial;      // [(pair * seg_max + segment)][k]
+    uint32_t nbits, ld4, k;
+    uint32_t nprobe;         // probes per query (pair i = q * nprobe + p)
+    uint32_t nlist, rows_per_block, seg_max;
+    const int64_t * list_off; // [nlist + 1]
+    const uint32_t * pair_off, * work_off, * pairs; // the plan (IvfPlanParams)
+};
+
+/// LDS bytes of a scan block: the tile's queries, the list's centroid, vmin, step, and the merge lists.
+inline size_t sq_lds_bytes(uint32_t T, uint32_t ld4, uint32_t k) { return (size_t)(T + 3) * ld4 * 16 + (size_t)T * 5 * k * 8; }
+
+/// grid: any size; slot -> work item (list, query tile, row segment) as in ivf_batched_scan_kernel (an XCD walks one contiguous range).
+/// dynamic LDS: sq_lds_bytes(T, ld4, k).
+template <int METRIC, int T, int R>
+__global__ __launch_bounds__(BLOCK) void sq_ivf_scan_kernel(const SqIvfParams a)
+{
+    const uint32_t ld4 = a.ld4, k = a.k;
+    float4 * qs = reinterpret_cast<float4 *>(msvs_smem);     // [T][ld4]
+    float4 * cs = qs + (size_t)T * ld4;                      // [ld4] centroid of the item's list
+    float4 * vm = cs + ld4;                                  // [ld4]
+    float4 * st = vm + ld4;                                  // [ld4]
+    uint64_t * lds_merge = reinterpret_cast<uint64_t *>(st + ld4);
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, g = lane & 15;
+    const uint32_t ld16 = ld4 >> 2;       // 16-byte words per stored row
+    const uint32_t nb = ld4 >> 6;         // whole 256-column blocks
+    const uint32_t nu = nb + ((ld4 & 63) ? 1 : 0); // units per row: the blocks, then the tail
+    for (uint32_t c = tid; c < ld4; c += BLOCK)
+    {
+        vm[c] = a.vmin[c];
+        st[c] = a.step[c];
+    }
+
+    auto fma4 = [&](float4 & s, const float4 q, const float4 y) {
+        if (METRIC == M_L2)
+        {
+            float dx = __fsub_rn(q.x, y.x), dy = __fsub_rn(q.y, y.y), dz = __fsub_rn(q.z, y.z), dw = __fsub_rn(q.w, y.w);
+            s.x = __fadd_rn(s.x, __fmul_rn(dx, dx));
+            s.y = __fadd_rn(s.y, __fmul_rn(dy, dy));
+            s.z = __fadd_rn(s.z, __fmul_rn(dz, dz));
+            s.w = __fadd_rn(s.w, __fmul_rn(dw, dw));
+        }
+        else
+        {
+            s.x = __fadd_rn(s.x, __fmul_rn(q.x, y.x));
+            s.y = __fadd_rn(s.y, __fmul_rn(q.y, y.y));
+            s.z = __fadd_rn(s.z, __fmul_rn(q.z, y.z));
+            s.w = __fadd_rn(s.w, __fmul_rn(q.w, y.w));
+        }
+    };
+    // four codes (one float4 column) -> the decoded column
+    auto decode4 = [&](uint32_t w, uint32_t col) {
+        const float4 c = cs[col], m = vm[col], s = st[col];
+        float4 y;
+        y.x = __fadd_rn(c.x, __fadd_rn(m.x, __fmul_rn((float)(w & 255u), s.x)));
+        y.y = __fadd_rn(c.y, __fadd_rn(m.y, __fmul_rn((float)((w >> 8) & 255u), s.y)));
+        y.z = __fadd_rn(c.z, __fadd_rn(m.z, __fmul_rn((float)((w >> 16) & 255u), s.z)));
+        y.w = __fadd_rn(c.w, __fadd_rn(m.w, __fmul_rn((float)(w >> 24), s.w)));
+        return y;
+    };
+
+    const uint32_t total = a.work_off[a.nlist];
+    const uint32_t per_xcd = (total + 7) / 8;
+    for (uint32_t s = blockIdx.x; s < 8 * per_xcd; s += gridDim.x)
+    {
+        const uint32_t w = (s & 7) * per_xcd + (s >> 3);
+        if (w >= total)
+            continue;
+        uint32_t lo = 0, hi = a.nlist; // the list owning work item w: work_off[l] <= w < work_off[l + 1]
+        while (hi - lo > 1)
+        {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.work_off[mid] <= w)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint32_t l = lo;
+        const uint32_t lbeg = (uint32_t)a.list_off[l], lend = (uint32_t)a.list_off[l + 1];
+        const uint32_t local = w - a.work_off[l];
+        const uint32_t p0 = a.pair_off[l], pe = a.pair_off[l + 1];
+        const uint32_t ntile = (pe - p0 + T - 1) / T;
+        const uint32_t seg = local / ntile, tile = local - seg * ntile;
+        const uint32_t pb = p0 + tile * T;
+        const uint32_t row_begin = lbeg + seg * a.rows_per_block;
+        const uint32_t row_end = min(row_begin + a.rows_per_block, lend);
+        uint64_t * out[T];
+        __syncthreads(); // the previous item is done with the LDS
+#pragma unroll
+        for (int t = 0; t < T; t++)
+        {
+            const uint32_t pi = pb + t < pe ? pb + t : pe - 1; // short tiles repeat their last pair (same slot, same values)
+            const uint32_t qp = a.pairs[pi];
+            out[t] = a.partial + ((size_t)qp * a.seg_max + seg) * k;
+            const float4 * src = a.Q + (size_t)(qp / a.nprobe) * ld4;
+            for (uint32_t c = tid; c < ld4; c += BLOCK)
+                qs[t * ld4 + c] = src[c];
+        }
+        for (uint32_t c = tid; c < ld4; c += BLOCK)
+            cs[c] = a.cent[(size_t)l * ld4 + c];
+        __syncthreads();
+
+        WaveTopK<R> top[T];
+#pragma unroll
+        for (int t = 0; t < T; t++)
+            top[t].init();
+
+        // unit u of the row of this lane's group at step `base`: a whole block -> the lane's 16 bytes of it; the tail -> one 32-bit word
+        // per column the lane owns there (0 beyond the row)
+        auto load_unit = [&](uint32_t base, uint32_t u) {
+            const uint32_t r = min(base + grp, row_end - 1);
+            const uint4 * row = a.codes + (size_t)r * ld16;
+            if (u < nb)
+                return row[u * 16 + g];
+            const uint32_t * tail = reinterpret_cast<const uint32_t *>(row) + nb * 64;
+            const uint32_t tc = ld4 & 63;
+            uint4 v;
+            v.x = g < tc ? tail[g] : 0u;
+            v.y = g + 16 < tc ? tail[g + 16] : 0u;
+            v.z = g + 32 < tc ? tail[g + 32] : 0u;
+            v.w = g + 48 < tc ? tail[g + 48] : 0u;
+            return v;
+        };
+
+        uint32_t base = row_begin + wave * 4;
+        uint4 wnext = make_uint4(0, 0, 0, 0);
+        if (base < row_end)
+            wnext = load_unit(base, 0);
+        for (; base < row_end; base += 16)
+        {
+            const uint32_t r = base + grp;
+            const bool rv = r < row_end;
+            float4 acc[T];
+#pragma unroll
+            for (int t = 0; t < T; t++)
+                acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (uint32_t u = 0; u < nu; u++)
+            {
+                const uint4 cw = wnext;
+                // the next unit's codes are on their way while this one is decoded: the row's next unit, or the next step's first
+                if (u + 1 < nu)
+                    wnext = load_unit(base, u + 1);
+                else if (base + 16 < row_end)
+                    wnext = load_unit(base + 16, 0);
+                const uint32_t col0 = u * 64 + g; // the lane's columns of this unit: col0, + 16, + 32, + 48 (ascending)
+                const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                {
+                    const uint32_t col = col0 + 16 * e;
+                    if (col < ld4)
+                    {
+                        const float4 y = decode4(words[e], col);
+#pragma unroll
+                        for (int t = 0; t < T; t++)
+                            fma4(acc[t], qs[t * ld4 + col], y);
+                    }
+                }
+            }
+            // id + filter of the finished row (lane g == 0 of its group offers it), the cross-lane sum in tree order, the offers
+            uint32_t id = 0;
+            bool ok = rv && g == 0;
+            if (ok)
+            {
+                id = a.labels[r];
+                if (a.alive)
+                    ok = id < a.nbits && ((a.alive[id >> 6] >> (id & 63)) & 1);
+            }
+#pragma unroll
+            for (int t = 0; t < T; t++)
+            {
+                float sum = __fadd_rn(__fadd_rn(acc[t].x, acc[t].y), __fadd_rn(acc[t].z, acc[t].w));
+                sum = row16_tree_sum(sum);
+                top[t].offer(ok ? make_key<METRIC>(sum, id) : KEY_NONE, k, lane);
+            }
+        }
+
+        // 4 wave lists -> 1 block list per query, all T queries in one pass (as scan_rows):
+        // lists at lds_merge[(t * 4 + wave) * k + e], merged lists at lds_merge[T * 4 * k + t * k + e]
+        uint64_t * merged = lds_merge + (size_t)T * 4 * k;
+#pragma unroll
+        for (int t = 0; t < T; t++)
+            top[t].store(lds_merge + (t * 4 + wave) * k, k, lane);
+        for (uint32_t i = tid; i < T * k; i += BLOCK)
+            merged[i] = KEY_NONE;
+        __syncthreads();
+        for (uint32_t i = tid; i < T * 4 * k; i += BLOCK)
+        {
+            const uint32_t t = i / (4 * k), rem = i - t * 4 * k, wv = rem / k, e = rem - wv * k;
+            const uint64_t * lists = lds_merge + (size_t)t * 4 * k;
+            const uint64_t key = lists[wv * k + e];
+            if (key == KEY_NONE)
+                continue;
+            uint32_t pos = e; // rank = own index + #smaller keys in the other three lists (a row is in one wave's list only)
+            for (uint32_t o = 0; o < 4; o++)
+            {
+                if (o == wv)
+                    continue;
+                const uint64_t * ol = lists + o * k;
+                uint32_t blo = 0, bhi = k;
+                while (blo < bhi)
+                {
+                    const uint32_t mid = (blo + bhi) >> 1;
+                    if (ol[mid] < key)
+                        blo = mid + 1;
+                    else
+                        bhi = mid;
+                }
+                pos += blo;
+            }
+            if (pos < k)
+                merged[t * k + pos] = key;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < T; t++)
+            for (uint32_t e = tid; e < k; e += BLOCK)
+                out[t][e] = merged[t * k + e];
+    }
+}
+
+}
