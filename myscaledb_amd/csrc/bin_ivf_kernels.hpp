@@ -196,28 +196,12 @@ __global__ __launch_bounds__(BLOCK) void bin_ivf_scan_kernel(const BinIvfParams 
     const uint32_t per_xcd = (total + 7) / 8;
     for (uint32_t s = blockIdx.x; s < 8 * per_xcd; s += gridDim.x)
     {
-        const uint32_t w = (s & 7) * per_xcd + (s >> 3);
+        const uint32_t w = ivf_slot_item(s, per_xcd);
         if (w >= total)
             continue;
-        uint32_t lo = 0, hi = a.nlist; // the list owning work item w: work_off[l] <= w < work_off[l + 1]
-        while (hi - lo > 1)
-        {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (a.work_off[mid] <= w)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const uint32_t l = lo;
-        const uint32_t lbeg = (uint32_t)a.list_off[l], lend = (uint32_t)a.list_off[l + 1];
-        const uint32_t local = w - a.work_off[l];
-        const uint32_t p0 = a.pair_off[l], pe = a.pair_off[l + 1];
-        const uint32_t ntile = (pe - p0 + T - 1) / T;
-        const uint32_t seg = local / ntile, tile = local - seg * ntile;
-        const uint32_t pb = p0 + tile * T;
-        const uint32_t nt = min((uint32_t)T, pe - pb); // queries of this tile (>= 1)
-        const uint32_t row_begin = lbeg + seg * a.rows_per_block;
-        const uint32_t row_end = min(row_begin + a.rows_per_block, lend);
+        const IvfWorkItem it = ivf_work_item<T>(w, a.work_off, a.pair_off, a.list_off, a.nlist, a.rows_per_block);
+        const uint32_t seg = it.seg, pb = it.pair_begin, row_begin = it.row_begin, row_end = it.row_end;
+        const uint32_t nt = min((uint32_t)T, it.pair_end - pb); // queries of this tile (>= 1)
         __syncthreads(); // the previous item is done with the LDS
         for (uint32_t i = tid; i < nt * a.ld16; i += BLOCK)
         {

@@ -11,6 +11,7 @@
 #include "bin_kernels.hpp"
 #include "device_ops.hpp"
 #include "io_stream.hpp"
+#include "list_layout.hpp"
 
 namespace msvs
 {
@@ -349,25 +350,20 @@ static std::shared_ptr<msvs_bin_index::Image> bin_image(const msvs_bin_index * i
             MSVS_HIP(hipStreamSynchronize(stream));
         }
         // ... then list-major by (list, label, insertion position) on the host, and the permuted rows go up
-        std::vector<std::pair<uint64_t, uint32_t>> order(n);
         for (size_t i = 0; i < n; i++)
         {
             if (list[i] >= nlist)
                 fail(MSVS_ERR_DEVICE, "internal: row %zu was assigned to list %u of %zu", i, list[i], nlist);
-            order[i] = {(uint64_t)list[i] << 32 | (uint32_t)ix->labels[i], (uint32_t)i};
-            fresh->h_off[list[i] + 1]++;
+            l32[i] = (uint32_t)ix->labels[i];
         }
-        std::sort(order.begin(), order.end());
-        for (size_t l = 0; l < nlist; l++)
-        {
-            fresh->max_len = std::max<size_t>(fresh->max_len, (size_t)fresh->h_off[l + 1]);
-            fresh->h_off[l + 1] += fresh->h_off[l];
-        }
+        ListLayout lay = list_major_layout(list.data(), l32.data(), n, nlist);
+        fresh->h_off = std::move(lay.list_off);
+        fresh->max_len = lay.max_list_len;
+        fresh->perm = std::move(lay.order);
         std::vector<uint8_t> lm(n * ldb, 0);
         for (size_t i = 0; i < n; i++)
         {
-            const uint32_t src = order[i].second;
-            fresh->perm[i] = src;
+            const uint32_t src = fresh->perm[i];
             l32[i] = (uint32_t)ix->labels[src];
             memcpy(lm.data() + i * ldb, ix->rows.data() + (size_t)src * ix->nbytes, ix->nbytes);
         }
@@ -389,24 +385,17 @@ static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbyte
     const size_t ldb = (size_t)ld16 * 16;
     const uint32_t g = bin_lanes(ld16);
     const size_t nlist = img.nlist, P = std::min(nprobe, nlist);
-    // row segments: at most ~8 per list (the longest one), at least 2048 rows each, whole wavefront steps
-    const size_t rows_step = 4 * (64 / g);
-    const size_t want_rpb = options().bin_ivf_rpb >= 1 ? (size_t)options().bin_ivf_rpb : std::max<size_t>(2048, ceil_div(img.max_len, (size_t)8));
-    const uint32_t rpb = (uint32_t)std::min<size_t>(round_up(want_rpb, rows_step), 0x40000000u);
-    const size_t seg_max = std::max<size_t>(1, ceil_div(img.max_len, (size_t)rpb));
-    // queries per round: the partial lists of a round stay below 256 MB and its pairs in 31 bits
-    const size_t per_q = P * seg_max * k * 8 + nlist * 4 + P * 8 + ldb + k * 12;
-    const size_t chunk = std::max<size_t>(1, std::min({nx, ((size_t)256 << 20) / per_q, (size_t)0x7fffffff / (P * seg_max)}));
+    // row segments of whole wavefront steps; per query of a round: its distances to the centroids, probes and pairs, padded row, results
+    const SegmentPlan sp = plan_segments(img.max_len, options().bin_ivf_rpb, 4 * (64 / g), P, k, nlist * 4 + P * 8 + ldb + k * 12, nx);
+    const uint32_t rpb = sp.rpb;
+    const size_t seg_max = sp.seg_max, per_q = sp.per_q, chunk = sp.chunk;
     const size_t words = alive_bits ? std::max<size_t>(1, ceil_div(nbits, (size_t)64)) : 0;
     Scratch & scr = scratch_for(stream);
     scr.reserve(chunk * per_q + (nlist + 1) * 16 + words * 8 + 16 * 256, stream);
     unsigned char * dq = scr.take<unsigned char>(chunk * ldb);
     uint32_t * dist = scr.take<uint32_t>(chunk * nlist);
     int32_t * probes = scr.take<int32_t>(chunk * P);
-    uint32_t * pairs = scr.take<uint32_t>(chunk * P);
-    uint32_t * cnt_fill = scr.take<uint32_t>(2 * nlist);
-    uint32_t * pair_off = scr.take<uint32_t>(nlist + 1);
-    uint32_t * work_off = scr.take<uint32_t>(nlist + 1);
+    const GroupedPlan plan(scr, nlist, chunk * P);
     uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * k);
     int64_t * d_ids = scr.take<int64_t>(chunk * k);
     float * d_dis = scr.take<float>(chunk * k);
@@ -420,21 +409,8 @@ static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbyte
         launch_bin_assign(dq, img.cent.p, nq, nlist, ld16, nullptr, dist, stream);
         hipLaunchKernelGGL(bin_probe_select_kernel, dim3((unsigned)nq), dim3(BLOCK), 0, stream, dist, (uint32_t)nlist, (uint32_t)P, ld16 * 128u, probes);
         MSVS_HIP(hipGetLastError());
-        MSVS_HIP(hipMemsetAsync(cnt_fill, 0, 2 * nlist * 4, stream));
         MSVS_HIP(hipMemsetAsync(partial, 0xff, nq * P * seg_max * k * 8, stream)); // KEY_NONE: (pair, segment) slots without rows
-        IvfPlanParams pp{};
-        pp.probes = probes;
-        pp.list_off = img.list_off.p;
-        pp.n_pairs = (uint32_t)(nq * P);
-        pp.nlist = (uint32_t)nlist;
-        pp.rows_per_block = rpb;
-        pp.T = k <= 64 ? BIN_IVF_T : BIN_IVF_T / 2;
-        pp.cnt = cnt_fill;
-        pp.fill = cnt_fill + nlist;
-        pp.pair_off = pair_off;
-        pp.work_off = work_off;
-        pp.pairs = pairs;
-        launch_ivf_plan(pp, stream);
+        plan.run(probes, img.list_off.p, nq * P, rpb, k <= 64 ? BIN_IVF_T : BIN_IVF_T / 2, stream);
         BinIvfParams a{};
         a.Y = reinterpret_cast<const uint4 *>(img.rows.p);
         a.Q = reinterpret_cast<const uint4 *>(dq);
@@ -448,9 +424,9 @@ static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbyte
         a.rows_per_block = rpb;
         a.seg_max = (uint32_t)seg_max;
         a.list_off = img.list_off.p;
-        a.pair_off = pair_off;
-        a.work_off = work_off;
-        a.pairs = pairs;
+        a.pair_off = plan.pair_off;
+        a.work_off = plan.work_off;
+        a.pairs = plan.pairs;
         a.partial = partial;
         {
             ProfileScope prof("bin_ivf_scan", stream);
@@ -664,14 +640,7 @@ extern "C" int msvs_bin_index_search_params(const msvs_bin_index_t * ix, const u
     return guarded([&] {
         if (!ix)
             fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
-        auto p = parse_params(params);
-        for (const auto & kv : p)
-            if (kv.first != "nprobe")
-                fail(MSVS_ERR_INVALID_ARGUMENT, "unknown search parameter `%s`", kv.first.c_str());
-        const long nprobe = param_int(p, "nprobe", 1); // (the float IVFFLAT default)
-        if (nprobe < 1)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "nprobe must be >= 1");
-        bin_index_search(ix, x, nx, k, (size_t)nprobe, alive_bits, nbits, ids, dis);
+        bin_index_search(ix, x, nx, k, parse_nprobe(params), alive_bits, nbits, ids, dis);
     });
 }
 
@@ -749,20 +718,6 @@ extern "C" int msvs_bin_index_serialize_io(const msvs_bin_index_t * ix, const ms
     });
 }
 
-/// total bytes of a file section in pieces: the buffer grows with what has really been read, so a corrupt or truncated file
-/// ends in MSVS_ERR_IO (a short read) instead of an allocation sized by an untrusted header
-static void bin_read_grow(IoStream & f, std::vector<uint8_t> & v, size_t total)
-{
-    const size_t piece = (size_t)64 << 20;
-    for (size_t got = 0; got < total;)
-    {
-        const size_t m = std::min(piece, total - got);
-        v.resize(got + m);
-        f.read(v.data() + got, m);
-        got += m;
-    }
-}
-
 extern "C" int msvs_bin_index_load_io(const msvs_io_t * io, msvs_bin_index_t ** out)
 {
     return guarded([&] {
@@ -784,11 +739,11 @@ extern "C" int msvs_bin_index_load_io(const msvs_io_t * io, msvs_bin_index_t ** 
             // or truncated file ends in MSVS_ERR_IO (a short read) instead of a 2.8e14-byte allocation
             if (h.nbytes != 0 && h.n > SIZE_MAX / h.nbytes) // (n <= 0xfffffff0 and nbytes <= 65536 above: cannot wrap in 64 bits -- kept explicit)
                 fail(MSVS_ERR_IO, "corrupt msvs binary index header");
-            bin_read_grow(f, ix->rows, (size_t)h.n * (size_t)h.nbytes);
+            read_grow(f, ix->rows, (size_t)h.n * (size_t)h.nbytes);
             if (h.version == 2)
             {
                 ix->ncentroids = (size_t)h.nlist;
-                bin_read_grow(f, ix->centroids, (size_t)h.ncent * (size_t)h.nbytes); // (< 2^31 * 2^16)
+                read_grow(f, ix->centroids, (size_t)h.ncent * (size_t)h.nbytes); // (< 2^31 * 2^16)
             }
             // (the labels are sized by the id list's own count below, piece by piece like the rows -- not by the header)
         }
@@ -799,13 +754,7 @@ extern "C" int msvs_bin_index_load_io(const msvs_io_t * io, msvs_bin_index_t ** 
             const size_t rows_read = ix->nbytes ? ix->rows.size() / ix->nbytes : 0;
             if (n != rows_read)
                 fail(MSVS_ERR_IO, "corrupt msvs binary index: %llu ids for %zu rows", (unsigned long long)n, rows_read);
-            for (size_t got = 0; got < n;) // in pieces, like the rows: the buffer grows with what has really been read
-            {
-                const size_t m = std::min<size_t>((size_t)8 << 20, n - got);
-                ix->labels.resize(got + m);
-                f.read(ix->labels.data() + got, m * 8);
-                got += m;
-            }
+            read_grow(f, ix->labels, (size_t)n); // in pieces, like the rows: the buffer grows with what has really been read
             for (int64_t id : ix->labels)
                 if (id < 0 || id > 0xfffffff0ll)
                     fail(MSVS_ERR_IO, "corrupt msvs binary index: row id %lld outside the u32 row-offset range", (long long)id);

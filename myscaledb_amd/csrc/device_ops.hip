@@ -343,6 +343,26 @@ void launch_ivf_plan(const IvfPlanParams & p, hipStream_t stream)
     MSVS_HIP(hipGetLastError());
 }
 
+void GroupedPlan::run(const int32_t * probes, const int64_t * list_off, size_t n_pairs, uint32_t rows_per_block, uint32_t T, hipStream_t stream,
+                      const int64_t * whole_off) const
+{
+    IvfPlanParams pp{};
+    pp.probes = probes;
+    pp.list_off = list_off;
+    pp.whole_off = whole_off;
+    pp.n_pairs = (uint32_t)n_pairs;
+    pp.nlist = (uint32_t)nlist;
+    pp.rows_per_block = rows_per_block;
+    pp.T = T;
+    pp.cnt = counters;
+    pp.fill = counters + nlist;
+    pp.pair_off = pair_off;
+    pp.work_off = work_off;
+    pp.pairs = pairs;
+    MSVS_HIP(hipMemsetAsync(counters, 0, 2 * nlist * sizeof(uint32_t), stream));
+    launch_ivf_plan(pp, stream);
+}
+
 void launch_ivf_plan_rescan(const IvfPlanParams & p, hipStream_t stream)
 {
     if (p.n_pairs == 0)
@@ -757,6 +777,18 @@ long param_int(const std::map<std::string, std::string> & m, const char * key, l
     if (end == it->second.c_str() || *end != '\0')
         fail(MSVS_ERR_INVALID_ARGUMENT, "parameter `%s` value should be int, got `%s`", key, it->second.c_str());
     return v;
+}
+
+size_t parse_nprobe(const char * params)
+{
+    const auto p = parse_params(params);
+    for (const auto & kv : p)
+        if (kv.first != "nprobe")
+            fail(MSVS_ERR_INVALID_ARGUMENT, "unknown search parameter `%s`", kv.first.c_str());
+    const long nprobe = param_int(p, "nprobe", 1); // (the float IVFFLAT default)
+    if (nprobe < 1)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "nprobe must be >= 1");
+    return (size_t)nprobe;
 }
 
 }

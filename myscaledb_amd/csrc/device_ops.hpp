@@ -1,6 +1,8 @@
 // device_ops.hpp -- host-side launchers of the scan / merge kernels (all device pointers, stream-ordered).
 #pragma once
 
+#include <algorithm>
+
 #include "common.hpp"
 #include "scan_kernels.hpp"
 #include "mfma_scan_kernels.hpp"
@@ -101,6 +103,45 @@ void launch_ivf_plan(const IvfPlanParams & p, hipStream_t stream);
 bool ivf_plan_fused(const IvfPlanParams & p);
 /// Only the two exclusive scans again (pair_off, work_off) for another row range / work-item size of the same pairs.
 void launch_ivf_plan_rescan(const IvfPlanParams & p, hipStream_t stream);
+
+/// The grouping plan of a list-batched scan: its buffers out of an arena (in this order: 2 * nlist counter words, pair_off,
+/// work_off, pairs), and the launches that fill them.  Taken once per search; run() once per round of queries.
+struct GroupedPlan
+{
+    uint32_t * counters, * pair_off, * work_off, * pairs; // counters: cnt [nlist], fill [nlist]
+    size_t nlist;
+    GroupedPlan(Scratch & scr, size_t nlist_, size_t max_pairs)
+        : counters(scr.take<uint32_t>(2 * nlist_)), pair_off(scr.take<uint32_t>(nlist_ + 1)), work_off(scr.take<uint32_t>(nlist_ + 1)),
+          pairs(scr.take<uint32_t>(max_pairs)), nlist(nlist_)
+    {
+    }
+    /// zeroes the counters and groups the pairs of `probes` by list into work items of T queries x rows_per_block rows; whole_off:
+    /// see IvfPlanParams
+    void run(const int32_t * probes, const int64_t * list_off, size_t n_pairs, uint32_t rows_per_block, uint32_t T, hipStream_t stream,
+             const int64_t * whole_off = nullptr) const;
+};
+
+/// Row segments of a list scan and the queries of one round of it.
+struct SegmentPlan
+{
+    uint32_t rpb;   // rows per work item: `knob` if >= 1, else at most ~8 segments in the longest list and at least 2048 rows; whole row steps
+    size_t seg_max; // segments of the longest list
+    size_t per_q;   // scratch bytes per query: its partial lists + fixed_per_q
+    size_t chunk;   // queries per round: the partial lists of a round stay below 256 MB and its pairs in 31 bits
+};
+inline SegmentPlan plan_segments(size_t max_list_len, double knob, size_t row_step, size_t P, size_t k, size_t fixed_per_q, size_t nq)
+{
+    SegmentPlan s;
+    const size_t want_rpb = knob >= 1 ? (size_t)knob : std::max<size_t>(2048, ceil_div(max_list_len, (size_t)8));
+    s.rpb = (uint32_t)std::min<size_t>(round_up(want_rpb, row_step), 0x40000000u);
+    s.seg_max = std::max<size_t>(1, ceil_div(max_list_len, (size_t)s.rpb));
+    s.per_q = P * s.seg_max * k * 8 + fixed_per_q;
+    s.chunk = std::max<size_t>(1, std::min({nq, ((size_t)256 << 20) / s.per_q, (size_t)0x7fffffff / (P * s.seg_max)}));
+    return s;
+}
+
+/// "nprobe=N" of a search over a partitioned index (default 1); any other key and N < 1 are errors
+size_t parse_nprobe(const char * params);
 
 /// List-batched IVF scan over the plan's work items; T in {2, 4, 8}; fixed grid of `grid` blocks.
 void launch_ivf_batched_scan(int metric, uint32_t T, uint32_t grid, ScanParams a, hipStream_t stream);

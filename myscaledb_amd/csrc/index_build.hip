@@ -14,6 +14,7 @@
 #include "h16_scan_kernels.hpp"
 #include "index_internal.hpp"
 #include "ivf_build_kernels.hpp"
+#include "list_layout.hpp"
 
 using namespace msvs;
 
@@ -740,20 +741,21 @@ extern "C" int msvs_index_build(msvs_index_t * ix)
         const size_t nlist = ix->type == MSVS_INDEX_IVFFLAT ? ix->nlist : 1;
         if (ix->type == MSVS_INDEX_IVFFLAT && nlist == 0)
             fail(MSVS_ERR_NOT_READY, "IVFFLAT index has no centroids");
-        // rows kept on this shard, ordered by (list, id)
-        struct Ref
+        // rows kept on this shard in staged order (their list, id and place in the chunks), then list-major by (list, id)
+        struct Where
         {
-            int32_t list;
-            uint32_t id;
-            uint32_t chunk;
-            uint32_t row;
+            uint32_t chunk, row;
         };
-        std::vector<Ref> refs;
+        std::vector<int32_t> list;
+        std::vector<uint32_t> id;
+        std::vector<Where> where;
         {
             size_t held = 0;
             for (const auto & ch : ix->chunks)
                 held += ch.n;
-            refs.reserve(held);
+            list.reserve(held);
+            id.reserve(held);
+            where.reserve(held);
         }
         for (size_t c = 0; c < ix->chunks.size(); c++)
         {
@@ -774,27 +776,19 @@ extern "C" int msvs_index_build(msvs_index_t * ix)
                     if (g / per != (size_t)ix->shard_rank)
                         continue;
                 }
-                refs.push_back({l, (uint32_t)ch.ids[i], (uint32_t)c, (uint32_t)i});
+                list.push_back(l);
+                id.push_back((uint32_t)ch.ids[i]);
+                where.push_back({(uint32_t)c, (uint32_t)i});
             }
         }
-        std::stable_sort(refs.begin(), refs.end(), [](const Ref & a, const Ref & b) {
-            return a.list != b.list ? a.list < b.list : a.id < b.id;
-        });
-        const size_t n = refs.size();
+        const size_t n = list.size();
+        ListLayout lay = list_major_layout(list.data(), id.data(), n, nlist);
         ix->n = n;
-        ix->h_list_off.assign(nlist + 1, 0);
+        ix->h_list_off = std::move(lay.list_off);
+        ix->max_list_len = lay.max_list_len;
         ix->max_id = 0;
-        for (const auto & r : refs)
-        {
-            ix->h_list_off[r.list + 1]++;
-            ix->max_id = std::max<uint64_t>(ix->max_id, r.id);
-        }
-        ix->max_list_len = 0;
-        for (size_t l = 0; l < nlist; l++)
-        {
-            ix->max_list_len = std::max<size_t>(ix->max_list_len, (size_t)ix->h_list_off[l + 1]);
-            ix->h_list_off[l + 1] += ix->h_list_off[l];
-        }
+        for (const uint32_t v : id)
+            ix->max_id = std::max<uint64_t>(ix->max_id, v);
         ix->vecs.alloc(std::max<size_t>(n, 1) * ld);
         ix->row_ids.alloc(std::max<size_t>(n, 1));
         ix->list_off.alloc(nlist + 1);
@@ -803,9 +797,10 @@ extern "C" int msvs_index_build(msvs_index_t * ix)
         std::vector<std::vector<uint32_t>> src(ix->chunks.size());
         for (size_t p = 0; p < n; p++)
         {
-            h_ids[p] = refs[p].id;
-            pos[refs[p].chunk].push_back((uint32_t)p);
-            src[refs[p].chunk].push_back(refs[p].row);
+            const Where & w = where[lay.order[p]];
+            h_ids[p] = id[lay.order[p]];
+            pos[w.chunk].push_back((uint32_t)p);
+            src[w.chunk].push_back(w.row);
         }
         for (size_t c = 0; c < ix->chunks.size(); c++)
         {

@@ -9,6 +9,7 @@
 
 #include "index_internal.hpp"
 #include "io_stream.hpp"
+#include "list_layout.hpp"
 
 using namespace msvs;
 
@@ -227,9 +228,7 @@ extern "C" int msvs_index_load_io(const msvs_io_t * io, msvs_index_t ** out)
                 fail(MSVS_ERR_IO, "corrupt msvs index: list offsets are not a partition of the rows");
             ix->n = n;
             ix->h_list_off = off;
-            ix->max_list_len = 0;
-            for (size_t l = 0; l < nlist; l++)
-                ix->max_list_len = std::max<size_t>(ix->max_list_len, (size_t)(off[l + 1] - off[l]));
+            ix->max_list_len = longest_list(off);
             ix->vecs.alloc(std::max<size_t>(n, 1) * ld);
             ix->list_off.alloc(nlist + 1);
             MSVS_HIP(hipMemcpy(ix->list_off.p, off.data(), (nlist + 1) * 8, hipMemcpyHostToDevice));

@@ -65,5 +65,35 @@ struct IoStream
     }
 };
 
+/// `count` values of a file section in pieces of 64 MB: the buffer grows with what has really been read, so a corrupt or truncated
+/// file ends in MSVS_ERR_IO (a short read) instead of an allocation sized by an untrusted header
+template <typename V>
+inline void read_grow(IoStream & f, std::vector<V> & v, size_t count)
+{
+    const size_t piece = IO_CHUNK / sizeof(V);
+    for (size_t got = 0; got < count;)
+    {
+        const size_t m = std::min(piece, count - got);
+        v.resize(got + m);
+        f.read(v.data() + got, m * sizeof(V));
+        got += m;
+    }
+}
+
+inline void expect_end(IoStream & f)
+{
+    char c;
+    if (f.io->read(f.io->ctx, f.h, &c, 1) > 0)
+        fail(MSVS_ERR_IO, "index file `%s` is longer than its header says", f.name);
+}
+
+/// FNV-1a over n bytes: the check word of a file header
+inline uint64_t fnv1a(const void * p, size_t n)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; i++)
+        h = (h ^ static_cast<const unsigned char *>(p)[i]) * 0x100000001b3ull;
+    return h;
+}
 
 }

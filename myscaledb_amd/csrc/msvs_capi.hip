@@ -2135,25 +2135,11 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
     else
     {
         // group the (query, list) pairs by list, then one pass over each list segment per tile of T queries
-        IvfPlanParams pp{};
-        pp.probes = d_probes;
-        pp.list_off = list_off;
-        pp.whole_off = list_off;
-        pp.n_pairs = (uint32_t)(nq * nprobe);
-        pp.nlist = (uint32_t)ix.nlist;
-        pp.rows_per_block = pl.rpb;
-        pp.T = pl.T;
-        uint32_t * counters = scr.take<uint32_t>(2 * ix.nlist);
-        pp.cnt = counters;
-        pp.fill = counters + ix.nlist;
-        pp.pair_off = scr.take<uint32_t>(ix.nlist + 1);
-        pp.work_off = scr.take<uint32_t>(ix.nlist + 1);
-        pp.pairs = scr.take<uint32_t>(nq * nprobe);
-        MSVS_HIP(hipMemsetAsync(counters, 0, 2 * ix.nlist * sizeof(uint32_t), stream));
-        launch_ivf_plan(pp, stream);
-        a.pairs = pp.pairs;
-        a.pair_off = pp.pair_off;
-        a.work_off = pp.work_off;
+        const GroupedPlan plan(scr, ix.nlist, nq * nprobe);
+        plan.run(d_probes, list_off, nq * nprobe, pl.rpb, pl.T, stream, list_off);
+        a.pairs = plan.pairs;
+        a.pair_off = plan.pair_off;
+        a.work_off = plan.work_off;
         a.xcd_order = (uint32_t)options().ivf_xcd; // experiment knob; default on
         launch_ivf_batched_scan(scan_metric(m), pl.T, pl.grid, a, stream);
     }

@@ -255,6 +255,54 @@ struct ScanParams
     const float4 * Qsplit;   // candidate pass: the queries in split-bf16 step layout (split_queries_kernel)
 };
 
+/// The 4 wave lists of each of T queries -> one block list per query, all T in one pass: the merged top-k of query t goes to
+/// out[t][0..k) (global).  LDS: lists at lds_merge[(t*4 + wave)*k + e], merged lists at lds_merge[T*4*k + t*k + e].  All BLOCK
+/// threads participate; nobody may still be reading lds_merge when they arrive (2 barriers inside, none in front).
+template <int T, int R>
+__device__ __forceinline__ void tile_rank_merge(const WaveTopK<R> * top, uint64_t * lds_merge, uint64_t * const * out, uint32_t k)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint64_t * merged = lds_merge + (size_t)T * 4 * k;
+#pragma unroll
+    for (int t = 0; t < T; t++)
+        top[t].store(lds_merge + (t * 4 + wave) * k, k, lane);
+    for (uint32_t i = tid; i < T * k; i += BLOCK)
+        merged[i] = KEY_NONE;
+    __syncthreads();
+    for (uint32_t i = tid; i < T * 4 * k; i += BLOCK)
+    {
+        const uint32_t t = i / (4 * k), rem = i - t * 4 * k, w = rem / k, e = rem - w * k;
+        const uint64_t * lists = lds_merge + (size_t)t * 4 * k;
+        const uint64_t key = lists[w * k + e];
+        if (key == KEY_NONE)
+            continue;
+        uint32_t pos = e; // rank = own index + #smaller keys in the other three lists (keys are unique)
+        for (uint32_t o = 0; o < 4; o++)
+        {
+            if (o == w)
+                continue;
+            const uint64_t * l = lists + o * k;
+            uint32_t lo = 0, hi = k;
+            while (lo < hi)
+            {
+                uint32_t mid = (lo + hi) >> 1;
+                if (l[mid] < key)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            pos += lo;
+        }
+        if (pos < k)
+            merged[t * k + pos] = key;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < T; t++)
+        for (uint32_t e = tid; e < k; e += BLOCK)
+            out[t][e] = merged[t * k + e];
+}
+
 /// Scans rows [row_begin,row_end) for T queries already staged in LDS (qs[t*ld4 + c]) and leaves the block's
 /// merged top-k of query t in out[t][0..k) (global).  All BLOCK threads participate.
 template <int METRIC, int T, int R>
@@ -431,48 +479,9 @@ __device__ __forceinline__ void scan_rows(const ScanParams & a, uint32_t row_beg
         finish_row(r, rv, acc);
     }
 
-    // 4 wave lists -> 1 block list per query, all T queries in one pass (3 barriers per work item):
-    // lists at lds_merge[(t*4 + wave)*k + e], merged lists at lds_merge[T*4*k + t*k + e]
-    uint64_t * merged = lds_merge + (size_t)T * 4 * k;
+    // 4 wave lists -> 1 block list per query (3 barriers per work item with this one)
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < T; t++)
-        top[t].store(lds_merge + (t * 4 + wave) * k, k, lane);
-    for (uint32_t i = tid; i < T * k; i += BLOCK)
-        merged[i] = KEY_NONE;
-    __syncthreads();
-    for (uint32_t i = tid; i < T * 4 * k; i += BLOCK)
-    {
-        const uint32_t t = i / (4 * k), rem = i - t * 4 * k, w = rem / k, e = rem - w * k;
-        const uint64_t * lists = lds_merge + (size_t)t * 4 * k;
-        const uint64_t key = lists[w * k + e];
-        if (key == KEY_NONE)
-            continue;
-        uint32_t pos = e; // rank = own index + #smaller keys in the other three lists (keys are unique)
-        for (uint32_t o = 0; o < 4; o++)
-        {
-            if (o == w)
-                continue;
-            const uint64_t * l = lists + o * k;
-            uint32_t lo = 0, hi = k;
-            while (lo < hi)
-            {
-                uint32_t mid = (lo + hi) >> 1;
-                if (l[mid] < key)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            pos += lo;
-        }
-        if (pos < k)
-            merged[t * k + pos] = key;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < T; t++)
-        for (uint32_t e = tid; e < k; e += BLOCK)
-            out[t][e] = merged[t * k + e];
+    tile_rank_merge<T, R>(top, lds_merge, out, k);
 }
 
 /// Stage T query rows (zero padded) into LDS.  Queries beyond nq repeat the last valid one.
@@ -856,57 +865,70 @@ static __global__ __launch_bounds__(256) void ivf_scatter_lds_kernel(const IvfPl
             p.pairs[h[list[u]] + rank[u]] = base + u * 256 + tid;
 }
 
-/// grid: any size; block b handles work items b, b + gridDim.x, ...
+/// A work item of a grouped plan (IvfPlanParams): the rows [row_begin, row_end) of segment `seg` of list `list` for the pairs
+/// [pair_begin, pair_end) of its `tile`-th tile of T queries (a short last tile has fewer than T pairs).
+struct IvfWorkItem
+{
+    uint32_t list, seg, pair_begin, pair_end, row_begin, row_end;
+};
+
+/// Work order inside a list is [segment][query tile] (tile fastest): consecutive work items read the SAME rows for different
+/// query tiles.  w < work_off[nlist].
+template <int T>
+__device__ __forceinline__ IvfWorkItem ivf_work_item(uint32_t w, const uint32_t * work_off, const uint32_t * pair_off, const int64_t * list_off,
+                                                     uint32_t nlist, uint32_t rows_per_block)
+{
+    uint32_t lo = 0, hi = nlist; // the list owning work item w: work_off[l] <= w < work_off[l + 1]
+    while (hi - lo > 1)
+    {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (work_off[mid] <= w)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const uint32_t lbeg = (uint32_t)list_off[lo], lend = (uint32_t)list_off[lo + 1];
+    const uint32_t local = w - work_off[lo];
+    const uint32_t p0 = pair_off[lo], pe = pair_off[lo + 1];
+    const uint32_t ntile = (pe - p0 + T - 1) / T;
+    const uint32_t seg = local / ntile, tile = local - seg * ntile;
+    const uint32_t row_begin = lbeg + seg * rows_per_block;
+    return {lo, seg, p0 + tile * T, pe, row_begin, row_begin + min(rows_per_block, lend - row_begin)}; // (no 32-bit overflow near 2^32 rows)
+}
+
+/// Slot s of a grid walking `total` work items -> its work item, or `total` and beyond for a slot without one.  Blocks are
+/// dispatched round-robin over the 8 XCDs (block b -> XCD b % 8, a speed assumption only), so slot s = b + i*gridDim.x is mapped
+/// to work item (s % 8) * per_xcd + s / 8: every XCD walks one contiguous range, and the tiles sharing a row segment run back to
+/// back on ONE XCD's L2.  The slots run over [0, 8 * per_xcd), per_xcd = ceil(total / 8).
+__device__ __forceinline__ uint32_t ivf_slot_item(uint32_t s, uint32_t per_xcd) { return (s & 7) * per_xcd + (s >> 3); }
+
+/// grid: any size; block b handles slots b, b + gridDim.x, ...
 template <int METRIC, int T, int R>
 __global__ __launch_bounds__(BLOCK) void ivf_batched_scan_kernel(const ScanParams a)
 {
     float4 * qs = reinterpret_cast<float4 *>(msvs_smem);
     uint64_t * lds_merge = reinterpret_cast<uint64_t *>(msvs_smem + (size_t)T * a.ld4 * 16);
     const uint32_t total = a.work_off[a.nlist];
-    // Work order inside a list is [segment][query tile] (tile fastest): consecutive work items read the SAME rows
-    // for different query tiles.  Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8, a speed
-    // assumption only), so slot s = b + i*gridDim.x is mapped to work item (s % 8) * per_xcd + s / 8: every XCD
-    // walks one contiguous range, and the tiles sharing a row segment run back to back on ONE XCD's L2.
     const uint32_t per_xcd = (total + 7) / 8;
     for (uint32_t s = blockIdx.x; s < 8 * per_xcd; s += gridDim.x)
     {
-        const uint32_t w = a.xcd_order ? (s & 7) * per_xcd + (s >> 3) : s;
-        if (w >= total || (a.xcd_order && (s >> 3) >= per_xcd))
+        const uint32_t w = a.xcd_order ? ivf_slot_item(s, per_xcd) : s;
+        if (w >= total)
             continue;
-        // the list owning work item w: work_off[l] <= w < work_off[l+1]
-        uint32_t lo = 0, hi = a.nlist;
-        while (hi - lo > 1)
-        {
-            uint32_t mid = (lo + hi) >> 1;
-            if (a.work_off[mid] <= w)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const uint32_t l = lo;
-        const int64_t lbeg = a.list_off[l], lend = a.list_off[l + 1];
-        const uint32_t nseg = ((uint32_t)(lend - lbeg) + a.rows_per_block - 1) / a.rows_per_block;
-        const uint32_t local = w - a.work_off[l];
-        const uint32_t pe = a.pair_off[l + 1];
-        const uint32_t ntile = (pe - a.pair_off[l] + T - 1) / T;
-        const uint32_t seg = local / ntile, tile = local - seg * ntile;
-        (void)nseg;
-        const uint32_t pb = a.pair_off[l] + tile * T;
+        const IvfWorkItem it = ivf_work_item<T>(w, a.work_off, a.pair_off, a.list_off, a.nlist, a.rows_per_block);
         uint32_t qidx[T];
         uint64_t * out[T];
 #pragma unroll
         for (int t = 0; t < T; t++)
         {
-            uint32_t pi = pb + t < pe ? pb + t : pe - 1; // short tiles repeat their last pair (same slot, same values)
+            uint32_t pi = min(it.pair_begin + t, it.pair_end - 1); // short tiles repeat their last pair (same slot, same values)
             uint32_t qp = a.pairs[pi];
             qidx[t] = qp / a.nprobe;
-            out[t] = a.partial + ((size_t)qp * a.seg_max + seg) * a.k;
+            out[t] = a.partial + ((size_t)qp * a.seg_max + it.seg) * a.k;
         }
         __syncthreads();
         stage_queries<T>(a, qidx, qs);
-        const int64_t rb = lbeg + (int64_t)seg * a.rows_per_block;
-        const int64_t re = rb + a.rows_per_block < lend ? rb + a.rows_per_block : lend;
-        scan_rows<METRIC, T, R>(a, (uint32_t)rb, (uint32_t)re, qs, lds_merge, out);
+        scan_rows<METRIC, T, R>(a, it.row_begin, it.row_end, qs, lds_merge, out);
     }
 }
 

@@ -12,6 +12,7 @@
 #include "index_internal.hpp"
 #include "io_stream.hpp"
 #include "ivf_build_kernels.hpp"
+#include "list_layout.hpp"
 #include "sq_ivf_kernels.hpp"
 
 using namespace msvs;
@@ -32,14 +33,6 @@ inline float sq_ord2f(uint32_t o)
     float f;
     memcpy(&f, &u, 4);
     return f;
-}
-
-uint64_t fnv1a(const void * p, size_t n)
-{
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (size_t i = 0; i < n; i++)
-        h = (h ^ static_cast<const unsigned char *>(p)[i]) * 0x100000001b3ull;
-    return h;
 }
 }
 
@@ -318,44 +311,35 @@ extern "C" int msvs_sq_index_build(msvs_sq_index_t * ix)
             fail(MSVS_ERR_NOT_READY, "the IVFSQ index has no codebook yet (train / set_codebook)");
         hipStream_t stream = thread_stream();
         const size_t nlist = ix->nlist, n = ix->staged;
-        struct Ref
-        {
-            int32_t list;
-            uint32_t id, chunk, row;
-        };
-        std::vector<Ref> refs;
-        refs.reserve(n);
-        for (size_t c = 0; c < ix->chunks.size(); c++)
-            for (size_t i = 0; i < ix->chunks[c].n; i++)
-                refs.push_back({ix->chunks[c].list[i], (uint32_t)ix->chunks[c].ids[i], (uint32_t)c, (uint32_t)i});
-        std::stable_sort(refs.begin(), refs.end(), [](const Ref & a, const Ref & b) { return a.list != b.list ? a.list < b.list : a.id < b.id; });
-        ix->h_list_off.assign(nlist + 1, 0);
-        for (const auto & r : refs)
-            ix->h_list_off[r.list + 1]++;
-        ix->max_list_len = 0;
-        for (size_t l = 0; l < nlist; l++)
-        {
-            ix->max_list_len = std::max<size_t>(ix->max_list_len, (size_t)ix->h_list_off[l + 1]);
-            ix->h_list_off[l + 1] += ix->h_list_off[l];
-        }
+        std::vector<int32_t> list;
+        std::vector<uint32_t> id;
+        list.reserve(n);
+        id.reserve(n);
+        for (const auto & ch : ix->chunks)
+            for (size_t i = 0; i < ch.n; i++)
+            {
+                list.push_back(ch.list[i]);
+                id.push_back((uint32_t)ch.ids[i]);
+            }
+        ListLayout lay = list_major_layout(list.data(), id.data(), n, nlist);
+        ix->h_list_off = std::move(lay.list_off);
+        ix->max_list_len = lay.max_list_len;
         ix->codes.alloc(std::max<size_t>(n, 1) * ix->ld);
         ix->labels.alloc(std::max<size_t>(n, 1));
         ix->list_off.alloc(nlist + 1);
-        std::vector<uint32_t> h_labels(n);
-        std::vector<std::vector<uint32_t>> pos(ix->chunks.size());
-        for (size_t c = 0; c < ix->chunks.size(); c++)
-            pos[c].resize(ix->chunks[c].n);
+        std::vector<uint32_t> h_labels(n), pos(n); // pos: staged position -> list-major position
         for (size_t p = 0; p < n; p++)
         {
-            h_labels[p] = refs[p].id;
-            pos[refs[p].chunk][refs[p].row] = (uint32_t)p;
+            h_labels[p] = id[lay.order[p]];
+            pos[lay.order[p]] = (uint32_t)p;
         }
-        for (size_t c = 0; c < ix->chunks.size(); c++)
+        size_t first = 0; // staged position of the chunk's first row
+        for (size_t c = 0; c < ix->chunks.size(); first += ix->chunks[c].n, c++)
         {
             // a staged chunk goes to its list-major places and is released: staged + final codes never both whole beyond this point
             const size_t m = ix->chunks[c].n;
             DevBuf<uint32_t> d_pos(m);
-            MSVS_HIP(hipMemcpyAsync(d_pos.p, pos[c].data(), m * 4, hipMemcpyHostToDevice, stream));
+            MSVS_HIP(hipMemcpyAsync(d_pos.p, pos.data() + first, m * 4, hipMemcpyHostToDevice, stream));
             const uint32_t ld16 = ix->ld / 16;
             hipLaunchKernelGGL(sq_scatter_rows_kernel, dim3((unsigned)ceil_div(m * ld16, (size_t)256)), dim3(256), 0, stream,
                                reinterpret_cast<const uint4 *>(ix->chunks[c].codes.p), reinterpret_cast<uint4 *>(ix->codes.p), d_pos.p, m, ld16);
@@ -443,23 +427,17 @@ static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, 
         fail(MSVS_ERR_UNSUPPORTED_K, "min(nprobe, nlist) = %zu exceeds the coarse quantiser's top-k limit %d", P, MSVS_MAX_K);
     const uint32_t ld = ix.ld, ld4 = ld / 4;
     const int m = scan_metric(ix.metric);
-    // row segments: at most ~8 per list (the longest one), at least 2048 rows each, whole 16-row steps
-    const size_t want_rpb = options().sq_ivf_rpb >= 1 ? (size_t)options().sq_ivf_rpb : std::max<size_t>(2048, ceil_div(ix.max_list_len, (size_t)8));
-    const uint32_t rpb = (uint32_t)std::min<size_t>(round_up(want_rpb, (size_t)16), 0x40000000u);
-    const size_t seg_max = std::max<size_t>(1, ceil_div(ix.max_list_len, (size_t)rpb));
-    // queries per round: the partial lists of a round stay below 256 MB and its pairs in 31 bits
-    const size_t per_q = P * seg_max * k * 8 + (size_t)ld * 4 + P * 8 + 64;
-    const size_t chunk = std::max<size_t>(1, std::min({nq, ((size_t)256 << 20) / per_q, (size_t)0x7fffffff / (P * seg_max)}));
+    // row segments of whole 16-row steps; per query of a round: its padded row, its probes and pairs
+    const SegmentPlan sp = plan_segments(ix.max_list_len, options().sq_ivf_rpb, 16, P, k, (size_t)ld * 4 + P * 8 + 64, nq);
+    const uint32_t rpb = sp.rpb;
+    const size_t seg_max = sp.seg_max, per_q = sp.per_q, chunk = sp.chunk;
     const size_t last = nq % chunk;
     const size_t coarse = std::max(flat_scratch_bytes(nlist, chunk, (uint32_t)P, ld), last ? flat_scratch_bytes(nlist, last, (uint32_t)P, ld) : 0);
     Scratch & scr = scratch_for(stream);
     scr.reserve(chunk * per_q + coarse + (nlist + 1) * 16 + 16 * 256, stream);
     float * dq = scr.take<float>(chunk * ld);
     int32_t * probes = scr.take<int32_t>(chunk * P);
-    uint32_t * pairs = scr.take<uint32_t>(chunk * P);
-    uint32_t * cnt_fill = scr.take<uint32_t>(2 * nlist);
-    uint32_t * pair_off = scr.take<uint32_t>(nlist + 1);
-    uint32_t * work_off = scr.take<uint32_t>(nlist + 1);
+    const GroupedPlan plan(scr, nlist, chunk * P);
     uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * k);
     const size_t mark = scr.used;
     for (size_t q0 = 0; q0 < nq; q0 += chunk)
@@ -479,20 +457,7 @@ static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, 
         uint32_t T = n_pairs >= 16 * nlist ? 8 : (n_pairs >= 2 * nlist ? 4 : 2);
         while (T > 2 && sq_lds_bytes(T, ld4, (uint32_t)k) > SCAN_LDS_BUDGET)
             T /= 2;
-        MSVS_HIP(hipMemsetAsync(cnt_fill, 0, 2 * nlist * 4, stream));
-        IvfPlanParams pp{};
-        pp.probes = probes;
-        pp.list_off = ix.list_off.p;
-        pp.n_pairs = (uint32_t)n_pairs;
-        pp.nlist = (uint32_t)nlist;
-        pp.rows_per_block = rpb;
-        pp.T = T;
-        pp.cnt = cnt_fill;
-        pp.fill = cnt_fill + nlist;
-        pp.pair_off = pair_off;
-        pp.work_off = work_off;
-        pp.pairs = pairs;
-        launch_ivf_plan(pp, stream);
+        plan.run(probes, ix.list_off.p, n_pairs, rpb, T, stream);
         // 3. the list scan over the codes
         SqIvfParams a{};
         a.codes = reinterpret_cast<const uint4 *>(ix.codes.p);
@@ -511,9 +476,9 @@ static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, 
         a.rows_per_block = rpb;
         a.seg_max = (uint32_t)seg_max;
         a.list_off = ix.list_off.p;
-        a.pair_off = pair_off;
-        a.work_off = work_off;
-        a.pairs = pairs;
+        a.pair_off = plan.pair_off;
+        a.work_off = plan.work_off;
+        a.pairs = plan.pairs;
         {
             ProfileScope prof("sq_ivf_scan", stream);
             const uint32_t grid = (uint32_t)std::min<size_t>(2048, n_pairs * seg_max);
@@ -556,13 +521,7 @@ extern "C" int msvs_sq_index_search(const msvs_sq_index_t * ix, const float * qu
         DeviceGuard on_device(ix ? ix->device : -1);
         if (!ix)
             fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
-        auto p = parse_params(params);
-        for (const auto & kv : p)
-            if (kv.first != "nprobe")
-                fail(MSVS_ERR_INVALID_ARGUMENT, "unknown search parameter `%s`", kv.first.c_str());
-        const long nprobe = param_int(p, "nprobe", 1);
-        if (nprobe < 1)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "nprobe must be >= 1");
+        const size_t nprobe = parse_nprobe(params);
         check_k(k);
         if (!ix->ready)
             fail(MSVS_ERR_NOT_READY, "the IVFSQ index is not built");
@@ -581,7 +540,7 @@ extern "C" int msvs_sq_index_search(const msvs_sq_index_t * ix, const float * qu
         MSVS_HIP(hipMemcpyAsync(dq, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, stream));
         if (words)
             MSVS_HIP(hipMemcpyAsync(d_alive, alive_bits, words * 8, hipMemcpyHostToDevice, stream));
-        sq_search_device(*ix, dq, nq, k, (size_t)nprobe, d_alive, nbits, d_ids, d_dis, stream);
+        sq_search_device(*ix, dq, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream);
         MSVS_HIP(hipMemcpyAsync(ids, d_ids, nq * k * 8, hipMemcpyDeviceToHost, stream));
         MSVS_HIP(hipMemcpyAsync(dis, d_dis, nq * k * 4, hipMemcpyDeviceToHost, stream));
         MSVS_HIP(hipStreamSynchronize(stream));
@@ -657,28 +616,6 @@ struct SqIdHeader // 24 bytes
     uint64_t n;
     uint64_t check;
 };
-
-/// `total` bytes in pieces: the buffer grows with what has really been read, so a corrupt or truncated file ends in MSVS_ERR_IO (a
-/// short read) instead of an allocation sized by an untrusted header
-template <typename V>
-void read_grow(IoStream & f, std::vector<V> & v, size_t count)
-{
-    const size_t piece = ((size_t)64 << 20) / sizeof(V);
-    for (size_t got = 0; got < count;)
-    {
-        const size_t m = std::min(piece, count - got);
-        v.resize(got + m);
-        f.read(v.data() + got, m * sizeof(V));
-        got += m;
-    }
-}
-
-void expect_end(IoStream & f)
-{
-    char c;
-    if (f.io->read(f.io->ctx, f.h, &c, 1) > 0)
-        fail(MSVS_ERR_IO, "index file `%s` is longer than its header says", f.name);
-}
 }
 
 extern "C" int msvs_sq_index_serialize_io(const msvs_sq_index_t * ix, const msvs_io_t * io)
@@ -754,14 +691,10 @@ extern "C" int msvs_sq_index_load_io(const msvs_io_t * io, msvs_sq_index_t ** ou
             read_grow(f, lo, ix->dim);
             read_grow(f, hi, ix->dim);
             read_grow(f, ix->h_list_off, ix->nlist + 1);
-            if (ix->h_list_off[0] != 0 || ix->h_list_off[ix->nlist] != (int64_t)ix->n)
-                fail(MSVS_ERR_IO, "corrupt msvs IVFSQ index: the list offsets do not span the rows");
-            for (size_t l = 0; l < ix->nlist; l++)
-            {
-                if (ix->h_list_off[l + 1] < ix->h_list_off[l])
-                    fail(MSVS_ERR_IO, "corrupt msvs IVFSQ index: descending list offsets");
-                ix->max_list_len = std::max<size_t>(ix->max_list_len, (size_t)(ix->h_list_off[l + 1] - ix->h_list_off[l]));
-            }
+            const std::string bad = list_offsets_error(ix->h_list_off, ix->n, "msvs IVFSQ index");
+            if (!bad.empty())
+                fail(MSVS_ERR_IO, "%s", bad.c_str());
+            ix->max_list_len = longest_list(ix->h_list_off);
             read_grow(f, codes, ix->n * ix->dim);
             expect_end(f);
         }

@@ -168,33 +168,17 @@ __global__ __launch_bounds__(BLOCK) void sq_ivf_scan_kernel(const SqIvfParams a)
     const uint32_t per_xcd = (total + 7) / 8;
     for (uint32_t s = blockIdx.x; s < 8 * per_xcd; s += gridDim.x)
     {
-        const uint32_t w = (s & 7) * per_xcd + (s >> 3);
+        const uint32_t w = ivf_slot_item(s, per_xcd);
         if (w >= total)
             continue;
-        uint32_t lo = 0, hi = a.nlist; // the list owning work item w: work_off[l] <= w < work_off[l + 1]
-        while (hi - lo > 1)
-        {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (a.work_off[mid] <= w)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const uint32_t l = lo;
-        const uint32_t lbeg = (uint32_t)a.list_off[l], lend = (uint32_t)a.list_off[l + 1];
-        const uint32_t local = w - a.work_off[l];
-        const uint32_t p0 = a.pair_off[l], pe = a.pair_off[l + 1];
-        const uint32_t ntile = (pe - p0 + T - 1) / T;
-        const uint32_t seg = local / ntile, tile = local - seg * ntile;
-        const uint32_t pb = p0 + tile * T;
-        const uint32_t row_begin = lbeg + seg * a.rows_per_block;
-        const uint32_t row_end = min(row_begin + a.rows_per_block, lend);
+        const IvfWorkItem it = ivf_work_item<T>(w, a.work_off, a.pair_off, a.list_off, a.nlist, a.rows_per_block);
+        const uint32_t l = it.list, seg = it.seg, row_begin = it.row_begin, row_end = it.row_end;
         uint64_t * out[T];
         __syncthreads(); // the previous item is done with the LDS
 #pragma unroll
         for (int t = 0; t < T; t++)
         {
-            const uint32_t pi = pb + t < pe ? pb + t : pe - 1; // short tiles repeat their last pair (same slot, same values)
+            const uint32_t pi = min(it.pair_begin + t, it.pair_end - 1); // short tiles repeat their last pair (same slot, same values)
             const uint32_t qp = a.pairs[pi];
             out[t] = a.partial + ((size_t)qp * a.seg_max + seg) * k;
             const float4 * src = a.Q + (size_t)(qp / a.nprobe) * ld4;
@@ -280,47 +264,7 @@ __global__ __launch_bounds__(BLOCK) void sq_ivf_scan_kernel(const SqIvfParams a)
             }
         }
 
-        // 4 wave lists -> 1 block list per query, all T queries in one pass (as scan_rows):
-        // lists at lds_merge[(t * 4 + wave) * k + e], merged lists at lds_merge[T * 4 * k + t * k + e]
-        uint64_t * merged = lds_merge + (size_t)T * 4 * k;
-#pragma unroll
-        for (int t = 0; t < T; t++)
-            top[t].store(lds_merge + (t * 4 + wave) * k, k, lane);
-        for (uint32_t i = tid; i < T * k; i += BLOCK)
-            merged[i] = KEY_NONE;
-        __syncthreads();
-        for (uint32_t i = tid; i < T * 4 * k; i += BLOCK)
-        {
-            const uint32_t t = i / (4 * k), rem = i - t * 4 * k, wv = rem / k, e = rem - wv * k;
-            const uint64_t * lists = lds_merge + (size_t)t * 4 * k;
-            const uint64_t key = lists[wv * k + e];
-            if (key == KEY_NONE)
-                continue;
-            uint32_t pos = e; // rank = own index + #smaller keys in the other three lists (a row is in one wave's list only)
-            for (uint32_t o = 0; o < 4; o++)
-            {
-                if (o == wv)
-                    continue;
-                const uint64_t * ol = lists + o * k;
-                uint32_t blo = 0, bhi = k;
-                while (blo < bhi)
-                {
-                    const uint32_t mid = (blo + bhi) >> 1;
-                    if (ol[mid] < key)
-                        blo = mid + 1;
-                    else
-                        bhi = mid;
-                }
-                pos += blo;
-            }
-            if (pos < k)
-                merged[t * k + pos] = key;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < T; t++)
-            for (uint32_t e = tid; e < k; e += BLOCK)
-                out[t][e] = merged[t * k + e];
+        tile_rank_merge<T, R>(top, lds_merge, out, k); // (no barrier in front: the row loop reads the staged rows and tables, not lds_merge)
     }
 }
 

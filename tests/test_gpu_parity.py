@@ -475,6 +475,38 @@ def test_ivfflat_matrix_core_candidate_pass_matches_oracle(metric, n, d, nlist, 
     assert capi.prefilter_stats()[0] == q2
 
 
+@pytest.mark.parametrize("metric", [capi.METRIC_L2, capi.METRIC_IP])
+@pytest.mark.parametrize("d", [20, 100])  # 20: the tail-only row; 100: one full 64-column block plus a tail
+def test_canonical_grouped_scan_every_tile_and_list_size(metric, d, opt):
+    """The list-batched canonical scan (ivf_batched_scan_kernel) in every instantiation the planner can pick: query tiles of 2, 4 and
+    8 x k <= 64, <= 128 and > 128.  40 queries x 3 probes over 8 lists: about 15 pairs per list, so every tile size has full and
+    short tiles.  Segments: 16-row work items (many per list, a short last one) and the planned ones; the slots mapped XCD-contiguously
+    and plainly; three blocks walking all the items."""
+    n, nlist, nq, nprobe = 3000, 8, 40, 3
+    rng = np.random.default_rng(1000 * d + metric)
+    centers = rng.standard_normal((nlist, d), dtype=np.float32) * 2
+    x = (centers[rng.integers(0, nlist, n)] + rng.standard_normal((n, d), dtype=np.float32)).astype(np.float32)
+    q = (centers[rng.integers(0, nlist, nq)] + rng.standard_normal((nq, d), dtype=np.float32)).astype(np.float32)
+    ix = build_ivf(x, metric, nlist)
+    opt("ivf_pass", "0")
+    passes = capi.prefilter_stats()[0]
+    for k in (10, 100, 256):
+        oi, od, _ = oracle_on_exported(ix, q, nprobe, k, metric)
+        for t in (2, 4, 8):
+            opt("ivf_t", str(t))
+            same(*ix.search(q, k, "nprobe=%d" % nprobe), oi, od)  # planned segments
+            opt("ivf_rpb", "16")
+            same(*ix.search(q, k, "nprobe=%d" % nprobe), oi, od)
+            opt("ivf_xcd", "0")
+            same(*ix.search(q, k, "nprobe=%d" % nprobe), oi, od)
+            opt("ivf_xcd", None)
+            opt("ivf_grid", "3")
+            same(*ix.search(q, k, "nprobe=%d" % nprobe), oi, od)
+            opt("ivf_grid", None)
+            opt("ivf_rpb", None)
+    assert capi.prefilter_stats()[0] == passes  # the candidate pass stayed out of it
+
+
 def h16_keys(nq, cap=4096):
     """Candidate keys (approximate distance word << 32 | stored row position) and counts of this thread's last shadow pass."""
     import ctypes as C

@@ -148,6 +148,10 @@ PARITY = [
     (COS, 64, "ties", 300, 1, NLIST, "host"),
     (COS, 100, "clustered", 1, 256, 10 * NLIST, "device"),
     (COS, 768, "clustered", 3, 10, 1, "host"),
+    # the two (query tile, k class) pairs of the list scan the rows above do not reach: tile 2 (< 2 pairs per list) with 64 < k <= 128,
+    # and tile 8 (>= 16 pairs per list) with k > 128, where k = 256 no longer fits the tile's LDS and falls back to tile 4
+    (L2, 64, "clustered", 1, 100, 4, "host"),
+    (IP, 5, "ties", 16, 150, NLIST, "device"),
 ]
 
 
