@@ -528,6 +528,8 @@ MSVS_API int msvs_bm25_search_batch(const msvs_postings_t * postings, size_t nq,
  *     (below 3 % .. 40 % depending on how many queries share a list pass) -- the scan of a compacted view holding only the
  *     passing rows (same results, a fraction of the bytes).  Results are identical to msvs_index_search with the same bitmap. */
 typedef struct msvs_filter msvs_filter_t;
+/* The predicate compares VALUES, as SQL does: the constant is never cast into the column type (UInt8 `< 300` passes every row,
+ * unsigned `> -1` every row, UInt64 rows >= 2^63 are above every .i), and Float32 rows are compared with .f in double. */
 typedef struct { int64_t i; double f; } msvs_scalar_t; /* .i for integer columns, .f for float columns */
 enum msvs_dtype { MSVS_DT_UINT8 = 0, MSVS_DT_UINT16, MSVS_DT_UINT32, MSVS_DT_UINT64, MSVS_DT_INT8, MSVS_DT_INT16, MSVS_DT_INT32,
                   MSVS_DT_INT64, MSVS_DT_FLOAT32, MSVS_DT_FLOAT64 };
@@ -537,7 +539,8 @@ MSVS_API int msvs_filter_from_bits(const uint64_t * bits, size_t nbits, msvs_fil
 MSVS_API int msvs_filter_from_offsets(const uint64_t * part_offsets, size_t n, size_t nbits, int mem, msvs_filter_t ** out);
 MSVS_API int msvs_filter_from_predicate(const void * column, int dtype, size_t nrows, int mem, int op, msvs_scalar_t lo,
                                         msvs_scalar_t hi, msvs_filter_t ** out);
-MSVS_API int msvs_filter_combine(msvs_filter_t * a, const msvs_filter_t * b, int mode); /* a = a MODE b */
+MSVS_API int msvs_filter_combine(msvs_filter_t * a, const msvs_filter_t * b, int mode); /* a = a MODE b; a keeps its length,
+                                                                                           b is zero-extended or cut to it */
 MSVS_API int msvs_filter_count(const msvs_filter_t * f, uint64_t * alive, size_t * nbits);
 MSVS_API int msvs_filter_to_bits(const msvs_filter_t * f, uint64_t * bits_out);
 MSVS_API void msvs_filter_free(msvs_filter_t * f);

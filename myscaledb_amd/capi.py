@@ -822,17 +822,24 @@ class Filter:
         return cls(h)
 
     @classmethod
-    def from_offsets(cls, offsets, nbits):
-        """getFilterFromPipeline: the passing `_part_offset`s."""
-        off = np.ascontiguousarray(offsets, np.uint64)
+    def from_offsets(cls, offsets, nbits, device_ptr=None):
+        """getFilterFromPipeline: the passing `_part_offset`s (duplicates allowed, offsets >= nbits ignored).  offsets: array-like
+        (uploaded), or, for UInt64 offsets already on the device, their count plus device_ptr."""
         h = C.c_void_p()
-        _check(lib().msvs_filter_from_offsets(_p(off, C.c_uint64), C.c_size_t(off.size), C.c_size_t(nbits), MEM_HOST, C.byref(h)))
+        if device_ptr is not None:
+            n = int(offsets)
+            ptr, mem = C.cast(C.c_void_p(int(device_ptr)), C.POINTER(C.c_uint64)), MEM_DEVICE
+        else:
+            off = np.ascontiguousarray(offsets, np.uint64)
+            n, ptr, mem = off.size, _p(off, C.c_uint64), MEM_HOST
+        _check(lib().msvs_filter_from_offsets(ptr, C.c_size_t(n), C.c_size_t(nbits), mem, C.byref(h)))
         return cls(h)
 
     @classmethod
     def from_predicate(cls, column, op, lo, hi=0, device_ptr=None):
         """`column OP lo` (OP in OPS; "between": lo <= x <= hi).  column: numpy array (uploaded), or pass its dtype-carrying
-        empty view plus device_ptr / len via (dtype, nrows) tuple for a column already on the device."""
+        empty view plus device_ptr / len via (dtype, nrows) tuple for a column already on the device.  Values are compared, the
+        constant is not cast into the column type; an integer constant outside int64 raises ValueError."""
         if device_ptr is not None:
             dt, n = column
             ptr, mem = C.c_void_p(int(device_ptr)), MEM_DEVICE
@@ -841,6 +848,10 @@ class Filter:
             dt, n = col.dtype, col.size
             ptr, mem = col.ctypes.data_as(C.c_void_p), MEM_HOST
         isf = np.dtype(dt).kind == "f"
+        if not isf:  # msvs_scalar_t carries an int64: ctypes would wrap anything else silently
+            for c in (lo, hi):
+                if not -2 ** 63 <= int(c) < 2 ** 63:
+                    raise ValueError("integer constant %d does not fit msvs_scalar_t.i (int64)" % int(c))
         sl = _Scalar(0 if isf else int(lo), float(lo) if isf else 0.0)
         sh = _Scalar(0 if isf else int(hi), float(hi) if isf else 0.0)
         h = C.c_void_p()

@@ -4,7 +4,7 @@
 // `_part_offset`s out of it and sets one bit per row (performPrefilter / getFilterFromPipeline,
 // src/VectorIndex/Storages/MergeTreeSelectWithHybridSearchProcessor.cpp:905-1112).  Here:
 //   filter_from_offsets_kernel   : the same scatter of row offsets into a bitmap, on the device;
-//   filter_predicate_kernel<T>   : `column OP constant` (=, !=, <, <=, >, >=, BETWEEN) over a numeric column -> bitmap words
+//   filter_predicate_kernel      : `column OP constant` (=, !=, <, <=, >, >=, BETWEEN) over a numeric column -> bitmap words
 //                                  directly (one wavefront ballot = one 64-bit word), so a simple PREWHERE never leaves the GPU;
 //   filter_combine_kernel        : AND / OR / AND NOT of two bitmaps; filter_count_kernel: population count.
 //
@@ -44,24 +44,37 @@ static __global__ void filter_from_offsets_kernel(const uint64_t * offsets, size
         atomicOr(bits + (r >> 6), 1ull << (r & 63));
 }
 
-/// One wavefront per 64 rows: the ballot of the predicate IS the bitmap word.  NaN compares false (!= true), like the host.
-template <typename T>
-static __global__ void filter_predicate_kernel(const T * col, size_t n, int op, T lo, T hi, uint64_t * bits)
+// The predicate compares VALUES, never the constant cast into the column type (UInt8 `< 300` passes every row, `== 256` none):
+// the row is widened to a type W that holds both sides -- int64 for the 8..32-bit integers and Int64, double for Float32 and
+// Float64 -- and the constant arrives in W.  UInt64 against an int64 constant has no common type: a negative constant is below
+// every row, a non-negative one is compared as uint64 (so rows >= 2^63 are above every constant).
+template <typename W>
+__device__ __forceinline__ bool pred_lt(W a, W b) { return a < b; }
+template <typename W>
+__device__ __forceinline__ bool pred_eq(W a, W b) { return a == b; }
+__device__ __forceinline__ bool pred_lt(uint64_t x, int64_t c) { return c >= 0 && x < (uint64_t)c; }
+__device__ __forceinline__ bool pred_lt(int64_t c, uint64_t x) { return c < 0 || (uint64_t)c < x; }
+__device__ __forceinline__ bool pred_eq(uint64_t x, int64_t c) { return c >= 0 && x == (uint64_t)c; }
+
+/// One wavefront per 64 rows: the ballot of the predicate IS the bitmap word.  T: storage type (the load), W: the type the row
+/// is compared in, C: the constants' type.  NaN compares false (!= true), like the host.
+template <typename T, typename W, typename C>
+static __global__ void filter_predicate_kernel(const T * col, size_t n, int op, C lo, C hi, uint64_t * bits)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool pass = false;
     if (i < n)
     {
-        const T x = col[i];
+        const W x = (W)col[i];
         switch (op)
         {
-            case FOP_EQ: pass = x == lo; break;
-            case FOP_NE: pass = x != lo; break;
-            case FOP_LT: pass = x < lo; break;
-            case FOP_LE: pass = x <= lo; break;
-            case FOP_GT: pass = x > lo; break;
-            case FOP_GE: pass = x >= lo; break;
-            default: pass = x >= lo && x <= hi; break;
+            case FOP_EQ: pass = pred_eq(x, lo); break;
+            case FOP_NE: pass = !pred_eq(x, lo); break;
+            case FOP_LT: pass = pred_lt(x, lo); break;
+            case FOP_LE: pass = pred_lt(x, lo) || pred_eq(x, lo); break;
+            case FOP_GT: pass = pred_lt(lo, x); break;
+            case FOP_GE: pass = pred_lt(lo, x) || pred_eq(x, lo); break;
+            default: pass = (pred_lt(lo, x) || pred_eq(x, lo)) && (pred_lt(x, hi) || pred_eq(x, hi)); break;
         }
     }
     const uint64_t word = __ballot(pass);
@@ -69,14 +82,25 @@ static __global__ void filter_predicate_kernel(const T * col, size_t n, int op, 
         bits[i >> 6] = word;
 }
 
-/// mode 0: a &= b, 1: a |= b, 2: a &= ~b.  Words of b past nb count as zero.
-static __global__ void filter_combine_kernel(uint64_t * a, size_t na, const uint64_t * b, size_t nb, int mode)
+/// The bits of word i that lie inside a bitmap of nbits bits.
+__device__ __forceinline__ uint64_t filter_word_mask(size_t i, size_t nbits)
+{
+    if ((i + 1) * 64 <= nbits)
+        return ~0ull;
+    return nbits > i * 64 ? (~0ull >> (64 - (nbits - i * 64))) : 0ull;
+}
+
+/// mode 0: a &= b, 1: a |= b, 2: a &= ~b over the words of a.  Bits of b at or past bits_b count as zero whatever the word
+/// holds there, and nothing is left set in a at or past bits_a: a is as long as before, b zero-extended or cut to it.
+static __global__ void filter_combine_kernel(uint64_t * a, size_t na, size_t bits_a, const uint64_t * b, size_t bits_b, int mode)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= na)
         return;
-    const uint64_t w = i < nb ? b[i] : 0ull;
-    a[i] = mode == 0 ? (a[i] & w) : (mode == 1 ? (a[i] | w) : (a[i] & ~w));
+    const uint64_t mb = filter_word_mask(i, bits_b);
+    const uint64_t w = mb ? (b[i] & mb) : 0ull;
+    const uint64_t r = mode == 0 ? (a[i] & w) : (mode == 1 ? (a[i] | w) : (a[i] & ~w));
+    a[i] = r & filter_word_mask(i, bits_a);
 }
 
 static __global__ void filter_count_kernel(const uint64_t * bits, size_t words, size_t nbits, unsigned long long * out)
@@ -84,12 +108,7 @@ static __global__ void filter_count_kernel(const uint64_t * bits, size_t words, 
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t c = 0;
     if (i < words)
-    {
-        uint64_t w = bits[i];
-        if ((i + 1) * 64 > nbits) // bits past nbits do not count
-            w &= nbits > i * 64 ? (~0ull >> (64 - (nbits - i * 64))) : 0ull;
-        c = (uint32_t)__popcll(w);
-    }
+        c = (uint32_t)__popcll(bits[i] & filter_word_mask(i, nbits)); // bits past nbits do not count
     for (int o = 32; o > 0; o >>= 1)
         c += __shfl_xor(c, o);
     if ((threadIdx.x & 63) == 0 && c)

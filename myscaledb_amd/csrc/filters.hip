@@ -157,8 +157,9 @@ extern "C" int msvs_filter_from_offsets(const uint64_t * part_offsets, size_t n,
 
 namespace
 {
-template <typename T>
-void launch_predicate(const void * col, size_t n, int mem, int op, T lo, T hi, msvs_filter & f, hipStream_t stream)
+/// T: the column's storage type, W: the type its rows are compared in, C: the constants' type (filter_kernels.hpp).
+template <typename T, typename W, typename C>
+void launch_predicate(const void * col, size_t n, int mem, int op, C lo, C hi, msvs_filter & f, hipStream_t stream)
 {
     const T * d_col = static_cast<const T *>(col);
     DevBuf<T> tmp;
@@ -168,8 +169,8 @@ void launch_predicate(const void * col, size_t n, int mem, int op, T lo, T hi, m
         MSVS_HIP(hipMemcpyAsync(tmp.p, col, n * sizeof(T), hipMemcpyHostToDevice, stream));
         d_col = tmp.p;
     }
-    hipLaunchKernelGGL((filter_predicate_kernel<T>), dim3((unsigned)ceil_div(n, (size_t)256)), dim3(256), 0, stream, d_col, n, op, lo, hi,
-                       f.bits.p);
+    hipLaunchKernelGGL((filter_predicate_kernel<T, W, C>), dim3((unsigned)ceil_div(n, (size_t)256)), dim3(256), 0, stream, d_col, n, op,
+                       lo, hi, f.bits.p);
     MSVS_HIP(hipGetLastError());
     filter_recount(f, stream);
 }
@@ -189,16 +190,17 @@ extern "C" int msvs_filter_from_predicate(const void * column, int dtype, size_t
         if (nrows)
             switch (dtype)
             {
-                case MSVS_DT_UINT8: launch_predicate<uint8_t>(column, nrows, mem, op, (uint8_t)lo.i, (uint8_t)hi.i, *f, stream); break;
-                case MSVS_DT_UINT16: launch_predicate<uint16_t>(column, nrows, mem, op, (uint16_t)lo.i, (uint16_t)hi.i, *f, stream); break;
-                case MSVS_DT_UINT32: launch_predicate<uint32_t>(column, nrows, mem, op, (uint32_t)lo.i, (uint32_t)hi.i, *f, stream); break;
-                case MSVS_DT_UINT64: launch_predicate<uint64_t>(column, nrows, mem, op, (uint64_t)lo.i, (uint64_t)hi.i, *f, stream); break;
-                case MSVS_DT_INT8: launch_predicate<int8_t>(column, nrows, mem, op, (int8_t)lo.i, (int8_t)hi.i, *f, stream); break;
-                case MSVS_DT_INT16: launch_predicate<int16_t>(column, nrows, mem, op, (int16_t)lo.i, (int16_t)hi.i, *f, stream); break;
-                case MSVS_DT_INT32: launch_predicate<int32_t>(column, nrows, mem, op, (int32_t)lo.i, (int32_t)hi.i, *f, stream); break;
-                case MSVS_DT_INT64: launch_predicate<int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
-                case MSVS_DT_FLOAT32: launch_predicate<float>(column, nrows, mem, op, (float)lo.f, (float)hi.f, *f, stream); break;
-                case MSVS_DT_FLOAT64: launch_predicate<double>(column, nrows, mem, op, lo.f, hi.f, *f, stream); break;
+                // by value: the constant is never cast into the column type (msvs.h, msvs_scalar_t)
+                case MSVS_DT_UINT8: launch_predicate<uint8_t, int64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_UINT16: launch_predicate<uint16_t, int64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_UINT32: launch_predicate<uint32_t, int64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_UINT64: launch_predicate<uint64_t, uint64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_INT8: launch_predicate<int8_t, int64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_INT16: launch_predicate<int16_t, int64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_INT32: launch_predicate<int32_t, int64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_INT64: launch_predicate<int64_t, int64_t, int64_t>(column, nrows, mem, op, lo.i, hi.i, *f, stream); break;
+                case MSVS_DT_FLOAT32: launch_predicate<float, double, double>(column, nrows, mem, op, lo.f, hi.f, *f, stream); break;
+                case MSVS_DT_FLOAT64: launch_predicate<double, double, double>(column, nrows, mem, op, lo.f, hi.f, *f, stream); break;
                 default: fail(MSVS_ERR_INVALID_ARGUMENT, "unknown column type %d", dtype);
             }
         *out = f.release();
@@ -211,9 +213,9 @@ extern "C" int msvs_filter_combine(msvs_filter_t * a, const msvs_filter_t * b, i
         if (!a || !b || mode < 0 || mode > 2)
             fail(MSVS_ERR_INVALID_ARGUMENT, "null filter / unknown mode");
         hipStream_t stream = thread_stream();
-        const size_t wa = std::max<size_t>(1, ceil_div(a->nbits, (size_t)64)), wb = ceil_div(b->nbits, (size_t)64);
-        hipLaunchKernelGGL(filter_combine_kernel, dim3((unsigned)ceil_div(wa, (size_t)256)), dim3(256), 0, stream, a->bits.p, wa, b->bits.p,
-                           wb, mode);
+        const size_t wa = std::max<size_t>(1, ceil_div(a->nbits, (size_t)64));
+        hipLaunchKernelGGL(filter_combine_kernel, dim3((unsigned)ceil_div(wa, (size_t)256)), dim3(256), 0, stream, a->bits.p, wa, a->nbits,
+                           b->bits.p, b->nbits, mode);
         MSVS_HIP(hipGetLastError());
         filter_recount(*a, stream);
     });
