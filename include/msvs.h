@@ -193,6 +193,66 @@ MSVS_API int msvs_sq_index_export(const msvs_sq_index_t * index, float * centroi
 MSVS_API int msvs_sq_index_serialize_io(const msvs_sq_index_t * index, const struct msvs_io * io);
 MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t ** out);
 
+/* IVFPQ -- an inverted-file index of Float32 vectors that keeps product-quantised residual codes ONLY (no f32 row survives build):
+ * m code bytes (padded to 4) + a u32 label per row.  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All
+ * arithmetic is f32 with separately rounded operations (fl), no fma:
+ *   - contents: nlist centroids c_l; m sub-codebooks cb[s][j] (s < m, j < 256: 8 bits per sub-quantiser only) of dsub = dim / m
+ *     floats each; per row its list, label and m codes; rows inside a list in ascending label order;
+ *   - stored row x: the row as fed (L2, IP) or the normalised row (cosine; msvs_normalize_f32's arithmetic);
+ *   - decoded sub-vector of code j in sub-space s of list l: x^[t] = fl(c_l[s * dsub + t] + cb[s][j][t]), t < dsub;
+ *   - sub-score e of a (query or row) sub-vector q against x^, t ascending, a sequential sum starting at +0:
+ *     L2: sum of fl(fl(q_t - x^_t)^2); IP and cosine: sum of fl(q_t * x^_t);
+ *   - encode (every metric): code[s] = the j with the smallest L2 sub-score between the stored row's sub-vector and x^; ties go to the
+ *     lowest j; a NaN score never wins (all NaN: code 0);
+ *   - distance of a row: dis = +0, then dis = fl(dis + e(s, code[s])) for s = 0 .. m - 1 (the ADC sum over a per-(query, list)
+ *     look-up table); it equals a distance to the decoded row with the sums taken per sub-space first;
+ *   - search: the canonical exact top-min(nprobe, nlist) lists by (distance to the centroid, list id), every alive row of them
+ *     scored as above, top-k by (distance asc -- desc for IP --, label asc), strictly better than the metric's neutral value
+ *     (+-FLT_MAX), unfilled slots -1 and that value; cosine normalises the query, searches with IP and reports fl(1 - ip) in every
+ *     slot; the filter is indexed by label.  The search over what the index stores is exact; the quantiser is lossy.
+ *   - a row is assigned to its nearest centroid by L2 (L2 indexes) or by inner product (IP and cosine), as msvs_index_add does.
+ * create: params as msvs_index_create's for IVFFLAT (ncentroids, kmeans_iters, train_sample, seed, ...) plus m, the number of
+ *   sub-quantisers (required).  1 <= m <= 128, m divides dim, dim <= 8192, and the list scan's smallest LDS image, m KiB of tables +
+ *   8 * round_up(dim, 4) + 5 * 8 * MSVS_MAX_K bytes, fits 160 KiB: MSVS_ERR_INVALID_ARGUMENT otherwise, checked here and at load.
+ * train: the coarse centroids by the IVFFLAT k-means over the rows; then the residuals fl(x - c_l) of at most 262144 training rows
+ *   (row floor(i * n / cap), i < cap = min(n, 262144)); for every s the dsub columns of sub-space s go through the same k-means
+ *   (L2, 256 centroids, the same iterations and seed): its centroids are cb[s].  n < 256: MSVS_ERR_INVALID_ARGUMENT.  The same input
+ *   gives the same bits.  set_codebook: centroids (nlist * dim) and codebooks (m * 256 * dsub, [s][j][t]) from the caller; a
+ *   non-finite codebook entry is MSVS_ERR_INVALID_ARGUMENT and leaves the index without a codebook.  Both must precede add
+ *   (MSVS_ERR_NOT_READY from add before either; MSVS_ERR_INVALID_ARGUMENT from either after add).
+ * add: any number of chunks before build; rows are encoded as they arrive, only codes, lists and labels are staged.  ids: labels
+ *   in [0, 2^32 - 1) (MSVS_ERR_ID_RANGE otherwise), NULL = staging order; labels are expected to be distinct.
+ * search (host pointers): params "nprobe=P" (default 1).  search_device: device pointers, enqueued on hip_stream without host
+ *   synchronisation.  k <= MSVS_MAX_K and min(nprobe, nlist) <= MSVS_MAX_K (MSVS_ERR_UNSUPPORTED_K); k = 0 or nq = 0 is a no-op;
+ *   before build: MSVS_ERR_NOT_READY.
+ * export: centroids nlist * dim, codebooks m * 256 * dsub, nlist + 1 offsets, codes n * m in NATURAL order, labels n; any output
+ *   may be NULL.
+ * memory_usage after build <= n * (round_up(m, 16) + 8) + the centroids, codebooks and offsets + 4096 bytes.
+ * Files "pq_data" (header "MSVSPQ01", centroids, codebooks, offsets, codes in natural order) / "pq_ids" through the caller's stream
+ * openers (a built index only); load validates sizes, offsets, labels, the codebooks and a checksum of each header: a corrupt or
+ * truncated file is MSVS_ERR_IO. */
+typedef struct msvs_pq_index msvs_pq_index_t;
+MSVS_API int msvs_pq_index_create(int metric, size_t dim, const char * params, msvs_pq_index_t ** out);
+MSVS_API void msvs_pq_index_free(msvs_pq_index_t * index);
+MSVS_API int msvs_pq_index_train(msvs_pq_index_t * index, const float * x, size_t n, int mem);
+MSVS_API int msvs_pq_index_set_codebook(msvs_pq_index_t * index, const float * centroids, size_t nlist, const float * codebooks,
+                                        int mem);
+MSVS_API int msvs_pq_index_add(msvs_pq_index_t * index, const float * x, const int64_t * ids, size_t n, int mem);
+MSVS_API int msvs_pq_index_build(msvs_pq_index_t * index);
+MSVS_API int msvs_pq_index_ready(const msvs_pq_index_t * index);
+MSVS_API size_t msvs_pq_index_num_data(const msvs_pq_index_t * index);
+MSVS_API size_t msvs_pq_index_num_lists(const msvs_pq_index_t * index);
+MSVS_API size_t msvs_pq_index_memory_usage(const msvs_pq_index_t * index);
+MSVS_API int msvs_pq_index_search(const msvs_pq_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
+                                  const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_pq_index_search_device(const msvs_pq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t nprobe,
+                                         const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                         void * hip_stream);
+MSVS_API int msvs_pq_index_export(const msvs_pq_index_t * index, float * centroids, float * codebooks, int64_t * list_off,
+                                  uint8_t * codes, int64_t * ids);
+MSVS_API int msvs_pq_index_serialize_io(const msvs_pq_index_t * index, const struct msvs_io * io);
+MSVS_API int msvs_pq_index_load_io(const struct msvs_io * io, msvs_pq_index_t ** out);
+
 /* Resident blocks for the brute-force path: the GPU analogue of VICacheManager / VIWithMeta
  * (src/VectorIndex/Cache/VICacheObject.h:40-162) for the dense block a mark of a part turns into
  * (MergeTreeVSManager.cpp:1380-1392).  msvs_knn_f32 moves that block over PCIe on every query; here it is uploaded

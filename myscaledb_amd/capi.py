@@ -4,6 +4,7 @@ Fails loudly when the library is missing: there is deliberately no fallback path
 """
 import ctypes as C
 import os
+import struct
 
 import numpy as np
 
@@ -40,6 +41,9 @@ SYMBOLS = [
     "msvs_sq_index_create", "msvs_sq_index_free", "msvs_sq_index_train", "msvs_sq_index_set_codebook", "msvs_sq_index_add",
     "msvs_sq_index_build", "msvs_sq_index_ready", "msvs_sq_index_num_data", "msvs_sq_index_num_lists", "msvs_sq_index_memory_usage",
     "msvs_sq_index_search", "msvs_sq_index_search_device", "msvs_sq_index_export", "msvs_sq_index_serialize_io", "msvs_sq_index_load_io",
+    "msvs_pq_index_create", "msvs_pq_index_free", "msvs_pq_index_train", "msvs_pq_index_set_codebook", "msvs_pq_index_add",
+    "msvs_pq_index_build", "msvs_pq_index_ready", "msvs_pq_index_num_data", "msvs_pq_index_num_lists", "msvs_pq_index_memory_usage",
+    "msvs_pq_index_search", "msvs_pq_index_search_device", "msvs_pq_index_export", "msvs_pq_index_serialize_io", "msvs_pq_index_load_io",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
     "msvs_comm_free", "msvs_comm_all_reduce_u64", "msvs_comm_rank", "msvs_comm_size", "msvs_shard_search_device", "msvs_shard_search_device_async", "msvs_shard_search_drain", "msvs_shard_search_routed_device",
@@ -380,6 +384,122 @@ class SqIndex:
             _lib.msvs_sq_index_free.argtypes = [C.c_void_p]
             _lib.msvs_sq_index_free.restype = None
             _lib.msvs_sq_index_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class PqIndex:
+    """msvs_pq_index_t: the IVFPQ index -- coarse centroids, m sub-codebooks of 256 entries over the residuals, and per row its list,
+    label and m code bytes (no f32 row is kept).  params as Index's for IVFFLAT plus m ("ncentroids=N,m=M,kmeans_iters=I,...")."""
+
+    def __init__(self, metric, dim, params="", _handle=None, _m=None):
+        self.metric, self.dim = int(metric), int(dim)
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h, self.m = _handle, int(_m)
+        else:
+            _check(lib().msvs_pq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
+            self.m = int(dict(kv.split("=", 1) for kv in params.replace(" ", "").split(",") if "=" in kv)["m"])
+
+    def _size(self, name):
+        fn = getattr(lib(), name)
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_void_p]
+        return fn(self._h)
+
+    def train(self, x):
+        x = _f32(x).reshape(-1, self.dim)
+        _check(lib().msvs_pq_index_train(self._h, _p(x, C.c_float), C.c_size_t(x.shape[0]), MEM_HOST))
+
+    def set_codebook(self, centroids, codebooks):
+        """codebooks: [m, 256, dim / m]"""
+        c = _f32(centroids).reshape(-1, self.dim)
+        cb = _f32(codebooks).reshape(self.m, 256, self.dim // self.m)
+        _check(lib().msvs_pq_index_set_codebook(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(cb, C.c_float), MEM_HOST))
+
+    def add(self, x, ids=None):
+        x = _f32(x).reshape(-1, self.dim)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int64)
+        _check(lib().msvs_pq_index_add(self._h, _p(x, C.c_float), _p(ids, C.c_int64), C.c_size_t(x.shape[0]), MEM_HOST))
+
+    def build(self):
+        _check(lib().msvs_pq_index_build(self._h))
+
+    @property
+    def ready(self):
+        lib().msvs_pq_index_ready.argtypes = [C.c_void_p]
+        return bool(lib().msvs_pq_index_ready(self._h))
+
+    @property
+    def num_data(self):
+        return self._size("msvs_pq_index_num_data")
+
+    @property
+    def num_lists(self):
+        return self._size("msvs_pq_index_num_lists")
+
+    @property
+    def memory_usage(self):
+        return self._size("msvs_pq_index_memory_usage")
+
+    def search(self, queries, k, params="", alive=None, nbits=None):
+        """params: "nprobe=P"; alive: bool over labels, nbits: how many of them the filter covers (default all of `alive`)."""
+        q = _f32(queries).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), np.int64)
+        dis = np.empty((q.shape[0], k), np.float32)
+        bits = None if alive is None else pack_bits(alive)
+        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
+        _check(lib().msvs_pq_index_search(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), params.encode(),
+                                          _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        return ids, dis
+
+    def search_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """All arguments are raw device addresses (ints); enqueues on `stream` and returns immediately."""
+        _check(lib().msvs_pq_index_search_device(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(nprobe),
+                                                 C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
+                                                 C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
+                                                 C.c_void_p(int(stream)) if stream else None))
+
+    def export(self, with_lists=True):
+        """-> (centroids [nlist, dim], codebooks [m, 256, dim / m], list offsets [nlist + 1], codes [n, m] u8 in natural order,
+        labels [n]) in list-major order; with_lists=False (an index not built yet): the codebook only, None for the rest."""
+        nl, d, m = self.num_lists, self.dim, self.m
+        cent = np.empty((nl, d), np.float32)
+        cb = np.empty((m, 256, d // m), np.float32)
+        off = codes = labels = None
+        if with_lists:
+            n = self.num_data
+            off, codes, labels = np.empty(nl + 1, np.int64), np.empty((n, m), np.uint8), np.empty(n, np.int64)
+        _check(lib().msvs_pq_index_export(self._h, _p(cent, C.c_float), _p(cb, C.c_float), _p(off, C.c_int64), _p(codes, C.c_uint8),
+                                          _p(labels, C.c_int64)))
+        return cent, cb, off, codes, labels
+
+    def serialize_io(self, store):
+        """msvs_pq_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""
+        _check(lib().msvs_pq_index_serialize_io(self._h, C.byref(_DictIO(store).io)))
+
+    @classmethod
+    def load_io(cls, store, metric=None, dim=None, m=None):
+        """The geometry comes from the file's header (which the load has validated, check word included), never from the caller:
+        export() sizes its buffers by it.  metric / dim / m, where given, must agree with the file (ValueError otherwise)."""
+        h = C.c_void_p()
+        _check(lib().msvs_pq_index_load_io(C.byref(_DictIO(store).io), C.byref(h)))
+        # PqHeader: magic[8], u32 version, i32 metric, u64 dim, u64 m, ...
+        f_metric, f_dim, f_m = struct.unpack_from("<iQQ", bytes(store["pq_data"][:32]), 12)
+        ix = cls(f_metric, f_dim, _handle=h, _m=f_m)
+        for name, want, have in (("metric", metric, f_metric), ("dim", dim, f_dim), ("m", m, f_m)):
+            if want is not None and int(want) != have:
+                ix.close()
+                raise ValueError("the IVFPQ index file has %s = %d, the caller expects %d" % (name, have, int(want)))
+        return ix
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.msvs_pq_index_free.argtypes = [C.c_void_p]
+            _lib.msvs_pq_index_free.restype = None
+            _lib.msvs_pq_index_free(self._h)
             self._h = None
 
     __del__ = close

@@ -260,6 +260,9 @@ struct Options
     double pinned_fetch_max = 1048576; // ... up to this many bytes
     double bin_ivf_rpb = 0;     // partitioned binary index: rows per work item of the list scan (0 = planned: <= ~8 segments per list, >= 2048 rows; tests: small segments)
     double sq_ivf_rpb = 0;      // IVFSQ index: rows per work item of the list scan (0 = planned, as bin_ivf_rpb; tests: several segments per short list)
+    double pq_ivf_rpb = 0;      // IVFPQ index: rows per work item of the list scan (0 = planned, as bin_ivf_rpb: a segment rebuilds its tile's look-up
+                                // tables, so lists stay whole up to 2048 rows; tests: several segments per short list)
+    double pq_ivf_tables_only = 0; // IVFPQ list scan, measurement: tables are built, the row loop is skipped (results come out empty)
     double route_self_rccl = 0; // routed sharded search over an RCCL communicator: a rank's OWN piece also travels through ncclSend / ncclRecv (to itself, grouped)
                                 // instead of a device copy -- lets one rank on a 1-GPU box execute the point-to-point group path (tests)
 };

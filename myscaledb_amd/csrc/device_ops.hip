@@ -686,6 +686,7 @@ const OptionField g_option_fields[] = {
     {"route_self_rccl", &Options::route_self_rccl},
     {"bin_ivf_rpb", &Options::bin_ivf_rpb},
     {"sq_ivf_rpb", &Options::sq_ivf_rpb},
+    {"pq_ivf_rpb", &Options::pq_ivf_rpb}, {"pq_ivf_tables_only", &Options::pq_ivf_tables_only},
 };
 Options g_options;
 std::once_flag g_options_once;
