@@ -1029,6 +1029,22 @@ def debug_prune_stats():
     return int(out[0]), int(out[1])
 
 
+def debug_rerank_rows():
+    """(candidate rows the re-rank's first stage evaluated, rows its second chance evaluated), cumulative -- counted only under
+    rerank_stats = 1."""
+    out = (C.c_uint64 * 3)()
+    _check(lib().msvs_debug_rerank_rows(out))
+    return int(out[0]), int(out[1])
+
+
+def debug_rerank_skipped_chunks():
+    """Chunks of second-chance buffers the re-rank skipped whole because the first stage's hint left none of their keys
+    (rerank_chain = 1), cumulative -- counted only under rerank_stats = 1."""
+    out = (C.c_uint64 * 3)()
+    _check(lib().msvs_debug_rerank_rows(out))
+    return int(out[2])
+
+
 def debug_scan_rows():
     """(rows the shadow main launches read, rows their sample launches read), cumulative -- counted only under rerank_stats = 1."""
     out = (C.c_uint64 * 2)()

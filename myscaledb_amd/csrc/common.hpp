@@ -231,6 +231,7 @@ struct Options
     double merge_small = 1;   // msvs_merge_topk_device: nparts * k <= 256 keys per query merged by one wavefront (0: pack + block merge)
     double coarse_tail = 1;   // coarse quantiser of batches: selection + band re-rank in one launch, a wavefront per query (0: coarse_select_kernel + ivf_rerank_kernel)
     double coarse_band = 1;   // coarse quantiser of batches: only the candidates near the top-nprobe boundary are evaluated canonically (0: all 64)
+    double rerank_chain = 1;  // re-rank blocks: one prologue round trip, eps formed once, a lane's whole row in flight (0: loads where each step needs them)
     double rerank_hint = 1;   // second-chance re-rank: skip rows that cannot beat the first stage's k-th exact distance (0: evaluate the whole buffer)
     double bm25_wave = 1;     // BM25: wave-private streaming scorer (1) or the barrier-synchronised block scorer (0)
     double bm25_posting = 1;  // BM25: posting-as-unit scorer (bm25p_kernel) for batches of sparse terms; 0: always the dense accumulator, 2: always the posting scorer

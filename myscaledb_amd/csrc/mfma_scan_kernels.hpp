@@ -978,7 +978,8 @@ struct RerankParams
     int band; // probe lists (out_probes) only: candidates that are certainly inside / outside the exact top-k by their approximate
               // values alone are not evaluated (see ivf_rerank_kernel)
     uint64_t * ek_out; // nullable [nq]: a query WITHOUT a certificate leaves the k-th exact key of the candidates it evaluated here
-                       // (KEY_NONE: fewer than k) -- an upper bound of its true k-th distance for the second chance    // Round 6: the SECOND CHANCE in the same launch (result passes, 256-thread blocks): a query whose certificate fails has its whole
+                       // (KEY_NONE: fewer than k) -- an upper bound of its true k-th distance for the second chance
+    // Round 6: the SECOND CHANCE in the same launch (result passes, 256-thread blocks): a query whose certificate fails has its whole
     // candidate buffer re-ranked by its own block right away (rerank_all_query) instead of being queued for ivf_rerank_all_kernel --
     // one launch less, and the second chances (a sixth of the queries on SURVEY 8d's sigma-0.3 blobs) run beside the other queries'
     // first stage.  fuse_second != 0: `ra` is the second chance's view; what still fails goes to ra.failq_out / ra.nfail_out.
@@ -987,26 +988,86 @@ struct RerankParams
     // Round 6 (probe lists): only the queries qmap[0 .. *qcount) -- those coarse_tail_kernel could not serve with a band (block b = entry b)
     const uint32_t * qmap = nullptr;
     const uint32_t * qcount = nullptr;
+    // Round 8 (option rerank_chain, set by the launchers): everything a block needs besides rows and their ids is requested at its
+    // entry and kept in LDS, eps is formed once, and a 16-lane group has its lane's whole row in flight before the first update
+    // (0: the loads where each step needs them, row pieces four at a time).  The rows read and the arithmetic are the same.
+    int chain = 0;
+    unsigned long long * stat_rows = nullptr; // nullable (option rerank_stats): [0] += rows the first stage evaluates, [1] += the second chance,
+                                              // [2] += chunks of a second chance's buffer skipped because the hint left none of their keys
 };
 
-/// |approximate value - canonical value| <= eps for every row of the table and this query (sx, sq: upper bounds of |x|, |q|).
-/// L2: a = |x|^2 + |q|^2 - 2<x,q> with approximate norms and product; IP: a = <x,q>.
+/// |approximate value - canonical value| <= eps for every row of the table and this query (sx, sq: upper bounds of |x|, |q|;
+/// rho: qrho[q], read only when a.qrho is set).  L2: a = |x|^2 + |q|^2 - 2<x,q> with approximate norms and product; IP: a = <x,q>.
 template <int METRIC>
-__device__ __forceinline__ double rerank_eps(const RerankParams & a, double sx, double sq, uint32_t q)
+__device__ __forceinline__ double rerank_eps_rho(const RerankParams & a, double sx, double sq, float rho)
 {
-    const double c_dot = a.qrho ? a.c_dot + a.qrho_scale * (double)a.qrho[q] : a.c_dot;
+    const double c_dot = a.qrho ? a.c_dot + a.qrho_scale * (double)rho : a.c_dot;
     return (METRIC == M_L2 ? 2.0 * c_dot * sx * sq + a.c_norm * (sx * sx + sq * sq) + (a.c_canon + 4e-7) * (sx + sq) * (sx + sq)
                            : (c_dot + a.c_canon) * sx * sq)
         + 1e-30;
 }
 
 template <int METRIC>
+__device__ __forceinline__ double rerank_eps(const RerankParams & a, double sx, double sq, uint32_t q)
+{
+    return rerank_eps_rho<METRIC>(a, sx, sq, a.qrho ? a.qrho[q] : 0.f);
+}
+
+/// What a re-rank block reads about its query besides rows, fetched once (rerank_chain): the second chance's buffer fill and cut,
+/// and the error bound shared by the band, the early exit, both certificates and the second chance's hint.
+struct RerankQuery
+{
+    uint32_t cnt, thr; // RerankAllParams::qcnt[q], qthr[q]
+    bool usable;       // the norms are finite: eps means something
+    double eps;        // rerank_eps (0 unless usable)
+};
+
+/// The canonical accumulator of one lane over its pieces of a row (rerank_chain): whole batches of twelve pieces are requested,
+/// with the row's id (idp: nullable) behind the first of them, before the batch's first update; the updates run in ascending
+/// piece order, as in the four-at-a-time loop.  d = 768 is one batch, d = 1536 two.  What is left of other shapes (jfull % 12
+/// pieces and the tail) goes four at a time: a predicated batch of twelve for it cost 50 - 70 VGPRs, a wavefront per SIMD and more.
+template <int METRIC>
+__device__ __forceinline__ float4 canonical_row_chain(const float4 * yrow, const float4 * qrow, const uint32_t jfull, const uint32_t jtail,
+                                                      const uint32_t g, const uint32_t * idp, uint32_t & id)
+{
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t j = 0;
+    if (jfull < 12 && idp)
+        id = *idp;
+    for (; j + 12 <= jfull; j += 12)
+    {
+        float4 y[12];
+#pragma unroll
+        for (int u = 0; u < 12; u++)
+            y[u] = yrow[(j + u) * 16];
+        if (j == 0 && idp)
+            id = *idp;
+#pragma unroll
+        for (int u = 0; u < 12; u++)
+            canonical_update<METRIC>(acc, qrow[(j + u) * 16], y[u]);
+    }
+    for (; j + 4 <= jfull; j += 4)
+    {
+        const float4 y0 = yrow[j * 16], y1 = yrow[(j + 1) * 16], y2 = yrow[(j + 2) * 16], y3 = yrow[(j + 3) * 16];
+        canonical_update<METRIC>(acc, qrow[j * 16], y0);
+        canonical_update<METRIC>(acc, qrow[(j + 1) * 16], y1);
+        canonical_update<METRIC>(acc, qrow[(j + 2) * 16], y2);
+        canonical_update<METRIC>(acc, qrow[(j + 3) * 16], y3);
+    }
+    for (; j < jfull; j++)
+        canonical_update<METRIC>(acc, qrow[j * 16], yrow[j * 16]);
+    if (g < jtail)
+        canonical_update<METRIC>(acc, qrow[jfull * 16], yrow[jfull * 16]);
+    return acc;
+}
+
+template <int METRIC>
 __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const RerankAllParams & b, const uint32_t q, float4 * qs,
-                                                 const bool qs_ready, unsigned char * lds, const uint64_t hint);
+                                                 const bool qs_ready, unsigned char * lds, const uint64_t hint, const RerankQuery * pre);
 
 /// One block of 16 G threads per query: G groups of 16 lanes, a group per candidate row and round.  G = 16; 32 (all
 /// candidates of a k <= 12 search in flight at once) measured SLOWER: 70 against 47 us per 4096 queries -- kept as a knob.
-/// dynamic LDS: ld4*16 + 64*R*8 bytes.
+/// dynamic LDS: ld4*16 + 64*R*8 bytes, + 64*R*8 for the candidates' approximate keys under rerank_chain.
 template <int METRIC, int G, int R> // R: kc <= 64 R (256 candidates for 40 < k <= 128)
 __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a)
 {
@@ -1016,10 +1077,75 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
     if (a.qmap && blockIdx.x >= *a.qcount)
         return;
     const uint32_t q = a.qmap ? a.qmap[blockIdx.x] : blockIdx.x, ld4 = a.ld4, kc = a.kc;
-    for (uint32_t c = tid; c < ld4; c += 16 * G)
-        qs[c] = a.Q[(size_t)q * ld4 + c];
-    for (uint32_t c = tid; c < 64 * R; c += 16 * G)
-        keys[c] = KEY_NONE;
+    // rerank_chain (256-thread blocks; the G = 32 experiment keeps the four-at-a-time loops: twelve pieces in flight would cost it waves)
+    const bool chain = G == 16 && a.chain != 0;
+    uint64_t * ckeys = keys + 64 * R; // chain: cand[q][..], KEY_NONE padded
+    __shared__ double s_e, s_eps;
+    __shared__ uint64_t s_ak, s_ak1, s_bound;
+    __shared__ uint32_t s_nin, s_qcnt, s_qthr;
+    __shared__ int s_band, s_usable;
+    if (chain)
+    {
+        // ONE round trip for everything but rows and their ids: the requests below are all issued before the first of them is
+        // waited for.  The error bound is the same for the band, the early exit, the certificate and the second chance: formed once.
+        uint64_t ck[(64 * R + 16 * G - 1) / (16 * G)];
+#pragma unroll
+        for (uint32_t i = 0; i < (64 * R + 16 * G - 1) / (16 * G); i++)
+        {
+            const uint32_t c = tid + i * 16 * G;
+            ck[i] = c < kc ? a.cand[(size_t)q * kc + c] : KEY_NONE;
+        }
+        float qn = 0.f, rho = 0.f;
+        uint64_t bnd = KEY_NONE;
+        uint32_t cnt = 0, thr = 0;
+        if (tid == 0)
+        {
+            qn = a.qnorm[q];
+            if (a.qrho)
+                rho = a.qrho[q];
+            if (a.bound)
+                bnd = a.bound[q];
+            if (a.fuse_second)
+            {
+                cnt = a.ra.qcnt[q];
+                thr = a.ra.qthr[q];
+            }
+        }
+        for (uint32_t c = tid; c < ld4; c += 16 * G)
+            qs[c] = a.Q[(size_t)q * ld4 + c];
+#pragma unroll
+        for (uint32_t i = 0; i < (64 * R + 16 * G - 1) / (16 * G); i++)
+        {
+            const uint32_t c = tid + i * 16 * G;
+            if (c < 64 * R)
+            {
+                keys[c] = KEY_NONE;
+                ckeys[c] = ck[i];
+            }
+        }
+        if (tid == 0)
+        {
+            const bool usable = qn < 1e30f && a.xmax < 1e30f;
+            s_usable = usable ? 1 : 0;
+            s_eps = usable ? rerank_eps_rho<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), rho) : 0.0;
+            s_bound = bnd;
+            s_qcnt = cnt;
+            s_qthr = thr;
+        }
+    }
+    else
+    {
+        for (uint32_t c = tid; c < ld4; c += 16 * G)
+            qs[c] = a.Q[(size_t)q * ld4 + c];
+        for (uint32_t c = tid; c < 64 * R; c += 16 * G)
+            keys[c] = KEY_NONE;
+    }
+    if (tid == 0)
+    {
+        s_ak = s_ak1 = KEY_NONE;
+        s_nin = 0;
+        s_band = 0;
+    }
     __syncthreads();
     const uint32_t jfull = ld4 >> 4, jtail = ld4 & 15;
     // BAND (probe lists): only the SET of the k best rows leaves this kernel, and most of it is decided by the approximate
@@ -1030,43 +1156,47 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
     // min(last, bound) - 2 eps > a_(k).  The rest, the band around the boundary, is evaluated canonically and fills the
     // remaining slots in exact order.  On the bench step 3-4 of 64 centroid rows per query instead of 64 (45 -> ~10 us).
     __shared__ uint8_t s_state[64 * R]; // 0: evaluate, 1: certainly in, 2: certainly out
-    __shared__ uint64_t s_ak, s_ak1;
-    __shared__ uint32_t s_nin;
-    __shared__ int s_band;
     if (a.band && a.out_probes && kc > a.k && kc <= 16 * G)
     {
-        if (tid < kc)
-            keys[tid] = a.cand[(size_t)q * kc + tid];
-        if (tid == 0)
+        if (!chain) // (chain: the approximate keys are in ckeys already)
         {
-            s_ak = s_ak1 = KEY_NONE;
-            s_nin = 0;
-            s_band = 0;
+            if (tid < kc)
+                keys[tid] = a.cand[(size_t)q * kc + tid];
+            __syncthreads();
         }
-        __syncthreads();
-        const uint64_t mine = tid < kc ? keys[tid] : KEY_NONE;
+        const uint64_t * bk = chain ? ckeys : keys;
+        const uint64_t mine = tid < kc ? bk[tid] : KEY_NONE;
         uint32_t rank = 0; // of this candidate among all of them by approximate key
         if (mine != KEY_NONE)
         {
             for (uint32_t j = 0; j < kc; j++)
-                rank += keys[j] < mine || (keys[j] == mine && j < tid) ? 1u : 0u;
+                rank += bk[j] < mine || (bk[j] == mine && j < tid) ? 1u : 0u;
             if (rank == a.k - 1)
                 s_ak = mine;
             if (rank == a.k)
                 s_ak1 = mine;
         }
         __syncthreads();
-        const float qn = a.qnorm[q];
-        const bool usable = s_ak != KEY_NONE && s_ak1 != KEY_NONE && qn < 1e30f && a.xmax < 1e30f;
+        bool usable = s_ak != KEY_NONE && s_ak1 != KEY_NONE;
+        float qn = 0.f;
+        if (chain)
+            usable = usable && s_usable != 0;
+        else
+        {
+            qn = a.qnorm[q];
+            usable = usable && qn < 1e30f && a.xmax < 1e30f;
+        }
         double eps2 = 0.0, ak = 0.0, ak1 = 0.0;
         bool band_ok = usable;
         if (usable)
         {
-            eps2 = 2.0 * rerank_eps<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), q);
+            eps2 = 2.0 * (chain ? s_eps : rerank_eps<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), q));
             ak = (double)key_value<METRIC>(s_ak);
             ak1 = (double)key_value<METRIC>(s_ak1);
-            uint64_t last = keys[kc - 1]; // the candidates' largest approximate value comes last; KEY_NONE: every row is a candidate
-            if (a.bound && a.bound[q] < last)
+            uint64_t last = bk[kc - 1]; // the candidates' largest approximate value comes last; KEY_NONE: every row is a candidate
+            if (chain)
+                last = s_bound < last ? s_bound : last; // (no bound: KEY_NONE)
+            else if (a.bound && a.bound[q] < last)
                 last = a.bound[q];
             if (last != KEY_NONE)
             {
@@ -1098,18 +1228,12 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
         if (tid == 0)
             s_band = band_ok ? 1 : 0;
         __syncthreads();
-        if (tid < kc)
-            keys[tid] = KEY_NONE;
-        __syncthreads();
-    }
-    else
-    {
-        if (tid == 0)
+        if (!chain)
         {
-            s_band = 0;
-            s_nin = 0;
+            if (tid < kc)
+                keys[tid] = KEY_NONE;
+            __syncthreads();
         }
-        __syncthreads();
     }
     const bool band = s_band != 0;
     // Early exit: the candidates arrive in ascending approximate order, G per round.  Once the first ceil(k / G) rounds
@@ -1118,7 +1242,6 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
     // (valid whatever the order is; the order makes it effective).  List scan of the bench step: 57 % of the 32 candidates
     // per query are never read (of 69 % that are not results), 75 -> 50 us; the coarse quantiser's table lives in L2 and
     // gains nothing (measured), so the host leaves it off there and its candidates unsorted.
-    __shared__ double s_e, s_eps;
     __shared__ int s_skip;
     __shared__ uint64_t s_ek;
     const uint32_t first = a.early_exit && kc % G == 0 ? (a.k + G - 1) / G * G : kc; // every group walks kc / G rounds: the barrier is uniform
@@ -1139,7 +1262,14 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
                     s_ek = mine;
             }
             __syncthreads();
-            if (tid == 0)
+            if (tid == 0 && chain)
+            {
+                const bool usable = s_ek != KEY_NONE && s_usable != 0;
+                s_skip = usable ? 1 : 0;
+                if (usable)
+                    s_e = (double)key_value<METRIC>(s_ek);
+            }
+            else if (tid == 0)
             {
                 const float qn = a.qnorm[q];
                 const bool usable = s_ek != KEY_NONE && qn < 1e30f && a.xmax < 1e30f;
@@ -1153,7 +1283,7 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
             }
             __syncthreads();
         }
-        const uint64_t ck = a.cand[(size_t)q * kc + c]; // uniform over the 16 lanes that own candidate c
+        const uint64_t ck = chain ? ckeys[c] : a.cand[(size_t)q * kc + c]; // uniform over the 16 lanes that own candidate c
         if (ck == KEY_NONE || (band && s_state[c] != 0))
             continue;
         if (c - grp >= first && s_skip)
@@ -1169,24 +1299,37 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
         const uint32_t pos = (uint32_t)ck;
         const float4 * yrow = a.Y + (size_t)pos * ld4 + g;
         const float4 * qrow = qs + g;
+        if (a.stat_rows && g == 0)
+            atomicAdd(a.stat_rows, 1ull);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        uint32_t j = 0;
-        for (; j + 4 <= jfull; j += 4) // (8 pieces in flight measured slower here: 4096 blocks, the occupancy is the parallelism)
+        uint32_t id = pos;
+        if (chain)
         {
-            const float4 y0 = yrow[j * 16], y1 = yrow[(j + 1) * 16], y2 = yrow[(j + 2) * 16], y3 = yrow[(j + 3) * 16];
-            canonical_update<METRIC>(acc, qrow[j * 16], y0);
-            canonical_update<METRIC>(acc, qrow[(j + 1) * 16], y1);
-            canonical_update<METRIC>(acc, qrow[(j + 2) * 16], y2);
-            canonical_update<METRIC>(acc, qrow[(j + 3) * 16], y3);
+            // the lane's whole row in flight before the first update.  The launch holds 4 waves per SIMD since the second chance
+            // was fused in (101 VGPRs before this, 118 now): twelve pieces in flight cost no wave, where eight cost the
+            // unfused kernel its seventh.  Measured: DESIGN 4.2 "Round 8".
+            acc = canonical_row_chain<METRIC>(yrow, qrow, jfull, jtail, g, a.ids && g == 0 ? a.ids + pos : nullptr, id);
         }
-        for (; j < jfull; j++)
-            canonical_update<METRIC>(acc, qrow[j * 16], yrow[j * 16]);
-        if (g < jtail)
-            canonical_update<METRIC>(acc, qrow[jfull * 16], yrow[jfull * 16]);
+        else
+        {
+            uint32_t j = 0;
+            for (; j + 4 <= jfull; j += 4)
+            {
+                const float4 y0 = yrow[j * 16], y1 = yrow[(j + 1) * 16], y2 = yrow[(j + 2) * 16], y3 = yrow[(j + 3) * 16];
+                canonical_update<METRIC>(acc, qrow[j * 16], y0);
+                canonical_update<METRIC>(acc, qrow[(j + 1) * 16], y1);
+                canonical_update<METRIC>(acc, qrow[(j + 2) * 16], y2);
+                canonical_update<METRIC>(acc, qrow[(j + 3) * 16], y3);
+            }
+            for (; j < jfull; j++)
+                canonical_update<METRIC>(acc, qrow[j * 16], yrow[j * 16]);
+            if (g < jtail)
+                canonical_update<METRIC>(acc, qrow[jfull * 16], yrow[jfull * 16]);
+        }
         float s = __fadd_rn(__fadd_rn(acc.x, acc.y), __fadd_rn(acc.z, acc.w));
         s = row16_tree_sum(s);
         if (g == 0)
-            keys[c] = make_key<METRIC>(s, a.ids ? a.ids[pos] : pos);
+            keys[c] = make_key<METRIC>(s, chain || !a.ids ? id : a.ids[pos]);
     }
     __syncthreads();
     // exact top-k of the evaluated candidates: every key ranks itself among the 64 R slots (skipped / absent = KEY_NONE)
@@ -1226,25 +1369,33 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
     {
     // certificate (see the header comment): `last` = the smallest approximate key a non-candidate row can have; a
     // candidate list that is not full (and no truncated slice) holds every probed row
-    uint64_t last = a.cand[(size_t)q * kc + kc - 1];
-    if (a.bound && a.bound[q] < last)
-        last = a.bound[q];
+    uint64_t last;
+    if (chain)
+    {
+        last = ckeys[kc - 1];
+        last = s_bound < last ? s_bound : last; // (no bound: KEY_NONE)
+    }
+    else
+    {
+        last = a.cand[(size_t)q * kc + kc - 1];
+        if (a.bound && a.bound[q] < last)
+            last = a.bound[q];
+    }
     bool ok = true;
     if (last != KEY_NONE)
     {
         const uint64_t ek = s_ek;
-        const float qn = a.qnorm[q];
-        if (ek == KEY_NONE || !(qn < 1e30f) || !(a.xmax < 1e30f))
+        const float qn = chain ? 0.f : a.qnorm[q];
+        if (ek == KEY_NONE || (chain ? s_usable == 0 : !(qn < 1e30f) || !(a.xmax < 1e30f)))
             ok = false;
         else
         {
             const double al = (double)key_value<METRIC>(last), e = (double)key_value<METRIC>(ek);
-            const double sx = sqrt((double)a.xmax * 1.001), sq = sqrt((double)qn * 1.001);
-            const double eps = rerank_eps<METRIC>(a, sx, sq, q);
+            const double eps = chain ? s_eps : rerank_eps<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), q);
             ok = METRIC == M_L2 ? (al - eps > e) : (al + eps < e);
             if (a.stat_skip) // experiment: how many candidates an early exit could have skipped (approximate value beyond e_k +- eps)
             {
-                const uint64_t ck = lane < kc ? a.cand[(size_t)q * kc + lane] : KEY_NONE;
+                const uint64_t ck = lane >= kc ? KEY_NONE : chain ? ckeys[lane] : a.cand[(size_t)q * kc + lane];
                 const double aj = (double)key_value<METRIC>(ck);
                 const bool skippable = ck != KEY_NONE && (METRIC == M_L2 ? (aj - eps > e) : (aj + eps < e));
                 const uint32_t ns = (uint32_t)__popcll(__ballot(skippable)), nc = (uint32_t)__popcll(__ballot(ck != KEY_NONE));
@@ -1274,7 +1425,9 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
         return;
     // the second chance, here and now: every row of the query's candidate buffer, certified against the cut (rerank_all_query); the
     // query is in LDS already, the first stage's k-th exact key is the hint
-    const bool ok2 = rerank_all_query<METRIC>(a, a.ra, q, qs, true, msvs_smem + (size_t)ld4 * 16 + (size_t)64 * R * 8, s_ek);
+    const RerankQuery pre{s_qcnt, s_qthr, s_usable != 0, s_eps};
+    const bool ok2 = rerank_all_query<METRIC>(a, a.ra, q, qs, true, msvs_smem + (size_t)ld4 * 16 + (size_t)64 * R * 8 * (chain ? 2 : 1), s_ek,
+                                              chain ? &pre : nullptr);
     if (!ok2 && tid == 0)
     {
         a.ra.failq_out[atomicAdd(a.ra.nfail_out, 1u)] = q;
@@ -1301,7 +1454,7 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
 /// query has its certificate and its results are written.  Uniform over the block (barriers inside).
 template <int METRIC>
 __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const RerankAllParams & b, const uint32_t q, float4 * qs,
-                                                 const bool qs_ready, unsigned char * lds, const uint64_t hint)
+                                                 const bool qs_ready, unsigned char * lds, const uint64_t hint, const RerankQuery * pre)
 {
     uint64_t * best = reinterpret_cast<uint64_t *>(lds);          // [RA_KMAX] running exact top-k, ascending
     uint64_t * chunk = best + RA_KMAX;                            // [RA_CHUNK] this round's exact keys
@@ -1311,19 +1464,36 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = tid >> 4, g = tid & 15;
     const uint32_t ld4 = a.ld4, k = a.k;
     const uint32_t jfull = ld4 >> 4, jtail = ld4 & 15;
-    const uint32_t cnt = b.qcnt[q];
+    // rerank_chain: the query's scalars come from the caller's prologue (pre), or are requested here in one go; eps is formed once
+    const bool chain = a.chain != 0;
+    RerankQuery rq{0, 0, false, 0.0};
+    if (chain && pre)
+        rq = *pre;
+    else if (chain)
+    {
+        rq.cnt = b.qcnt[q];
+        rq.thr = b.qthr[q];
+        const float qn = a.qnorm[q], rho = a.qrho ? a.qrho[q] : 0.f;
+        rq.usable = qn < 1e30f && a.xmax < 1e30f;
+        if (rq.usable)
+            rq.eps = rerank_eps_rho<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), rho);
+    }
+    rq.thr = __builtin_amdgcn_readfirstlane(rq.thr); // (the same in every lane: scalar registers)
+    rq.cnt = __builtin_amdgcn_readfirstlane(rq.cnt);
+    const uint32_t cnt = chain ? rq.cnt : b.qcnt[q];
     bool ok = cnt <= b.cap; // an overflowed buffer dropped rows below the cut: nothing to certify
     __syncthreads();        // whoever used the LDS arrays before is done with them
     if (!ok)
         return false;
     // rows that cannot beat the first stage's k-th exact distance are skipped
-    const float qn0 = a.qnorm[q];
-    const bool have_hint = hint != KEY_NONE && qn0 < 1e30f && a.xmax < 1e30f;
-    double e0 = 0.0, eps0 = 0.0;
+    const float qn0 = chain ? 0.f : a.qnorm[q];
+    const bool have_hint = hint != KEY_NONE && (chain ? rq.usable : qn0 < 1e30f && a.xmax < 1e30f);
+    double e0 = 0.0, eps0 = chain ? rq.eps : 0.0; // (chain: the certificate below takes the same eps)
     if (have_hint)
     {
         e0 = (double)key_value<METRIC>(hint);
-        eps0 = rerank_eps<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn0 * 1.001), q);
+        if (!chain)
+            eps0 = rerank_eps<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn0 * 1.001), q);
     }
     if (!qs_ready)
         for (uint32_t c = tid; c < ld4; c += 256)
@@ -1361,39 +1531,56 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
             __syncthreads();
         }
         const uint32_t ntake = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        if (chain && ntake == 0) // (uniform) the hint left nothing of this chunk: the running top-k stays as it is
+        {
+            if (a.stat_rows && tid == 0)
+                atomicAdd(a.stat_rows + 2, 1ull);
+            __syncthreads(); // everybody has read wcnt before the next chunk writes it
+            continue;
+        }
         for (uint32_t c = grp; c < ntake; c += 16)
         {
             const uint32_t pos = sel[c];
             const float4 * yrow = a.Y + (size_t)pos * ld4 + g;
             const float4 * qrow = qs + g;
+            if (a.stat_rows && g == 0)
+                atomicAdd(a.stat_rows + 1, 1ull);
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            uint32_t j = 0;
-            for (; j + 8 <= jfull; j += 8) // 8 row pieces in flight per lane (the arithmetic stays in column order)
+            uint32_t id = pos;
+            if (chain)
             {
-                float4 y[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++)
-                    y[u] = yrow[(j + u) * 16];
-#pragma unroll
-                for (int u = 0; u < 8; u++)
-                    canonical_update<METRIC>(acc, qrow[(j + u) * 16], y[u]);
+                acc = canonical_row_chain<METRIC>(yrow, qrow, jfull, jtail, g, a.ids && g == 0 ? a.ids + pos : nullptr, id);
             }
-            for (; j + 4 <= jfull; j += 4)
+            else
             {
-                const float4 y0 = yrow[j * 16], y1 = yrow[(j + 1) * 16], y2 = yrow[(j + 2) * 16], y3 = yrow[(j + 3) * 16];
-                canonical_update<METRIC>(acc, qrow[j * 16], y0);
-                canonical_update<METRIC>(acc, qrow[(j + 1) * 16], y1);
-                canonical_update<METRIC>(acc, qrow[(j + 2) * 16], y2);
-                canonical_update<METRIC>(acc, qrow[(j + 3) * 16], y3);
+                uint32_t j = 0;
+                for (; j + 8 <= jfull; j += 8) // 8 row pieces in flight per lane (the arithmetic stays in column order)
+                {
+                    float4 y[8];
+#pragma unroll
+                    for (int u = 0; u < 8; u++)
+                        y[u] = yrow[(j + u) * 16];
+#pragma unroll
+                    for (int u = 0; u < 8; u++)
+                        canonical_update<METRIC>(acc, qrow[(j + u) * 16], y[u]);
+                }
+                for (; j + 4 <= jfull; j += 4)
+                {
+                    const float4 y0 = yrow[j * 16], y1 = yrow[(j + 1) * 16], y2 = yrow[(j + 2) * 16], y3 = yrow[(j + 3) * 16];
+                    canonical_update<METRIC>(acc, qrow[j * 16], y0);
+                    canonical_update<METRIC>(acc, qrow[(j + 1) * 16], y1);
+                    canonical_update<METRIC>(acc, qrow[(j + 2) * 16], y2);
+                    canonical_update<METRIC>(acc, qrow[(j + 3) * 16], y3);
+                }
+                for (; j < jfull; j++)
+                    canonical_update<METRIC>(acc, qrow[j * 16], yrow[j * 16]);
+                if (g < jtail)
+                    canonical_update<METRIC>(acc, qrow[jfull * 16], yrow[jfull * 16]);
             }
-            for (; j < jfull; j++)
-                canonical_update<METRIC>(acc, qrow[j * 16], yrow[j * 16]);
-            if (g < jtail)
-                canonical_update<METRIC>(acc, qrow[jfull * 16], yrow[jfull * 16]);
             float s = __fadd_rn(__fadd_rn(acc.x, acc.y), __fadd_rn(acc.z, acc.w));
             s = row16_tree_sum(s);
             if (g == 0)
-                chunk[c] = make_key<METRIC>(s, a.ids ? a.ids[pos] : pos);
+                chunk[c] = make_key<METRIC>(s, chain || !a.ids ? id : a.ids[pos]);
         }
         __syncthreads();
         // the k best of (running k, this chunk): every key ranks itself among the RA_KMAX + RA_CHUNK slots
@@ -1419,19 +1606,18 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
     // certificate against the cut
     if (tid == 0)
     {
-        const uint32_t cutw = b.qthr[q];
+        const uint32_t cutw = chain ? rq.thr : b.qthr[q];
         bool good = true;
         if (cutw != 0xFFFFFFFFu)
         {
             const uint64_t ek = best[k - 1];
-            const float qn = a.qnorm[q];
-            if (ek == KEY_NONE || !(qn < 1e30f) || !(a.xmax < 1e30f))
+            const float qn = chain ? 0.f : a.qnorm[q];
+            if (ek == KEY_NONE || (chain ? !rq.usable : !(qn < 1e30f) || !(a.xmax < 1e30f)))
                 good = false;
             else
             {
                 const double al = (double)key_value<METRIC>((uint64_t)cutw << 32), e = (double)key_value<METRIC>(ek);
-                const double sx = sqrt((double)a.xmax * 1.001), sq = sqrt((double)qn * 1.001);
-                const double eps = rerank_eps<METRIC>(a, sx, sq, q);
+                const double eps = chain ? eps0 : rerank_eps<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), q);
                 good = METRIC == M_L2 ? (al - eps > e) : (al + eps < e);
             }
         }
@@ -1452,7 +1638,7 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
 }
 
 template <int METRIC>
-__global__ __launch_bounds__(256) void ivf_rerank_all_kernel(const RerankParams a, const RerankAllParams b)
+__global__ __launch_bounds__(256, 4) void ivf_rerank_all_kernel(const RerankParams a, const RerankAllParams b)
 {
     float4 * qs = reinterpret_cast<float4 *>(msvs_smem);
     unsigned char * lds = msvs_smem + (size_t)a.ld4 * 16;
@@ -1460,7 +1646,7 @@ __global__ __launch_bounds__(256) void ivf_rerank_all_kernel(const RerankParams 
     for (uint32_t f = blockIdx.x; f < nf; f += gridDim.x)
     {
         const uint32_t q = b.failq_in[f];
-        const bool ok = rerank_all_query<METRIC>(a, b, q, qs, false, lds, b.ek_in ? b.ek_in[q] : KEY_NONE);
+        const bool ok = rerank_all_query<METRIC>(a, b, q, qs, false, lds, b.ek_in ? b.ek_in[q] : KEY_NONE, nullptr);
         if (!ok && threadIdx.x == 0)
         {
             b.failq_out[atomicAdd(b.nfail_out, 1u)] = q;

@@ -633,6 +633,7 @@ static RerankParams table_rerank_params(const msvs_index & ix, const TablePass &
     rp.band = t.out_probes && h16 && options().coarse_band != 0 ? 1 : 0;
     rp.stat_fail = prefilter_fail_counter() + (t.out_probes ? 1 : 0); // msvs_prefilter_stats / msvs_coarse_stats
     rp.stat_skip = options().rerank_stats != 0 ? prefilter_fail_counter() + (t.out_probes ? 4 : 2) : nullptr;
+    rp.stat_rows = options().rerank_stats != 0 && !t.out_probes ? prefilter_fail_counter() + 12 : nullptr; // msvs_debug_rerank_rows
     return rp;
 }
 
@@ -1664,6 +1665,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     rp.ek_out = ek_hint;
     rp.stat_fail = second ? nullptr : prefilter_fail_counter(); // the statistic counts queries that reach the canonical scan
     rp.stat_skip = options().rerank_stats != 0 ? prefilter_fail_counter() + 2 : nullptr;
+    rp.stat_rows = options().rerank_stats != 0 ? prefilter_fail_counter() + 12 : nullptr; // msvs_debug_rerank_rows
     // the second chance inside the re-rank launch (256-thread blocks: every shape but the rerank_groups = 32 experiment)
     const bool fused = second && options().rerank_fused != 0 && (pl.kc > 64 || options().rerank_groups != 32);
     uint32_t * failq2 = failq;
@@ -2089,6 +2091,7 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         rp.nfail = nfail;
         rp.early_exit = options().rerank_early != 0 ? 1 : 0;
         rp.stat_fail = prefilter_fail_counter();
+        rp.stat_rows = options().rerank_stats != 0 ? prefilter_fail_counter() + 12 : nullptr; // msvs_debug_rerank_rows
         launch_ivf_rerank(scan_metric(m), rp, (uint32_t)nq, stream);
         g_prefilter_queries.fetch_add(nq, std::memory_order_relaxed);
         // queries without a certificate: canonical scan, one query per block (normally zero of them)
@@ -2309,6 +2312,20 @@ extern "C" __attribute__((visibility("default"))) int msvs_debug_rerank_stats(ui
         MSVS_HIP(hipMemcpy(v, prefilter_fail_counter() + 2, 48, hipMemcpyDeviceToHost));
         for (int i = 0; i < 6; i++)
             out[i] = v[i];
+    });
+}
+
+/// Tests / measurement (not in msvs.h; needs rerank_stats = 1): candidate rows the re-rank of result passes evaluated canonically,
+/// cumulative -- out3[0] = by the first stage (ivf_rerank_kernel), out3[1] = by the second chance (rerank_all_query); out3[2] =
+/// chunks of second-chance buffers skipped whole because the hint left none of their keys (rerank_chain = 1 only).
+extern "C" __attribute__((visibility("default"))) int msvs_debug_rerank_rows(uint64_t * out3)
+{
+    return guarded([&] {
+        unsigned long long v[3];
+        MSVS_HIP(hipDeviceSynchronize());
+        MSVS_HIP(hipMemcpy(v, prefilter_fail_counter() + 12, 24, hipMemcpyDeviceToHost));
+        for (int i = 0; i < 3; i++)
+            out3[i] = v[i];
     });
 }
 
