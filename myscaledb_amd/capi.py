@@ -20,6 +20,8 @@ METRICS = {"L2": METRIC_L2, "IP": METRIC_IP, "Cosine": METRIC_COSINE, "COSINE": 
 
 OK, ERR_INVALID_ARGUMENT, ERR_NOT_IMPLEMENTED, ERR_DEVICE, ERR_OOM, ERR_NOT_READY, ERR_UNSUPPORTED_K, ERR_ID_RANGE, \
     ERR_IO = range(9)
+ERR_ABORTED = 236  # MSVS_ERR_ABORTED: a build cancelled through Index.set_cancel
+CANCEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 
 SYMBOLS = [
     "msvs_last_error", "msvs_version", "msvs_device_count", "msvs_set_device", "msvs_device_synchronize",
@@ -724,6 +726,13 @@ class Index:
 
     def build(self):
         _check(lib().msvs_index_build(self._h))
+
+    def set_cancel(self, fn):
+        """msvs_index_set_cancel: fn() is polled between the k-means iterations of train, at every add and at build; a true result
+        makes that call raise MsvsError with ERR_ABORTED.  None clears it.  The C callback is kept alive on the object."""
+        cb = None if fn is None else CANCEL_FN(lambda _ctx: 1 if fn() else 0)
+        _check(lib().msvs_index_set_cancel(self._h, cb, None))
+        self._cancel_cb = cb
 
     def export_list(self, l, length):
         """(vecs [length, dim] f32, ids [length] i64) of inverted list l (length from export(with_vecs=False)'s offsets)."""

@@ -10,6 +10,7 @@ import pytest
 import myscaledb_amd.capi as capi
 import myscaledb_amd.host as mhost
 from golden_util import TextIndex, eval_filter, f32_of, load_goldens, materialize, tokenize
+from ivf_build_ref import check_float_assign
 from oracle import oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -1007,10 +1008,9 @@ def test_ivfflat_structure_invariants_and_full_probe_equals_flat():
     back = {int(i): r for r, i in enumerate(lids)}
     pick = rng.integers(0, n, 200)
     assert all((vecs[back[int(ids[p])]] == x[p]).all() for p in pick)  # rows moved intact
-    # every row sits in (one of) its nearest list(s): compare against the oracle's canonical assignment
-    a = o.assign(x[pick], cent)
-    got = np.searchsorted(off, [back[int(ids[p])] for p in pick], side="right") - 1
-    assert (a == got).mean() > 0.97  # MFMA assignment may differ only on near-ties
+    # every row sits in its nearest list: all 12000 against the float64 argmin, equal wherever the gap exceeds the f32 error bound
+    got = np.searchsorted(off, [back[int(i)] for i in ids], side="right") - 1
+    check_float_assign(got, x, cent, False)
     # probing every list == exhaustive search
     q = rng.standard_normal((9, d), dtype=np.float32)
     i1, d1 = ix.search(q, 10, "nprobe=%d" % nlist)
