@@ -285,9 +285,104 @@ class BinIndex:
     __del__ = close
 
 
-class SqIndex:
+class _CodedIndex:
+    """What SqIndex and PqIndex share: the handle and every call that differs only in the C prefix (`_c`)."""
+    _c = None  # "msvs_sq_index" / "msvs_pq_index"
+
+    def _fn(self, name):
+        return getattr(lib(), "%s_%s" % (self._c, name))
+
+    def _size(self, name):
+        fn = self._fn(name)
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_void_p]
+        return fn(self._h)
+
+    def train(self, x):
+        x = _f32(x).reshape(-1, self.dim)
+        _check(self._fn("train")(self._h, _p(x, C.c_float), C.c_size_t(x.shape[0]), MEM_HOST))
+
+    def add(self, x, ids=None):
+        x = _f32(x).reshape(-1, self.dim)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int64)
+        _check(self._fn("add")(self._h, _p(x, C.c_float), _p(ids, C.c_int64), C.c_size_t(x.shape[0]), MEM_HOST))
+
+    def build(self):
+        _check(self._fn("build")(self._h))
+
+    @property
+    def ready(self):
+        fn = self._fn("ready")
+        fn.argtypes = [C.c_void_p]
+        return bool(fn(self._h))
+
+    @property
+    def num_data(self):
+        return self._size("num_data")
+
+    @property
+    def num_lists(self):
+        return self._size("num_lists")
+
+    @property
+    def memory_usage(self):
+        return self._size("memory_usage")
+
+    def search(self, queries, k, params="", alive=None, nbits=None):
+        """params: "nprobe=P"; alive: bool over labels, nbits: how many of them the filter covers (default all of `alive`)."""
+        q = _f32(queries).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), np.int64)
+        dis = np.empty((q.shape[0], k), np.float32)
+        bits = None if alive is None else pack_bits(alive)
+        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
+        _check(self._fn("search")(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), params.encode(),
+                                  _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        return ids, dis
+
+    def search_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """All arguments are raw device addresses (ints); enqueues on `stream` and returns immediately."""
+        _check(self._fn("search_device")(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(nprobe),
+                                         C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
+                                         C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
+                                         C.c_void_p(int(stream)) if stream else None))
+
+    def serialize_io(self, store):
+        """msvs_{sq,pq}_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""
+        _check(self._fn("serialize_io")(self._h, C.byref(_DictIO(store).io)))
+
+    @classmethod
+    def _load(cls, store, file, fmt):
+        """-> (handle, the fields `fmt` at byte 12 of the data file's header).  The geometry comes from that header (which the
+        load has validated, check word included), never from the caller: export() sizes its buffers by it."""
+        h = C.c_void_p()
+        _check(getattr(lib(), cls._c + "_load_io")(C.byref(_DictIO(store).io), C.byref(h)))
+        return h, struct.unpack_from(fmt, bytes(store[file][:12 + struct.calcsize(fmt)]), 12)
+
+    def _agree(self, kind, **wanted):
+        """a loaded index whose geometry the caller also gave: it must be the file's (else closed, ValueError)"""
+        for name, want in wanted.items():
+            have = getattr(self, name)
+            if want is not None and int(want) != have:
+                self.close()
+                raise ValueError("the %s index file has %s = %d, the caller expects %d" % (kind, name, have, int(want)))
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            fn = getattr(_lib, self._c + "_free")
+            fn.argtypes = [C.c_void_p]
+            fn.restype = None
+            fn(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class SqIndex(_CodedIndex):
     """msvs_sq_index_t: the IVFSQ index -- coarse centroids, one per-dimension 8-bit quantiser of the residuals, and per row its
     list, label and dim code bytes (no f32 row is kept).  params as Index's for IVFFLAT ("ncentroids=N,kmeans_iters=I,...")."""
+    _c = "msvs_sq_index"
 
     def __init__(self, metric, dim, params="", _handle=None):
         self.metric, self.dim = int(metric), int(dim)
@@ -297,65 +392,11 @@ class SqIndex:
         else:
             _check(lib().msvs_sq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
 
-    def _size(self, name):
-        fn = getattr(lib(), name)
-        fn.restype = C.c_size_t
-        fn.argtypes = [C.c_void_p]
-        return fn(self._h)
-
-    def train(self, x):
-        x = _f32(x).reshape(-1, self.dim)
-        _check(lib().msvs_sq_index_train(self._h, _p(x, C.c_float), C.c_size_t(x.shape[0]), MEM_HOST))
-
     def set_codebook(self, centroids, vmin, vmax):
         c = _f32(centroids).reshape(-1, self.dim)
         lo, hi = _f32(vmin).reshape(self.dim), _f32(vmax).reshape(self.dim)
         _check(lib().msvs_sq_index_set_codebook(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(lo, C.c_float), _p(hi, C.c_float),
                                                 MEM_HOST))
-
-    def add(self, x, ids=None):
-        x = _f32(x).reshape(-1, self.dim)
-        if ids is not None:
-            ids = np.ascontiguousarray(ids, np.int64)
-        _check(lib().msvs_sq_index_add(self._h, _p(x, C.c_float), _p(ids, C.c_int64), C.c_size_t(x.shape[0]), MEM_HOST))
-
-    def build(self):
-        _check(lib().msvs_sq_index_build(self._h))
-
-    @property
-    def ready(self):
-        lib().msvs_sq_index_ready.argtypes = [C.c_void_p]
-        return bool(lib().msvs_sq_index_ready(self._h))
-
-    @property
-    def num_data(self):
-        return self._size("msvs_sq_index_num_data")
-
-    @property
-    def num_lists(self):
-        return self._size("msvs_sq_index_num_lists")
-
-    @property
-    def memory_usage(self):
-        return self._size("msvs_sq_index_memory_usage")
-
-    def search(self, queries, k, params="", alive=None, nbits=None):
-        """params: "nprobe=P"; alive: bool over labels, nbits: how many of them the filter covers (default all of `alive`)."""
-        q = _f32(queries).reshape(-1, self.dim)
-        ids = np.empty((q.shape[0], k), np.int64)
-        dis = np.empty((q.shape[0], k), np.float32)
-        bits = None if alive is None else pack_bits(alive)
-        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
-        _check(lib().msvs_sq_index_search(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), params.encode(),
-                                          _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
-        return ids, dis
-
-    def search_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
-        """All arguments are raw device addresses (ints); enqueues on `stream` and returns immediately."""
-        _check(lib().msvs_sq_index_search_device(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(nprobe),
-                                                 C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
-                                                 C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
-                                                 C.c_void_p(int(stream)) if stream else None))
 
     def export(self, with_lists=True):
         """-> (centroids [nlist, dim], vmin [dim], vmax [dim], list offsets [nlist + 1], codes [n, dim] u8 in natural column order,
@@ -371,29 +412,18 @@ class SqIndex:
                                           _p(codes, C.c_uint8), _p(labels, C.c_int64)))
         return cent, lo, hi, off, codes, labels
 
-    def serialize_io(self, store):
-        """msvs_sq_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""
-        _check(lib().msvs_sq_index_serialize_io(self._h, C.byref(_DictIO(store).io)))
-
     @classmethod
-    def load_io(cls, store, metric, dim):
-        h = C.c_void_p()
-        _check(lib().msvs_sq_index_load_io(C.byref(_DictIO(store).io), C.byref(h)))
-        return cls(metric, dim, _handle=h)
-
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.msvs_sq_index_free.argtypes = [C.c_void_p]
-            _lib.msvs_sq_index_free.restype = None
-            _lib.msvs_sq_index_free(self._h)
-            self._h = None
-
-    __del__ = close
+    def load_io(cls, store, metric=None, dim=None):
+        """metric / dim come from the file (SqHeader: magic[8], u32 version, i32 metric, u64 dim, ...); where given, they must
+        agree with it (ValueError otherwise)."""
+        h, (f_metric, f_dim) = cls._load(store, "sq_data", "<iQ")
+        return cls(f_metric, f_dim, _handle=h)._agree("IVFSQ", metric=metric, dim=dim)
 
 
-class PqIndex:
+class PqIndex(_CodedIndex):
     """msvs_pq_index_t: the IVFPQ index -- coarse centroids, m sub-codebooks of 256 entries over the residuals, and per row its list,
     label and m code bytes (no f32 row is kept).  params as Index's for IVFFLAT plus m ("ncentroids=N,m=M,kmeans_iters=I,...")."""
+    _c = "msvs_pq_index"
 
     def __init__(self, metric, dim, params="", _handle=None, _m=None):
         self.metric, self.dim = int(metric), int(dim)
@@ -404,65 +434,11 @@ class PqIndex:
             _check(lib().msvs_pq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
             self.m = int(dict(kv.split("=", 1) for kv in params.replace(" ", "").split(",") if "=" in kv)["m"])
 
-    def _size(self, name):
-        fn = getattr(lib(), name)
-        fn.restype = C.c_size_t
-        fn.argtypes = [C.c_void_p]
-        return fn(self._h)
-
-    def train(self, x):
-        x = _f32(x).reshape(-1, self.dim)
-        _check(lib().msvs_pq_index_train(self._h, _p(x, C.c_float), C.c_size_t(x.shape[0]), MEM_HOST))
-
     def set_codebook(self, centroids, codebooks):
         """codebooks: [m, 256, dim / m]"""
         c = _f32(centroids).reshape(-1, self.dim)
         cb = _f32(codebooks).reshape(self.m, 256, self.dim // self.m)
         _check(lib().msvs_pq_index_set_codebook(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(cb, C.c_float), MEM_HOST))
-
-    def add(self, x, ids=None):
-        x = _f32(x).reshape(-1, self.dim)
-        if ids is not None:
-            ids = np.ascontiguousarray(ids, np.int64)
-        _check(lib().msvs_pq_index_add(self._h, _p(x, C.c_float), _p(ids, C.c_int64), C.c_size_t(x.shape[0]), MEM_HOST))
-
-    def build(self):
-        _check(lib().msvs_pq_index_build(self._h))
-
-    @property
-    def ready(self):
-        lib().msvs_pq_index_ready.argtypes = [C.c_void_p]
-        return bool(lib().msvs_pq_index_ready(self._h))
-
-    @property
-    def num_data(self):
-        return self._size("msvs_pq_index_num_data")
-
-    @property
-    def num_lists(self):
-        return self._size("msvs_pq_index_num_lists")
-
-    @property
-    def memory_usage(self):
-        return self._size("msvs_pq_index_memory_usage")
-
-    def search(self, queries, k, params="", alive=None, nbits=None):
-        """params: "nprobe=P"; alive: bool over labels, nbits: how many of them the filter covers (default all of `alive`)."""
-        q = _f32(queries).reshape(-1, self.dim)
-        ids = np.empty((q.shape[0], k), np.int64)
-        dis = np.empty((q.shape[0], k), np.float32)
-        bits = None if alive is None else pack_bits(alive)
-        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
-        _check(lib().msvs_pq_index_search(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), params.encode(),
-                                          _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
-        return ids, dis
-
-    def search_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
-        """All arguments are raw device addresses (ints); enqueues on `stream` and returns immediately."""
-        _check(lib().msvs_pq_index_search_device(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(nprobe),
-                                                 C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
-                                                 C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
-                                                 C.c_void_p(int(stream)) if stream else None))
 
     def export(self, with_lists=True):
         """-> (centroids [nlist, dim], codebooks [m, 256, dim / m], list offsets [nlist + 1], codes [n, m] u8 in natural order,
@@ -478,33 +454,12 @@ class PqIndex:
                                           _p(labels, C.c_int64)))
         return cent, cb, off, codes, labels
 
-    def serialize_io(self, store):
-        """msvs_pq_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""
-        _check(lib().msvs_pq_index_serialize_io(self._h, C.byref(_DictIO(store).io)))
-
     @classmethod
     def load_io(cls, store, metric=None, dim=None, m=None):
-        """The geometry comes from the file's header (which the load has validated, check word included), never from the caller:
-        export() sizes its buffers by it.  metric / dim / m, where given, must agree with the file (ValueError otherwise)."""
-        h = C.c_void_p()
-        _check(lib().msvs_pq_index_load_io(C.byref(_DictIO(store).io), C.byref(h)))
-        # PqHeader: magic[8], u32 version, i32 metric, u64 dim, u64 m, ...
-        f_metric, f_dim, f_m = struct.unpack_from("<iQQ", bytes(store["pq_data"][:32]), 12)
-        ix = cls(f_metric, f_dim, _handle=h, _m=f_m)
-        for name, want, have in (("metric", metric, f_metric), ("dim", dim, f_dim), ("m", m, f_m)):
-            if want is not None and int(want) != have:
-                ix.close()
-                raise ValueError("the IVFPQ index file has %s = %d, the caller expects %d" % (name, have, int(want)))
-        return ix
-
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.msvs_pq_index_free.argtypes = [C.c_void_p]
-            _lib.msvs_pq_index_free.restype = None
-            _lib.msvs_pq_index_free(self._h)
-            self._h = None
-
-    __del__ = close
+        """metric / dim / m come from the file (PqHeader: magic[8], u32 version, i32 metric, u64 dim, u64 m, ...); where given,
+        they must agree with it (ValueError otherwise)."""
+        h, (f_metric, f_dim, f_m) = cls._load(store, "pq_data", "<iQQ")
+        return cls(f_metric, f_dim, _handle=h, _m=f_m)._agree("IVFPQ", metric=metric, dim=dim, m=m)
 
 
 def normalize(x):
