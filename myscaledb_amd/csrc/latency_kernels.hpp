@@ -257,16 +257,19 @@ __device__ inline void lat_select_probes(const uint64_t * src, uint32_t total, u
             tl[u] = hi[u] == H ? lo[u] : 0xFFFFFFFFu;
         L = wave_kth_word<NW>(tl, np - below, hist, lane);
     }
+    // Fewer than np admitted keys (an inner-product query with an infinite element: the centroids that score -inf or NaN are no
+    // entries): H is KEY_NONE's word and every empty slot ties with it.  The empty slots are not taken in lane order -- they would
+    // push the admitted keys of higher lanes past np -- but fill the places the admitted keys leave.
     uint32_t run = 0;
 #pragma unroll
     for (int u = 0; u < NW; u++)
     {
-        const bool take = hi[u] < H || (hi[u] == H && lo[u] <= L);
+        const bool take = (hi[u] < H || (hi[u] == H && lo[u] <= L)) && !(hi[u] == 0xFFFFFFFFu && lo[u] == 0xFFFFFFFFu);
         const uint64_t mask = __ballot(take);
         const uint32_t pos = run + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
         if (take && pos < np)
         {
-            probes[pos] = hi[u] == 0xFFFFFFFFu && lo[u] == 0xFFFFFFFFu ? -1 : (int32_t)lo[u];
+            probes[pos] = (int32_t)lo[u];
             // (the two-launch search: an L2 key's high word, read by the radius pruning of L2 searches only; METRIC given: the key's
             // value as the merge launch of the batched coarse quantiser leaves it -- the general path's pre-pruning reads it for
             // L2 and cosine searches)
@@ -276,6 +279,14 @@ __device__ inline void lat_select_probes(const uint64_t * src, uint32_t total, u
                 dis[pos] = key_value<METRIC>((uint64_t)hi[u] << 32 | lo[u]);
         }
         run += (uint32_t)__popcll(mask);
+    }
+    for (uint32_t pos = run + lane; pos < np; pos += WAVE)
+    {
+        probes[pos] = -1;
+        if constexpr (METRIC < 0)
+            dis[pos] = ord2f(0xFFFFFFFFu);
+        else
+            dis[pos] = key_value<METRIC>(KEY_NONE);
     }
 }
 

@@ -1020,7 +1020,17 @@ struct RerankQuery
     uint32_t cnt, thr; // RerankAllParams::qcnt[q], qthr[q]
     bool usable;       // the norms are finite: eps means something
     double eps;        // rerank_eps (0 unless usable)
+    bool finite;       // |q|^2 is a number: so are the approximate keys (see rerank_query_finite)
 };
+
+/// A query whose squared norm is inf or NaN (an infinite, NaN or overflowing element) can have NaN approximate values -- split
+/// bf16: hi = inf, lo = q - hi = NaN -- and a NaN value is no key: the row never becomes a candidate, although its canonical
+/// inner product may be +inf.  For such a query a candidate list that is not full does NOT hold every probed row, so nothing
+/// certifies it, not even an empty list: it goes to the canonical fallback.
+__device__ __forceinline__ bool rerank_query_finite(float qn)
+{
+    return qn <= 3.402823466e+38f;
+}
 
 /// The canonical accumulator of one lane over its pieces of a row (rerank_chain): whole batches of twelve pieces are requested,
 /// with the row's id (idp: nullable) behind the first of them, before the batch's first update; the updates run in ascending
@@ -1083,7 +1093,7 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
     __shared__ double s_e, s_eps;
     __shared__ uint64_t s_ak, s_ak1, s_bound;
     __shared__ uint32_t s_nin, s_qcnt, s_qthr;
-    __shared__ int s_band, s_usable;
+    __shared__ int s_band, s_usable, s_finite;
     if (chain)
     {
         // ONE round trip for everything but rows and their ids: the requests below are all issued before the first of them is
@@ -1127,6 +1137,7 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
         {
             const bool usable = qn < 1e30f && a.xmax < 1e30f;
             s_usable = usable ? 1 : 0;
+            s_finite = rerank_query_finite(qn) ? 1 : 0;
             s_eps = usable ? rerank_eps_rho<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), rho) : 0.0;
             s_bound = bnd;
             s_qcnt = cnt;
@@ -1382,10 +1393,12 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
             last = a.bound[q];
     }
     bool ok = true;
-    if (last != KEY_NONE)
+    const float qn = chain ? 0.f : a.qnorm[q];
+    if (chain ? s_finite == 0 : !rerank_query_finite(qn))
+        ok = false; // (rows with a NaN approximate value are missing from the list: it proves nothing)
+    else if (last != KEY_NONE)
     {
         const uint64_t ek = s_ek;
-        const float qn = chain ? 0.f : a.qnorm[q];
         if (ek == KEY_NONE || (chain ? s_usable == 0 : !(qn < 1e30f) || !(a.xmax < 1e30f)))
             ok = false;
         else
@@ -1425,7 +1438,7 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
         return;
     // the second chance, here and now: every row of the query's candidate buffer, certified against the cut (rerank_all_query); the
     // query is in LDS already, the first stage's k-th exact key is the hint
-    const RerankQuery pre{s_qcnt, s_qthr, s_usable != 0, s_eps};
+    const RerankQuery pre{s_qcnt, s_qthr, s_usable != 0, s_eps, s_finite != 0};
     const bool ok2 = rerank_all_query<METRIC>(a, a.ra, q, qs, true, msvs_smem + (size_t)ld4 * 16 + (size_t)64 * R * 8 * (chain ? 2 : 1), s_ek,
                                               chain ? &pre : nullptr);
     if (!ok2 && tid == 0)
@@ -1466,7 +1479,7 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
     const uint32_t jfull = ld4 >> 4, jtail = ld4 & 15;
     // rerank_chain: the query's scalars come from the caller's prologue (pre), or are requested here in one go; eps is formed once
     const bool chain = a.chain != 0;
-    RerankQuery rq{0, 0, false, 0.0};
+    RerankQuery rq{0, 0, false, 0.0, true};
     if (chain && pre)
         rq = *pre;
     else if (chain)
@@ -1475,6 +1488,7 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
         rq.thr = b.qthr[q];
         const float qn = a.qnorm[q], rho = a.qrho ? a.qrho[q] : 0.f;
         rq.usable = qn < 1e30f && a.xmax < 1e30f;
+        rq.finite = rerank_query_finite(qn);
         if (rq.usable)
             rq.eps = rerank_eps_rho<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn * 1.001), rho);
     }
@@ -1482,6 +1496,8 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
     rq.cnt = __builtin_amdgcn_readfirstlane(rq.cnt);
     const uint32_t cnt = chain ? rq.cnt : b.qcnt[q];
     bool ok = cnt <= b.cap; // an overflowed buffer dropped rows below the cut: nothing to certify
+    if (!(chain ? rq.finite : rerank_query_finite(a.qnorm[q])))
+        ok = false;         // so did NaN approximate values (rerank_query_finite)
     __syncthreads();        // whoever used the LDS arrays before is done with them
     if (!ok)
         return false;
