@@ -16,40 +16,6 @@
 namespace msvs
 {
 
-template <int METRIC, int G>
-static void bin_dispatch_r(const BinParams & a, hipStream_t stream)
-{
-    const dim3 grid(a.n_blocks, a.nq);
-    const size_t lds = (size_t)a.ld16 * 16 + (size_t)5 * a.k * 8;
-    if (a.k <= 64)
-        hipLaunchKernelGGL((bin_scan_kernel<METRIC, G, 1>), grid, dim3(BLOCK), lds, stream, a);
-    else
-        hipLaunchKernelGGL((bin_scan_kernel<METRIC, G, 4>), grid, dim3(BLOCK), lds, stream, a);
-}
-
-template <int METRIC>
-static void bin_dispatch_g(uint32_t g, const BinParams & a, hipStream_t stream)
-{
-    switch (g)
-    {
-        case 1:
-            bin_dispatch_r<METRIC, 1>(a, stream);
-            break;
-        case 2:
-            bin_dispatch_r<METRIC, 2>(a, stream);
-            break;
-        case 4:
-            bin_dispatch_r<METRIC, 4>(a, stream);
-            break;
-        case 8:
-            bin_dispatch_r<METRIC, 8>(a, stream);
-            break;
-        default:
-            bin_dispatch_r<METRIC, 16>(a, stream);
-            break;
-    }
-}
-
 /// lanes per row: one 16-byte word each per step
 static uint32_t bin_lanes(uint32_t ld16)
 {
@@ -81,70 +47,48 @@ static void launch_bin_assign(const unsigned char * dy, const unsigned char * dc
     a.dist = dist;
     const dim3 grid((unsigned)ceil_div(n, (size_t)(BLOCK / g)));
     const size_t lds = (size_t)a.tile * ld16 * 16;
-    switch (g)
-    {
-        case 1:
-            hipLaunchKernelGGL((bin_assign_kernel<1>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((bin_assign_kernel<2>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        case 4:
-            hipLaunchKernelGGL((bin_assign_kernel<4>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        case 8:
-            hipLaunchKernelGGL((bin_assign_kernel<8>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((bin_assign_kernel<16>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-    }
+    with_int<1, 2, 4, 8, 16>(g, [&](auto lanes) {
+        hipLaunchKernelGGL((bin_assign_kernel<decltype(lanes)::value>), grid, dim3(BLOCK), lds, stream, a);
+    });
     MSVS_HIP(hipGetLastError());
 }
 
-template <int METRIC, int G>
-static void bin_ivf_dispatch_r(uint32_t grid, const BinIvfParams & a, hipStream_t stream)
+/// g: lanes per row, a power of two up to 16 (bin_lanes)
+static void launch_bin_scan(int metric, uint32_t g, const BinParams & a, hipStream_t stream)
 {
-    const bool reg = a.ld16 == (uint32_t)G;
-    if (a.k <= 64)
-    {
-        const size_t lds = (size_t)BIN_IVF_T * a.ld16 * 16 + (size_t)5 * a.k * 8;
-        if (reg)
-            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T, 1, true>), dim3(grid), dim3(BLOCK), lds, stream, a);
-        else
-            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T, 1, false>), dim3(grid), dim3(BLOCK), lds, stream, a);
-    }
-    else
-    {
-        const size_t lds = (size_t)(BIN_IVF_T / 2) * a.ld16 * 16 + (size_t)5 * a.k * 8;
-        if (reg)
-            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T / 2, 4, true>), dim3(grid), dim3(BLOCK), lds, stream, a);
-        else
-            hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, BIN_IVF_T / 2, 4, false>), dim3(grid), dim3(BLOCK), lds, stream, a);
-    }
+    ProfileScope prof("bin_scan", stream);
+    const dim3 grid(a.n_blocks, a.nq);
+    const size_t lds = (size_t)a.ld16 * 16 + (size_t)5 * a.k * 8;
+    with_int<B_HAMMING, B_JACCARD>(metric == MSVS_METRIC_HAMMING ? B_HAMMING : B_JACCARD, [&](auto m) {
+        with_int<1, 2, 4, 8, 16>(g, [&](auto lanes) {
+            with_int<1, 4>(a.k <= 64 ? 1 : 4, [&](auto r) {
+                constexpr int METRIC = decltype(m)::value, G = decltype(lanes)::value, R = decltype(r)::value;
+                hipLaunchKernelGGL((bin_scan_kernel<METRIC, G, R>), grid, dim3(BLOCK), lds, stream, a);
+            });
+        });
+    });
+    MSVS_HIP(hipGetLastError());
 }
 
-template <int METRIC>
-static void bin_ivf_dispatch_g(uint32_t g, uint32_t grid, const BinIvfParams & a, hipStream_t stream)
+/// List scan over the plan's work items; tiles of BIN_IVF_T queries with one top-k register per lane up to k = 64, half the tile and
+/// four registers beyond; REG: the row fits the group's registers (ld16 == G).
+static void launch_bin_ivf_scan(int metric, uint32_t g, uint32_t grid, const BinIvfParams & a, hipStream_t stream)
 {
-    switch (g)
-    {
-        case 1:
-            bin_ivf_dispatch_r<METRIC, 1>(grid, a, stream);
-            break;
-        case 2:
-            bin_ivf_dispatch_r<METRIC, 2>(grid, a, stream);
-            break;
-        case 4:
-            bin_ivf_dispatch_r<METRIC, 4>(grid, a, stream);
-            break;
-        case 8:
-            bin_ivf_dispatch_r<METRIC, 8>(grid, a, stream);
-            break;
-        default:
-            bin_ivf_dispatch_r<METRIC, 16>(grid, a, stream);
-            break;
-    }
+    ProfileScope prof("bin_ivf_scan", stream);
+    with_int<B_HAMMING, B_JACCARD>(metric == MSVS_METRIC_HAMMING ? B_HAMMING : B_JACCARD, [&](auto m) {
+        with_int<1, 2, 4, 8, 16>(g, [&](auto lanes) {
+            with_bool(a.k <= 64, [&](auto small) {
+                with_bool(a.ld16 == (uint32_t)decltype(lanes)::value, [&](auto reg) {
+                    constexpr int METRIC = decltype(m)::value, G = decltype(lanes)::value;
+                    constexpr int T = decltype(small)::value ? BIN_IVF_T : BIN_IVF_T / 2, R = decltype(small)::value ? 1 : 4;
+                    constexpr bool REG = decltype(reg)::value;
+                    const size_t lds = (size_t)T * a.ld16 * 16 + (size_t)5 * a.k * 8;
+                    hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, T, R, REG>), dim3(grid), dim3(BLOCK), lds, stream, a);
+                });
+            });
+        });
+    });
+    MSVS_HIP(hipGetLastError());
 }
 
 }
@@ -195,14 +139,7 @@ static void bin_search_rows(const unsigned char * dy, const uint32_t * d_labels,
     a.k = (uint32_t)k;
     a.nq = (uint32_t)nx;
     a.partial = partial;
-    {
-        ProfileScope prof("bin_scan", stream);
-        if (metric == MSVS_METRIC_HAMMING)
-            bin_dispatch_g<B_HAMMING>(g, a, stream);
-        else
-            bin_dispatch_g<B_JACCARD>(g, a, stream);
-        MSVS_HIP(hipGetLastError());
-    }
+    launch_bin_scan(metric, g, a, stream);
     MergeParams m{};
     m.partial = partial;
     m.n_lists = n_blocks;
@@ -428,15 +365,7 @@ static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbyte
         a.work_off = plan.work_off;
         a.pairs = plan.pairs;
         a.partial = partial;
-        {
-            ProfileScope prof("bin_ivf_scan", stream);
-            const uint32_t grid = (uint32_t)std::min<size_t>(2048, nq * P * seg_max);
-            if (metric == MSVS_METRIC_HAMMING)
-                bin_ivf_dispatch_g<B_HAMMING>(g, grid, a, stream);
-            else
-                bin_ivf_dispatch_g<B_JACCARD>(g, grid, a, stream);
-            MSVS_HIP(hipGetLastError());
-        }
+        launch_bin_ivf_scan(metric, g, (uint32_t)std::min<size_t>(2048, nq * P * seg_max), a, stream);
         MergeParams m{};
         m.partial = partial;
         m.n_lists = (uint32_t)(P * seg_max);

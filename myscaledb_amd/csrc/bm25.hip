@@ -627,41 +627,31 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
                         MSVS_HIP(hipGetLastError());
                         return;
                     }
-#define MSVS_BM25R(RR) \
-    do \
-    { \
-        if (lean) \
-            hipLaunchKernelGGL((bm25l_kernel<BM25_TOPK, RR, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp); \
-        else if (big_slots) \
-            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK, RR, 16384>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp); \
-        else \
-            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK, RR, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp); \
-    } while (0)
-                    if (r == 1) MSVS_BM25R(1); else if (r == 2) MSVS_BM25R(2); else MSVS_BM25R(4);
-#undef MSVS_BM25R
+                    with_int<1, 2, 4>(r, [&](auto rr) {
+                        constexpr int R = decltype(rr)::value;
+                        if (lean)
+                            hipLaunchKernelGGL((bm25l_kernel<BM25_TOPK, R, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
+                        else if (big_slots)
+                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK, R, 16384>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
+                        else
+                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK, R, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
+                    });
                     MSVS_HIP(hipGetLastError());
                     return;
                 }
-                if (r == 1)
-                    hipLaunchKernelGGL((bm25p_kernel<BM25_TOPK, 1>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, w);
-                else if (r == 2)
-                    hipLaunchKernelGGL((bm25p_kernel<BM25_TOPK, 2>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, w);
-                else
-                    hipLaunchKernelGGL((bm25p_kernel<BM25_TOPK, 4>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, w);
+                with_int<1, 2, 4>(r, [&](auto rr) {
+                    hipLaunchKernelGGL((bm25p_kernel<BM25_TOPK, decltype(rr)::value>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, w);
+                });
                 MSVS_HIP(hipGetLastError());
                 return;
             }
             const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div((size_t)lists * slots_bound, (size_t)BW_WAVES), (size_t)cus * bw_blocks_per_cu(nf1k)));
-#define MSVS_BM25W(RR, NF) hipLaunchKernelGGL((bm25w_kernel<BM25_TOPK, RR, NF>), dim3(grid), dim3(64 * BW_WAVES), 0, stream, w)
-            if (nf1k)
-            {
-                if (r == 1) MSVS_BM25W(1, 1); else if (r == 2) MSVS_BM25W(2, 1); else MSVS_BM25W(4, 1);
-            }
-            else
-            {
-                if (r == 1) MSVS_BM25W(1, 4); else if (r == 2) MSVS_BM25W(2, 4); else MSVS_BM25W(4, 4);
-            }
-#undef MSVS_BM25W
+            with_int<1, 4>(nf1k ? 1 : 4, [&](auto nf) {
+                with_int<1, 2, 4>(r, [&](auto rr) {
+                    constexpr int R = decltype(rr)::value, NF = decltype(nf)::value;
+                    hipLaunchKernelGGL((bm25w_kernel<BM25_TOPK, R, NF>), dim3(grid), dim3(64 * BW_WAVES), 0, stream, w);
+                });
+            });
         }
         else
         {
@@ -669,18 +659,9 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
             p.bstep = step;
             const size_t lds = (size_t)5 * p.kk * 8;
             const dim3 grid(lists, (uint32_t)std::min<size_t>(slots_bound, std::max<size_t>(1, 2048 / lists)));
-            switch (r_for_k(p.kk))
-            {
-                case 1:
-                    hipLaunchKernelGGL((bm25_score_kernel<BM25_TOPK, 1>), grid, dim3(BLOCK), lds, stream, p);
-                    break;
-                case 2:
-                    hipLaunchKernelGGL((bm25_score_kernel<BM25_TOPK, 2>), grid, dim3(BLOCK), lds, stream, p);
-                    break;
-                default:
-                    hipLaunchKernelGGL((bm25_score_kernel<BM25_TOPK, 4>), grid, dim3(BLOCK), lds, stream, p);
-                    break;
-            }
+            with_int<1, 2, 4>(r_for_k(p.kk), [&](auto rr) {
+                hipLaunchKernelGGL((bm25_score_kernel<BM25_TOPK, decltype(rr)::value>), grid, dim3(BLOCK), lds, stream, p);
+            });
         }
         MSVS_HIP(hipGetLastError());
     };
@@ -856,21 +837,10 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     fp.qsel = failq;
     fp.nsel = nfail;
     launch_topk(fp, n_chunks, 1, std::min<size_t>(nq, wave ? nq : 4), spi, n_chunks);
-    switch (r_for_k((uint32_t)k))
-    {
-        case 1:
-            hipLaunchKernelGGL((bm25_fb_merge_kernel<1>), dim3((unsigned)nq), dim3(BLOCK), lds_k, stream, partial, n_chunks, n_chunks,
-                               (uint32_t)k, failq, nfail, d_ids, d_scores);
-            break;
-        case 2:
-            hipLaunchKernelGGL((bm25_fb_merge_kernel<2>), dim3((unsigned)nq), dim3(BLOCK), lds_k, stream, partial, n_chunks, n_chunks,
-                               (uint32_t)k, failq, nfail, d_ids, d_scores);
-            break;
-        default:
-            hipLaunchKernelGGL((bm25_fb_merge_kernel<4>), dim3((unsigned)nq), dim3(BLOCK), lds_k, stream, partial, n_chunks, n_chunks,
-                               (uint32_t)k, failq, nfail, d_ids, d_scores);
-            break;
-    }
+    with_int<1, 2, 4>(r_for_k((uint32_t)k), [&](auto rr) {
+        hipLaunchKernelGGL((bm25_fb_merge_kernel<decltype(rr)::value>), dim3((unsigned)nq), dim3(BLOCK), lds_k, stream, partial, n_chunks,
+                           n_chunks, (uint32_t)k, failq, nfail, d_ids, d_scores);
+    });
     MSVS_HIP(hipGetLastError());
     g_bm25_queries.fetch_add(nq, std::memory_order_relaxed);
 }

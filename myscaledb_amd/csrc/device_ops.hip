@@ -200,45 +200,6 @@ FlatPlan plan_flat(size_t n_rows, size_t nq, uint32_t ld4, uint32_t k)
     return p;
 }
 
-template <int METRIC, int T>
-static void flat_dispatch_r(const FlatPlan & plan, const ScanParams & a, hipStream_t stream)
-{
-    dim3 grid(plan.n_blocks, plan.n_qtiles);
-    size_t lds = scan_lds_bytes(T, a.ld4, a.k);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((flat_scan_kernel<METRIC, T, 1>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((flat_scan_kernel<METRIC, T, 2>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((flat_scan_kernel<METRIC, T, 4>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-    }
-}
-
-template <int METRIC>
-static void flat_dispatch_t(const FlatPlan & plan, const ScanParams & a, hipStream_t stream)
-{
-    switch (plan.T)
-    {
-        case 1:
-            flat_dispatch_r<METRIC, 1>(plan, a, stream);
-            break;
-        case 2:
-            flat_dispatch_r<METRIC, 2>(plan, a, stream);
-            break;
-        case 4:
-            flat_dispatch_r<METRIC, 4>(plan, a, stream);
-            break;
-        default:
-            flat_dispatch_r<METRIC, 8>(plan, a, stream);
-            break;
-    }
-}
-
 void launch_flat_scan(int metric, const FlatPlan & plan, ScanParams a, hipStream_t stream)
 {
     a.rows_per_block = plan.rows_per_block;
@@ -246,29 +207,16 @@ void launch_flat_scan(int metric, const FlatPlan & plan, ScanParams a, hipStream
     if (scan_lds_bytes(plan.T, a.ld4, a.k) > 160 * 1024)
         fail(MSVS_ERR_INVALID_ARGUMENT, "dimension %u too large for the LDS query tile", a.ld4 * 4);
     ProfileScope prof("flat_scan", stream);
-    if (metric == M_IP)
-        flat_dispatch_t<M_IP>(plan, a, stream);
-    else
-        flat_dispatch_t<M_L2>(plan, a, stream);
+    const dim3 grid(plan.n_blocks, plan.n_qtiles);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<1, 2, 4, 8>(plan.T, [&](auto t) {
+            with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                constexpr int METRIC = decltype(m)::value, T = decltype(t)::value, R = decltype(r)::value;
+                hipLaunchKernelGGL((flat_scan_kernel<METRIC, T, R>), grid, dim3(BLOCK), scan_lds_bytes(T, a.ld4, a.k), stream, a);
+            });
+        });
+    });
     MSVS_HIP(hipGetLastError());
-}
-
-template <int METRIC>
-static void merge_dispatch(const MergeParams & a, uint32_t nq, hipStream_t stream)
-{
-    size_t lds = merge_lds_bytes(a.k, 0);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((merge_kernel<METRIC, 1>), dim3(nq), dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((merge_kernel<METRIC, 2>), dim3(nq), dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((merge_kernel<METRIC, 4>), dim3(nq), dim3(BLOCK), lds, stream, a);
-            break;
-    }
 }
 
 void launch_merge(int metric, MergeParams a, uint32_t nq, hipStream_t stream)
@@ -276,30 +224,13 @@ void launch_merge(int metric, MergeParams a, uint32_t nq, hipStream_t stream)
     if (nq == 0)
         return;
     ProfileScope prof("merge", stream);
-    if (metric == M_IP)
-        merge_dispatch<M_IP>(a, nq, stream);
-    else
-        merge_dispatch<M_L2>(a, nq, stream);
+    const size_t lds = merge_lds_bytes(a.k, 0);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+            hipLaunchKernelGGL((merge_kernel<decltype(m)::value, decltype(r)::value>), dim3(nq), dim3(BLOCK), lds, stream, a);
+        });
+    });
     MSVS_HIP(hipGetLastError());
-}
-
-template <int METRIC>
-static void ivf_dispatch(const ScanParams & a, hipStream_t stream)
-{
-    dim3 grid(a.seg_max, a.nprobe, a.nq);
-    size_t lds = scan_lds_bytes(1, a.ld4, a.k);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((ivf_scan_kernel<METRIC, 1>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((ivf_scan_kernel<METRIC, 2>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((ivf_scan_kernel<METRIC, 4>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-    }
 }
 
 void launch_ivf_scan(int metric, ScanParams a, hipStream_t stream)
@@ -307,10 +238,13 @@ void launch_ivf_scan(int metric, ScanParams a, hipStream_t stream)
     if (a.nq == 0 || a.nprobe == 0 || a.seg_max == 0)
         return;
     ProfileScope prof("ivf_scan", stream);
-    if (metric == M_IP)
-        ivf_dispatch<M_IP>(a, stream);
-    else
-        ivf_dispatch<M_L2>(a, stream);
+    const dim3 grid(a.seg_max, a.nprobe, a.nq);
+    const size_t lds = scan_lds_bytes(1, a.ld4, a.k);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+            hipLaunchKernelGGL((ivf_scan_kernel<decltype(m)::value, decltype(r)::value>), grid, dim3(BLOCK), lds, stream, a);
+        });
+    });
     MSVS_HIP(hipGetLastError());
 }
 
@@ -371,41 +305,6 @@ void launch_ivf_plan_rescan(const IvfPlanParams & p, hipStream_t stream)
     MSVS_HIP(hipGetLastError());
 }
 
-template <int METRIC, int T>
-static void ivf_batched_dispatch_r(uint32_t grid, const ScanParams & a, hipStream_t stream)
-{
-    size_t lds = scan_lds_bytes(T, a.ld4, a.k);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((ivf_batched_scan_kernel<METRIC, T, 1>), dim3(grid), dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((ivf_batched_scan_kernel<METRIC, T, 2>), dim3(grid), dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((ivf_batched_scan_kernel<METRIC, T, 4>), dim3(grid), dim3(BLOCK), lds, stream, a);
-            break;
-    }
-}
-
-template <int METRIC>
-static void ivf_batched_dispatch_t(uint32_t T, uint32_t grid, const ScanParams & a, hipStream_t stream)
-{
-    switch (T)
-    {
-        case 2:
-            ivf_batched_dispatch_r<METRIC, 2>(grid, a, stream);
-            break;
-        case 4:
-            ivf_batched_dispatch_r<METRIC, 4>(grid, a, stream);
-            break;
-        default:
-            ivf_batched_dispatch_r<METRIC, 8>(grid, a, stream);
-            break;
-    }
-}
-
 void launch_ivf_batched_scan(int metric, uint32_t T, uint32_t grid, ScanParams a, hipStream_t stream)
 {
     if (grid == 0)
@@ -413,29 +312,16 @@ void launch_ivf_batched_scan(int metric, uint32_t T, uint32_t grid, ScanParams a
     if (scan_lds_bytes(T, a.ld4, a.k) > 160 * 1024)
         fail(MSVS_ERR_INVALID_ARGUMENT, "dimension %u too large for the LDS query tile", a.ld4 * 4);
     ProfileScope prof("ivf_scan", stream);
-    if (metric == M_IP)
-        ivf_batched_dispatch_t<M_IP>(T, grid, a, stream);
-    else
-        ivf_batched_dispatch_t<M_L2>(T, grid, a, stream);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<2, 4, 8>(T, [&](auto t) {
+            with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                constexpr int METRIC = decltype(m)::value, TQ = decltype(t)::value, R = decltype(r)::value;
+                const size_t lds = scan_lds_bytes(TQ, a.ld4, a.k);
+                hipLaunchKernelGGL((ivf_batched_scan_kernel<METRIC, TQ, R>), dim3(grid), dim3(BLOCK), lds, stream, a);
+            });
+        });
+    });
     MSVS_HIP(hipGetLastError());
-}
-
-template <int METRIC>
-static void ivf_merge_dispatch(const IvfMergeParams & a, uint32_t nq, hipStream_t stream)
-{
-    size_t lds = merge_lds_bytes(a.k, a.nprobe);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((ivf_merge_kernel<METRIC, 1>), dim3(nq), dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((ivf_merge_kernel<METRIC, 2>), dim3(nq), dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((ivf_merge_kernel<METRIC, 4>), dim3(nq), dim3(BLOCK), lds, stream, a);
-            break;
-    }
 }
 
 void launch_ivf_merge(int metric, IvfMergeParams a, uint32_t nq, hipStream_t stream)
@@ -443,10 +329,12 @@ void launch_ivf_merge(int metric, IvfMergeParams a, uint32_t nq, hipStream_t str
     if (nq == 0)
         return;
     ProfileScope prof("merge", stream);
-    if (metric == M_IP)
-        ivf_merge_dispatch<M_IP>(a, nq, stream);
-    else
-        ivf_merge_dispatch<M_L2>(a, nq, stream);
+    const size_t lds = merge_lds_bytes(a.k, a.nprobe);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+            hipLaunchKernelGGL((ivf_merge_kernel<decltype(m)::value, decltype(r)::value>), dim3(nq), dim3(BLOCK), lds, stream, a);
+        });
+    });
     MSVS_HIP(hipGetLastError());
 }
 
@@ -472,32 +360,20 @@ void launch_split_queries(const float * Q, uint32_t nq, uint32_t ld4, void * out
     MSVS_HIP(hipGetLastError());
 }
 
-template <int METRIC, int NQG>
-static void mfma_scan_dispatch(bool main_phase, uint32_t grid, const ScanParams & a, hipStream_t stream)
-{
-    if (main_phase)
-        hipLaunchKernelGGL((ivf_mfma_scan_big_kernel<METRIC, NQG, 1>), dim3(grid), dim3(NQG * BLOCK), 0, stream, a);
-    else
-        hipLaunchKernelGGL((ivf_mfma_scan_big_kernel<METRIC, NQG, 0>), dim3(grid), dim3(NQG * BLOCK), 0, stream, a);
-}
-
 void launch_ivf_mfma_scan(int metric, uint32_t nqg, uint32_t grid, ScanParams a, hipStream_t stream,
                           const char * profile_name, bool main_phase)
 {
     if (grid == 0)
         return;
     ProfileScope prof(profile_name, stream);
-    if (nqg == 2)
-    {
-        if (metric == M_IP)
-            mfma_scan_dispatch<M_IP, 2>(main_phase, grid, a, stream);
-        else
-            mfma_scan_dispatch<M_L2, 2>(main_phase, grid, a, stream);
-    }
-    else if (metric == M_IP)
-        mfma_scan_dispatch<M_IP, 1>(main_phase, grid, a, stream);
-    else
-        mfma_scan_dispatch<M_L2, 1>(main_phase, grid, a, stream);
+    with_int<2, 1>(nqg, [&](auto g) {
+        with_int<M_IP, M_L2>(metric, [&](auto m) {
+            with_bool(main_phase, [&](auto p) {
+                constexpr int METRIC = decltype(m)::value, NQG = decltype(g)::value, MAIN = decltype(p)::value;
+                hipLaunchKernelGGL((ivf_mfma_scan_big_kernel<METRIC, NQG, MAIN>), dim3(grid), dim3(NQG * BLOCK), 0, stream, a);
+            });
+        });
+    });
     MSVS_HIP(hipGetLastError());
 }
 
@@ -550,25 +426,18 @@ void launch_ivf_rerank(int metric, RerankParams a, uint32_t nq, hipStream_t stre
     if (lds > 64 * 1024)
         fail(MSVS_ERR_INVALID_ARGUMENT, "dimension %u too large for the re-rank block", a.ld4 * 4);
     ProfileScope prof("rerank", stream);
-    const bool ip = metric == M_IP;
     if (a.kc > 64) // 256 candidates (40 < k <= 128)
-    {
-        if (ip)
-            hipLaunchKernelGGL((ivf_rerank_kernel<M_IP, 16, 4>), dim3(nq), dim3(256), lds, stream, a);
-        else
-            hipLaunchKernelGGL((ivf_rerank_kernel<M_L2, 16, 4>), dim3(nq), dim3(256), lds, stream, a);
-    }
+        with_int<M_IP, M_L2>(metric, [&](auto m) {
+            hipLaunchKernelGGL((ivf_rerank_kernel<decltype(m)::value, 16, 4>), dim3(nq), dim3(256), lds, stream, a);
+        });
     else if (options().rerank_groups != 32)
-    {
-        if (ip)
-            hipLaunchKernelGGL((ivf_rerank_kernel<M_IP, 16, 1>), dim3(nq), dim3(256), lds, stream, a);
-        else
-            hipLaunchKernelGGL((ivf_rerank_kernel<M_L2, 16, 1>), dim3(nq), dim3(256), lds, stream, a);
-    }
-    else if (ip)
-        hipLaunchKernelGGL((ivf_rerank_kernel<M_IP, 32, 1>), dim3(nq), dim3(512), lds, stream, a);
+        with_int<M_IP, M_L2>(metric, [&](auto m) {
+            hipLaunchKernelGGL((ivf_rerank_kernel<decltype(m)::value, 16, 1>), dim3(nq), dim3(256), lds, stream, a);
+        });
     else
-        hipLaunchKernelGGL((ivf_rerank_kernel<M_L2, 32, 1>), dim3(nq), dim3(512), lds, stream, a);
+        with_int<M_IP, M_L2>(metric, [&](auto m) {
+            hipLaunchKernelGGL((ivf_rerank_kernel<decltype(m)::value, 32, 1>), dim3(nq), dim3(512), lds, stream, a);
+        });
     MSVS_HIP(hipGetLastError());
 }
 
@@ -583,30 +452,10 @@ void launch_ivf_rerank_all(int metric, const RerankParams & a0, const RerankAllP
     const size_t lds = (size_t)a.ld4 * 16 + (2 * RA_KMAX + RA_CHUNK) * 8 + RA_CHUNK * 4 + 16;
     ProfileScope prof("rerank", stream);
     const uint32_t grid = std::min<uint32_t>(nq, 2048); // usually nobody is on the list: every block exits at once
-    if (metric == M_IP)
-        hipLaunchKernelGGL((ivf_rerank_all_kernel<M_IP>), dim3(grid), dim3(256), lds, stream, a, b);
-    else
-        hipLaunchKernelGGL((ivf_rerank_all_kernel<M_L2>), dim3(grid), dim3(256), lds, stream, a, b);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        hipLaunchKernelGGL((ivf_rerank_all_kernel<decltype(m)::value>), dim3(grid), dim3(256), lds, stream, a, b);
+    });
     MSVS_HIP(hipGetLastError());
-}
-
-template <int METRIC>
-static void ivf_subset_dispatch(const ScanParams & a, uint32_t z, hipStream_t stream)
-{
-    dim3 grid(a.seg_max, a.nprobe, z);
-    size_t lds = scan_lds_bytes(1, a.ld4, a.k);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((ivf_scan_subset_kernel<METRIC, 1>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((ivf_scan_subset_kernel<METRIC, 2>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((ivf_scan_subset_kernel<METRIC, 4>), grid, dim3(BLOCK), lds, stream, a);
-            break;
-    }
 }
 
 void launch_ivf_scan_subset(int metric, ScanParams a, uint32_t z, hipStream_t stream)
@@ -614,29 +463,14 @@ void launch_ivf_scan_subset(int metric, ScanParams a, uint32_t z, hipStream_t st
     if (z == 0 || a.nprobe == 0 || a.seg_max == 0)
         return;
     ProfileScope prof("fallback_scan", stream);
-    if (metric == M_IP)
-        ivf_subset_dispatch<M_IP>(a, z, stream);
-    else
-        ivf_subset_dispatch<M_L2>(a, z, stream);
+    const dim3 grid(a.seg_max, a.nprobe, z);
+    const size_t lds = scan_lds_bytes(1, a.ld4, a.k);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+            hipLaunchKernelGGL((ivf_scan_subset_kernel<decltype(m)::value, decltype(r)::value>), grid, dim3(BLOCK), lds, stream, a);
+        });
+    });
     MSVS_HIP(hipGetLastError());
-}
-
-template <int METRIC>
-static void ivf_merge_subset_dispatch(const IvfMergeParams & a, uint32_t blocks, hipStream_t stream)
-{
-    size_t lds = merge_lds_bytes(a.k, a.nprobe);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((ivf_merge_subset_kernel<METRIC, 1>), dim3(blocks), dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((ivf_merge_subset_kernel<METRIC, 2>), dim3(blocks), dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((ivf_merge_subset_kernel<METRIC, 4>), dim3(blocks), dim3(BLOCK), lds, stream, a);
-            break;
-    }
 }
 
 void launch_ivf_merge_subset(int metric, IvfMergeParams a, uint32_t blocks, hipStream_t stream)
@@ -644,10 +478,13 @@ void launch_ivf_merge_subset(int metric, IvfMergeParams a, uint32_t blocks, hipS
     if (blocks == 0)
         return;
     ProfileScope prof("fallback_merge", stream);
-    if (metric == M_IP)
-        ivf_merge_subset_dispatch<M_IP>(a, blocks, stream);
-    else
-        ivf_merge_subset_dispatch<M_L2>(a, blocks, stream);
+    const size_t lds = merge_lds_bytes(a.k, a.nprobe);
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+            constexpr int METRIC = decltype(m)::value, R = decltype(r)::value;
+            hipLaunchKernelGGL((ivf_merge_subset_kernel<METRIC, R>), dim3(blocks), dim3(BLOCK), lds, stream, a);
+        });
+    });
     MSVS_HIP(hipGetLastError());
 }
 

@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "scan_kernels.hpp"
 #include "mfma_scan_kernels.hpp"
 
@@ -74,8 +75,6 @@ struct ProfileScope
 void profile_enable(bool on);
 void profile_get(const char * name, uint64_t * calls, double * total_ms);
 void profile_reset();
-
-inline int r_for_k(uint32_t k) { return k <= 64 ? 1 : (k <= 128 ? 2 : 4); }
 
 struct FlatPlan
 {

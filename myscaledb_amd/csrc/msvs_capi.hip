@@ -837,23 +837,21 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
                 // and stores, not its loop)
                 const int nt = options().coarse_gemm_tq == 128 ? 2 : 1, ns = options().coarse_gemm_tc == 128 ? 2 : 1;
                 const dim3 ggrid((unsigned)ceil_div(nq, (size_t)(64 * nt)), (unsigned)ceil_div((size_t)G, (size_t)(2 * ns)));
-                auto go = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, ggrid, dim3(256), 0, stream, ix.c_shadow.p, ix.h_nch, qh, qinfo, t.norms, (uint32_t)t.n, (uint32_t)nq,
-                                       sample);
-                };
-                if (scan_metric(m) == M_IP)
-                    nt == 2 ? (ns == 2 ? go(coarse_gemm_kernel<M_IP, 2, 2>) : go(coarse_gemm_kernel<M_IP, 2, 1>))
-                            : (ns == 2 ? go(coarse_gemm_kernel<M_IP, 1, 2>) : go(coarse_gemm_kernel<M_IP, 1, 1>));
-                else
-                    nt == 2 ? (ns == 2 ? go(coarse_gemm_kernel<M_L2, 2, 2>) : go(coarse_gemm_kernel<M_L2, 2, 1>))
-                            : (ns == 2 ? go(coarse_gemm_kernel<M_L2, 1, 2>) : go(coarse_gemm_kernel<M_L2, 1, 1>));
+                with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                    with_int<2, 1>(nt, [&](auto ntc) {
+                        with_int<2, 1>(ns, [&](auto nsc) {
+                            constexpr int METRIC = decltype(mc)::value, NT = decltype(ntc)::value, NS = decltype(nsc)::value;
+                            hipLaunchKernelGGL((coarse_gemm_kernel<METRIC, NT, NS>), ggrid, dim3(256), 0, stream, ix.c_shadow.p, ix.h_nch, qh, qinfo,
+                                               t.norms, (uint32_t)t.n, (uint32_t)nq, sample);
+                        });
+                    });
+                });
             }
-            else if (scan_metric(m) == M_IP)
-                hipLaunchKernelGGL((coarse_h16_kernel<M_IP>), dim3(cgrid), dim3(BLOCK), 0, stream, ix.c_shadow.p, ix.h_nch, qh, qinfo,
-                                   t.norms, (uint32_t)t.n, (uint32_t)nq, sample);
             else
-                hipLaunchKernelGGL((coarse_h16_kernel<M_L2>), dim3(cgrid), dim3(BLOCK), 0, stream, ix.c_shadow.p, ix.h_nch, qh, qinfo,
-                                   t.norms, (uint32_t)t.n, (uint32_t)nq, sample);
+                with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                    hipLaunchKernelGGL((coarse_h16_kernel<decltype(mc)::value>), dim3(cgrid), dim3(BLOCK), 0, stream, ix.c_shadow.p, ix.h_nch, qh,
+                                       qinfo, t.norms, (uint32_t)t.n, (uint32_t)nq, sample);
+                });
         }
         else
         {
@@ -877,10 +875,9 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
             h.nprobe = G;
             h.sample_out = sample;
             const uint32_t sgrid = device_cu_count() * 8;
-            if (scan_metric(m) == M_IP)
-                hipLaunchKernelGGL((h16_sample_kernel<M_IP, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, h);
-            else
-                hipLaunchKernelGGL((h16_sample_kernel<M_L2, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, h);
+            with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                hipLaunchKernelGGL((h16_sample_kernel<decltype(mc)::value, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, h);
+            });
         }
         // round 6: selection + band re-rank of the probe lists in ONE launch, a wavefront per query (coarse_tail_kernel); the block-per-query
         // re-rank then serves only the queries whose band could not be formed
@@ -916,12 +913,10 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
         {
             const RerankParams rp = table_rerank_params(ix, t, a, qn16, cand, bound, kc, failq, nfail, true, qrho);
             const dim3 tgrid((unsigned)ceil_div(nq, (size_t)(BLOCK / WAVE)));
-            if (scan_metric(m) == M_IP)
-                hipLaunchKernelGGL((coarse_tail_kernel<M_IP>), tgrid, dim3(BLOCK), 0, stream, sample, (uint32_t)nq, n_pad, rp, cand, bound, failq2c, nslow,
-                                   (uint32_t)t.n, slow_stamp, seq, slow_inline ? 1 : 0);
-            else
-                hipLaunchKernelGGL((coarse_tail_kernel<M_L2>), tgrid, dim3(BLOCK), 0, stream, sample, (uint32_t)nq, n_pad, rp, cand, bound, failq2c, nslow,
-                                   (uint32_t)t.n, slow_stamp, seq, slow_inline ? 1 : 0);
+            with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                hipLaunchKernelGGL((coarse_tail_kernel<decltype(mc)::value>), tgrid, dim3(BLOCK), 0, stream, sample, (uint32_t)nq, n_pad, rp, cand,
+                                   bound, failq2c, nslow, (uint32_t)t.n, slow_stamp, seq, slow_inline ? 1 : 0);
+            });
         }
         else
             hipLaunchKernelGGL(coarse_select_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(BLOCK), 0, stream, sample, (uint32_t)nq,
@@ -967,24 +962,19 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
         const uint32_t mth = (uint32_t)std::min<size_t>(64, std::max<size_t>(4, ceil_div(target * n_pad, std::max<size_t>(t.n, 1))));
         const bool few = nq <= 32 && options().flat_sample_few != 0; // one query tile: sample and cut in one launch
         if (few)
-        {
-            if (scan_metric(m) == M_IP)
-                hipLaunchKernelGGL((flat_sample_few_kernel<M_IP>), dim3(gs), dim3(BLOCK), 0, stream, ix.shadow.p, ix.h_nch, qh, qinfo, t.norms, gs,
-                                   (uint32_t)nq, sample, blk_stride, nrows, t.ids, t.alive, a.nbits, mth, qstate, qstate + nq, sched + 8);
-            else
-                hipLaunchKernelGGL((flat_sample_few_kernel<M_L2>), dim3(gs), dim3(BLOCK), 0, stream, ix.shadow.p, ix.h_nch, qh, qinfo, t.norms, gs,
-                                   (uint32_t)nq, sample, blk_stride, nrows, t.ids, t.alive, a.nbits, mth, qstate, qstate + nq, sched + 8);
-        }
+            with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                hipLaunchKernelGGL((flat_sample_few_kernel<decltype(mc)::value>), dim3(gs), dim3(BLOCK), 0, stream, ix.shadow.p, ix.h_nch, qh, qinfo,
+                                   t.norms, gs, (uint32_t)nq, sample, blk_stride, nrows, t.ids, t.alive, a.nbits, mth, qstate, qstate + nq,
+                                   sched + 8);
+            });
         else
         {
             const uint32_t items = (uint32_t)(ceil_div((size_t)gs, (size_t)2) * ceil_div(ceil_div(nq, (size_t)32), (size_t)2));
             const uint32_t cgrid = (uint32_t)std::min<size_t>(ceil_div((size_t)items, (size_t)4), (size_t)device_cu_count() * 2);
-            if (scan_metric(m) == M_IP)
-                hipLaunchKernelGGL((coarse_h16_kernel<M_IP>), dim3(cgrid), dim3(BLOCK), 0, stream, ix.shadow.p, ix.h_nch, qh, qinfo, t.norms,
-                                   n_pad, (uint32_t)nq, sample, blk_stride, nrows, t.ids, t.alive, a.nbits);
-            else
-                hipLaunchKernelGGL((coarse_h16_kernel<M_L2>), dim3(cgrid), dim3(BLOCK), 0, stream, ix.shadow.p, ix.h_nch, qh, qinfo, t.norms,
-                                   n_pad, (uint32_t)nq, sample, blk_stride, nrows, t.ids, t.alive, a.nbits);
+            with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                hipLaunchKernelGGL((coarse_h16_kernel<decltype(mc)::value>), dim3(cgrid), dim3(BLOCK), 0, stream, ix.shadow.p, ix.h_nch, qh, qinfo,
+                                   t.norms, n_pad, (uint32_t)nq, sample, blk_stride, nrows, t.ids, t.alive, a.nbits);
+            });
         }
         if (!few)
             hipLaunchKernelGGL(flat_cut_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(BLOCK), 0, stream, sample, (uint32_t)nq, n_pad, mth,
@@ -1180,31 +1170,6 @@ static void h16_launch(uint32_t grid, size_t lds, const H16Params & a, hipStream
     hipLaunchKernelGGL((h16_scan_kernel<METRIC, NCB, I8>), dim3(grid), dim3(64 * H_NW), lds, stream, a);
 }
 
-template <int METRIC>
-static void h16_dispatch(uint32_t ncb, uint32_t grid, size_t lds, const H16Params & a, hipStream_t stream)
-{
-    switch (ncb)
-    {
-        case 1: h16_launch<METRIC, 1>(grid, lds, a, stream); break;
-        case 2: h16_launch<METRIC, 2>(grid, lds, a, stream); break;
-        case 3: h16_launch<METRIC, 3>(grid, lds, a, stream); break;
-        default: h16_launch<METRIC, 4>(grid, lds, a, stream); break;
-    }
-}
-
-/// The list scan over the int8 residual shadow (M_IP: inner-product and cosine indexes, query images).
-template <int METRIC>
-static void h8_dispatch(uint32_t ncb, uint32_t grid, size_t lds, const H16Params & a, hipStream_t stream)
-{
-    switch (ncb)
-    {
-        case 1: h16_launch<METRIC, 1, true>(grid, lds, a, stream); break;
-        case 2: h16_launch<METRIC, 2, true>(grid, lds, a, stream); break;
-        case 3: h16_launch<METRIC, 3, true>(grid, lds, a, stream); break;
-        default: h16_launch<METRIC, 4, true>(grid, lds, a, stream); break;
-    }
-}
-
 template <int METRIC, int NCB, int NRB, int RING>
 static void h16_flat_launch(uint32_t grid, size_t lds, const H16Params & a, const H16FlatParams & f, hipStream_t stream)
 {
@@ -1244,10 +1209,7 @@ static void h16_flat_dispatch(int metric, uint32_t ncb, int shape, uint32_t grid
                               const H16FlatParams & f, hipStream_t stream)
 {
     ProfileScope prof("flat_shadow_scan", stream);
-    if (metric == M_IP)
-        h16_flat_dispatch_m<M_IP>(ncb, shape, grid, lds, a, f, stream);
-    else
-        h16_flat_dispatch_m<M_L2>(ncb, shape, grid, lds, a, f, stream);
+    with_int<M_IP, M_L2>(metric, [&](auto mc) { h16_flat_dispatch_m<decltype(mc)::value>(ncb, shape, grid, lds, a, f, stream); });
 }
 
 /// Experiments (option h16_stamps): the per-item wall-clock stamps of the last main launch (H16Params::stamps).
@@ -1524,14 +1486,12 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         ProfileScope prof("ivf_sample_scan", stream);
         a.work_off = pa.work_off;
         const uint32_t sgrid = device_cu_count() * 8; // one wavefront per (list, 32-query column block), grid-stride
-        if (ix.h8 && scan_metric(m) == M_IP)
-            hipLaunchKernelGGL((h16_sample_kernel<M_IP, 1, true>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
-        else if (ix.h8)
-            hipLaunchKernelGGL((h16_sample_kernel<M_L2, 1, true>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
-        else if (scan_metric(m) == M_IP)
-            hipLaunchKernelGGL((h16_sample_kernel<M_IP, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
-        else
-            hipLaunchKernelGGL((h16_sample_kernel<M_L2, 1>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
+        with_bool(ix.h8, [&](auto i8) {
+            with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                constexpr int METRIC = decltype(mc)::value;
+                hipLaunchKernelGGL((h16_sample_kernel<METRIC, 1, decltype(i8)::value>), dim3(sgrid), dim3(BLOCK), 0, stream, a);
+            });
+        });
         if (nprobe <= 64 && options().wave_select != 0)
         {
             // probe pruning (h16_scan_kernels.hpp: H16Prune): L2 indexes whose coarse pass left every centroid's approximate
@@ -1626,14 +1586,14 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
                 a.stamps = g_h16_stamps.p;
                 g_h16_stamp_grid = grid;
             }
-            if (ix.h8 && scan_metric(m) == M_IP)
-                h8_dispatch<M_IP>(pl.h_ncb, grid, lds, a, stream);
-            else if (ix.h8)
-                h8_dispatch<M_L2>(pl.h_ncb, grid, lds, a, stream);
-            else if (scan_metric(m) == M_IP)
-                h16_dispatch<M_IP>(pl.h_ncb, grid, lds, a, stream);
-            else
-                h16_dispatch<M_L2>(pl.h_ncb, grid, lds, a, stream);
+            // the fp16 shadow or (h8) the int8 residual shadow (there M_IP: inner-product and cosine indexes, query images); 1 to 4 column blocks
+            with_bool(ix.h8, [&](auto i8) {
+                with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
+                    with_int<1, 2, 3, 4>(pl.h_ncb, [&](auto cb) {
+                        h16_launch<decltype(mc)::value, decltype(cb)::value, decltype(i8)::value>(grid, lds, a, stream);
+                    });
+                });
+            });
         }
     }
     MSVS_HIP(hipGetLastError());

@@ -251,28 +251,17 @@ static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStrea
     hipLaunchKernelGGL((pq_ivf_scan_kernel<METRIC, T, R>), dim3(grid), dim3(BLOCK), lds, stream, a);
 }
 
-template <int METRIC, int T>
-static void pq_dispatch_r(uint32_t grid, size_t lds, const PqIvfParams & a, hipStream_t stream)
-{
-    switch (r_for_k(a.k))
-    {
-        case 1: pq_launch<METRIC, T, 1>(grid, lds, a, stream); break;
-        case 2: pq_launch<METRIC, T, 2>(grid, lds, a, stream); break;
-        default: pq_launch<METRIC, T, 4>(grid, lds, a, stream); break;
-    }
-}
-
-template <int METRIC>
-static void pq_dispatch_t(uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
+/// tiles of 1, 2, 4 or 8 queries
+static void launch_pq_ivf_scan(int metric, uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
 {
     const size_t lds = pq_lds_bytes(T, a.m, a.ld, a.k);
-    switch (T)
-    {
-        case 1: pq_dispatch_r<METRIC, 1>(grid, lds, a, stream); break;
-        case 2: pq_dispatch_r<METRIC, 2>(grid, lds, a, stream); break;
-        case 4: pq_dispatch_r<METRIC, 4>(grid, lds, a, stream); break;
-        default: pq_dispatch_r<METRIC, 8>(grid, lds, a, stream); break;
-    }
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<1, 2, 4, 8>(T, [&](auto t) {
+            with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                pq_launch<decltype(m)::value, decltype(t)::value, decltype(r)::value>(grid, lds, a, stream);
+            });
+        });
+    });
 }
 
 /// search_device of coded_ivf.hpp with this index's shapes: row segments of whole 256-row steps (a segment rebuilds its tile's
@@ -302,10 +291,7 @@ static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, 
             a.dsub = (uint32_t)ix.dsub;
             a.mw = ix.mw;
             a.tables_only = options().pq_ivf_tables_only != 0;
-            if (r.metric == M_IP)
-                pq_dispatch_t<M_IP>(T, grid, a, stream);
-            else
-                pq_dispatch_t<M_L2>(T, grid, a, stream);
+            launch_pq_ivf_scan(r.metric, T, grid, a, stream);
         });
 }
 

@@ -206,16 +206,12 @@ void lat_launch(const msvs_index & ix, LatCtx & c, const float * Q, size_t nq, u
     const size_t lds1 = sh.lds1, lds2 = sh.lds2;
     const dim3 g1(p.c_blocks, (unsigned)nq), g2((unsigned)grid_x, (unsigned)nq);
     ProfileScope prof("lat_search", stream);
-    if (ix.metric == MSVS_METRIC_L2)
-    {
-        hipLaunchKernelGGL((lat_coarse_kernel<M_L2>), g1, dim3(BLOCK), lds1, stream, p);
-        hipLaunchKernelGGL((lat_scan_kernel<M_L2>), g2, dim3(BLOCK), lds2, stream, p);
-    }
-    else
-    {
-        hipLaunchKernelGGL((lat_coarse_kernel<M_IP>), g1, dim3(BLOCK), lds1, stream, p);
-        hipLaunchKernelGGL((lat_scan_kernel<M_IP>), g2, dim3(BLOCK), lds2, stream, p);
-    }
+    // <M_L2, M_IP>, not the other launchers' <M_IP, M_L2>: the same mapping (scan_metric gives only these two), listed L2 first so that
+    // the kernels keep their order in the code object
+    with_int<M_L2, M_IP>(scan_metric(ix.metric), [&](auto m) {
+        hipLaunchKernelGGL((lat_coarse_kernel<decltype(m)::value>), g1, dim3(BLOCK), lds1, stream, p);
+        hipLaunchKernelGGL((lat_scan_kernel<decltype(m)::value>), g2, dim3(BLOCK), lds2, stream, p);
+    });
     MSVS_HIP(hipGetLastError());
 }
 
@@ -281,31 +277,19 @@ bool msvs::coarse_few_launch(const msvs_index & ix, const float * dq, size_t nq,
     p.done_q = c.cf_done.p;
     const dim3 g1(p.c_blocks, (unsigned)groups);
     ProfileScope prof("coarse_few", stream);
+    // (L2 first and one nest per kernel: the kernels' order in the code object, as in lat_launch)
     if (dense)
-    {
-        if (ix.metric == MSVS_METRIC_L2)
-        {
-            if (T == 1)
-                hipLaunchKernelGGL((coarse_dense_kernel<M_L2, 1>), g1, dim3(BLOCK), lds, stream, p);
-            else
-                hipLaunchKernelGGL((coarse_dense_kernel<M_L2, LAT_COARSE_T>), g1, dim3(BLOCK), lds, stream, p);
-        }
-        else if (T == 1)
-            hipLaunchKernelGGL((coarse_dense_kernel<M_IP, 1>), g1, dim3(BLOCK), lds, stream, p);
-        else
-            hipLaunchKernelGGL((coarse_dense_kernel<M_IP, LAT_COARSE_T>), g1, dim3(BLOCK), lds, stream, p);
-    }
-    else if (ix.metric == MSVS_METRIC_L2)
-    {
-        if (T == 1)
-            hipLaunchKernelGGL((coarse_few_kernel<M_L2, 1>), g1, dim3(BLOCK), lds, stream, p);
-        else
-            hipLaunchKernelGGL((coarse_few_kernel<M_L2, LAT_COARSE_T>), g1, dim3(BLOCK), lds, stream, p);
-    }
-    else if (T == 1)
-        hipLaunchKernelGGL((coarse_few_kernel<M_IP, 1>), g1, dim3(BLOCK), lds, stream, p);
+        with_int<M_L2, M_IP>(scan_metric(ix.metric), [&](auto m) {
+            with_int<1, LAT_COARSE_T>(T, [&](auto t) {
+                hipLaunchKernelGGL((coarse_dense_kernel<decltype(m)::value, decltype(t)::value>), g1, dim3(BLOCK), lds, stream, p);
+            });
+        });
     else
-        hipLaunchKernelGGL((coarse_few_kernel<M_IP, LAT_COARSE_T>), g1, dim3(BLOCK), lds, stream, p);
+        with_int<M_L2, M_IP>(scan_metric(ix.metric), [&](auto m) {
+            with_int<1, LAT_COARSE_T>(T, [&](auto t) {
+                hipLaunchKernelGGL((coarse_few_kernel<decltype(m)::value, decltype(t)::value>), g1, dim3(BLOCK), lds, stream, p);
+            });
+        });
     MSVS_HIP(hipGetLastError());
     return true;
 }

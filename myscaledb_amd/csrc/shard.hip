@@ -26,12 +26,11 @@ void merge_topk_device(const int64_t * d_ids, size_t ids_stride, const float * d
     {
         // a few short lists per query: one wavefront ranks them (merge_small_kernel)
         const dim3 grid((unsigned)ceil_div(nq, (size_t)(BLOCK / WAVE)));
-        if (metric == MSVS_METRIC_IP)
-            hipLaunchKernelGGL((merge_small_kernel<M_IP>), grid, dim3(BLOCK), 0, stream, d_ids, ids_stride, d_dis, dis_stride, (uint32_t)nparts,
-                               (uint32_t)nq, (uint32_t)k, d_out_ids, d_out_dis);
-        else
-            hipLaunchKernelGGL((merge_small_kernel<M_L2>), grid, dim3(BLOCK), 0, stream, d_ids, ids_stride, d_dis, dis_stride, (uint32_t)nparts,
-                               (uint32_t)nq, (uint32_t)k, d_out_ids, d_out_dis);
+        // (scan_metric sends everything but L2 to M_IP: the same fork as metric == MSVS_METRIC_IP only behind the check above)
+        with_int<M_IP, M_L2>(scan_metric(metric), [&](auto m) {
+            hipLaunchKernelGGL((merge_small_kernel<decltype(m)::value>), grid, dim3(BLOCK), 0, stream, d_ids, ids_stride, d_dis, dis_stride,
+                               (uint32_t)nparts, (uint32_t)nq, (uint32_t)k, d_out_ids, d_out_dis);
+        });
         MSVS_HIP(hipGetLastError());
         return;
     }
@@ -39,12 +38,10 @@ void merge_topk_device(const int64_t * d_ids, size_t ids_stride, const float * d
     const size_t total = nparts * nq * k;
     scr.reserve(total * 8 + 8192, stream);
     uint64_t * keys_q = scr.take<uint64_t>(total); // [nq][nparts][k]
-    if (metric == MSVS_METRIC_IP)
-        hipLaunchKernelGGL((pack_keys_kernel<M_IP>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream, d_ids,
+    with_int<M_IP, M_L2>(scan_metric(metric), [&](auto m) { // (L2 or IP only, see above)
+        hipLaunchKernelGGL((pack_keys_kernel<decltype(m)::value>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream, d_ids,
                            ids_stride, d_dis, dis_stride, keys_q, (uint32_t)nparts, (uint32_t)nq, (uint32_t)k);
-    else
-        hipLaunchKernelGGL((pack_keys_kernel<M_L2>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream, d_ids,
-                           ids_stride, d_dis, dis_stride, keys_q, (uint32_t)nparts, (uint32_t)nq, (uint32_t)k);
+    });
     MSVS_HIP(hipGetLastError());
     MergeParams m{};
     m.partial = keys_q;

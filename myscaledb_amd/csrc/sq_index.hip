@@ -185,39 +185,17 @@ extern "C" size_t msvs_sq_index_memory_usage(const msvs_sq_index_t * ix)
 
 // ------------------------------------------------------------------------------------------- search
 
-template <int METRIC, int T>
-static void sq_dispatch_r(uint32_t grid, const SqIvfParams & a, hipStream_t stream)
+/// tiles of 2, 4 or 8 queries (no T = 1)
+static void launch_sq_ivf_scan(int metric, uint32_t T, uint32_t grid, const SqIvfParams & a, hipStream_t stream)
 {
-    const size_t lds = sq_lds_bytes(T, a.ld4, a.k);
-    switch (r_for_k(a.k))
-    {
-        case 1:
-            hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, T, 1>), dim3(grid), dim3(BLOCK), lds, stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, T, 2>), dim3(grid), dim3(BLOCK), lds, stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, T, 4>), dim3(grid), dim3(BLOCK), lds, stream, a);
-            break;
-    }
-}
-
-template <int METRIC>
-static void sq_dispatch_t(uint32_t T, uint32_t grid, const SqIvfParams & a, hipStream_t stream)
-{
-    switch (T)
-    {
-        case 2:
-            sq_dispatch_r<METRIC, 2>(grid, a, stream);
-            break;
-        case 4:
-            sq_dispatch_r<METRIC, 4>(grid, a, stream);
-            break;
-        default:
-            sq_dispatch_r<METRIC, 8>(grid, a, stream);
-            break;
-    }
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        with_int<2, 4, 8>(T, [&](auto t) {
+            with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                constexpr int METRIC = decltype(m)::value, TQ = decltype(t)::value, R = decltype(r)::value;
+                hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, TQ, R>), dim3(grid), dim3(BLOCK), sq_lds_bytes(TQ, a.ld4, a.k), stream, a);
+            });
+        });
+    });
 }
 
 /// search_device of coded_ivf.hpp with this index's shapes: row segments of whole 16-row steps, tiles of 2, 4 or 8 queries
@@ -242,10 +220,7 @@ static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, 
             a.vmin = reinterpret_cast<const float4 *>(ix.d_vmin.p);
             a.step = reinterpret_cast<const float4 *>(ix.d_step.p);
             a.ld4 = ld4;
-            if (r.metric == M_IP)
-                sq_dispatch_t<M_IP>(T, grid, a, stream);
-            else
-                sq_dispatch_t<M_L2>(T, grid, a, stream);
+            launch_sq_ivf_scan(r.metric, T, grid, a, stream);
         });
 }
 
