@@ -194,10 +194,10 @@ MSVS_API int msvs_sq_index_serialize_io(const msvs_sq_index_t * index, const str
 MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t ** out);
 
 /* IVFPQ -- an inverted-file index of Float32 vectors that keeps product-quantised residual codes ONLY (no f32 row survives build):
- * m code bytes (padded to 4) + a u32 label per row.  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All
+ * m code bytes, or ceil(m / 2) at bit_size=4, (padded to 4) + a u32 label per row.  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All
  * arithmetic is f32 with separately rounded operations (fl), no fma:
- *   - contents: nlist centroids c_l; m sub-codebooks cb[s][j] (s < m, j < 256: 8 bits per sub-quantiser only) of dsub = dim / m
- *     floats each; per row its list, label and m codes; rows inside a list in ascending label order;
+ *   - contents: nlist centroids c_l; m sub-codebooks cb[s][j] (s < m, j < ksub = 1 << bit_size: 256 entries, or 16 at bit_size=4) of
+ *     dsub = dim / m floats each; per row its list, label and m codes; rows inside a list in ascending label order;
  *   - stored row x: the row as fed (L2, IP) or the normalised row (cosine; msvs_normalize_f32's arithmetic);
  *   - decoded sub-vector of code j in sub-space s of list l: x^[t] = fl(c_l[s * dsub + t] + cb[s][j][t]), t < dsub;
  *   - sub-score e of a (query or row) sub-vector q against x^, t ascending, a sequential sum starting at +0:
@@ -212,12 +212,16 @@ MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t **
  *     slot; the filter is indexed by label.  The search over what the index stores is exact; the quantiser is lossy.
  *   - a row is assigned to its nearest centroid by L2 (L2 indexes) or by inner product (IP and cosine), as msvs_index_add does.
  * create: params as msvs_index_create's for IVFFLAT (ncentroids, kmeans_iters, train_sample, seed, ...) plus m, the number of
- *   sub-quantisers (required).  1 <= m <= 128, m divides dim, dim <= 8192, and the list scan's smallest LDS image, m KiB of tables +
- *   8 * round_up(dim, 4) + 5 * 8 * MSVS_MAX_K bytes, fits 160 KiB: MSVS_ERR_INVALID_ARGUMENT otherwise, checked here and at load.
+ *   sub-quantisers (required), and bit_size, the bits of a code: 8 (the default) or 4, anything else MSVS_ERR_INVALID_ARGUMENT.
+ *   bit_size=8: 1 <= m <= 128, m divides dim, dim <= 8192, and the list scan's smallest LDS image, m KiB of tables +
+ *   8 * round_up(dim, 4) + 5 * 8 * MSVS_MAX_K bytes, fits 160 KiB.  bit_size=4: 1 <= m <= 256, m divides dim, dim <= 8192 (the image,
+ *   64 * m + 8 * round_up(dim, 4) + 5 * 8 * MSVS_MAX_K bytes, always fits); a row keeps ceil(m / 2) code bytes (padded to 4, pad
+ *   nibbles 0).  MSVS_ERR_INVALID_ARGUMENT otherwise, checked here and at load.  With ksub in place of 256 everything above and
+ *   below holds for both; without bit_size, or with bit_size=8, every result and every file byte is what it was.
  * train: the coarse centroids by the IVFFLAT k-means over the rows; then the residuals fl(x - c_l) of at most 262144 training rows
  *   (row floor(i * n / cap), i < cap = min(n, 262144)); for every s the dsub columns of sub-space s go through the same k-means
- *   (L2, 256 centroids, the same iterations and seed): its centroids are cb[s].  n < 256: MSVS_ERR_INVALID_ARGUMENT.  The same input
- *   gives the same bits.  set_codebook: centroids (nlist * dim) and codebooks (m * 256 * dsub, [s][j][t]) from the caller; a
+ *   (L2, ksub centroids, the same iterations and seed): its centroids are cb[s].  n < ksub: MSVS_ERR_INVALID_ARGUMENT.  The same input
+ *   gives the same bits.  set_codebook: centroids (nlist * dim) and codebooks (m * ksub * dsub, [s][j][t]) from the caller; a
  *   non-finite codebook entry is MSVS_ERR_INVALID_ARGUMENT and leaves the index without a codebook.  Both must precede add
  *   (MSVS_ERR_NOT_READY from add before either; MSVS_ERR_INVALID_ARGUMENT from either after add).
  * add: any number of chunks before build; rows are encoded as they arrive, only codes, lists and labels are staged.  ids: labels
@@ -225,12 +229,16 @@ MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t **
  * search (host pointers): params "nprobe=P" (default 1).  search_device: device pointers, enqueued on hip_stream without host
  *   synchronisation.  k <= MSVS_MAX_K and min(nprobe, nlist) <= MSVS_MAX_K (MSVS_ERR_UNSUPPORTED_K); k = 0 or nq = 0 is a no-op;
  *   before build: MSVS_ERR_NOT_READY.
- * export: centroids nlist * dim, codebooks m * 256 * dsub, nlist + 1 offsets, codes n * m in NATURAL order, labels n; any output
- *   may be NULL.
- * memory_usage after build <= n * (round_up(m, 16) + 8) + the centroids, codebooks and offsets + 4096 bytes.
+ * export: centroids nlist * dim, codebooks m * ksub * dsub, nlist + 1 offsets, codes n * m in NATURAL order, one code a byte in both
+ *   forms (values < ksub), labels n; any output may be NULL.  bit_size: 4 or 8 (0 for NULL): what a host that loaded an index
+ *   sizes export's codebook buffer by.
+ * memory_usage after build <= n * (round_up(m, 16) + 8) + the centroids, codebooks and offsets + 4096 bytes; at bit_size=4
+ *   <= n * (round_up(ceil(m / 2), 16) + 8) + the centroids, 16 * dim * 4 bytes of codebooks, the offsets + 4096 bytes.
  * Files "pq_data" (header "MSVSPQ01", centroids, codebooks, offsets, codes in natural order) / "pq_ids" through the caller's stream
  * openers (a built index only); load validates sizes, offsets, labels, the codebooks and a checksum of each header: a corrupt or
- * truncated file is MSVS_ERR_IO. */
+ * truncated file is MSVS_ERR_IO.  The header's reserved word is 0 for an 8-bit index and 4 for a 4-bit one, whose codes are
+ * n * ceil(m / 2) bytes, code s in the low nibble of byte s / 2 for even s, else the high one; any other reserved word, an m beyond
+ * the form's limit and a non-zero pad nibble (odd m) are MSVS_ERR_IO too (a library without the 4-bit form refuses such a file). */
 typedef struct msvs_pq_index msvs_pq_index_t;
 MSVS_API int msvs_pq_index_create(int metric, size_t dim, const char * params, msvs_pq_index_t ** out);
 MSVS_API void msvs_pq_index_free(msvs_pq_index_t * index);
@@ -243,6 +251,7 @@ MSVS_API int msvs_pq_index_ready(const msvs_pq_index_t * index);
 MSVS_API size_t msvs_pq_index_num_data(const msvs_pq_index_t * index);
 MSVS_API size_t msvs_pq_index_num_lists(const msvs_pq_index_t * index);
 MSVS_API size_t msvs_pq_index_memory_usage(const msvs_pq_index_t * index);
+MSVS_API size_t msvs_pq_index_bit_size(const msvs_pq_index_t * index);
 MSVS_API int msvs_pq_index_search(const msvs_pq_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
                                   const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
 MSVS_API int msvs_pq_index_search_device(const msvs_pq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t nprobe,

@@ -45,6 +45,7 @@ SYMBOLS = [
     "msvs_sq_index_search", "msvs_sq_index_search_device", "msvs_sq_index_export", "msvs_sq_index_serialize_io", "msvs_sq_index_load_io",
     "msvs_pq_index_create", "msvs_pq_index_free", "msvs_pq_index_train", "msvs_pq_index_set_codebook", "msvs_pq_index_add",
     "msvs_pq_index_build", "msvs_pq_index_ready", "msvs_pq_index_num_data", "msvs_pq_index_num_lists", "msvs_pq_index_memory_usage",
+    "msvs_pq_index_bit_size",
     "msvs_pq_index_search", "msvs_pq_index_search_device", "msvs_pq_index_export", "msvs_pq_index_serialize_io", "msvs_pq_index_load_io",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
@@ -421,8 +422,9 @@ class SqIndex(_CodedIndex):
 
 
 class PqIndex(_CodedIndex):
-    """msvs_pq_index_t: the IVFPQ index -- coarse centroids, m sub-codebooks of 256 entries over the residuals, and per row its list,
-    label and m code bytes (no f32 row is kept).  params as Index's for IVFFLAT plus m ("ncentroids=N,m=M,kmeans_iters=I,...")."""
+    """msvs_pq_index_t: the IVFPQ index -- coarse centroids, m sub-codebooks of 256 entries (16 with bit_size=4) over the residuals,
+    and per row its list, label and m codes (no f32 row is kept).  params as Index's for IVFFLAT plus m and, optionally, bit_size
+    ("ncentroids=N,m=M,bit_size=4,kmeans_iters=I,...").  .bits is the index's own answer (msvs_pq_index_bit_size): 4 or 8."""
     _c = "msvs_pq_index"
 
     def __init__(self, metric, dim, params="", _handle=None, _m=None):
@@ -433,19 +435,21 @@ class PqIndex(_CodedIndex):
         else:
             _check(lib().msvs_pq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
             self.m = int(dict(kv.split("=", 1) for kv in params.replace(" ", "").split(",") if "=" in kv)["m"])
+        self.bits = self._size("bit_size")
 
     def set_codebook(self, centroids, codebooks):
-        """codebooks: [m, 256, dim / m]"""
+        """codebooks: [m, 1 << bits, dim / m]"""
         c = _f32(centroids).reshape(-1, self.dim)
-        cb = _f32(codebooks).reshape(self.m, 256, self.dim // self.m)
+        cb = _f32(codebooks).reshape(self.m, 1 << self.bits, self.dim // self.m)
         _check(lib().msvs_pq_index_set_codebook(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(cb, C.c_float), MEM_HOST))
 
     def export(self, with_lists=True):
-        """-> (centroids [nlist, dim], codebooks [m, 256, dim / m], list offsets [nlist + 1], codes [n, m] u8 in natural order,
-        labels [n]) in list-major order; with_lists=False (an index not built yet): the codebook only, None for the rest."""
+        """-> (centroids [nlist, dim], codebooks [m, 1 << bits, dim / m], list offsets [nlist + 1], codes [n, m] u8 in natural order
+        (one code a byte), labels [n]) in list-major order; with_lists=False (an index not built yet): the codebook only, None for
+        the rest."""
         nl, d, m = self.num_lists, self.dim, self.m
         cent = np.empty((nl, d), np.float32)
-        cb = np.empty((m, 256, d // m), np.float32)
+        cb = np.empty((m, 1 << self.bits, d // m), np.float32)
         off = codes = labels = None
         if with_lists:
             n = self.num_data
@@ -455,11 +459,11 @@ class PqIndex(_CodedIndex):
         return cent, cb, off, codes, labels
 
     @classmethod
-    def load_io(cls, store, metric=None, dim=None, m=None):
-        """metric / dim / m come from the file (PqHeader: magic[8], u32 version, i32 metric, u64 dim, u64 m, ...); where given,
-        they must agree with it (ValueError otherwise)."""
+    def load_io(cls, store, metric=None, dim=None, m=None, bits=None):
+        """metric / dim / m come from the file (PqHeader: magic[8], u32 version, i32 metric, u64 dim, u64 m, ...), bits from the
+        loaded index; where given, they must agree with it (ValueError otherwise)."""
         h, (f_metric, f_dim, f_m) = cls._load(store, "pq_data", "<iQQ")
-        return cls(f_metric, f_dim, _handle=h, _m=f_m)._agree("IVFPQ", metric=metric, dim=dim, m=m)
+        return cls(f_metric, f_dim, _handle=h, _m=f_m)._agree("IVFPQ", metric=metric, dim=dim, m=m, bits=bits)
 
 
 def normalize(x):

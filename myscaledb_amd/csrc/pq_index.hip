@@ -1,5 +1,5 @@
-// pq_index.hip -- the IVFPQ index (include/msvs.h: msvs_pq_index_*): coarse centroids + m sub-quantisers of 256 entries over the
-// residuals; codes, lists and labels are all the index keeps.  Semantics and layout: pq_ivf_kernels.hpp, DESIGN.md 4.12.
+// pq_index.hip -- the IVFPQ index (include/msvs.h: msvs_pq_index_*): coarse centroids + m sub-quantisers of 256 (bit_size 8) or 16
+// (bit_size 4) entries over the residuals; codes, lists and labels are all the index keeps.  Semantics and layout: pq_ivf_kernels.hpp, DESIGN.md 4.12.
 // Here: the geometry, the sub-codebooks (finiteness, residual sampling, training), the scan's shapes, LDS attribute and dispatch,
 // the data file and the stored order of the code words.  Everything the index has in common with IVFSQ -- staging, add, build, the
 // search skeleton, labels, the id file -- is coded_ivf.hpp, which also lists what is reused as it is.
@@ -15,13 +15,17 @@ namespace
 {
 constexpr const char * PQ = "IVFPQ";
 constexpr size_t PQ_TRAIN_ROWS = 262144; // residuals the sub-codebooks are trained on at most
-constexpr size_t PQ_KSUB = 256;          // entries of a sub-codebook (8 bits)
 
-/// dim / m of an index that can exist: the smallest tile with the largest k must fit the scan's LDS
-inline bool pq_fits(size_t dim, size_t m)
+/// sub-quantisers an index of this bit size has at most: a stored row stays within 128 bytes
+inline size_t pq_max_m(size_t bits) { return bits == 4 ? 256 : 128; }
+
+/// dim / m / bit size of an index that can exist: the smallest tile with the largest k must fit the scan's LDS
+inline bool pq_fits(size_t dim, size_t m, size_t bits)
 {
-    return dim >= 1 && dim <= 8192 && m >= 1 && m <= 128 && dim % m == 0
-        && pq_lds_bytes(1, (uint32_t)m, padded_dim(dim), MSVS_MAX_K) <= PQ_LDS_BUDGET;
+    if ((bits != 4 && bits != 8) || dim < 1 || dim > 8192 || m < 1 || m > pq_max_m(bits) || dim % m != 0)
+        return false;
+    const size_t lds = bits == 4 ? pq4_lds_bytes(1, (uint32_t)m, padded_dim(dim), MSVS_MAX_K) : pq_lds_bytes(1, (uint32_t)m, padded_dim(dim), MSVS_MAX_K);
+    return lds <= PQ_LDS_BUDGET;
 }
 }
 
@@ -30,38 +34,44 @@ inline bool pq_fits(size_t dim, size_t m)
 struct msvs_pq_index : CodedIvf
 {
     size_t m = 0, dsub = 0;
-    uint32_t mw = 0;         // 32-bit words of a stored row: ceil(m / 4)
-    std::vector<float> h_cb; // [m][256][dsub]
-    DevBuf<float> cbT;       // [m][dsub][256]
+    size_t bits = 8, ksub = 256; // bits of a code, entries of a sub-codebook (1 << bits)
+    uint32_t mw = 0;         // 32-bit words of a stored row: ceil(m / 4), 4-bit: ceil(m / 8)
+    std::vector<float> h_cb; // [m][ksub][dsub]
+    DevBuf<float> cbT;       // [m][dsub][256]; 4-bit: pq4_cb_index
     const uint32_t * code_words() const { return reinterpret_cast<const uint32_t *>(codes.p); }
     uint32_t * code_words() { return reinterpret_cast<uint32_t *>(codes.p); }
 };
 
-static void pq_set_geometry(msvs_pq_index & ix, int metric, size_t dim, size_t m)
+static void pq_set_geometry(msvs_pq_index & ix, int metric, size_t dim, size_t m, size_t bits)
 {
+    ix.bits = bits;
+    ix.ksub = (size_t)1 << bits;
     ix.metric = metric;
     ix.dim = dim;
     ix.m = m;
     ix.dsub = dim / m;
     ix.ld = padded_dim(dim);
-    ix.mw = (uint32_t)ceil_div(m, (size_t)4);
+    ix.mw = (uint32_t)ceil_div(m, (size_t)(32 / bits));
     ix.row_bytes = ix.mw * 4;
 }
 
-/// centroids (nlist x ld on the device already) + sub-codebooks [m][256][dsub] on the host -> the index's codebook
+/// centroids (nlist x ld on the device already) + sub-codebooks [m][ksub][dsub] on the host -> the index's codebook
 static void pq_set_codebooks(msvs_pq_index & ix, const float * cb, hipStream_t stream)
 {
-    const size_t d = ix.dim, m = ix.m, dsub = ix.dsub;
-    for (size_t i = 0; i < PQ_KSUB * d; i++)
+    const size_t d = ix.dim, m = ix.m, dsub = ix.dsub, ksub = ix.ksub;
+    for (size_t i = 0; i < ksub * d; i++)
         if (!std::isfinite(cb[i]))
-            fail(MSVS_ERR_INVALID_ARGUMENT, "codebook entry %zu of sub-quantiser %zu is not finite", (i / dsub) % PQ_KSUB, i / (PQ_KSUB * dsub));
-    ix.h_cb.assign(cb, cb + PQ_KSUB * d);
-    std::vector<float> t(PQ_KSUB * d);
+            fail(MSVS_ERR_INVALID_ARGUMENT, "codebook entry %zu of sub-quantiser %zu is not finite", (i / dsub) % ksub, i / (ksub * dsub));
+    ix.h_cb.assign(cb, cb + ksub * d);
+    std::vector<float> t(ksub * d);
     for (size_t s = 0; s < m; s++)
-        for (size_t j = 0; j < PQ_KSUB; j++)
+        for (size_t j = 0; j < ksub; j++)
             for (size_t u = 0; u < dsub; u++)
-                t[(s * dsub + u) * PQ_KSUB + j] = cb[(s * PQ_KSUB + j) * dsub + u];
-    ix.cbT.alloc(PQ_KSUB * d);
+            {
+                const size_t at = ix.bits == 4 ? pq4_cb_index((uint32_t)s, (uint32_t)u, (uint32_t)j, (uint32_t)m, (uint32_t)dsub) : (s * dsub + u) * ksub + j;
+                t[at] = cb[(s * ksub + j) * dsub + u];
+            }
+    ix.cbT.alloc(ksub * d);
     MSVS_HIP(hipMemcpyAsync(ix.cbT.p, t.data(), t.size() * 4, hipMemcpyHostToDevice, stream));
     finish_codebook(ix, stream); // (synchronises: t is about to go)
 }
@@ -97,13 +107,16 @@ extern "C" int msvs_pq_index_create(int metric, size_t dim, const char * params,
         check_metric(metric, PQ);
         auto p = parse_params(params);
         check_ncentroids(p);
-        const long m = param_int(p, "m", 0);
-        if (m < 1 || !pq_fits(dim, (size_t)m))
+        const long m = param_int(p, "m", 0), bits = param_int(p, "bit_size", 8);
+        if (bits != 4 && bits != 8)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the IVFPQ index has 4 or 8 bits per sub-quantiser (bit_size %ld)", bits);
+        if (m < 1 || !pq_fits(dim, (size_t)m, (size_t)bits))
             fail(MSVS_ERR_INVALID_ARGUMENT,
-                 "the IVFPQ index needs 1 <= m <= 128 dividing 1 <= dim <= 8192 and tables of m KiB + 8 * dim + 10 KiB within 160 KiB (dim %zu, m %ld)",
-                 dim, m);
+                 "the IVFPQ index needs 1 <= m <= 128 (256 at bit_size=4) dividing 1 <= dim <= 8192 and tables of m KiB (m / 16 KiB) + 8 * dim + "
+                 "10 KiB within 160 KiB (dim %zu, m %ld, bit_size %ld)",
+                 dim, m, bits);
         std::unique_ptr<msvs_pq_index> ix(new msvs_pq_index);
-        pq_set_geometry(*ix, metric, dim, (size_t)m);
+        pq_set_geometry(*ix, metric, dim, (size_t)m, (size_t)bits);
         ix->params = params ? params : "";
         MSVS_HIP(hipGetDevice(&ix->device));
         *out = ix.release();
@@ -120,7 +133,7 @@ extern "C" int msvs_pq_index_set_codebook(msvs_pq_index_t * ix, const float * ce
             fail(MSVS_ERR_INVALID_ARGUMENT, "null index / codebook");
         check_codebook_time(*ix);
         hipStream_t stream = thread_stream();
-        std::vector<float> cb(PQ_KSUB * ix->dim);
+        std::vector<float> cb(ix->ksub * ix->dim);
         if (mem == MSVS_MEM_DEVICE)
             MSVS_HIP(hipMemcpyAsync(cb.data(), codebooks, cb.size() * 4, hipMemcpyDeviceToHost, stream));
         else
@@ -138,8 +151,9 @@ extern "C" int msvs_pq_index_train(msvs_pq_index_t * ix, const float * x, size_t
         DeviceGuard on_device(ix ? ix->device : -1);
         check_rows(ix, x, n);
         check_codebook_time(*ix);
-        if (n < PQ_KSUB)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "the IVFPQ index needs at least 256 training rows (%zu given)", n);
+        const size_t ksub = ix->ksub;
+        if (n < ksub)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the IVFPQ index needs at least %zu training rows (%zu given)", ksub, n);
         hipStream_t stream = thread_stream();
         const size_t d = ix->dim, m = ix->m, dsub = ix->dsub;
         pq_drop_codebook(*ix);
@@ -178,22 +192,22 @@ extern "C" int msvs_pq_index_train(msvs_pq_index_t * ix, const float * x, size_t
                 MSVS_HIP(hipStreamSynchronize(stream)); // d_x / h_pick are reused by the next step
             }
         }
-        // every sub-codebook: the same trainer over the sub-space's columns, L2, 256 centroids, the caller's iterations and seed
+        // every sub-codebook: the same trainer over the sub-space's columns, L2, ksub centroids, the caller's iterations and seed
         std::string sub_params;
         for (const auto & kv : parse_params(ix->params.c_str()))
-            if (kv.first != "ncentroids" && kv.first != "m")
+            if (kv.first != "ncentroids" && kv.first != "m" && kv.first != "bit_size")
                 sub_params += kv.first + "=" + kv.second + ",";
-        sub_params += "ncentroids=256";
+        sub_params += "ncentroids=" + std::to_string(ksub);
         DevBuf<float> d_sub(cap * dsub);
-        std::vector<float> cb(PQ_KSUB * d);
+        std::vector<float> cb(ksub * d);
         for (size_t s = 0; s < m; s++)
         {
             MSVS_HIP(hipMemcpy2DAsync(d_sub.p, dsub * 4, d_res.p + s * dsub, d * 4, dsub * 4, cap, hipMemcpyDeviceToDevice, stream));
             MSVS_HIP(hipStreamSynchronize(stream));
             const TmpIndex tmp = kmeans(MSVS_METRIC_L2, dsub, sub_params, d_sub.p, cap, MSVS_MEM_DEVICE);
-            if (tmp->nlist != PQ_KSUB)
+            if (tmp->nlist != ksub)
                 fail(MSVS_ERR_DEVICE, "internal: sub-quantiser %zu came out with %zu centroids", s, tmp->nlist);
-            MSVS_HIP(hipMemcpy2D(cb.data() + s * PQ_KSUB * dsub, dsub * 4, tmp->centroids.p, (size_t)tmp->ld * 4, dsub * 4, PQ_KSUB,
+            MSVS_HIP(hipMemcpy2D(cb.data() + s * ksub * dsub, dsub * 4, tmp->centroids.p, (size_t)tmp->ld * 4, dsub * 4, ksub,
                                  hipMemcpyDeviceToHost));
         }
         pq_set_codebooks_or_drop(*ix, cb.data(), stream);
@@ -204,6 +218,12 @@ extern "C" int msvs_pq_index_add(msvs_pq_index_t * ix, const float * x, const in
 {
     return guarded([&] {
         add_rows(ix, x, ids, n, mem, PQ, true, [&](const float * d_x, const int32_t * d_assign, size_t cnt, uint8_t * dst, hipStream_t stream) {
+            if (ix->bits == 4)
+            {
+                hipLaunchKernelGGL(pq4_encode_kernel, dim3((unsigned)ceil_div(cnt, (size_t)16)), dim3(BLOCK), 0, stream, d_x, d_assign,
+                                   ix->centroids.p, ix->cbT.p, cnt, ix->ld, (uint32_t)ix->m, (uint32_t)ix->dsub, ix->mw * 4, dst);
+                return;
+            }
             // the encoder stages a row and its centroid in LDS: more than 64 KiB of it (dim > 8184, beside its 64 static bytes) needs the
             // attribute raised once
             static std::once_flag once;
@@ -232,33 +252,43 @@ extern "C" int msvs_pq_index_ready(const msvs_pq_index_t * ix) { return ix && ix
 extern "C" size_t msvs_pq_index_num_data(const msvs_pq_index_t * ix) { return ix ? (ix->ready ? ix->n : ix->staged) : 0; }
 extern "C" size_t msvs_pq_index_num_lists(const msvs_pq_index_t * ix) { return ix ? ix->nlist : 0; }
 extern "C" size_t msvs_pq_index_memory_usage(const msvs_pq_index_t * ix) { return ix ? coded_bytes(*ix) + ix->cbT.bytes() : 0; }
+extern "C" size_t msvs_pq_index_bit_size(const msvs_pq_index_t * ix) { return ix ? ix->bits : 0; }
 
 // ------------------------------------------------------------------------------------------- search
 
-template <int METRIC, int T, int R>
+template <int BITS, int METRIC, int T, int R>
 static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStream_t stream)
 {
+    constexpr auto kernel = BITS == 4 ? &pq4_ivf_scan_kernel<METRIC, T, R> : &pq_ivf_scan_kernel<METRIC, T, R>;
     // more than 64 KiB of dynamic LDS needs the attribute raised once per kernel
     static std::once_flag once;
     std::call_once(once, [] {
-        const void * fn = reinterpret_cast<const void *>(&pq_ivf_scan_kernel<METRIC, T, R>);
+        const void * fn = reinterpret_cast<const void *>(kernel);
         hipFuncAttributes fa{};
         MSVS_HIP(hipFuncGetAttributes(&fa, fn));
         if (fa.sharedSizeBytes != 0) // PQ_LDS_BUDGET: the dynamic image may be the whole LDS
             fail(MSVS_ERR_DEVICE, "the IVFPQ list scan has %zu bytes of static LDS: pq_fits no longer holds", (size_t)fa.sharedSizeBytes);
         MSVS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQ_LDS_BUDGET));
     });
-    hipLaunchKernelGGL((pq_ivf_scan_kernel<METRIC, T, R>), dim3(grid), dim3(BLOCK), lds, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, stream, a);
 }
 
-/// tiles of 1, 2, 4 or 8 queries
-static void launch_pq_ivf_scan(int metric, uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
+/// the scan's LDS image of either form
+static size_t pq_image_bytes(size_t bits, uint32_t T, uint32_t m, uint32_t ld, uint32_t k)
 {
-    const size_t lds = pq_lds_bytes(T, a.m, a.ld, a.k);
-    with_int<M_IP, M_L2>(metric, [&](auto m) {
-        with_int<1, 2, 4, 8>(T, [&](auto t) {
-            with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
-                pq_launch<decltype(m)::value, decltype(t)::value, decltype(r)::value>(grid, lds, a, stream);
+    return bits == 4 ? pq4_lds_bytes(T, m, ld, k) : pq_lds_bytes(T, m, ld, k);
+}
+
+/// tiles of 1, 2, 4 or 8 queries; 256- or 16-entry tables
+static void launch_pq_ivf_scan(size_t bits, int metric, uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
+{
+    const size_t lds = pq_image_bytes(bits, T, a.m, a.ld, a.k);
+    with_int<8, 4>((int)bits, [&](auto b) {
+        with_int<M_IP, M_L2>(metric, [&](auto m) {
+            with_int<1, 2, 4, 8>(T, [&](auto t) {
+                with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                    pq_launch<decltype(b)::value, decltype(m)::value, decltype(t)::value, decltype(r)::value>(grid, lds, a, stream);
+                });
             });
         });
     });
@@ -274,7 +304,7 @@ static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, 
         [&](size_t n_pairs, size_t k_) {
             const size_t nlist = ix.nlist;
             uint32_t T = n_pairs >= 16 * nlist ? 8 : (n_pairs >= 2 * nlist ? 4 : (n_pairs >= nlist ? 2 : 1));
-            while (T > 1 && pq_lds_bytes(T, (uint32_t)ix.m, ix.ld, (uint32_t)k_) > PQ_LDS_BUDGET)
+            while (T > 1 && pq_image_bytes(ix.bits, T, (uint32_t)ix.m, ix.ld, (uint32_t)k_) > PQ_LDS_BUDGET)
                 T /= 2;
             return T;
         },
@@ -291,7 +321,7 @@ static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, 
             a.dsub = (uint32_t)ix.dsub;
             a.mw = ix.mw;
             a.tables_only = options().pq_ivf_tables_only != 0;
-            launch_pq_ivf_scan(r.metric, T, grid, a, stream);
+            launch_pq_ivf_scan(ix.bits, r.metric, T, grid, a, stream);
         });
 }
 
@@ -320,7 +350,15 @@ extern "C" int msvs_pq_index_search(const msvs_pq_index_t * ix, const float * qu
 /// rows of a piece of the codes that passes through the host at a time: whole blocks of 64
 static size_t pq_piece_rows(uint32_t mw) { return std::max<size_t>(64, (((size_t)64 << 20) / (mw * 4)) & ~(size_t)63); }
 
-/// the built index's codes in NATURAL order (n x m) and its labels, on the host
+/// code s of row r of a piece of stored rows (pq_code_word from the piece's first row)
+static uint8_t pq_code_of(const uint32_t * words, size_t r, size_t s, uint32_t mw, size_t bits)
+{
+    if (bits == 4)
+        return (uint8_t)((words[pq_code_word(r, (uint32_t)(s >> 3), mw)] >> (4 * (s & 7))) & 15u);
+    return (uint8_t)(words[pq_code_word(r, (uint32_t)(s >> 2), mw)] >> (8 * (s & 3)));
+}
+
+/// the built index's codes in NATURAL order (n x m, one code a byte) and its labels, on the host
 static void pq_fetch(const msvs_pq_index & ix, uint8_t * codes, int64_t * ids, hipStream_t stream)
 {
     const uint32_t mw = ix.mw;
@@ -334,7 +372,7 @@ static void pq_fetch(const msvs_pq_index & ix, uint8_t * codes, int64_t * ids, h
         MSVS_HIP(hipStreamSynchronize(stream));
         for (size_t r = 0; r < cnt; r++)
             for (size_t s = 0; s < ix.m; s++)
-                codes[(r0 + r) * ix.m + s] = (uint8_t)(buf[pq_code_word(r, (uint32_t)(s >> 2), mw)] >> (8 * (s & 3)));
+                codes[(r0 + r) * ix.m + s] = pq_code_of(buf.data(), r, s, mw, ix.bits);
     }
     fetch_labels(ix, ids, stream);
 }
@@ -360,9 +398,12 @@ struct PqHeader // 64 bytes, little endian
     uint32_t version; // 1
     int32_t metric;
     uint64_t dim, m, nlist, n;
-    uint64_t reserved;
+    uint64_t reserved; // 0: 8 bits per code, one code a byte; 4: 4 bits, two codes a byte (even s in the low nibble)
     uint64_t check; // FNV-1a of the bytes before it
 };
+
+/// bytes of a row's codes in the data file
+inline size_t pq_file_row_bytes(size_t m, size_t bits) { return bits == 4 ? (m + 1) / 2 : m; }
 }
 
 extern "C" int msvs_pq_index_serialize_io(const msvs_pq_index_t * ix, const msvs_io_t * io)
@@ -374,6 +415,15 @@ extern "C" int msvs_pq_index_serialize_io(const msvs_pq_index_t * ix, const msvs
         std::vector<uint8_t> codes(ix->n * ix->m);
         std::vector<int64_t> ids(ix->n);
         pq_fetch(*ix, codes.data(), ids.data(), thread_stream());
+        if (ix->bits == 4)
+        {
+            // two codes a byte, in place (byte r * fb + i is written after the codes it is made of, at r * m + 2i and beyond, are read)
+            const size_t m = ix->m, fb = pq_file_row_bytes(m, 4);
+            for (size_t r = 0; r < ix->n; r++)
+                for (size_t i = 0; i < fb; i++)
+                    codes[r * fb + i] = (uint8_t)(codes[r * m + 2 * i] | (2 * i + 1 < m ? codes[r * m + 2 * i + 1] << 4 : 0));
+            codes.resize(ix->n * fb);
+        }
         {
             IoStream f(io, "pq_data", 1);
             PqHeader h{};
@@ -384,6 +434,7 @@ extern "C" int msvs_pq_index_serialize_io(const msvs_pq_index_t * ix, const msvs
             h.m = ix->m;
             h.nlist = ix->nlist;
             h.n = ix->n;
+            h.reserved = ix->bits == 4 ? 4 : 0;
             h.check = fnv1a(&h, offsetof(PqHeader, check));
             f.write(&h, sizeof(h));
             f.write(ix->h_cent.data(), ix->h_cent.size() * 4);
@@ -411,16 +462,23 @@ extern "C" int msvs_pq_index_load_io(const msvs_io_t * io, msvs_pq_index_t ** ou
             PqHeader h{};
             f.read(&h, sizeof(h));
             if (memcmp(h.magic, "MSVSPQ01", 8) != 0 || h.version != 1 || h.check != fnv1a(&h, offsetof(PqHeader, check))
-                || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || h.m > 128 || !pq_fits((size_t)h.dim, (size_t)h.m) || h.reserved != 0)
+                || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || (h.reserved != 0 && h.reserved != 4))
                 fail(MSVS_ERR_IO, "corrupt msvs IVFPQ index header");
-            pq_set_geometry(*ix, h.metric, (size_t)h.dim, (size_t)h.m);
+            const size_t bits = h.reserved == 4 ? 4 : 8;
+            if (h.m > pq_max_m(bits) || !pq_fits((size_t)h.dim, (size_t)h.m, bits))
+                fail(MSVS_ERR_IO, "corrupt msvs IVFPQ index header");
+            pq_set_geometry(*ix, h.metric, (size_t)h.dim, (size_t)h.m, bits);
             ix->nlist = (size_t)h.nlist;
             ix->n = (size_t)h.n;
             read_grow(f, cent, ix->nlist * ix->dim);
-            read_grow(f, cb, PQ_KSUB * ix->dim);
+            read_grow(f, cb, ix->ksub * ix->dim);
             read_list_offsets(f, *ix, PQ);
-            read_grow(f, codes, ix->n * ix->m);
+            read_grow(f, codes, ix->n * pq_file_row_bytes(ix->m, bits));
             expect_end(f);
+            if (bits == 4 && ix->m % 2)
+                for (size_t r = 0, fb = pq_file_row_bytes(ix->m, 4); r < ix->n; r++)
+                    if (codes[r * fb + fb - 1] >> 4)
+                        fail(MSVS_ERR_IO, "corrupt msvs IVFPQ index: the pad nibble of row %zu is not zero", r);
             for (float v : cb)
                 if (!std::isfinite(v))
                     fail(MSVS_ERR_IO, "corrupt msvs IVFPQ index: a codebook entry is not finite");
@@ -437,9 +495,11 @@ extern "C" int msvs_pq_index_load_io(const msvs_io_t * io, msvs_pq_index_t ** ou
         {
             const size_t cnt = std::min(piece, ix->n - r0), words = round_up(cnt, 64) * mw;
             buf.assign(words, 0);
+            // a file row's bytes are the stored row's words, little endian, in either form (8-bit: byte s; 4-bit: two codes a byte)
+            const size_t fb = pq_file_row_bytes(ix->m, ix->bits);
             for (size_t r = 0; r < cnt; r++)
-                for (size_t s = 0; s < ix->m; s++)
-                    buf[pq_code_word(r, (uint32_t)(s >> 2), mw)] |= (uint32_t)codes[(r0 + r) * ix->m + s] << (8 * (s & 3));
+                for (size_t i = 0; i < fb; i++)
+                    buf[pq_code_word(r, (uint32_t)(i >> 2), mw)] |= (uint32_t)codes[(r0 + r) * fb + i] << (8 * (i & 3));
             MSVS_HIP(hipMemcpyAsync(ix->code_words() + r0 * mw, buf.data(), words * 4, hipMemcpyHostToDevice, stream));
             MSVS_HIP(hipStreamSynchronize(stream));
         }

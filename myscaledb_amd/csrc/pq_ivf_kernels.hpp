@@ -10,6 +10,11 @@
 // Stored codes: a row is mw = ceil(m / 4) 32-bit words (code s in byte s % 4 of word s / 4, zero padded); the rows, list-major, are
 // kept in blocks of 64 TRANSPOSED: word w of row r is codes[((r / 64) * mw + w) * 64 + r % 64].  The scan takes one row per lane, so a
 // wavefront's load of word w is 256 contiguous bytes (two pieces where its 64 rows straddle a block).  pq_code_word is the map.
+//
+// The 4-bit form (bit_size = 4; the pq4_* names at the end of this file): the same definitions with 16 entries per sub-quantiser.  A
+// row is mw = ceil(m / 8) words, code s in bits 4 * (s % 8) .. + 3 of word s / 8, pad nibbles 0, in the same transposed blocks; the
+// codebooks sit on the device in groups of four sub-spaces (pq4_cb_index); the tables are 64 * m bytes per query, so tiles of up to
+// 8 queries fit the LDS at every m <= 256.  The 8-bit kernels above it are untouched by it.
 #pragma once
 
 #include "scan_kernels.hpp"
@@ -273,6 +278,222 @@ __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
                             {
                                 const uint32_t code = (words[e] >> (8 * b)) & 255u;
                                 const float * src = lut + ((size_t)s * 256 + code) * T;
+#pragma unroll
+                                for (int t = 0; t < T; t++)
+                                    dis[t] = __fadd_rn(dis[t], src[t]);
+                            }
+                        }
+                    }
+                }
+                uint32_t id = 0;
+                bool ok = rv;
+                if (ok)
+                {
+                    id = a.labels[r];
+                    if (a.alive)
+                        ok = id < a.nbits && ((a.alive[id >> 6] >> (id & 63)) & 1);
+                }
+#pragma unroll
+                for (int t = 0; t < T; t++)
+                    top[t].offer(ok ? make_key<METRIC>(dis[t], id) : KEY_NONE, k, lane);
+            }
+        }
+
+        tile_rank_merge<T, R>(top, lds_merge, out, k); // (no barrier in front: the row loop reads the tables, not lds_merge)
+    }
+}
+
+// ------------------------------------------------------------------------------------------ the 4-bit form
+
+/// floats between the entries u and u + 1 of one codebook entry in the device copy of the 16-entry codebooks: 16 for every
+/// sub-space of the group of four that s belongs to (the last group has m % 4 of them when 4 does not divide m)
+__host__ __device__ inline uint32_t pq4_cb_stride(uint32_t s, uint32_t m) { return (m - (s & ~3u) < 4u ? m - (s & ~3u) : 4u) * 16; }
+
+/// index of cb[s][j][u] in that copy: [group of four sub-spaces][u][sub-space in the group][j], 16 * dim floats in all, no padding.
+/// The 64 lanes of a wavefront that build tables are (4 consecutive sub-spaces) x (16 entries), so their load at step u is 256
+/// contiguous bytes; the 16 lanes that encode one row read 64 contiguous bytes.
+__host__ __device__ inline size_t pq4_cb_index(uint32_t s, uint32_t u, uint32_t j, uint32_t m, uint32_t dsub)
+{
+    return (size_t)(s >> 2) * dsub * 64 + (size_t)u * pq4_cb_stride(s, m) + (s & 3) * 16 + j;
+}
+
+/// LDS bytes of a 4-bit scan block: 16-entry tables, the tile's queries, the list's centroid, the merge lists.
+inline size_t pq4_lds_bytes(uint32_t T, uint32_t m, uint32_t ld, uint32_t k)
+{
+    return (size_t)T * m * 64 + (size_t)(T + 1) * ld * 4 + (size_t)T * 5 * k * 8;
+}
+
+/// the minimum over each group of 16 consecutive lanes, in all of them
+__device__ __forceinline__ uint64_t pq4_group_min(uint64_t v)
+{
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1)
+    {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+        const uint64_t other = (uint64_t)hi << 32 | lo;
+        v = other < v ? other : v;
+    }
+    return v;
+}
+
+/// pq_encode_kernel with 16 entries: codes[r][s / 2] (rows of mp = 4 * mw bytes; bytes ceil(m / 2) .. mp - 1 untouched) holds code s in
+/// its low (s even) or high nibble.  A block takes 16 rows, 16 lanes a row, lane j entry j (cb4: pq4_cb_index); the argmin over the
+/// key (ordered word of e, j) is four shuffles.  Lane 0 of a row collects two codes and writes the whole byte: no byte has two writers.
+/// Rows beyond n are computed as row n - 1 and not written (every lane stays in the shuffles); n >= 1.
+static __global__ __launch_bounds__(BLOCK) void pq4_encode_kernel(const float * X, const int32_t * list, const float * C, const float * cb4,
+                                                                  size_t n, uint32_t ld, uint32_t m, uint32_t dsub, uint32_t mp, uint8_t * codes)
+{
+    const uint32_t tid = threadIdx.x, j = tid & 15;
+    const size_t r = (size_t)blockIdx.x * 16 + (tid >> 4);
+    const size_t rc = r < n ? r : n - 1;
+    const float * x = X + rc * ld;
+    const float * c = C + (size_t)list[rc] * ld;
+    uint32_t byte = 0;
+    for (uint32_t s = 0; s < m; s++)
+    {
+        const float * cb = cb4 + pq4_cb_index(s, 0, j, m, dsub);
+        const uint32_t gw = pq4_cb_stride(s, m), c0 = s * dsub;
+        float e = 0.f;
+        for (uint32_t t = 0; t < dsub; t++)
+        {
+            const float xh = __fadd_rn(c[c0 + t], cb[(size_t)t * gw]);
+            const float df = __fsub_rn(x[c0 + t], xh);
+            e = __fadd_rn(e, __fmul_rn(df, df));
+        }
+        const uint64_t best = pq4_group_min(e == e ? ((uint64_t)f2ord(e) << 32 | j) : KEY_NONE); // (a NaN score never wins)
+        const uint32_t code = best == KEY_NONE ? 0u : (uint32_t)(best & 15u);
+        byte = (s & 1) ? byte | code << 4 : code;
+        if (j == 0 && r < n && ((s & 1) || s + 1 == m))
+            codes[r * mp + (s >> 1)] = (uint8_t)byte;
+    }
+}
+
+/// pq_ivf_scan_kernel with 16-entry tables, lut[(s * 16 + j) * T + t]: the same work items, prologue, arithmetic, top-k and merge.
+/// dynamic LDS: pq4_lds_bytes(T, m, ld, k); a.cbT is the pq4_cb_index copy, a.mw = ceil(m / 8).
+/// The tables are built by (sub-space, entry) pairs, 16 sub-spaces a pass (the last pass is partial when 16 does not divide m); the
+/// row loop is one lane per row with eight codes a word.
+template <int METRIC, int T, int R>
+__global__ __launch_bounds__(BLOCK) void pq4_ivf_scan_kernel(const PqIvfParams a)
+{
+    const uint32_t ld = a.ld, k = a.k, m = a.m, dsub = a.dsub, mw = a.mw;
+    float * lut = reinterpret_cast<float *>(msvs_smem); // [m][16][T]
+    float * qs = lut + (size_t)m * 16 * T;              // [ld][T]
+    float * cs = qs + (size_t)ld * T;                   // [ld] centroid of the item's list
+    uint64_t * lds_merge = reinterpret_cast<uint64_t *>(cs + ld);
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t nu = (mw + 3) >> 2; // units of four code words per row
+
+    const uint32_t total = a.work_off[a.nlist];
+    const uint32_t per_xcd = (total + 7) / 8;
+    for (uint32_t slot = blockIdx.x; slot < 8 * per_xcd; slot += gridDim.x)
+    {
+        const uint32_t w = ivf_slot_item(slot, per_xcd);
+        if (w >= total)
+            continue;
+        const IvfWorkItem it = ivf_work_item<T>(w, a.work_off, a.pair_off, a.list_off, a.nlist, a.rows_per_block);
+        const uint32_t l = it.list, seg = it.seg, row_begin = it.row_begin, row_end = it.row_end;
+        uint64_t * out[T];
+        __syncthreads(); // the previous item is done with the LDS
+#pragma unroll
+        for (int t = 0; t < T; t++)
+        {
+            const uint32_t pi = min(it.pair_begin + t, it.pair_end - 1); // short tiles repeat their last pair (same slot, same values)
+            const uint32_t qp = a.pairs[pi];
+            out[t] = a.partial + ((size_t)qp * a.seg_max + seg) * k;
+            const float * src = a.Q + (size_t)(qp / a.nprobe) * ld;
+            for (uint32_t c = tid; c < ld; c += BLOCK)
+                qs[c * T + t] = src[c];
+        }
+        for (uint32_t c = tid; c < ld; c += BLOCK)
+            cs[c] = a.cent[(size_t)l * ld + c];
+        __syncthreads();
+
+        // the tables: thread (sub, j) of a pass scores entry j of sub-space s0 + sub against the tile's queries; s < m keeps both the
+        // codebook load and the table index (s * 16 + j) * T + t < m * 16 * T inside their arrays
+        for (uint32_t s0 = 0; s0 < m; s0 += 16)
+        {
+            const uint32_t s = s0 + (tid >> 4), j = tid & 15;
+            if (s < m)
+            {
+                const float * cb = a.cbT + pq4_cb_index(s, 0, j, m, dsub);
+                const uint32_t gw = pq4_cb_stride(s, m), c0 = s * dsub;
+                float e[T];
+#pragma unroll
+                for (int t = 0; t < T; t++)
+                    e[t] = 0.f;
+                for (uint32_t u = 0; u < dsub; u++)
+                {
+                    const float xh = __fadd_rn(cs[c0 + u], cb[(size_t)u * gw]);
+                    const float * q = qs + (size_t)(c0 + u) * T;
+#pragma unroll
+                    for (int t = 0; t < T; t++)
+                    {
+                        if (METRIC == M_L2)
+                        {
+                            const float df = __fsub_rn(q[t], xh);
+                            e[t] = __fadd_rn(e[t], __fmul_rn(df, df));
+                        }
+                        else
+                            e[t] = __fadd_rn(e[t], __fmul_rn(q[t], xh));
+                    }
+                }
+                float * dst = lut + ((size_t)s * 16 + j) * T;
+#pragma unroll
+                for (int t = 0; t < T; t++)
+                    dst[t] = e[t];
+            }
+        }
+        __syncthreads();
+
+        WaveTopK<R> top[T];
+#pragma unroll
+        for (int t = 0; t < T; t++)
+            top[t].init();
+
+        // unit u (code words 4u .. 4u + 3, 0 beyond the row's mw words: those are never loaded) of row r
+        auto load_unit = [&](uint32_t r, uint32_t u) {
+            const uint32_t * p = a.codes + pq_code_word(r, u * 4, mw);
+            const uint32_t left = mw - u * 4;
+            uint4 v;
+            v.x = p[0];
+            v.y = left > 1 ? p[64] : 0u;
+            v.z = left > 2 ? p[128] : 0u;
+            v.w = left > 3 ? p[192] : 0u;
+            return v;
+        };
+
+        if (!a.tables_only && row_begin < row_end)
+        {
+            uint4 wnext = load_unit(min(row_begin + tid, row_end - 1), 0);
+            for (uint32_t base = row_begin; base < row_end; base += BLOCK)
+            {
+                const uint32_t r = base + tid;
+                const bool rv = r < row_end;
+                const uint32_t rc = min(r, row_end - 1); // lanes beyond the segment repeat its last row and offer nothing
+                float dis[T];
+#pragma unroll
+                for (int t = 0; t < T; t++)
+                    dis[t] = 0.f;
+                for (uint32_t u = 0; u < nu; u++)
+                {
+                    const uint4 cw = wnext;
+                    // the next unit's codes are on their way while this one is looked up: the row's next unit, or the next step's first
+                    if (u + 1 < nu)
+                        wnext = load_unit(rc, u + 1);
+                    else if (base + BLOCK < row_end)
+                        wnext = load_unit(min(r + BLOCK, row_end - 1), 0);
+                    const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                    {
+#pragma unroll
+                        for (int b = 0; b < 8; b++)
+                        {
+                            const uint32_t s = u * 32 + e * 8 + b;
+                            if (s < m) // (pad nibbles and the words that were not loaded)
+                            {
+                                const uint32_t code = (words[e] >> (4 * b)) & 15u;
+                                const float * src = lut + ((size_t)s * 16 + code) * T;
 #pragma unroll
                                 for (int t = 0; t < T; t++)
                                     dis[t] = __fadd_rn(dis[t], src[t]);

@@ -10,8 +10,13 @@ scan of the original rows on the first 256 queries; memory_usage and build secon
 Every batch size runs in a child process of its own under a time limit, and the run stops at the first child that fails.  Writes one
 JSON file (default profiles/pq_ivf.json).
 
+An entry of --ms is M for an 8-bit index or Mx4 for a 4-bit one (bit_size=4), named pqM / pqMx4 in the output: --ms 96,192x4,96x4
+puts 8-bit m = 96 beside its equal-bytes 4-bit partner m = 192 and the half-size m = 96 (profiles/pq4_ivf.json).  The counter run
+then takes the first 8-bit and the first 4-bit entry, whose scan kernels have names of their own.  --no-competitors leaves the IVFSQ
+and IVFFLAT indexes out.
+
     python -m tools.bench_pq_ivf [--rows N] [--dim D] [--nlist L] [--ms 96,48] [--batches 64,1024,4096] [--nprobe P] [--ks 10,100]
-                                 [--reps R] [--no-counters] [--out FILE]
+                                 [--reps R] [--no-counters] [--no-competitors] [--out FILE]
 """
 import argparse
 import glob
@@ -60,6 +65,16 @@ def built(make, x, a):
     return ix, time.perf_counter() - t0
 
 
+def pq_name(spec):
+    m, bits = spec
+    return "pq%d" % m if bits == 8 else "pq%dx%d" % (m, bits)
+
+
+def pq_params(spec):
+    m, bits = spec
+    return ",m=%d" % m if bits == 8 else ",m=%d,bit_size=%d" % (m, bits)  # (an 8-bit index is created as it always was)
+
+
 def profiled(fn):
     capi.profile_enable(True)
     capi.profile_reset()
@@ -74,15 +89,16 @@ def child(a, nq):
     x, q = data(a, nq)
     params = "ncentroids=%d,kmeans_iters=4,train_sample=%d" % (a.nlist, min(a.rows, 64 * a.nlist))
     index, build_s = {}, {}
-    for m in a.ms:
-        index["pq%d" % m], build_s["pq%d" % m] = built(lambda: capi.PqIndex(capi.METRIC_L2, a.dim, params + ",m=%d" % m), x, a)
-    index["sq"], build_s["sq"] = built(lambda: capi.SqIndex(capi.METRIC_L2, a.dim, params), x, a)
-    index["ivfflat"], build_s["ivfflat"] = built(lambda: capi.Index(capi.INDEX_IVFFLAT, capi.METRIC_L2, a.dim, params), x, a)
+    for spec in a.ms:
+        index[pq_name(spec)], build_s[pq_name(spec)] = built(lambda: capi.PqIndex(capi.METRIC_L2, a.dim, params + pq_params(spec)), x, a)
+    if not a.no_competitors:
+        index["sq"], build_s["sq"] = built(lambda: capi.SqIndex(capi.METRIC_L2, a.dim, params), x, a)
+        index["ivfflat"], build_s["ivfflat"] = built(lambda: capi.Index(capi.INDEX_IVFFLAT, capi.METRIC_L2, a.dim, params), x, a)
     sp = "nprobe=%d" % a.nprobe
     nt = min(nq, 256)
     truth, _ = capi.knn(q[:nt], x, 10, capi.METRIC_L2)
     out = {"queries": nq, "build_s": build_s, "memory_usage": {n: ix.memory_usage for n, ix in index.items()}, "k": {}}
-    lens = np.diff(index["pq%d" % a.ms[0]].export()[2])
+    lens = np.diff(index[pq_name(a.ms[0])].export()[2])
     out["longest_list"], out["empty_lists"] = int(lens.max()), int((lens == 0).sum())
     for k in a.ks:
         runs = {n: (lambda ix: lambda: ix.search(q, k, sp))(ix) for n, ix in index.items()}
@@ -100,8 +116,8 @@ def child(a, nq):
         tables = {}
         capi.set_option("pq_ivf_tables_only", 1)
         try:
-            for m in a.ms:
-                tables["pq%d" % m] = profiled(runs["pq%d" % m])["pq_ivf_scan"]["ms"]
+            for spec in a.ms:
+                tables[pq_name(spec)] = profiled(runs[pq_name(spec)])["pq_ivf_scan"]["ms"]
         finally:
             capi.set_option("pq_ivf_tables_only")
 
@@ -118,7 +134,7 @@ def child(a, nq):
             "recall_10_in_k": {n: share(r[0], k) for n, r in results.items()},
         }
     # the row-segment length: the PQ scan kernel alone (first m, first k) at the planned default (0) and at fixed lengths
-    name, run = "pq%d" % a.ms[0], (lambda: index["pq%d" % a.ms[0]].search(q, a.ks[0], sp))
+    run = lambda: index[pq_name(a.ms[0])].search(q, a.ks[0], sp)
     out["rpb_sweep_scan_ms"] = {}
     try:
         for rpb in (0, 256, 512, 1024, 2048):
@@ -131,21 +147,27 @@ def child(a, nq):
 
 
 def counter_child(a, nq):
-    """one PQ index of rows / 8 rows in nlist / 8 lists (lists as long as the full shape's), one batch searched twice"""
+    """PQ indexes (the first 8-bit and the first 4-bit entry of --ms) of rows / 8 rows in nlist / 8 lists (lists as long as the full
+    shape's), one batch searched twice through each"""
     capi.set_device(0)
     a.rows, a.nlist = max(4096, a.rows // 8), max(8, a.nlist // 8)
     x, q = data(a, nq)
-    ix, _ = built(lambda: capi.PqIndex(capi.METRIC_L2, a.dim, "ncentroids=%d,kmeans_iters=4,m=%d" % (a.nlist, a.ms[0])), x, a)
-    for _ in range(2):
-        ix.search(q, a.ks[0], "nprobe=%d" % min(a.nprobe, a.nlist))
-    return {"rows": a.rows, "nlist": a.nlist, "queries": nq, "m": a.ms[0], "k": a.ks[0]}
+    specs = [next(s for s in a.ms if s[1] == bits) for bits in (8, 4) if any(s[1] == bits for s in a.ms)]
+    for spec in specs:
+        ix, _ = built(lambda: capi.PqIndex(capi.METRIC_L2, a.dim, "ncentroids=%d,kmeans_iters=4" % a.nlist + pq_params(spec)), x, a)
+        for _ in range(2):
+            ix.search(q, a.ks[0], "nprobe=%d" % min(a.nprobe, a.nlist))
+        ix.close()
+    return {"rows": a.rows, "nlist": a.nlist, "queries": nq, "indexes": [pq_name(s) for s in specs], "k": a.ks[0]}
 
 
 def spawn(a, extra, limit, prefix=()):
     cmd = list(prefix) + [sys.executable, "-m", "tools.bench_pq_ivf"] + extra
     for key in ("rows", "dim", "nlist", "nprobe", "reps"):
         cmd += ["--" + key, str(getattr(a, key))]
-    cmd += ["--ms", ",".join(map(str, a.ms)), "--ks", ",".join(map(str, a.ks))]
+    cmd += ["--ms", ",".join(pq_name(s)[2:] for s in a.ms), "--ks", ",".join(map(str, a.ks))]
+    if a.no_competitors:
+        cmd.append("--no-competitors")
     p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=limit, cwd=ROOT)  # the child's progress lines (stderr) pass through
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
     if p.returncode != 0 or not line:
@@ -165,14 +187,19 @@ def counters(a, limit):
         c = sqlite3.connect(dbs[0])
         cols = [r[1] for r in c.execute("pragma table_info(counters_collection)")]
         name_col = "kernel_name" if "kernel_name" in cols else "name"
-        sums = {}
-        for nm, cn, calls, total in c.execute("select %s, counter_name, count(*), sum(value) from counters_collection group by %s, counter_name"
-                                              % (name_col, name_col)):
-            if "pq_ivf_scan_kernel" in nm:
-                sums[cn] = sums.get(cn, 0.0) + float(total)
-        conflict, active = sums.get("SQ_LDS_BANK_CONFLICT"), sums.get("SQ_LDS_IDX_ACTIVE")
-        return {"shape": shape, "SQ_LDS_BANK_CONFLICT": conflict, "SQ_LDS_IDX_ACTIVE": active,
-                "conflict_share_of_active": conflict / active if conflict is not None and active else None}
+        out = {"shape": shape}
+        for kernel in ("pq_ivf_scan_kernel", "pq4_ivf_scan_kernel"):  # the 8-bit and the 4-bit scan
+            sums = {}
+            for nm, cn, calls, total in c.execute("select %s, counter_name, count(*), sum(value) from counters_collection group by %s, counter_name"
+                                                  % (name_col, name_col)):
+                if kernel in nm:
+                    sums[cn] = sums.get(cn, 0.0) + float(total)
+            if not sums:
+                continue
+            conflict, active = sums.get("SQ_LDS_BANK_CONFLICT"), sums.get("SQ_LDS_IDX_ACTIVE")
+            out[kernel] = {"SQ_LDS_BANK_CONFLICT": conflict, "SQ_LDS_IDX_ACTIVE": active,
+                           "conflict_share_of_active": conflict / active if conflict is not None and active else None}
+        return out
 
 
 def main():
@@ -180,7 +207,7 @@ def main():
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--nlist", type=int, default=1024)
-    ap.add_argument("--ms", default="96,48")
+    ap.add_argument("--ms", default="96,48", help="sub-quantisers of the PQ indexes: M (8 bits a code) or Mx4 (bit_size=4)")
     ap.add_argument("--batches", default="64,1024,4096")
     ap.add_argument("--nprobe", type=int, default=32)
     ap.add_argument("--ks", default="10,100")
@@ -189,12 +216,13 @@ def main():
                     help="seconds per batch size (a child process each: it generates the rows, builds the indexes, measures and runs the "
                          "exact scan); 0: 300 + 300 per 2^20 rows")
     ap.add_argument("--no-counters", action="store_true", help="skip the counter-only run (it needs rocprofv3)")
+    ap.add_argument("--no-competitors", action="store_true", help="the PQ indexes only: no IVFSQ and no IVFFLAT index")
     ap.add_argument("--counter-batch", type=int, default=1024)
     ap.add_argument("--out", default=os.path.join("profiles", "pq_ivf.json"))
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--counter-child", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
-    a.ms = [int(v) for v in a.ms.split(",")]
+    a.ms = [(int(v.split("x")[0]), int(v.split("x")[1]) if "x" in v else 8) for v in a.ms.split(",")]
     a.ks = [int(v) for v in a.ks.split(",")]
     limit = a.limit if a.limit > 0 else 300 + 300 * max(1, a.rows >> 20)
     if a.child:
@@ -203,7 +231,7 @@ def main():
     if a.counter_child:
         print("RESULT " + json.dumps(counter_child(a, a.counter_child)))
         return
-    res = {"rows": a.rows, "dim": a.dim, "nlist": a.nlist, "ms": a.ms, "ks": a.ks, "nprobe": a.nprobe, "metric": "L2", "version": capi.version(),
+    res = {"rows": a.rows, "dim": a.dim, "nlist": a.nlist, "ms": [pq_name(s) for s in a.ms], "ks": a.ks, "nprobe": a.nprobe, "metric": "L2", "version": capi.version(),
            "batches": []}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 
@@ -212,7 +240,7 @@ def main():
             json.dump(res, f, indent=1)
             f.write("\n")
 
-    for nq in [int(v) for v in a.batches.split(",")]:
+    for nq in [int(v) for v in a.batches.split(",") if v]:  # (--batches "": the counter run alone)
         res["batches"].append(spawn(a, ["--child", str(nq)], limit))
         write()
     if not a.no_counters:
