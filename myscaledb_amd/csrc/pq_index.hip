@@ -17,15 +17,14 @@ constexpr const char * PQ = "IVFPQ";
 constexpr size_t PQ_TRAIN_ROWS = 262144; // residuals the sub-codebooks are trained on at most
 
 /// sub-quantisers an index of this bit size has at most: a stored row stays within 128 bytes
-inline size_t pq_max_m(size_t bits) { return bits == 4 ? 256 : 128; }
+inline size_t pq_max_m(size_t bits) { return 1024 / bits; }
 
 /// dim / m / bit size of an index that can exist: the smallest tile with the largest k must fit the scan's LDS
 inline bool pq_fits(size_t dim, size_t m, size_t bits)
 {
     if ((bits != 4 && bits != 8) || dim < 1 || dim > 8192 || m < 1 || m > pq_max_m(bits) || dim % m != 0)
         return false;
-    const size_t lds = bits == 4 ? pq4_lds_bytes(1, (uint32_t)m, padded_dim(dim), MSVS_MAX_K) : pq_lds_bytes(1, (uint32_t)m, padded_dim(dim), MSVS_MAX_K);
-    return lds <= PQ_LDS_BUDGET;
+    return pq_lds_bytes(bits, 1, (uint32_t)m, padded_dim(dim), MSVS_MAX_K) <= PQ_LDS_BUDGET;
 }
 }
 
@@ -37,9 +36,8 @@ struct msvs_pq_index : CodedIvf
     size_t bits = 8, ksub = 256; // bits of a code, entries of a sub-codebook (1 << bits)
     uint32_t mw = 0;         // 32-bit words of a stored row: ceil(m / 4), 4-bit: ceil(m / 8)
     std::vector<float> h_cb; // [m][ksub][dsub]
-    DevBuf<float> cbT;       // [m][dsub][256]; 4-bit: pq4_cb_index
+    DevBuf<float> cbT;       // the same in the order of pq_cb_index
     const uint32_t * code_words() const { return reinterpret_cast<const uint32_t *>(codes.p); }
-    uint32_t * code_words() { return reinterpret_cast<uint32_t *>(codes.p); }
 };
 
 static void pq_set_geometry(msvs_pq_index & ix, int metric, size_t dim, size_t m, size_t bits)
@@ -64,13 +62,12 @@ static void pq_set_codebooks(msvs_pq_index & ix, const float * cb, hipStream_t s
             fail(MSVS_ERR_INVALID_ARGUMENT, "codebook entry %zu of sub-quantiser %zu is not finite", (i / dsub) % ksub, i / (ksub * dsub));
     ix.h_cb.assign(cb, cb + ksub * d);
     std::vector<float> t(ksub * d);
-    for (size_t s = 0; s < m; s++)
-        for (size_t j = 0; j < ksub; j++)
-            for (size_t u = 0; u < dsub; u++)
-            {
-                const size_t at = ix.bits == 4 ? pq4_cb_index((uint32_t)s, (uint32_t)u, (uint32_t)j, (uint32_t)m, (uint32_t)dsub) : (s * dsub + u) * ksub + j;
-                t[at] = cb[(s * ksub + j) * dsub + u];
-            }
+    with_int<8, 4>((int)ix.bits, [&](auto b) {
+        for (uint32_t s = 0; s < m; s++)
+            for (uint32_t j = 0; j < ksub; j++)
+                for (uint32_t u = 0; u < dsub; u++)
+                    t[pq_cb_index<decltype(b)::value>(s, u, j, (uint32_t)m, (uint32_t)dsub)] = cb[((size_t)s * ksub + j) * dsub + u];
+    });
     ix.cbT.alloc(ksub * d);
     MSVS_HIP(hipMemcpyAsync(ix.cbT.p, t.data(), t.size() * 4, hipMemcpyHostToDevice, stream));
     finish_codebook(ix, stream); // (synchronises: t is about to go)
@@ -259,7 +256,7 @@ extern "C" size_t msvs_pq_index_bit_size(const msvs_pq_index_t * ix) { return ix
 template <int BITS, int METRIC, int T, int R>
 static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStream_t stream)
 {
-    constexpr auto kernel = BITS == 4 ? &pq4_ivf_scan_kernel<METRIC, T, R> : &pq_ivf_scan_kernel<METRIC, T, R>;
+    constexpr auto kernel = &pq_ivf_scan_kernel<BITS, METRIC, T, R>;
     // more than 64 KiB of dynamic LDS needs the attribute raised once per kernel
     static std::once_flag once;
     std::call_once(once, [] {
@@ -273,16 +270,10 @@ static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStrea
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, stream, a);
 }
 
-/// the scan's LDS image of either form
-static size_t pq_image_bytes(size_t bits, uint32_t T, uint32_t m, uint32_t ld, uint32_t k)
-{
-    return bits == 4 ? pq4_lds_bytes(T, m, ld, k) : pq_lds_bytes(T, m, ld, k);
-}
-
 /// tiles of 1, 2, 4 or 8 queries; 256- or 16-entry tables
 static void launch_pq_ivf_scan(size_t bits, int metric, uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
 {
-    const size_t lds = pq_image_bytes(bits, T, a.m, a.ld, a.k);
+    const size_t lds = pq_lds_bytes(bits, T, a.m, a.ld, a.k);
     with_int<8, 4>((int)bits, [&](auto b) {
         with_int<M_IP, M_L2>(metric, [&](auto m) {
             with_int<1, 2, 4, 8>(T, [&](auto t) {
@@ -304,7 +295,7 @@ static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, 
         [&](size_t n_pairs, size_t k_) {
             const size_t nlist = ix.nlist;
             uint32_t T = n_pairs >= 16 * nlist ? 8 : (n_pairs >= 2 * nlist ? 4 : (n_pairs >= nlist ? 2 : 1));
-            while (T > 1 && pq_image_bytes(ix.bits, T, (uint32_t)ix.m, ix.ld, (uint32_t)k_) > PQ_LDS_BUDGET)
+            while (T > 1 && pq_lds_bytes(ix.bits, T, (uint32_t)ix.m, ix.ld, (uint32_t)k_) > PQ_LDS_BUDGET)
                 T /= 2;
             return T;
         },
@@ -347,33 +338,49 @@ extern "C" int msvs_pq_index_search(const msvs_pq_index_t * ix, const float * qu
 
 // ------------------------------------------------------------------------------------------- export and files
 
-/// rows of a piece of the codes that passes through the host at a time: whole blocks of 64
-static size_t pq_piece_rows(uint32_t mw) { return std::max<size_t>(64, (((size_t)64 << 20) / (mw * 4)) & ~(size_t)63); }
+/// bytes of a row's codes in the data file: they are the stored row's words, little endian, without the pad (8 bits: byte s is code
+/// s; 4 bits: two codes a byte, even s in the low nibble)
+static size_t pq_file_row_bytes(size_t m, size_t bits) { return ceil_div(m * bits, (size_t)8); }
+
+/// The stored rows through the host, a piece of whole blocks of 64 rows at a time: fn(the piece's first row, its rows, its words
+/// (pq_code_word from that row)), on the words that came down from the device (kind: device to host) or, zero before fn, go up after it.
+template <typename F>
+static void pq_each_piece(const msvs_pq_index & ix, hipMemcpyKind kind, hipStream_t stream, F && fn)
+{
+    const uint32_t mw = ix.mw;
+    const size_t piece = std::max<size_t>(64, (((size_t)64 << 20) / (mw * 4)) & ~(size_t)63);
+    std::vector<uint32_t> buf;
+    for (size_t r0 = 0; r0 < ix.n; r0 += piece)
+    {
+        const size_t cnt = std::min(piece, ix.n - r0), words = round_up(cnt, 64) * mw;
+        uint32_t * d_words = reinterpret_cast<uint32_t *>(ix.codes.p) + r0 * mw;
+        buf.assign(words, 0);
+        const bool down = kind == hipMemcpyDeviceToHost;
+        if (!down)
+            fn(r0, cnt, buf.data());
+        MSVS_HIP(hipMemcpyAsync(down ? buf.data() : d_words, down ? d_words : buf.data(), words * 4, kind, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+        if (down)
+            fn(r0, cnt, buf.data());
+    }
+}
 
 /// code s of row r of a piece of stored rows (pq_code_word from the piece's first row)
 static uint8_t pq_code_of(const uint32_t * words, size_t r, size_t s, uint32_t mw, size_t bits)
 {
-    if (bits == 4)
-        return (uint8_t)((words[pq_code_word(r, (uint32_t)(s >> 3), mw)] >> (4 * (s & 7))) & 15u);
-    return (uint8_t)(words[pq_code_word(r, (uint32_t)(s >> 2), mw)] >> (8 * (s & 3)));
+    const size_t cpw = 32 / bits, ksub = (size_t)1 << bits;
+    return (uint8_t)((words[pq_code_word(r, (uint32_t)(s / cpw), mw)] >> (bits * (s % cpw))) & (ksub - 1));
 }
 
 /// the built index's codes in NATURAL order (n x m, one code a byte) and its labels, on the host
 static void pq_fetch(const msvs_pq_index & ix, uint8_t * codes, int64_t * ids, hipStream_t stream)
 {
-    const uint32_t mw = ix.mw;
-    const size_t piece = pq_piece_rows(mw);
-    std::vector<uint32_t> buf;
-    for (size_t r0 = 0; codes && r0 < ix.n; r0 += piece)
-    {
-        const size_t cnt = std::min(piece, ix.n - r0), words = round_up(cnt, 64) * mw;
-        buf.resize(words);
-        MSVS_HIP(hipMemcpyAsync(buf.data(), ix.code_words() + r0 * mw, words * 4, hipMemcpyDeviceToHost, stream));
-        MSVS_HIP(hipStreamSynchronize(stream));
-        for (size_t r = 0; r < cnt; r++)
-            for (size_t s = 0; s < ix.m; s++)
-                codes[(r0 + r) * ix.m + s] = pq_code_of(buf.data(), r, s, mw, ix.bits);
-    }
+    if (codes)
+        pq_each_piece(ix, hipMemcpyDeviceToHost, stream, [&](size_t r0, size_t cnt, const uint32_t * words) {
+            for (size_t r = 0; r < cnt; r++)
+                for (size_t s = 0; s < ix.m; s++)
+                    codes[(r0 + r) * ix.m + s] = pq_code_of(words, r, s, ix.mw, ix.bits);
+        });
     fetch_labels(ix, ids, stream);
 }
 
@@ -401,9 +408,6 @@ struct PqHeader // 64 bytes, little endian
     uint64_t reserved; // 0: 8 bits per code, one code a byte; 4: 4 bits, two codes a byte (even s in the low nibble)
     uint64_t check; // FNV-1a of the bytes before it
 };
-
-/// bytes of a row's codes in the data file
-inline size_t pq_file_row_bytes(size_t m, size_t bits) { return bits == 4 ? (m + 1) / 2 : m; }
 }
 
 extern "C" int msvs_pq_index_serialize_io(const msvs_pq_index_t * ix, const msvs_io_t * io)
@@ -412,18 +416,15 @@ extern "C" int msvs_pq_index_serialize_io(const msvs_pq_index_t * ix, const msvs
         DeviceGuard on_device(ix ? ix->device : -1);
         check_index(ix);
         check_built(*ix, PQ);
-        std::vector<uint8_t> codes(ix->n * ix->m);
+        const size_t fb = pq_file_row_bytes(ix->m, ix->bits);
+        std::vector<uint8_t> codes(ix->n * fb);
         std::vector<int64_t> ids(ix->n);
-        pq_fetch(*ix, codes.data(), ids.data(), thread_stream());
-        if (ix->bits == 4)
-        {
-            // two codes a byte, in place (byte r * fb + i is written after the codes it is made of, at r * m + 2i and beyond, are read)
-            const size_t m = ix->m, fb = pq_file_row_bytes(m, 4);
-            for (size_t r = 0; r < ix->n; r++)
+        pq_each_piece(*ix, hipMemcpyDeviceToHost, thread_stream(), [&](size_t r0, size_t cnt, const uint32_t * words) {
+            for (size_t r = 0; r < cnt; r++)
                 for (size_t i = 0; i < fb; i++)
-                    codes[r * fb + i] = (uint8_t)(codes[r * m + 2 * i] | (2 * i + 1 < m ? codes[r * m + 2 * i + 1] << 4 : 0));
-            codes.resize(ix->n * fb);
-        }
+                    codes[(r0 + r) * fb + i] = (uint8_t)(words[pq_code_word(r, (uint32_t)(i >> 2), ix->mw)] >> (8 * (i & 3)));
+        });
+        fetch_labels(*ix, ids.data(), thread_stream());
         {
             IoStream f(io, "pq_data", 1);
             PqHeader h{};
@@ -488,21 +489,12 @@ extern "C" int msvs_pq_index_load_io(const msvs_io_t * io, msvs_pq_index_t ** ou
         upload_centroids(*ix, cent.data(), ix->nlist, MSVS_MEM_HOST, stream);
         pq_set_codebooks(*ix, cb.data(), stream);
         alloc_lists(*ix, ix->n, 64, true, stream);
-        const uint32_t mw = ix->mw;
-        const size_t piece = pq_piece_rows(mw);
-        std::vector<uint32_t> buf;
-        for (size_t r0 = 0; r0 < ix->n; r0 += piece)
-        {
-            const size_t cnt = std::min(piece, ix->n - r0), words = round_up(cnt, 64) * mw;
-            buf.assign(words, 0);
-            // a file row's bytes are the stored row's words, little endian, in either form (8-bit: byte s; 4-bit: two codes a byte)
-            const size_t fb = pq_file_row_bytes(ix->m, ix->bits);
+        const size_t fb = pq_file_row_bytes(ix->m, ix->bits);
+        pq_each_piece(*ix, hipMemcpyHostToDevice, stream, [&](size_t r0, size_t cnt, uint32_t * words) {
             for (size_t r = 0; r < cnt; r++)
                 for (size_t i = 0; i < fb; i++)
-                    buf[pq_code_word(r, (uint32_t)(i >> 2), mw)] |= (uint32_t)codes[(r0 + r) * fb + i] << (8 * (i & 3));
-            MSVS_HIP(hipMemcpyAsync(ix->code_words() + r0 * mw, buf.data(), words * 4, hipMemcpyHostToDevice, stream));
-            MSVS_HIP(hipStreamSynchronize(stream));
-        }
+                    words[pq_code_word(r, (uint32_t)(i >> 2), ix->mw)] |= (uint32_t)codes[(r0 + r) * fb + i] << (8 * (i & 3));
+        });
         finish_load(*ix, ids, stream);
         *out = ix.release();
     });

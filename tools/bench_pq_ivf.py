@@ -12,7 +12,7 @@ JSON file (default profiles/pq_ivf.json).
 
 An entry of --ms is M for an 8-bit index or Mx4 for a 4-bit one (bit_size=4), named pqM / pqMx4 in the output: --ms 96,192x4,96x4
 puts 8-bit m = 96 beside its equal-bytes 4-bit partner m = 192 and the half-size m = 96 (profiles/pq4_ivf.json).  The counter run
-then takes the first 8-bit and the first 4-bit entry, whose scan kernels have names of their own.  --no-competitors leaves the IVFSQ
+then takes the first 8-bit and the first 4-bit entry, whose scan kernels differ in their first template argument.  --no-competitors leaves the IVFSQ
 and IVFFLAT indexes out.
 
     python -m tools.bench_pq_ivf [--rows N] [--dim D] [--nlist L] [--ms 96,48] [--batches 64,1024,4096] [--nprobe P] [--ks 10,100]
@@ -22,6 +22,7 @@ import argparse
 import glob
 import json
 import os
+import re
 import sqlite3
 import subprocess
 import sys
@@ -35,6 +36,8 @@ sys.path.insert(0, ROOT)
 import myscaledb_amd.capi as capi  # noqa: E402
 
 F = np.float32
+# the profiler names the scan "void msvs::pq_ivf_scan_kernel<8, 0, 8, 1>(msvs::PqIvfParams)"; a mangled name (...ILi8E...) is read too
+SCAN_BITS = re.compile(r"pq_ivf_scan_kernel(?:<|ILi)(\d+)")
 FAMILIES = ("pq_ivf_scan", "sq_ivf_scan", "ivf_scan", "ivf_plan", "flat_scan", "merge", "coarse_pass")
 
 
@@ -188,11 +191,14 @@ def counters(a, limit):
         cols = [r[1] for r in c.execute("pragma table_info(counters_collection)")]
         name_col = "kernel_name" if "kernel_name" in cols else "name"
         out = {"shape": shape}
-        for kernel in ("pq_ivf_scan_kernel", "pq4_ivf_scan_kernel"):  # the 8-bit and the 4-bit scan
+        # one scan kernel, told apart by its first template argument (the bits of a code); the keys are the names the two scans had
+        # when they were two kernels, so that earlier profiles stay comparable
+        for kernel, bits in (("pq_ivf_scan_kernel", 8), ("pq4_ivf_scan_kernel", 4)):
             sums = {}
             for nm, cn, calls, total in c.execute("select %s, counter_name, count(*), sum(value) from counters_collection group by %s, counter_name"
                                                   % (name_col, name_col)):
-                if kernel in nm:
+                got = SCAN_BITS.search(nm)
+                if got and int(got.group(1)) == bits:
                     sums[cn] = sums.get(cn, 0.0) + float(total)
             if not sums:
                 continue
