@@ -299,11 +299,24 @@ class _CodedIndex:
         fn.argtypes = [C.c_void_p]
         return fn(self._h)
 
-    def train(self, x):
+    @staticmethod
+    def _dev(a):
+        """a raw device address (int; 0 / None: null) as a pointer argument"""
+        return C.c_void_p(int(a)) if a else None
+
+    def train(self, x, n=None, mem=MEM_HOST):
+        """mem=MEM_DEVICE: `x` is a raw device address (int) of n dense rows."""
+        if mem == MEM_DEVICE:
+            _check(self._fn("train")(self._h, self._dev(x), C.c_size_t(n), mem))
+            return
         x = _f32(x).reshape(-1, self.dim)
         _check(self._fn("train")(self._h, _p(x, C.c_float), C.c_size_t(x.shape[0]), MEM_HOST))
 
-    def add(self, x, ids=None):
+    def add(self, x, ids=None, n=None, mem=MEM_HOST):
+        """mem=MEM_DEVICE: `x` and `ids` (None: the staging positions) are raw device addresses (ints) of n rows / labels."""
+        if mem == MEM_DEVICE:
+            _check(self._fn("add")(self._h, self._dev(x), self._dev(ids), C.c_size_t(n), mem))
+            return
         x = _f32(x).reshape(-1, self.dim)
         if ids is not None:
             ids = np.ascontiguousarray(ids, np.int64)
@@ -393,7 +406,11 @@ class SqIndex(_CodedIndex):
         else:
             _check(lib().msvs_sq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
 
-    def set_codebook(self, centroids, vmin, vmax):
+    def set_codebook(self, centroids, vmin, vmax, nlist=None, mem=MEM_HOST):
+        """mem=MEM_DEVICE: centroids, vmin and vmax are raw device addresses (ints); nlist is the number of centroid rows."""
+        if mem == MEM_DEVICE:
+            _check(lib().msvs_sq_index_set_codebook(self._h, self._dev(centroids), C.c_size_t(nlist), self._dev(vmin), self._dev(vmax), mem))
+            return
         c = _f32(centroids).reshape(-1, self.dim)
         lo, hi = _f32(vmin).reshape(self.dim), _f32(vmax).reshape(self.dim)
         _check(lib().msvs_sq_index_set_codebook(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(lo, C.c_float), _p(hi, C.c_float),
@@ -437,8 +454,11 @@ class PqIndex(_CodedIndex):
             self.m = int(dict(kv.split("=", 1) for kv in params.replace(" ", "").split(",") if "=" in kv)["m"])
         self.bits = self._size("bit_size")
 
-    def set_codebook(self, centroids, codebooks):
-        """codebooks: [m, 1 << bits, dim / m]"""
+    def set_codebook(self, centroids, codebooks, nlist=None, mem=MEM_HOST):
+        """codebooks: [m, 1 << bits, dim / m]; mem=MEM_DEVICE: both are raw device addresses (ints), nlist the number of centroid rows."""
+        if mem == MEM_DEVICE:
+            _check(lib().msvs_pq_index_set_codebook(self._h, self._dev(centroids), C.c_size_t(nlist), self._dev(codebooks), mem))
+            return
         c = _f32(centroids).reshape(-1, self.dim)
         cb = _f32(codebooks).reshape(self.m, 1 << self.bits, self.dim // self.m)
         _check(lib().msvs_pq_index_set_codebook(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(cb, C.c_float), MEM_HOST))
