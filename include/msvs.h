@@ -238,7 +238,27 @@ MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t **
  * openers (a built index only); load validates sizes, offsets, labels, the codebooks and a checksum of each header: a corrupt or
  * truncated file is MSVS_ERR_IO.  The header's reserved word is 0 for an 8-bit index and 4 for a 4-bit one, whose codes are
  * n * ceil(m / 2) bytes, code s in the low nibble of byte s / 2 for even s, else the high one; any other reserved word, an m beyond
- * the form's limit and a non-zero pad nibble (odd m) are MSVS_ERR_IO too (a library without the 4-bit form refuses such a file). */
+ * the form's limit and a non-zero pad nibble (odd m) are MSVS_ERR_IO too (a library without the 4-bit form refuses such a file).
+ *
+ * query_tables=1 (create; 0 is the default, anything else MSVS_ERR_INVALID_ARGUMENT; both bit sizes, all three metrics): look-up tables
+ * that depend on the query alone.  Codebooks, training, assignment and the codes are exactly what they are without it -- a row's
+ * codes are the same bytes in both forms; only the distance of a row is another sum, and an L2 index keeps one f32 more per row.
+ * With q the query (normalised first for cosine), c = c_l, fl as above, no fma:
+ *   - query table (no list in it): P[s][j] = the sequential sum from +0, t ascending, of fl(q[s * dsub + t] * cb[s][j][t]);
+ *   - row term (L2 indexes only, per stored row of list l): g(s) = the sequential sum from +0, t ascending, of
+ *     fl(cb_t * fl(fl(c_t + c_t) + cb_t)) with cb = cb[s][code[s]] and c_t = c_l[s * dsub + t]; w = +0, then w = fl(w + g(s)) for
+ *     s = 0 .. m - 1.  The library computes w at build and at load; no file holds it;
+ *   - pair term: b(q, l) = the canonical distance (L2) or inner product (IP, cosine) of q to c_l, the value the lists are ranked by;
+ *   - row score: acc = +0, then acc = fl(acc + P[s][code[s]]), s ascending; L2: dis = fl(fl(b + w) - fl(2 * acc)); IP and cosine:
+ *     dis = fl(b + acc).
+ * Admission, order, padding, cosine's fl(1 - ip), the filter, the probes and the limits on k and nprobe are those above.  It equals
+ * |q - (c + cb)|^2 (q . (c + cb)) up to rounding, with another summation order than the default form: results of the two forms differ
+ * in their last bits.  query_tables: 1 for such an index, else 0 (0 for NULL).  export_row_terms: w of the n rows in list-major order
+ * (export's); MSVS_ERR_INVALID_ARGUMENT for an index that keeps none (query_tables=0, IP, cosine), MSVS_ERR_NOT_READY before build.
+ * memory_usage: the bound above + 4 * n for an L2 index of this form only.  Files: bit 8 of the header's reserved word is set (0x100
+ * for 8-bit codes, 0x104 for 4-bit), every other byte of pq_data but the check word, and all of pq_ids, is the file of the same index
+ * without the form; every other reserved word stays MSVS_ERR_IO (a library without the form refuses such a file).  Without
+ * query_tables, or with query_tables=0, every result, every file byte and every error is what it was. */
 typedef struct msvs_pq_index msvs_pq_index_t;
 MSVS_API int msvs_pq_index_create(int metric, size_t dim, const char * params, msvs_pq_index_t ** out);
 MSVS_API void msvs_pq_index_free(msvs_pq_index_t * index);
@@ -252,6 +272,8 @@ MSVS_API size_t msvs_pq_index_num_data(const msvs_pq_index_t * index);
 MSVS_API size_t msvs_pq_index_num_lists(const msvs_pq_index_t * index);
 MSVS_API size_t msvs_pq_index_memory_usage(const msvs_pq_index_t * index);
 MSVS_API size_t msvs_pq_index_bit_size(const msvs_pq_index_t * index);
+MSVS_API int msvs_pq_index_query_tables(const msvs_pq_index_t * index);
+MSVS_API int msvs_pq_index_export_row_terms(const msvs_pq_index_t * index, float * w);
 MSVS_API int msvs_pq_index_search(const msvs_pq_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
                                   const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
 MSVS_API int msvs_pq_index_search_device(const msvs_pq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t nprobe,

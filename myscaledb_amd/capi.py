@@ -45,7 +45,7 @@ SYMBOLS = [
     "msvs_sq_index_search", "msvs_sq_index_search_device", "msvs_sq_index_export", "msvs_sq_index_serialize_io", "msvs_sq_index_load_io",
     "msvs_pq_index_create", "msvs_pq_index_free", "msvs_pq_index_train", "msvs_pq_index_set_codebook", "msvs_pq_index_add",
     "msvs_pq_index_build", "msvs_pq_index_ready", "msvs_pq_index_num_data", "msvs_pq_index_num_lists", "msvs_pq_index_memory_usage",
-    "msvs_pq_index_bit_size",
+    "msvs_pq_index_bit_size", "msvs_pq_index_query_tables", "msvs_pq_index_export_row_terms",
     "msvs_pq_index_search", "msvs_pq_index_search_device", "msvs_pq_index_export", "msvs_pq_index_serialize_io", "msvs_pq_index_load_io",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
@@ -453,6 +453,15 @@ class PqIndex(_CodedIndex):
             _check(lib().msvs_pq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
             self.m = int(dict(kv.split("=", 1) for kv in params.replace(" ", "").split(",") if "=" in kv)["m"])
         self.bits = self._size("bit_size")
+        fn = lib().msvs_pq_index_query_tables
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        self.query_tables = int(fn(self._h))  # 1: tables that depend on the query alone (create's query_tables=1, or the file's form)
+
+    def export_row_terms(self):
+        """-> w [n] f32 in list-major order (export's): the row terms of an L2 index with query_tables=1; MsvsError for any other."""
+        w = np.empty(self.num_data, np.float32)
+        _check(lib().msvs_pq_index_export_row_terms(self._h, _p(w, C.c_float)))
+        return w
 
     def set_codebook(self, centroids, codebooks, nlist=None, mem=MEM_HOST):
         """codebooks: [m, 1 << bits, dim / m]; mem=MEM_DEVICE: both are raw device addresses (ints), nlist the number of centroid rows."""
@@ -479,11 +488,11 @@ class PqIndex(_CodedIndex):
         return cent, cb, off, codes, labels
 
     @classmethod
-    def load_io(cls, store, metric=None, dim=None, m=None, bits=None):
-        """metric / dim / m come from the file (PqHeader: magic[8], u32 version, i32 metric, u64 dim, u64 m, ...), bits from the
-        loaded index; where given, they must agree with it (ValueError otherwise)."""
+    def load_io(cls, store, metric=None, dim=None, m=None, bits=None, query_tables=None):
+        """metric / dim / m come from the file (PqHeader: magic[8], u32 version, i32 metric, u64 dim, u64 m, ...), bits and
+        query_tables from the loaded index; where given, they must agree with it (ValueError otherwise)."""
         h, (f_metric, f_dim, f_m) = cls._load(store, "pq_data", "<iQQ")
-        return cls(f_metric, f_dim, _handle=h, _m=f_m)._agree("IVFPQ", metric=metric, dim=dim, m=m, bits=bits)
+        return cls(f_metric, f_dim, _handle=h, _m=f_m)._agree("IVFPQ", metric=metric, dim=dim, m=m, bits=bits, query_tables=query_tables)
 
 
 def normalize(x):

@@ -345,6 +345,17 @@ struct ScanRound
     size_t nbits, k, P, seg_max;
     uint32_t rpb;
     int metric; // M_L2 / M_IP
+    // what an index asked for through RoundExtra (null otherwise)
+    size_t nq = 0;                   // queries of the round
+    const float * probe_dis = nullptr; // [query][probe] the canonical distance / inner product to every probe's centroid
+    void * extra = nullptr;          // nq * RoundExtra::bytes_per_q bytes of the search's arena, 256-byte aligned
+};
+
+/// What an index wants of a round beside the common buffers: scratch bytes per query of its own, the coarse step's distances.
+struct RoundExtra
+{
+    size_t bytes_per_q = 0;
+    bool probe_dis = false;
 };
 
 /// the fields every grouped scan's parameter block has
@@ -369,10 +380,12 @@ inline void fill_scan_params(Params & a, const CodedIvf & ix, const ScanRound & 
 /// Everything on the device, enqueued on `stream`: queries padded (and normalised for cosine) into scratch, the canonical coarse
 /// quantiser over the centroids, the plan, the list scan over the codes, the per-query merge.  Row segments are whole steps of
 /// row_step rows (rpb_knob: the index's option); pick_T(n_pairs, k) is the round's query tile, scan(T, grid, round) its launch.
-template <class PickT, class Scan>
+/// extra: what the index wants beside (RoundExtra); prepare(round) enqueues its per-query work of a round, after the queries are
+/// padded and normalised and before the plan (its round has no plan-dependent field to read: T, grid and the scan come later).
+template <class PickT, class Prepare, class Scan>
 inline void search_device(const CodedIvf & ix, const char * name, const char * prof_name, const float * d_queries, size_t nq, size_t k,
                           size_t nprobe, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream,
-                          size_t row_step, double rpb_knob, PickT pick_T, Scan scan)
+                          size_t row_step, double rpb_knob, RoundExtra extra, PickT pick_T, Prepare prepare, Scan scan)
 {
     check_k(k);
     check_built(ix, name);
@@ -388,15 +401,18 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
     const uint32_t ld = ix.ld;
     const int m = scan_metric(ix.metric);
     // per query of a round: its padded row, its probes and pairs
-    const SegmentPlan sp = plan_segments(ix.max_list_len, rpb_knob, row_step, P, k, (size_t)ld * 4 + P * 8 + 64, nq);
+    const SegmentPlan sp = plan_segments(ix.max_list_len, rpb_knob, row_step, P, k,
+                                         (size_t)ld * 4 + P * 8 + 64 + extra.bytes_per_q + (extra.probe_dis ? P * 4 : 0), nq);
     const uint32_t rpb = sp.rpb;
     const size_t seg_max = sp.seg_max, per_q = sp.per_q, chunk = sp.chunk;
     const size_t last = nq % chunk;
     const size_t coarse = std::max(flat_scratch_bytes(nlist, chunk, (uint32_t)P, ld), last ? flat_scratch_bytes(nlist, last, (uint32_t)P, ld) : 0);
     Scratch & scr = scratch_for(stream);
-    scr.reserve(chunk * per_q + coarse + (nlist + 1) * 16 + 16 * 256, stream);
+    scr.reserve(chunk * per_q + coarse + (nlist + 1) * 16 + 18 * 256, stream);
     float * dq = scr.take<float>(chunk * ld);
     int32_t * probes = scr.take<int32_t>(chunk * P);
+    float * probe_dis = extra.probe_dis ? scr.take<float>(chunk * P) : nullptr;
+    void * extra_buf = extra.bytes_per_q ? scr.take<unsigned char>(chunk * extra.bytes_per_q) : nullptr;
     const GroupedPlan plan(scr, nlist, chunk * P);
     uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * k);
     const size_t mark = scr.used;
@@ -411,7 +427,11 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
         MergeParams co{};
         co.mode = 1;
         co.out_probes = probes;
+        co.out_probe_dis = probe_dis;
         flat_search_device(scr, m, ix.centroids.p, nullptr, nlist, ld, dq, nqc, (uint32_t)P, nullptr, 0, co, stream);
+        const ScanRound round{dq, probes, plan, partial, d_alive, nbits, k, P, seg_max, rpb, m, nqc, probe_dis, extra_buf};
+        prepare(round);
+        MSVS_HIP(hipGetLastError());
         // 2. (query, list) pairs grouped by list -> (list, query tile, row segment) items
         const size_t n_pairs = nqc * P;
         const uint32_t T = pick_T(n_pairs, k);
@@ -420,7 +440,7 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
         {
             ProfileScope prof(prof_name, stream);
             const uint32_t grid = (uint32_t)std::min<size_t>(2048, n_pairs * seg_max);
-            scan(T, grid, ScanRound{dq, probes, plan, partial, d_alive, nbits, k, P, seg_max, rpb, m});
+            scan(T, grid, round);
             MSVS_HIP(hipGetLastError());
         }
         // 4. per-query top-k over the valid segments of its probed lists
@@ -437,6 +457,16 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
         im.cosine = ix.metric == MSVS_METRIC_COSINE;
         launch_ivf_merge(m, im, (uint32_t)nqc, stream);
     }
+}
+
+/// ... for an index that wants nothing beside
+template <class PickT, class Scan>
+inline void search_device(const CodedIvf & ix, const char * name, const char * prof_name, const float * d_queries, size_t nq, size_t k,
+                          size_t nprobe, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream,
+                          size_t row_step, double rpb_knob, PickT pick_T, Scan scan)
+{
+    search_device(ix, name, prof_name, d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, row_step, rpb_knob, RoundExtra{}, pick_T,
+                  [](const ScanRound &) {}, scan);
 }
 
 /// The host-pointer entry: queries and filter staged to the device, dev(d_queries, nprobe, d_alive, d_ids, d_dis, stream) is the

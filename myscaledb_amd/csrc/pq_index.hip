@@ -1,8 +1,9 @@
 // pq_index.hip -- the IVFPQ index (include/msvs.h: msvs_pq_index_*): coarse centroids + m sub-quantisers of 256 (bit_size 8) or 16
 // (bit_size 4) entries over the residuals; codes, lists and labels are all the index keeps.  Semantics and layout: pq_ivf_kernels.hpp, DESIGN.md 4.12.
 // Here: the geometry, the sub-codebooks (finiteness, residual sampling, training), the scan's shapes, LDS attribute and dispatch,
-// the data file and the stored order of the code words.  Everything the index has in common with IVFSQ -- staging, add, build, the
-// search skeleton, labels, the id file -- is coded_ivf.hpp, which also lists what is reused as it is.
+// the data file and the stored order of the code words, the form (query_tables) with its row terms and per-query tables.
+// Everything the index has in common with IVFSQ -- staging, add, build, the search skeleton, labels, the id file -- is
+// coded_ivf.hpp, which also lists what is reused as it is.
 #include <cmath>
 #include <mutex>
 
@@ -37,8 +38,30 @@ struct msvs_pq_index : CodedIvf
     uint32_t mw = 0;         // 32-bit words of a stored row: ceil(m / 4), 4-bit: ceil(m / 8)
     std::vector<float> h_cb; // [m][ksub][dsub]
     DevBuf<float> cbT;       // the same in the order of pq_cb_index
+    int form = 0;            // query_tables: 1 = tables that depend on the query alone (pq_ivf_kernels.hpp)
+    DevBuf<float> row_w;     // form 1, L2: the row term of every list-major row (max(n, 1) floats), else empty
+    bool keeps_row_terms() const { return form == 1 && metric == MSVS_METRIC_L2; }
     const uint32_t * code_words() const { return reinterpret_cast<const uint32_t *>(codes.p); }
 };
+
+/// the row terms of a built or loaded index that keeps them: allocated and computed from the stored codes (build and load_io both
+/// end here, so the two cannot drift apart); synchronises
+static void pq_compute_row_terms(msvs_pq_index & ix, hipStream_t stream)
+{
+    if (!ix.keeps_row_terms())
+        return;
+    ix.row_w.alloc(std::max<size_t>(ix.n, 1));
+    MSVS_HIP(hipMemsetAsync(ix.row_w.p, 0, ix.row_w.bytes(), stream));
+    if (ix.n)
+        with_int<8, 4>((int)ix.bits, [&](auto b) {
+            hipLaunchKernelGGL((pq_row_terms_kernel<decltype(b)::value>), dim3((unsigned)ceil_div(ix.n, (size_t)256)), dim3(256), 0, stream,
+                               ix.code_words(), ix.list_off.p, ix.centroids.p, ix.cbT.p, ix.n, (uint32_t)ix.nlist, ix.ld, (uint32_t)ix.m,
+                               (uint32_t)ix.dsub, ix.mw, ix.row_w.p);
+        });
+    MSVS_HIP(hipGetLastError());
+    MSVS_HIP(hipStreamSynchronize(stream));
+    MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
+}
 
 static void pq_set_geometry(msvs_pq_index & ix, int metric, size_t dim, size_t m, size_t bits)
 {
@@ -107,6 +130,9 @@ extern "C" int msvs_pq_index_create(int metric, size_t dim, const char * params,
         const long m = param_int(p, "m", 0), bits = param_int(p, "bit_size", 8);
         if (bits != 4 && bits != 8)
             fail(MSVS_ERR_INVALID_ARGUMENT, "the IVFPQ index has 4 or 8 bits per sub-quantiser (bit_size %ld)", bits);
+        const long form = param_int(p, "query_tables", 0);
+        if (form != 0 && form != 1)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "query_tables is 0 or 1 (%ld)", form);
         if (m < 1 || !pq_fits(dim, (size_t)m, (size_t)bits))
             fail(MSVS_ERR_INVALID_ARGUMENT,
                  "the IVFPQ index needs 1 <= m <= 128 (256 at bit_size=4) dividing 1 <= dim <= 8192 and tables of m KiB (m / 16 KiB) + 8 * dim + "
@@ -114,6 +140,7 @@ extern "C" int msvs_pq_index_create(int metric, size_t dim, const char * params,
                  dim, m, bits);
         std::unique_ptr<msvs_pq_index> ix(new msvs_pq_index);
         pq_set_geometry(*ix, metric, dim, (size_t)m, (size_t)bits);
+        ix->form = (int)form;
         ix->params = params ? params : "";
         MSVS_HIP(hipGetDevice(&ix->device));
         *out = ix.release();
@@ -192,7 +219,7 @@ extern "C" int msvs_pq_index_train(msvs_pq_index_t * ix, const float * x, size_t
         // every sub-codebook: the same trainer over the sub-space's columns, L2, ksub centroids, the caller's iterations and seed
         std::string sub_params;
         for (const auto & kv : parse_params(ix->params.c_str()))
-            if (kv.first != "ncentroids" && kv.first != "m" && kv.first != "bit_size")
+            if (kv.first != "ncentroids" && kv.first != "m" && kv.first != "bit_size" && kv.first != "query_tables")
                 sub_params += kv.first + "=" + kv.second + ",";
         sub_params += "ncentroids=" + std::to_string(ksub);
         DevBuf<float> d_sub(cap * dsub);
@@ -238,25 +265,35 @@ extern "C" int msvs_pq_index_add(msvs_pq_index_t * ix, const float * x, const in
 extern "C" int msvs_pq_index_build(msvs_pq_index_t * ix)
 {
     return guarded([&] {
+        const bool was_ready = ix && ix->ready;
         build_lists(ix, PQ, 64, true, [&](const uint8_t * src, uint8_t * dst, const uint32_t * d_pos, size_t cnt, hipStream_t stream) {
             hipLaunchKernelGGL(pq_scatter_rows_kernel, dim3((unsigned)ceil_div(cnt * ix->mw, (size_t)256)), dim3(256), 0, stream,
                                reinterpret_cast<const uint32_t *>(src), reinterpret_cast<uint32_t *>(dst), d_pos, cnt, ix->mw);
         });
+        if (!was_ready)
+        {
+            DeviceGuard on_device(ix->device);
+            pq_compute_row_terms(*ix, thread_stream());
+        }
     });
 }
 
 extern "C" int msvs_pq_index_ready(const msvs_pq_index_t * ix) { return ix && ix->ready ? 1 : 0; }
 extern "C" size_t msvs_pq_index_num_data(const msvs_pq_index_t * ix) { return ix ? (ix->ready ? ix->n : ix->staged) : 0; }
 extern "C" size_t msvs_pq_index_num_lists(const msvs_pq_index_t * ix) { return ix ? ix->nlist : 0; }
-extern "C" size_t msvs_pq_index_memory_usage(const msvs_pq_index_t * ix) { return ix ? coded_bytes(*ix) + ix->cbT.bytes() : 0; }
+extern "C" size_t msvs_pq_index_memory_usage(const msvs_pq_index_t * ix)
+{
+    return ix ? coded_bytes(*ix) + ix->cbT.bytes() + ix->row_w.bytes() : 0;
+}
 extern "C" size_t msvs_pq_index_bit_size(const msvs_pq_index_t * ix) { return ix ? ix->bits : 0; }
+extern "C" int msvs_pq_index_query_tables(const msvs_pq_index_t * ix) { return ix ? ix->form : 0; }
 
 // ------------------------------------------------------------------------------------------- search
 
-template <int BITS, int METRIC, int T, int R>
+template <int BITS, int METRIC, int T, int R, int FORM>
 static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStream_t stream)
 {
-    constexpr auto kernel = &pq_ivf_scan_kernel<BITS, METRIC, T, R>;
+    constexpr auto kernel = &pq_ivf_scan_kernel<BITS, METRIC, T, R, FORM>;
     // more than 64 KiB of dynamic LDS needs the attribute raised once per kernel
     static std::once_flag once;
     std::call_once(once, [] {
@@ -270,34 +307,60 @@ static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStrea
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, stream, a);
 }
 
-/// tiles of 1, 2, 4 or 8 queries; 256- or 16-entry tables
-static void launch_pq_ivf_scan(size_t bits, int metric, uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
+/// tiles of 1, 2, 4 or 8 queries; 256- or 16-entry tables; built per (query, list) pair or copied from the query's (form)
+static void launch_pq_ivf_scan(size_t bits, int form, int metric, uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
 {
-    const size_t lds = pq_lds_bytes(bits, T, a.m, a.ld, a.k);
-    with_int<8, 4>((int)bits, [&](auto b) {
-        with_int<M_IP, M_L2>(metric, [&](auto m) {
-            with_int<1, 2, 4, 8>(T, [&](auto t) {
-                with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
-                    pq_launch<decltype(b)::value, decltype(m)::value, decltype(t)::value, decltype(r)::value>(grid, lds, a, stream);
+    const size_t lds = pq_lds_bytes(bits, T, a.m, a.ld, a.k, form);
+    with_int<1, 0>(form, [&](auto f) {
+        with_int<8, 4>((int)bits, [&](auto b) {
+            with_int<M_IP, M_L2>(metric, [&](auto m) {
+                with_int<1, 2, 4, 8>(T, [&](auto t) {
+                    with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                        pq_launch<decltype(b)::value, decltype(m)::value, decltype(t)::value, decltype(r)::value, decltype(f)::value>(grid, lds, a,
+                                                                                                                                      stream);
+                    });
                 });
             });
         });
     });
 }
 
+/// the tables of the nq padded queries of a round (form 1): P[query][s * ksub + j]
+static void launch_pq_query_tables(const msvs_pq_index & ix, const float * dq, size_t nq, float * P, hipStream_t stream)
+{
+    constexpr int TQ = 8;
+    ProfileScope prof("pq_query_tables", stream);
+    with_int<8, 4>((int)ix.bits, [&](auto b) {
+        constexpr int BITS = decltype(b)::value;
+        const dim3 grid((unsigned)ceil_div(nq, (size_t)TQ), (unsigned)ceil_div(ix.m, (size_t)(BLOCK >> BITS)));
+        hipLaunchKernelGGL((pq_query_table_kernel<BITS, TQ>), grid, dim3(BLOCK), 0, stream, dq, ix.cbT.p, (uint32_t)nq, ix.ld, (uint32_t)ix.m,
+                           (uint32_t)ix.dsub, P);
+    });
+}
+
 /// search_device of coded_ivf.hpp with this index's shapes: row segments of whole 256-row steps (a segment rebuilds its tile's
-/// tables); the tile by the pairs per list, 1 to 8 queries, halved until its tables fit
+/// tables, or copies them in form 1); the tile by the pairs per list, 1 to 8 queries, halved until its tables fit.  Form 1 takes the
+/// probes' distances from the coarse step and 4 * ksub * m bytes per query of the round for the query tables, from the same arena
 static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, size_t nq, size_t k, size_t nprobe, const uint64_t * d_alive,
                              size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
 {
+    if (ix.ready && ix.keeps_row_terms() && !ix.row_w.p)
+        fail(MSVS_ERR_NOT_READY, "the IVFPQ index has no row terms: its build did not finish");
+    RoundExtra extra;
+    extra.bytes_per_q = ix.form ? ix.m * ix.ksub * 4 : 0;
+    extra.probe_dis = ix.form != 0;
     search_device(
-        ix, PQ, "pq_ivf_scan", d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, BLOCK, options().pq_ivf_rpb,
+        ix, PQ, "pq_ivf_scan", d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, BLOCK, options().pq_ivf_rpb, extra,
         [&](size_t n_pairs, size_t k_) {
             const size_t nlist = ix.nlist;
             uint32_t T = n_pairs >= 16 * nlist ? 8 : (n_pairs >= 2 * nlist ? 4 : (n_pairs >= nlist ? 2 : 1));
-            while (T > 1 && pq_lds_bytes(ix.bits, T, (uint32_t)ix.m, ix.ld, (uint32_t)k_) > PQ_LDS_BUDGET)
+            while (T > 1 && pq_lds_bytes(ix.bits, T, (uint32_t)ix.m, ix.ld, (uint32_t)k_, ix.form) > PQ_LDS_BUDGET)
                 T /= 2;
             return T;
+        },
+        [&](const ScanRound & r) {
+            if (ix.form)
+                launch_pq_query_tables(ix, r.dq, r.nq, static_cast<float *>(r.extra), stream);
         },
         [&](uint32_t T, uint32_t grid, const ScanRound & r) {
             PqIvfParams a{};
@@ -312,7 +375,10 @@ static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, 
             a.dsub = (uint32_t)ix.dsub;
             a.mw = ix.mw;
             a.tables_only = options().pq_ivf_tables_only != 0;
-            launch_pq_ivf_scan(ix.bits, r.metric, T, grid, a, stream);
+            a.qtab = static_cast<const float *>(r.extra);
+            a.pair_b = r.probe_dis;
+            a.row_w = ix.row_w.p;
+            launch_pq_ivf_scan(ix.bits, ix.form, r.metric, T, grid, a, stream);
         });
 }
 
@@ -397,6 +463,26 @@ extern "C" int msvs_pq_index_export(const msvs_pq_index_t * ix, float * centroid
     });
 }
 
+extern "C" int msvs_pq_index_export_row_terms(const msvs_pq_index_t * ix, float * w)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_index(ix);
+        if (!ix->keeps_row_terms())
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the IVFPQ index keeps no row terms (query_tables=1 and L2 only)");
+        check_built(*ix, PQ);
+        if (!w)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
+        if (!ix->n)
+            return;
+        if (!ix->row_w.p)
+            fail(MSVS_ERR_NOT_READY, "the IVFPQ index has no row terms: its build did not finish");
+        hipStream_t stream = thread_stream();
+        MSVS_HIP(hipMemcpyAsync(w, ix->row_w.p, ix->n * 4, hipMemcpyDeviceToHost, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+    });
+}
+
 namespace
 {
 struct PqHeader // 64 bytes, little endian
@@ -405,7 +491,7 @@ struct PqHeader // 64 bytes, little endian
     uint32_t version; // 1
     int32_t metric;
     uint64_t dim, m, nlist, n;
-    uint64_t reserved; // 0: 8 bits per code, one code a byte; 4: 4 bits, two codes a byte (even s in the low nibble)
+    uint64_t reserved; // 0: 8 bits per code, one code a byte; 4: 4 bits, two codes a byte (even s in the low nibble); + 0x100: query_tables=1
     uint64_t check; // FNV-1a of the bytes before it
 };
 }
@@ -435,7 +521,7 @@ extern "C" int msvs_pq_index_serialize_io(const msvs_pq_index_t * ix, const msvs
             h.m = ix->m;
             h.nlist = ix->nlist;
             h.n = ix->n;
-            h.reserved = ix->bits == 4 ? 4 : 0;
+            h.reserved = (ix->bits == 4 ? 4 : 0) | (ix->form ? 0x100 : 0);
             h.check = fnv1a(&h, offsetof(PqHeader, check));
             f.write(&h, sizeof(h));
             f.write(ix->h_cent.data(), ix->h_cent.size() * 4);
@@ -463,9 +549,10 @@ extern "C" int msvs_pq_index_load_io(const msvs_io_t * io, msvs_pq_index_t ** ou
             PqHeader h{};
             f.read(&h, sizeof(h));
             if (memcmp(h.magic, "MSVSPQ01", 8) != 0 || h.version != 1 || h.check != fnv1a(&h, offsetof(PqHeader, check))
-                || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || (h.reserved != 0 && h.reserved != 4))
+                || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || ((h.reserved & ~(uint64_t)0x100) != 0 && (h.reserved & ~(uint64_t)0x100) != 4))
                 fail(MSVS_ERR_IO, "corrupt msvs IVFPQ index header");
-            const size_t bits = h.reserved == 4 ? 4 : 8;
+            const size_t bits = (h.reserved & 4) ? 4 : 8;
+            ix->form = (h.reserved & 0x100) ? 1 : 0;
             if (h.m > pq_max_m(bits) || !pq_fits((size_t)h.dim, (size_t)h.m, bits))
                 fail(MSVS_ERR_IO, "corrupt msvs IVFPQ index header");
             pq_set_geometry(*ix, h.metric, (size_t)h.dim, (size_t)h.m, bits);
@@ -496,6 +583,7 @@ extern "C" int msvs_pq_index_load_io(const msvs_io_t * io, msvs_pq_index_t ** ou
                     words[pq_code_word(r, (uint32_t)(i >> 2), ix->mw)] |= (uint32_t)codes[(r0 + r) * fb + i] << (8 * (i & 3));
         });
         finish_load(*ix, ids, stream);
+        pq_compute_row_terms(*ix, stream);
         *out = ix.release();
     });
 }

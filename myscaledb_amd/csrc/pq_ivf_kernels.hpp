@@ -16,6 +16,9 @@
 // The scan is ONE kernel for both widths (pq_ivf_scan_kernel<BITS, ...>): the tables are 4 * ksub * m bytes per query, so at 4 bits
 // tiles of up to 8 queries fit the LDS at every m <= 256.  The encoders are two algorithms (a block per row at 256 entries, 16 lanes
 // per row at 16) over the same sub-score and lane-minimum helpers.
+//
+// query_tables=1 is a second definition of a row's distance over the same codebooks and codes, with tables that depend on the query
+// alone (below, "the query-table form"): its two kernels, and the scan's FORM = 1.
 #pragma once
 
 #include "scan_kernels.hpp"
@@ -185,6 +188,87 @@ static __global__ void pq_scatter_rows_kernel(const uint32_t * src, uint32_t * d
     dst[pq_code_word(pos[r], (uint32_t)(i - r * mw), mw)] = src[i];
 }
 
+// ------------------------------------------------------------------------------------------ the query-table form (query_tables=1)
+//
+//   query table : P[s][j] = sum over t ascending, sequential from +0, of fl(q[s * dsub + t] * cb[s][j][t]): no list in it;
+//   row term    : (L2) g(s) = the same kind of sum of fl(cb_t * fl(fl(c_t + c_t) + cb_t)), cb = cb[s][code[s]], c_t = c_l[s * dsub + t];
+//                 w = +0, then w = fl(w + g(s)), s ascending: one f32 a stored row;
+//   pair term   : b = the canonical distance (L2) or inner product (IP, cosine) of q to c_l, as the coarse quantiser ranks the lists;
+//   row score   : acc = +0, then acc = fl(acc + P[s][code[s]]), s ascending; dis = fl(fl(b + w) - fl(2 * acc)) (L2), fl(b + acc) (IP).
+
+/// P[q][s * ksub + j] for the nq padded queries (ld floats each) of a round.  grid: (ceil(nq / TQ), ceil(m / SPP)); thread (sub, j)
+/// of a block as in the scan's table build, its codebook entry read once for the block's TQ queries.  Queries beyond nq repeat the
+/// last one and are not written (nq >= 1); s < m keeps the codebook load and the table index inside their arrays.
+template <int BITS, int TQ>
+static __global__ __launch_bounds__(BLOCK) void pq_query_table_kernel(const float * Q, const float * cbT, uint32_t nq, uint32_t ld, uint32_t m,
+                                                                      uint32_t dsub, float * P)
+{
+    constexpr uint32_t KSUB = 1u << BITS, SPP = BLOCK / KSUB;
+    const uint32_t s = blockIdx.y * SPP + threadIdx.x / KSUB, j = threadIdx.x % KSUB;
+    if (s >= m)
+        return;
+    const uint32_t q0 = blockIdx.x * TQ, gw = pq_cb_stride<BITS>(s, m), c0 = s * dsub;
+    const float * cb = cbT + pq_cb_index<BITS>(s, 0, j, m, dsub);
+    const float * q[TQ];
+    float e[TQ];
+#pragma unroll
+    for (int t = 0; t < TQ; t++)
+    {
+        q[t] = Q + (size_t)min(q0 + t, nq - 1) * ld + c0;
+        e[t] = 0.f;
+    }
+    for (uint32_t u = 0; u < dsub; u++)
+    {
+        const float v = cb[(size_t)u * gw];
+#pragma unroll
+        for (int t = 0; t < TQ; t++)
+            e[t] = __fadd_rn(e[t], __fmul_rn(q[t][u], v));
+    }
+#pragma unroll
+    for (int t = 0; t < TQ; t++)
+        if (q0 + t < nq)
+            P[((size_t)(q0 + t) * m + s) * KSUB + j] = e[t];
+}
+
+/// w[r] for the n list-major rows of an L2 index, one thread a row: its list by bisection of list_off (the last l with
+/// list_off[l] <= r: empty lists share their offset with the next one), its codes from the stored words (pq_code_word).
+template <int BITS>
+static __global__ void pq_row_terms_kernel(const uint32_t * codes, const int64_t * list_off, const float * C, const float * cbT, size_t n,
+                                           uint32_t nlist, uint32_t ld, uint32_t m, uint32_t dsub, uint32_t mw, float * w)
+{
+    constexpr uint32_t KSUB = 1u << BITS, CPW = 32 / BITS;
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n)
+        return;
+    uint32_t lo = 0, hi = nlist; // list_off[lo] <= r < list_off[hi] (list_off[0] = 0, list_off[nlist] = n)
+    while (hi - lo > 1)
+    {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (list_off[mid] <= (int64_t)r)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const float * c = C + (size_t)lo * ld;
+    float acc = 0.f;
+    uint32_t word = 0;
+    for (uint32_t s = 0; s < m; s++)
+    {
+        if (s % CPW == 0)
+            word = codes[pq_code_word(r, s / CPW, mw)];
+        const uint32_t code = (word >> (BITS * (s % CPW))) & (KSUB - 1), gw = pq_cb_stride<BITS>(s, m);
+        const float * cb = cbT + pq_cb_index<BITS>(s, 0, code, m, dsub);
+        float g = 0.f;
+        for (uint32_t t = 0; t < dsub; t++)
+        {
+            const float v = cb[(size_t)t * gw], ct = c[s * dsub + t];
+            g = __fadd_rn(g, __fmul_rn(v, __fadd_rn(__fadd_rn(ct, ct), v)));
+        }
+        acc = __fadd_rn(acc, g);
+    }
+    w[r] = acc;
+}
+
 // ------------------------------------------------------------------------------------------ list scan
 
 struct PqIvfParams
@@ -202,20 +286,28 @@ struct PqIvfParams
     uint32_t tables_only;    // measurement: the row loop is skipped (every partial list comes out empty)
     const int64_t * list_off; // [nlist + 1]
     const uint32_t * pair_off, * work_off, * pairs; // the plan (IvfPlanParams)
+    // the query-table form (FORM 1) only
+    const float * qtab;   // [query of the round][s * ksub + j]: pq_query_table_kernel's P
+    const float * pair_b; // [query][probe], indexed like pairs: the canonical distance / inner product of the query to the probe's centroid
+    const float * row_w;  // [row]: pq_row_terms_kernel's w (L2 indexes)
 };
 
 /// LDS bytes of a scan block: the tile's look-up tables (4 * ksub bytes per query and sub-space), its queries, the list's centroid,
-/// and the merge lists.
-inline size_t pq_lds_bytes(size_t bits, uint32_t T, uint32_t m, uint32_t ld, uint32_t k)
+/// and the merge lists.  The query-table form stages no query and no centroid: tables, merge lists and the tile's T pair terms.
+inline size_t pq_lds_bytes(size_t bits, uint32_t T, uint32_t m, uint32_t ld, uint32_t k, int form = 0)
 {
-    return (size_t)T * m * ((size_t)4 << bits) + (size_t)(T + 1) * ld * 4 + (size_t)T * 5 * k * 8;
+    const size_t tables = (size_t)T * m * ((size_t)4 << bits), merge = (size_t)T * 5 * k * 8;
+    return form ? tables + merge + (size_t)T * 4 : tables + (size_t)(T + 1) * ld * 4 + merge;
 }
 
 /// grid: any size; slot -> work item (list, query tile, row segment) as in sq_ivf_scan_kernel.  dynamic LDS: pq_lds_bytes(BITS, T, m, ld, k).
 /// Tables and queries keep the T queries of the tile innermost: lut[(s * KSUB + j) * T + t], qs[c * T + t] -- one LDS read serves the
 /// whole tile (T <= 4) or half of it.  BITS enters in three places only: the size of a table, which (sub-space, entry) pair a thread
 /// of the table build takes (and where its codebook entry is), and how a code comes out of a word.
-template <int BITS, int METRIC, int T, int R>
+/// FORM 1 (query_tables=1; dynamic LDS pq_lds_bytes(BITS, T, m, ld, k, 1)): the prologue stages no query and no centroid and computes
+/// nothing -- it copies the table P of each tile query (pq_query_table_kernel) into lut and the pairs' terms b into bs; the row loop
+/// sums the same look-ups and the row's score is fl(fl(b + w[r]) - fl(2 * acc)) (L2) or fl(b + acc) (IP, cosine).
+template <int BITS, int METRIC, int T, int R, int FORM = 0>
 __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
 {
     constexpr uint32_t KSUB = 1u << BITS;  // entries of a table
@@ -223,9 +315,10 @@ __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
     constexpr uint32_t SPP = BLOCK / KSUB; // sub-spaces per pass of the table build: 1 or 16
     const uint32_t ld = a.ld, k = a.k, m = a.m, dsub = a.dsub, mw = a.mw;
     float * lut = reinterpret_cast<float *>(msvs_smem); // [m][KSUB][T]
-    float * qs = lut + (size_t)m * KSUB * T;            // [ld][T]
-    float * cs = qs + (size_t)ld * T;                   // [ld] centroid of the item's list
-    uint64_t * lds_merge = reinterpret_cast<uint64_t *>(cs + ld);
+    float * qs = lut + (size_t)m * KSUB * T;            // [ld][T] (FORM 0)
+    float * cs = qs + (size_t)ld * T;                   // [ld] centroid of the item's list (FORM 0)
+    uint64_t * lds_merge = reinterpret_cast<uint64_t *>(FORM ? qs : cs + ld); // (the tables are a multiple of 64 bytes)
+    float * bs = reinterpret_cast<float *>(lds_merge + (size_t)T * 5 * k); // [T] the pairs' terms (FORM 1)
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t nu = (mw + 3) >> 2; // units of four code words per row
 
@@ -246,18 +339,37 @@ __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
             const uint32_t pi = min(it.pair_begin + t, it.pair_end - 1); // short tiles repeat their last pair (same slot, same values)
             const uint32_t qp = a.pairs[pi];
             out[t] = a.partial + ((size_t)qp * a.seg_max + seg) * k;
+            if (FORM)
+            {
+                // the query's table, four entries a load (m * KSUB is a multiple of 16, a table is 64-byte aligned): i4 < m * KSUB / 4
+                // keeps the load inside the query's table and the stores below m * KSUB * T
+                const float4 * src = reinterpret_cast<const float4 *>(a.qtab + (size_t)(qp / a.nprobe) * m * KSUB);
+                for (uint32_t i4 = tid; i4 < m * (KSUB / 4); i4 += BLOCK)
+                {
+                    const float4 v = src[i4];
+                    float * dst = lut + (size_t)i4 * 4 * T + t;
+                    dst[0] = v.x;
+                    dst[T] = v.y;
+                    dst[2 * T] = v.z;
+                    dst[3 * T] = v.w;
+                }
+                if (tid == 0)
+                    bs[t] = a.pair_b[qp];
+                continue;
+            }
             const float * src = a.Q + (size_t)(qp / a.nprobe) * ld;
             for (uint32_t c = tid; c < ld; c += BLOCK)
                 qs[c * T + t] = src[c];
         }
-        for (uint32_t c = tid; c < ld; c += BLOCK)
-            cs[c] = a.cent[(size_t)l * ld + c];
+        if (!FORM)
+            for (uint32_t c = tid; c < ld; c += BLOCK)
+                cs[c] = a.cent[(size_t)l * ld + c];
         __syncthreads();
 
         // the tables: thread (sub, j) of a pass scores entry j of sub-space s0 + sub against the tile's queries (cb[s][j] read once for
         // all T).  Where a pass holds several sub-spaces the last one may be partial: s < m keeps both the codebook load and the table
         // index (s * KSUB + j) * T + t < m * KSUB * T inside their arrays
-        for (uint32_t s0 = 0; s0 < m; s0 += SPP)
+        for (uint32_t s0 = 0; !FORM && s0 < m; s0 += SPP)
         {
             const uint32_t s = SPP == 1 ? s0 : s0 + tid / KSUB, j = SPP == 1 ? tid : tid % KSUB;
             if (SPP == 1 || s < m)
@@ -356,6 +468,13 @@ __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
                     id = a.labels[r];
                     if (a.alive)
                         ok = id < a.nbits && ((a.alive[id >> 6] >> (id & 63)) & 1);
+                }
+                if (FORM)
+                {
+                    const float w = METRIC == M_L2 ? a.row_w[rc] : 0.f;
+#pragma unroll
+                    for (int t = 0; t < T; t++)
+                        dis[t] = METRIC == M_L2 ? __fsub_rn(__fadd_rn(bs[t], w), __fmul_rn(2.f, dis[t])) : __fadd_rn(bs[t], dis[t]);
                 }
 #pragma unroll
                 for (int t = 0; t < T; t++)

@@ -15,8 +15,13 @@ puts 8-bit m = 96 beside its equal-bytes 4-bit partner m = 192 and the half-size
 then takes the first 8-bit and the first 4-bit entry, whose scan kernels differ in their first template argument.  --no-competitors leaves the IVFSQ
 and IVFFLAT indexes out.
 
+--query-tables builds every PQ index a second time in the query-table form (query_tables=1), named pqMqt / pqMx4qt: the same rows in
+the same chunks over the first one's codebook (set_codebook from its export), so the two hold the same codes and differ in the
+distance alone; they alternate with the others, the table kernel of the form is the family pq_query_tables, and the prologue share
+(pq_ivf_tables_only) is taken for both forms (profiles/pq_qt_ivf.json: --ms 96,48,96x4,48x4 --ks 10 --query-tables --no-competitors).
+
     python -m tools.bench_pq_ivf [--rows N] [--dim D] [--nlist L] [--ms 96,48] [--batches 64,1024,4096] [--nprobe P] [--ks 10,100]
-                                 [--reps R] [--no-counters] [--no-competitors] [--out FILE]
+                                 [--reps R] [--no-counters] [--no-competitors] [--query-tables] [--out FILE]
 """
 import argparse
 import glob
@@ -38,7 +43,7 @@ import myscaledb_amd.capi as capi  # noqa: E402
 F = np.float32
 # the profiler names the scan "void msvs::pq_ivf_scan_kernel<8, 0, 8, 1>(msvs::PqIvfParams)"; a mangled name (...ILi8E...) is read too
 SCAN_BITS = re.compile(r"pq_ivf_scan_kernel(?:<|ILi)(\d+)")
-FAMILIES = ("pq_ivf_scan", "sq_ivf_scan", "ivf_scan", "ivf_plan", "flat_scan", "merge", "coarse_pass")
+FAMILIES = ("pq_ivf_scan", "pq_query_tables", "sq_ivf_scan", "ivf_scan", "ivf_plan", "flat_scan", "merge", "coarse_pass")
 
 
 def blobs(rng, centres, n):
@@ -68,6 +73,18 @@ def built(make, x, a):
     return ix, time.perf_counter() - t0
 
 
+def built_twin(first, spec, x, a):
+    """-> (the query-table index over `first`'s codebook and the same rows in the same chunks, build seconds without training)"""
+    t0 = time.perf_counter()
+    cent, cb = first.export(with_lists=False)[:2]
+    ix = capi.PqIndex(capi.METRIC_L2, a.dim, pq_params(spec)[1:] + ",query_tables=1")
+    ix.set_codebook(cent, cb)
+    for b in range(0, a.rows, 1 << 17):
+        ix.add(x[b:b + (1 << 17)], np.arange(b, min(a.rows, b + (1 << 17)), dtype=np.int64))
+    ix.build()
+    return ix, time.perf_counter() - t0
+
+
 def pq_name(spec):
     m, bits = spec
     return "pq%d" % m if bits == 8 else "pq%dx%d" % (m, bits)
@@ -94,6 +111,8 @@ def child(a, nq):
     index, build_s = {}, {}
     for spec in a.ms:
         index[pq_name(spec)], build_s[pq_name(spec)] = built(lambda: capi.PqIndex(capi.METRIC_L2, a.dim, params + pq_params(spec)), x, a)
+        if a.query_tables:
+            index[pq_name(spec) + "qt"], build_s[pq_name(spec) + "qt"] = built_twin(index[pq_name(spec)], spec, x, a)
     if not a.no_competitors:
         index["sq"], build_s["sq"] = built(lambda: capi.SqIndex(capi.METRIC_L2, a.dim, params), x, a)
         index["ivfflat"], build_s["ivfflat"] = built(lambda: capi.Index(capi.INDEX_IVFFLAT, capi.METRIC_L2, a.dim, params), x, a)
@@ -119,8 +138,8 @@ def child(a, nq):
         tables = {}
         capi.set_option("pq_ivf_tables_only", 1)
         try:
-            for spec in a.ms:
-                tables[pq_name(spec)] = profiled(runs[pq_name(spec)])["pq_ivf_scan"]["ms"]
+            for n in [n for n in runs if n.startswith("pq")]:
+                tables[n] = profiled(runs[n])["pq_ivf_scan"]["ms"]
         finally:
             capi.set_option("pq_ivf_tables_only")
 
@@ -171,6 +190,8 @@ def spawn(a, extra, limit, prefix=()):
     cmd += ["--ms", ",".join(pq_name(s)[2:] for s in a.ms), "--ks", ",".join(map(str, a.ks))]
     if a.no_competitors:
         cmd.append("--no-competitors")
+    if a.query_tables:
+        cmd.append("--query-tables")
     p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=limit, cwd=ROOT)  # the child's progress lines (stderr) pass through
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
     if p.returncode != 0 or not line:
@@ -223,6 +244,7 @@ def main():
                          "exact scan); 0: 300 + 300 per 2^20 rows")
     ap.add_argument("--no-counters", action="store_true", help="skip the counter-only run (it needs rocprofv3)")
     ap.add_argument("--no-competitors", action="store_true", help="the PQ indexes only: no IVFSQ and no IVFFLAT index")
+    ap.add_argument("--query-tables", action="store_true", help="every PQ index once more with query_tables=1 over the same codebook")
     ap.add_argument("--counter-batch", type=int, default=1024)
     ap.add_argument("--out", default=os.path.join("profiles", "pq_ivf.json"))
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
