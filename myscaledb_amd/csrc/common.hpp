@@ -206,6 +206,9 @@ struct Options
     double flat_rot = 0;      // FLAT shadow pass, several tiles: tile t starts flat_rot * t rounds into its segment and wraps around (0: all tiles in step)
     double flat_segb = 0;     // FLAT shadow pass: blocks per segment (0: 64 / 128 / 256 for one / several / many tiles)
     double h16_stamps = 0;    // experiments: the main launch records per-item wall-clock stamps (msvs_debug_h16_stamps)
+    double h16_items = 1;     // shadow list scan: the plan writes item tables, the sample and main launch load one record per item and the main
+                              // launch fills only a tile's valid rows, pieces and constants requested together (0: search over work_off, padded
+                              // tile fill; 1: where the plan takes three launches; 2: in the fused small-batch plan as well)
     double lat_path = 1;      // few-query IVFFLAT searches in two self-merging launches (latency_kernels.hpp): 0 off,
                               // 1 for 1-2 queries per call, 2 up to 4
     double filter_compact_below = -1;  // filtered searches run over a compacted view when less than this fraction of the

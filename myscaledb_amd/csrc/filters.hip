@@ -151,6 +151,8 @@ extern "C" int msvs_filter_from_offsets(const uint64_t * part_offsets, size_t n,
             MSVS_HIP(hipGetLastError());
             filter_recount(*f, stream); // also orders tmp's release after the kernel
         }
+        else
+            MSVS_HIP(hipStreamSynchronize(stream)); // (no offsets: the filter is the cleared words -- complete when the call returns, like every other)
         *out = f.release();
     });
 }

@@ -36,6 +36,7 @@
 #pragma once
 
 #include "mfma_scan_kernels.hpp"
+#include <type_traits>
 
 namespace msvs
 {
@@ -93,6 +94,10 @@ struct H16Params
     const float * pc;         // [nq * nprobe] C_p
     const uint32_t * qmm;     // [2 nq] the query's {min, max} of C_p (h8_cmin / float bits)
     const double * qxq;       // [nq] X Q
+    // nullable (option h16_items): the plan's item table of THIS launch's partition (IvfPlanParams::items for the main launch, items2
+    // for the sample launch) and its capacity; a launch with more items than that resolves them by the search
+    const IvfItem * items;
+    uint32_t items_cap;
     uint64_t * stamps;       // nullable (option h16_stamps): [grid][H_STAMP_ITEMS][4] {item popped, tile resident, rows done, l << 32 | nvalid << 8}
                               // in wall_clock64 ticks (100 MHz), [grid][0][0] = items of the workgroup
 };
@@ -498,6 +503,21 @@ __device__ __forceinline__ float2 h8_pair_info(const float2 * pinfo, const float
         const bool fine = cmax < 3.0e38f; // (a pair outside the model: the whole query goes to the fallback)
         const double xq = qxq[q];
         const double off = fine ? 2.0 * ((double)pc[qp] - (double)cmin) * xq * (1.0 + 1e-3) : 0.0;
+        pi.y = (float)((double)pi.y - off); // fl(fl|r_q|^2 - off): two roundings of |r_q|^2 (set_error_model_i8r)
+    }
+    return pi;
+}
+
+/// The same from the words already loaded (have_pc = the pc form): for a caller that requests all of them at once -- h8_pair_info asks
+/// for the maximum first and for the rest only when the pair is inside the model, three round trips one behind the other.
+__device__ __forceinline__ float2 h8_pair_info_of(float2 pi, const bool have_pc, const float pcv, const uint32_t wmin, const uint32_t wmax,
+                                                  const double xq)
+{
+    if (have_pc)
+    {
+        const float cmin = h8_cmin(wmin), cmax = __uint_as_float(wmax);
+        const bool fine = cmax < 3.0e38f; // (a pair outside the model: the whole query goes to the fallback)
+        const double off = fine ? 2.0 * ((double)pcv - (double)cmin) * xq * (1.0 + 1e-3) : 0.0;
         pi.y = (float)((double)pi.y - off); // fl(fl|r_q|^2 - off): two roundings of |r_q|^2 (set_error_model_i8r)
     }
     return pi;
@@ -1416,8 +1436,10 @@ __device__ __forceinline__ uint32_t h16_next_item(uint32_t * sched, const uint32
 /// the tile can (the last tile of a list; most tiles once the probe pruning has thinned the pairs) loads and multiplies only the
 /// column blocks it has queries for (round 4: the per-item stamps of option h16_stamps showed 61 % of the bench step's items
 /// holding <= 32 queries; 0.505 -> 0.475 ms).
+/// (Launch bounds: the one-column-block fp16 form runs two workgroups per CU -- four waves per SIMD, 128 VGPRs -- and sat exactly at
+/// that limit before it carried both set-up forms; the bound keeps it there.)
 template <int METRIC, int NCB, bool I8 = false>
-__global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
+__global__ __launch_bounds__(64 * H_NW, (NCB == 1 && !I8) ? 4 : 1) void h16_scan_kernel(const H16Params a)
 {
     constexpr uint32_t TQ = 32 * NCB;
     constexpr uint32_t NW = H_NW;
@@ -1435,6 +1457,9 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t total = a.work_off[a.nlist];
     uint64_t * const stamp = a.stamps ? a.stamps + (size_t)blockIdx.x * H_STAMP_ITEMS * 4 : nullptr;
+    // option h16_items (a.items given): the short set-up; its records come from the table unless the launch has more items than the
+    // table holds (never, by ivf_items_capacity: then every item is resolved by the search, uniformly)
+    const bool fast = a.items != nullptr, table = fast && total <= a.items_cap;
     uint32_t n_items = 0;
     for (;;)
     {
@@ -1452,36 +1477,132 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
         n_items++;
         if (stamp && tid == 0 && n_items < H_STAMP_ITEMS)
             stamp[n_items * 4 + 0] = wall_clock64();
-        uint32_t lo = 0, hi = a.nlist;
-        while (hi - lo > 1)
+        // the item's record (plan_items.hpp): one load out of the plan's table, or formed here behind the search over work_off and
+        // the list's six offsets (item t of the list = (row segment, tile); block 0 is the sample launch's)
+        uint32_t l, hb, b_first, b_end, pb, nvalid, lbeg32, lend32;
+        if (table)
         {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (a.work_off[mid] <= w)
-                lo = mid;
-            else
-                hi = mid;
+            // (w comes out of LDS: uniform, but not to the compiler; two 16-byte loads, no copy of the record through the stack)
+            const uint4 * const rec = reinterpret_cast<const uint4 *>(a.items + __builtin_amdgcn_readfirstlane(w));
+            const uint4 r0 = rec[0], r1 = rec[1];
+            l = r0.x, hb = r0.y, b_first = r0.z, b_end = r0.w;
+            pb = r1.x, nvalid = r1.y, lbeg32 = r1.z, lend32 = r1.w;
         }
-        const uint32_t l = lo;
-        const int64_t lbeg = a.list_off[l], lend = a.list_off[l + 1];
-        const uint32_t nblk = a.hoff[l + 1] - a.hoff[l];
-        const uint32_t pe = a.pair_off[l + 1], p0 = a.pair_off[l];
-        // item t of the list = (row segment, tile): the tiles of a segment are consecutive items (they meet in one XCD's L2)
-        const uint32_t t_in = w - a.work_off[l], ntiles = (pe - p0 + TQ - 1) / TQ;
-        const uint32_t seg = t_in / ntiles, tidx = t_in - seg * ntiles;
-        uint32_t b_first = 1, b_end = nblk; // (block 0 is the sample launch's)
-        if (a.seg_blocks)
+        else
         {
-            const uint32_t nseg = plan_nseg(nblk - 1, a.seg_blocks[0]);
-            const uint32_t per = (nblk - 1 + nseg - 1) / nseg;
-            b_first = 1 + seg * per;
-            b_end = b_first + per < nblk ? b_first + per : nblk;
+            uint32_t lo = 0, hi = a.nlist;
+            while (hi - lo > 1)
+            {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (a.work_off[mid] <= w)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const uint32_t nblk = a.hoff[lo + 1] - a.hoff[lo];
+            const IvfItem it = ivf_make_item(w, lo, a.work_off[lo], a.pair_off[lo], a.pair_off[lo + 1], 1u, nblk, a.seg_blocks ? a.seg_blocks[0] : 0u,
+                                             TQ, a.hoff[lo], (uint32_t)a.list_off[lo], (uint32_t)a.list_off[lo + 1]);
+            l = it.list, hb = it.hb, b_first = it.b_first, b_end = it.b_end;
+            pb = it.pair_begin, nvalid = it.nvalid, lbeg32 = it.lbeg, lend32 = it.lend;
         }
-        const uint32_t pb = p0 + tidx * TQ;
-        const uint32_t nvalid = pe - pb < TQ ? pe - pb : TQ;
+        // (every lane holds the same record: scalars from here on -- the item's fields live through the whole stream)
+        l = __builtin_amdgcn_readfirstlane(l), hb = __builtin_amdgcn_readfirstlane(hb);
+        b_first = __builtin_amdgcn_readfirstlane(b_first), b_end = __builtin_amdgcn_readfirstlane(b_end);
+        pb = __builtin_amdgcn_readfirstlane(pb), nvalid = __builtin_amdgcn_readfirstlane(nvalid);
+        lbeg32 = __builtin_amdgcn_readfirstlane(lbeg32), lend32 = __builtin_amdgcn_readfirstlane(lend32);
+        const uint32_t pe = pb + nvalid;
+        const int64_t lbeg = lbeg32, lend = lend32;
         // column blocks this item needs, and the rows of its tile in LDS
         const uint32_t ncb_e = (nvalid + 31) >> 5;
         const uint32_t tq_e = 32 * ncb_e;
 
+        if (fast)
+        {
+            // Two waits remain between the record and the tile barrier -- the pair words, then everything that needs them.  A thread reads the pair word of every tile piece it fetches (and of the tile row
+            // whose constants it fetches) itself, so the constants (pair info, cut) and the pieces are all requested together.  Only the
+            // nvalid rows that hold a query are filled.  INVARIANT: the rows nvalid .. tq_e - 1 of the item's column blocks keep what
+            // the previous item (or nobody) left there.  That is harmless: row i of the product depends on row i of the tile alone (a NaN
+            // or Inf pattern of the fp16 form stays in its own row; the i8r products are integers), and a padding row's cut is
+            // h16_stream_cut(0), under which every comparison of the epilogue is false whatever the value, NaN included -- a padding
+            // row is never offered, as before.
+            const uint32_t npieces = nvalid * tnch * 8;
+            // U pieces in flight per thread.  No branch between the loads and the stores (hipcc sinks a load into the branch that alone
+            // uses it, and the pieces then go one round trip after the other): a piece past the end IS the last piece, loaded and
+            // stored again by its thread -- the same bytes at the same place.
+            auto fill = [&](const uint32_t first_piece, auto in_flight, auto with_constants) {
+                constexpr int U = decltype(in_flight)::value;
+                uint32_t pw[U], pqi[U], pch[U], pslot[U];
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                {
+                    const uint32_t pp = first_piece + u * 64 * NW;
+                    const uint32_t p = pp < npieces ? pp : npieces - 1;
+                    pslot[u] = p & 7;
+                    pch[u] = (p >> 3) / nvalid;
+                    pqi[u] = (p >> 3) - pch[u] * nvalid;
+                    pw[u] = a.pairs[pb + pqi[u]];
+                }
+                uint32_t cw = 0;
+                if constexpr (decltype(with_constants)::value)
+                {
+                    cw = a.pairs[pb + (tid < nvalid ? tid : nvalid - 1)];
+                    asm volatile("" : "+v"(cw)); // (a use up here: the load stays with the other pair words, out of the branch below)
+                }
+                u32x4 v[U];
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                {
+                    // (i8r: the image of the PAIR under L2, of the QUERY under inner product and cosine)
+                    const uint32_t img = I8 && METRIC == M_L2 ? pw[u] : pw[u] / a.nprobe;
+                    v[u] = reinterpret_cast<const u32x4 *>(a.Qh)[((size_t)img * tnch + pch[u]) * 8 + (pslot[u] ^ ((pqi[u] >> 1) & 7))];
+                }
+                if constexpr (decltype(with_constants)::value)
+                {
+                    const uint32_t q = cw / a.nprobe;
+                    float2 qi = I8 ? a.pinfo[cw] : a.qinfo[q];
+                    uint32_t thr = a.qthr[q];
+                    if constexpr (I8)
+                    {
+                        // every word h8_pair_info reads, requested at once
+                        float pcv = 0.f;
+                        uint32_t wmin = 0, wmax = 0;
+                        double xq = 0.0;
+                        if (a.pc)
+                        {
+                            pcv = a.pc[cw];
+                            wmin = a.qmm[2 * q];
+                            wmax = a.qmm[2 * q + 1];
+                            xq = a.qxq[q];
+                        }
+                        asm volatile("" : "+v"(qi.x), "+v"(qi.y), "+v"(thr), "+v"(pcv), "+v"(wmin), "+v"(wmax), "+v"(xq));
+                        qi = h8_pair_info_of(qi, a.pc != nullptr, pcv, wmin, wmax, xq);
+                    }
+                    else
+                        asm volatile("" : "+v"(qi.x), "+v"(qi.y), "+v"(thr)); // (a use up here: requested behind the pieces, waited for with them)
+                    if (tid < tq_e)
+                    {
+                        const bool ok = tid < nvalid;
+                        qrow_s[tid] = ok ? q : 0u;
+                        m2_s[tid] = ok ? qi.x : 0.f;
+                        qn_s[tid] = ok ? qi.y : 0.f;
+                        thr_s[tid] = h16_stream_cut<METRIC>(ok ? thr : 0u); // padding queries of a short tile never pass
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                    *reinterpret_cast<u32x4 *>(tile + ((pch[u] * TQ + pqi[u]) * 8 + pslot[u]) * 16) = v[u];
+            };
+            if (npieces <= 64 * NW) // (uniform: tiles of a few queries, one piece per thread)
+                fill(tid, std::integral_constant<int, 1>{}, std::true_type{});
+            else
+            {
+                fill(tid, std::integral_constant<int, 4>{}, std::true_type{});
+                for (uint32_t base = 4 * 64 * NW; base < npieces; base += 4 * 64 * NW) // (a uniform trip count)
+                    fill(base + tid, std::integral_constant<int, 4>{}, std::false_type{});
+            }
+        }
+        else
+        {
         if (tid < TQ)
         {
             const bool v = tid < nvalid;
@@ -1520,6 +1641,7 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
                         *reinterpret_cast<uint4 *>(tile + at[u]) = v[u];
             }
         }
+        }
         __syncthreads();
         if (stamp && tid == 0 && n_items < H_STAMP_ITEMS)
         {
@@ -1528,7 +1650,7 @@ __global__ __launch_bounds__(64 * H_NW) void h16_scan_kernel(const H16Params a)
         }
         uint32_t * const stage = stage_s + wave * 3 * H_STAGE;
 #define MSVS_H16_STREAM(N)                                                                                                         \
-    h16_stream<METRIC, N, H_RING, 1, I8>(a, tile, TQ * 128, m2_s, qn_s, thr_s, qrow_s, stage, lane, nch, a.hoff[l], b_first + wave, NW, b_end, lbeg, lend, nvalid)
+    h16_stream<METRIC, N, H_RING, 1, I8>(a, tile, TQ * 128, m2_s, qn_s, thr_s, qrow_s, stage, lane, nch, hb, b_first + wave, NW, b_end, lbeg, lend, nvalid)
         if constexpr (NCB == 1)
             MSVS_H16_STREAM(1);
         else if (ncb_e == 1)
@@ -1566,22 +1688,50 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
     static_assert(!I8 || NQB == 1, "i8r: one column block");
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r32 = lane & 31, h = lane >> 5;
     const uint32_t nch = a.nch, total = a.work_off[a.nlist];
+    // (a.items: the plan's table of this launch's items -- one record load instead of the search and the five offsets; see h16_scan_kernel)
+    const bool table = a.items != nullptr && total <= a.items_cap;
     for (uint32_t w = blockIdx.x * 4 + wave; w < total; w += gridDim.x * 4)
     {
-        uint32_t lo = 0, hi = a.nlist;
-        while (hi - lo > 1)
+        uint32_t hb, pb, nvalid;
+        int64_t lbeg, lend;
+        if (table)
         {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (a.work_off[mid] <= w)
-                lo = mid;
-            else
-                hi = mid;
+            const uint4 * const rec = reinterpret_cast<const uint4 *>(a.items + __builtin_amdgcn_readfirstlane(w)); // (one item per wavefront)
+            const uint4 r0 = rec[0], r1 = rec[1];
+            hb = __builtin_amdgcn_readfirstlane(r0.y);
+            pb = __builtin_amdgcn_readfirstlane(r1.x);
+            nvalid = __builtin_amdgcn_readfirstlane(r1.y);
+            lbeg = (uint32_t)__builtin_amdgcn_readfirstlane(r1.z); // (rows up to 0xfffffff0: unsigned)
+            lend = (uint32_t)__builtin_amdgcn_readfirstlane(r1.w);
         }
-        const uint32_t l = lo;
-        const int64_t lbeg = a.list_off[l], lend = a.list_off[l + 1];
-        const uint32_t pe = a.pair_off[l + 1];
-        const uint32_t pb = a.pair_off[l] + (w - a.work_off[l]) * 32 * NQB;
-        const uint32_t nvalid = pe - pb < 32u * NQB ? pe - pb : 32u * NQB;
+        else
+        {
+            uint32_t lo = 0, hi = a.nlist;
+            while (hi - lo > 1)
+            {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (a.work_off[mid] <= w)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const uint32_t l = lo;
+            lbeg = a.list_off[l];
+            lend = a.list_off[l + 1];
+            const uint32_t pe = a.pair_off[l + 1];
+            pb = a.pair_off[l] + (w - a.work_off[l]) * 32 * NQB;
+            nvalid = pe - pb < 32u * NQB ? pe - pb : 32u * NQB;
+            hb = a.hoff[l];
+        }
+        // (the row block's address needs the record alone: its first chunk is requested with the pair words, not behind them)
+        const u32x4 * const bp = reinterpret_cast<const u32x4 *>(a.H) + (size_t)hb * nch * 256 + lane;
+        u32x4 br[2][4];
+        if (table)
+        {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                br[0][j] = bp[j * 64];
+        }
         // this lane's queries (A operand row r32 of each column block); short tiles repeat their last pair
         uint32_t qp[NQB];
         float2 qi[NQB];
@@ -1595,7 +1745,6 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
             qi[b] = I8 ? h8_pair_info(a.pinfo, a.pc, a.qmm, a.qxq, qp[b], q) : a.qinfo[q];
             ap[b] = reinterpret_cast<const u32x4 *>(a.Qh) + (size_t)(I8 && METRIC == M_L2 ? qp[b] : q) * (I8 ? 2 * nch : nch) * 8 + h;
         }
-        const u32x4 * const bp = reinterpret_cast<const u32x4 *>(a.H) + (size_t)a.hoff[l] * nch * 256 + lane;
         const int64_t row = lbeg + r32;
         bool ok = row < lend;
         float xn = 0.f, xs = 0.f;
@@ -1622,8 +1771,9 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
             for (int r = 0; r < 16; r++)
                 acc[b][r] = 0.f;
         i32x16 ach = {}, acl = {};
-        u32x4 ar[2][NQB][4], al[2][I8 ? 4 : 1], br[2][4];
-        auto load = [&](const int s, const uint32_t c) {
+        u32x4 ar[2][NQB][4], al[2][I8 ? 4 : 1];
+        auto load = [&](const int s, const uint32_t c, auto with_rows) {
+            constexpr bool rows = decltype(with_rows)::value;
 #pragma unroll
             for (int j = 0; j < 4; j++)
             {
@@ -1632,7 +1782,8 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
                     ar[s][b][j] = ap[b][(size_t)(I8 ? 2 * c : c) * 8 + 2 * j];
                 if (I8)
                     al[s][j] = ap[0][(size_t)(2 * c + 1) * 8 + 2 * j];
-                br[s][j] = bp[(size_t)c * 256 + j * 64];
+                if constexpr (rows)
+                    br[s][j] = bp[(size_t)c * 256 + j * 64];
             }
         };
         auto mul = [&](const int s) {
@@ -1652,17 +1803,20 @@ __global__ __launch_bounds__(BLOCK) void h16_sample_kernel(const H16Params a)
                                                                     __builtin_bit_cast(half8, br[s][j]), acc[b], 0, 0, 0);
             }
         };
-        load(0, 0);
+        if (table)
+            load(0, 0, std::false_type{}); // (the rows of chunk 0 are on their way)
+        else
+            load(0, 0, std::true_type{});
         const uint32_t last = nch - 1;
         for (uint32_t c = 0; c < nch; c += 2)
         {
-            load(1, c + 1 < last ? c + 1 : last);
+            load(1, c + 1 < last ? c + 1 : last, std::true_type{});
             __builtin_amdgcn_sched_barrier(0);
             mul(0);
             __builtin_amdgcn_sched_barrier(0);
             if (c + 1 >= nch)
                 break;
-            load(0, c + 2 < last ? c + 2 : last);
+            load(0, c + 2 < last ? c + 2 : last, std::true_type{});
             __builtin_amdgcn_sched_barrier(0);
             mul(1);
             __builtin_amdgcn_sched_barrier(0);

@@ -400,6 +400,13 @@ static size_t big_cand_cap(size_t nprobe, size_t slices_max)
     return std::min<size_t>(nprobe * slices_max * BG_SLICE_K, limit);
 }
 
+/// Bytes of one item table of the shadow list scan (option h16_items), whatever its tile: tiles of >= 32 pairs, segments chosen on
+/// the device for 4 items per CU (ivf_items_capacity), and the arena's alignment.
+static size_t h16_item_table_bytes(size_t n_pairs, size_t nlist)
+{
+    return (size_t)ivf_items_capacity(n_pairs, nlist, 32, 4 * device_cu_count()) * sizeof(IvfItem) + 256;
+}
+
 /// allow_pass: false for a search over a compacted view (it runs the canonical plan, whose partial lists can be LARGER than the
 /// candidate pass's buffers: an inner-product index with one giant list has many segments per probe -- round 4's sparse-filter
 /// case overflowed an arena reserved for the candidate-pass plan)
@@ -422,6 +429,7 @@ static size_t index_search_scratch(const msvs_index & ix, size_t nq, uint32_t k,
             + nq * (size_t)p.kc * 8 + nq * 32 + 8192
             + fallback_cap(nq, nprobe, p.seg_max1, k) * nprobe * (size_t)p.seg_max1 * k * 8
             + (p.h16 ? nq * ((size_t)ix.h_nch * 128 + 8 + 4 + 4) + 2048 + nq * nprobe * H_ROWS * 4 + 4 * ix.nlist + 4096 : 0)
+            + (p.h16 ? 3 * h16_item_table_bytes(nq * nprobe, ix.nlist) : 0) // the item tables: sample launch, main launch, second plan
             + (p.h16 && ix.h8 ? nq * nprobe * i8r_pair_bytes(ix) + nq * i8r_query_bytes(ix) + nq * 8 + 2048 + nq * 16 + 512 : 0); // i8r: the pairs' images, constants, the bound;
                                                                                               // the per-query min / max words (counters) and X Q of h8_pairs_wave_kernel
     else
@@ -1241,6 +1249,10 @@ struct H16Last
     size_t nq = 0;
     hipStream_t stream = nullptr;
     const float * qbound = nullptr; // i8r: the queries' coefficients of |x||q| (set_error_model_i8r)
+    // the main launch's plan and item table, the sample launch's (msvs_debug_h16_items)
+    const uint32_t * work_off = nullptr, * pair_off = nullptr, * seg_out = nullptr, * work_off2 = nullptr, * pair_off2 = nullptr;
+    const IvfItem * items = nullptr, * items2 = nullptr;
+    uint32_t items_cap = 0, items2_cap = 0, nlist = 0;
 };
 static thread_local H16Last g_h16_last;
 
@@ -1358,6 +1370,20 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     const bool prune2 = options().h16_prune != 0 && prune_pays && (prepared.coarse_words || prepared.probe_words || prepared.probe_dis)
         && ix.list_radius.p && k <= 128 && nprobe <= 64 && options().wave_select != 0
         && (!prepared.probe_dis || ((ix.metric == MSVS_METRIC_L2 || ix.metric == MSVS_METRIC_COSINE) && !d_alive));
+    // the item tables (option h16_items): the plan leaves one record per work item of either launch, sized by the plan's own rules.  When
+    // a second pruning stage follows, the main launch reads THAT plan's table: this plan writes the sample launch's alone
+    // (a fused small-batch plan keeps the search unless h16_items = 2: its one-block launch pays more for writing the records than the
+    // few short items of a batch of <= 8192 pairs gain -- measured, DESIGN 4.2 "Round 9")
+    const bool use_items = options().h16_items == 2 || (options().h16_items != 0 && !ivf_plan_fused(pp));
+    const uint32_t items_cap = (uint32_t)std::min<uint64_t>(ivf_items_capacity(pp.n_pairs, pp.nlist, pp.T, want_segs ? pp.seg_target_items : 0), 0xffffffffu);
+    if (use_items)
+    {
+        pp.hoff = ix.hoff.p;
+        pp.items_cap = items_cap;
+        pp.items = prune2 ? nullptr : scr.take<IvfItem>(items_cap);
+        pp.items2_cap = (uint32_t)std::min<uint64_t>(ivf_items_capacity(pp.n_pairs, pp.nlist, pp.T2, 0), 0xffffffffu);
+        pp.items2 = scr.take<IvfItem>(pp.items2_cap);
+    }
     if (options().rerank_stats != 0)
     {
         pp.stat_rows = prefilter_fail_counter() + 10;
@@ -1485,6 +1511,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     {
         ProfileScope prof("ivf_sample_scan", stream);
         a.work_off = pa.work_off;
+        a.items = pp.items2;
+        a.items_cap = pp.items2_cap;
         const uint32_t sgrid = device_cu_count() * 8; // one wavefront per (list, 32-query column block), grid-stride
         with_bool(ix.h8, [&](auto i8) {
             with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
@@ -1550,6 +1578,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         p2.pairs = scr.take<uint32_t>(nq * nprobe);
         p2.seg_out = seg_words ? seg_words + 1 : nullptr;
         p2.work_off2 = nullptr;
+        p2.items2 = nullptr;
+        p2.items = use_items ? scr.take<IvfItem>(items_cap) : nullptr; // (a table of its own: the same bound, fewer pairs)
         if (options().rerank_stats != 0)
         {
             p2.stat_rows = prefilter_fail_counter() + 10;
@@ -1560,6 +1590,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         pp.pair_off = p2.pair_off;
         pp.work_off = p2.work_off;
         pp.seg_out = p2.seg_out;
+        pp.items = p2.items;
         a.pairs = pp.pairs;
         a.pair_off = pp.pair_off;
     }
@@ -1567,6 +1598,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         ProfileScope prof("ivf_scan", stream);
         a.work_off = pp.work_off;
         a.seg_blocks = pp.seg_out;
+        a.items = pp.items;
+        a.items_cap = pp.items_cap;
         a.sched = sched + 8;
         {
             if (options().h16_stamps != 0)
@@ -1597,7 +1630,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         }
     }
     MSVS_HIP(hipGetLastError());
-    g_h16_last = H16Last{partial, qstate + nq, pl.h_cap, nq, stream, qbound};
+    g_h16_last = H16Last{partial, qstate + nq, pl.h_cap, nq, stream, qbound, pp.work_off, pp.pair_off, pp.seg_out, pa.work_off, pa.pair_off,
+                         a.items, pa.items2, a.items_cap, pa.items2_cap, (uint32_t)ix.nlist};
     launch_cand_select(partial, qstate + nq, qstate, pl.h_cap, (uint32_t)nq, pl.kc, cand, bound, stream);
     RerankParams rp{};
     rp.Y = reinterpret_cast<const float4 *>(ix.vecs.p);
@@ -2370,6 +2404,55 @@ extern "C" __attribute__((visibility("default"))) int msvs_debug_h16_keys(uint64
         const size_t take = std::min<size_t>(cap_out, h.cap);
         MSVS_HIP(hipMemcpy2D(keys_out, cap_out * 8, h.partial, (size_t)h.cap * 8, take * 8, nq, hipMemcpyDeviceToHost));
         g_h16_last = H16Last{}; // one fetch per pass: a later search that takes another path must not be mistaken for it
+    });
+}
+
+/// Tests only (not in msvs.h): the item tables of this thread's last shadow list scan, read back from the device (before
+/// msvs_debug_h16_keys, which retires the record).  out[0] = 1 when the main launch was given a table, [1] its capacity, [2] the
+/// launch's work items (work_off[nlist]: the kernel reads the table when [2] <= [1]), [3] the blocks per segment the plan chose (0: one
+/// segment per list), [4] the records of the table that do not fit the plan they were written for -- a sanity check, not a
+/// restatement of the plan (tests/test_plan_items_host.py is that): a record's shadow block, block range and tile split show in the
+/// search results only (their list is not the one
+/// work_off assigns, their pairs lie outside the list's, no pair, blocks the wrong way round); [5] .. [7]: given, capacity and work
+/// items of the sample launch, out[8] its misfits.
+extern "C" __attribute__((visibility("default"))) int msvs_debug_h16_items(uint32_t * out)
+{
+    return guarded([&] {
+        const H16Last & h = g_h16_last;
+        if (!h.work_off)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "no shadow list scan on record");
+        MSVS_HIP(hipStreamSynchronize(h.stream));
+        auto table = [&](const uint32_t * d_work, const uint32_t * d_pair, const IvfItem * d_items, uint32_t cap, uint32_t * o) {
+            std::vector<uint32_t> work(h.nlist + 1), pair_off(h.nlist + 1);
+            MSVS_HIP(hipMemcpy(work.data(), d_work, work.size() * 4, hipMemcpyDeviceToHost));
+            MSVS_HIP(hipMemcpy(pair_off.data(), d_pair, pair_off.size() * 4, hipMemcpyDeviceToHost));
+            const uint32_t total = work[h.nlist];
+            o[0] = d_items ? 1u : 0u;
+            o[1] = cap;
+            o[2] = total;
+            uint32_t bad = 0;
+            if (d_items && total <= cap)
+            {
+                std::vector<IvfItem> it(total);
+                if (total)
+                    MSVS_HIP(hipMemcpy(it.data(), d_items, (size_t)total * sizeof(IvfItem), hipMemcpyDeviceToHost));
+                for (uint32_t w = 0; w < total; w++)
+                {
+                    const uint32_t l = (uint32_t)(std::upper_bound(work.begin(), work.end(), w) - work.begin()) - 1;
+                    const IvfItem & r = it[w];
+                    if (r.list != l || r.nvalid == 0 || r.pair_begin < pair_off[l] || r.pair_begin + r.nvalid > pair_off[l + 1] || r.b_first > r.b_end
+                        || r.lbeg > r.lend)
+                        bad++;
+                }
+            }
+            return bad;
+        };
+        uint32_t seg = 0;
+        if (h.seg_out)
+            MSVS_HIP(hipMemcpy(&seg, h.seg_out, 4, hipMemcpyDeviceToHost));
+        out[3] = seg;
+        out[4] = table(h.work_off, h.pair_off, h.items, h.items_cap, out);
+        out[8] = table(h.work_off2, h.pair_off2, h.items2, h.items2_cap, out + 5);
     });
 }
 

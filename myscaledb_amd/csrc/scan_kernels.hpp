@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan_items.hpp"
+
 // __fmul_rn/__fadd_rn/__fsub_rn are plain operators in this toolchain: keep the compiler from fusing them.
 #pragma clang fp contract(off)
 
@@ -602,18 +604,112 @@ struct IvfPlanParams
     // pruning -- a batch of 64 queries keeps ~64 lists, one item per list would leave three quarters of the CUs idle (plan_nseg)
     uint32_t * seg_out = nullptr;
     uint32_t seg_target_items = 0;
+    // Item tables (nullable; plan_items.hpp): record w of `items` = work item w of the first partition, of `items2` of the second, over
+    // 32-row blocks (a partition of rows_per_block >= its longest range: one segment per list, or seg_out's segments), so that a scan
+    // launch loads one record where it would search work_off and read six offsets.  hoff (nullable): the lists' first shadow blocks.
+    // Capacities from ivf_items_capacity.  Written by the scatter launch (three-launch plan) or by the fused plan's one launch.
+    IvfItem * items = nullptr;
+    IvfItem * items2 = nullptr;
+    uint32_t items_cap = 0, items2_cap = 0;
+    const uint32_t * hoff = nullptr;
     uint32_t * pairs_out = nullptr; // nullable, HOST-visible (pinned): the scan launch leaves the number of pairs in the plan here (a hint for the
                                     // next search's choice of stages: read by the host without any synchronisation, stale by design)
 };
 
-/// Segments of a list of `blocks` 32-row blocks at a segment size of sb blocks (rounded to the nearest count, at least one;
-/// an empty range has none), and the blocks per segment that go with it: shared by the plan kernel and the scan kernel.
-__host__ __device__ inline uint32_t plan_nseg(uint32_t blocks, uint32_t sb)
+// (plan_nseg, the item record IvfItem and its builder ivf_make_item: plan_items.hpp)
+
+/// The item tables of a plan (IvfPlanParams::items / items2).  What the records of ONE list are made from: its work items start at
+/// `work`, its c pairs at p0, its partition's blocks are [b_lo, b_hi) of the list; n = their number (0: no pair, no row or no table).
+struct PlanListItems
 {
-    if (blocks == 0)
-        return 0;
-    const uint32_t n = (blocks + sb / 2) / sb;
-    return n ? n : 1;
+    uint32_t l, work, p0, c, b_lo, b_hi, seg_blocks, T, hb, lbeg, lend, n;
+};
+
+/// ... of list l in the first (second = false) or the second partition, from the list's final offsets (work_l = work_off[l] or
+/// work_off2[l]; seg_blocks as the scan launch chose it, 0 in the second partition).
+static __device__ __forceinline__ PlanListItems plan_list_items(const IvfPlanParams & p, const bool second, const uint32_t l, const uint32_t work_l,
+                                                                const uint32_t p0, const uint32_t c, const uint32_t seg_blocks)
+{
+    PlanListItems g{};
+    if (c == 0 || (second ? !p.items2 || !p.work_off2 : !p.items))
+        return g;
+    const int64_t * const off = second ? p.list_off2 : p.list_off, * const end = second ? p.list_end2 : p.list_end;
+    const int64_t base = p.whole_off ? p.whole_off[l] : off[l], lb = off[l], le = end ? end[l] : off[l + 1];
+    g.l = l, g.work = work_l, g.p0 = p0, g.c = c;
+    g.b_lo = (uint32_t)((lb - base + 31) >> 5), g.b_hi = g.b_lo + (uint32_t)((le - lb + 31) >> 5);
+    g.seg_blocks = second ? 0u : seg_blocks, g.T = second ? p.T2 : p.T;
+    g.hb = p.hoff ? p.hoff[l] : 0u, g.lbeg = (uint32_t)base, g.lend = (uint32_t)le;
+    g.n = ivf_list_items(c, g.b_hi - g.b_lo, g.seg_blocks, g.T);
+    return g;
+}
+
+/// Record i of the list.  A record past the table's capacity is not written: the table's readers then resolve every item by the
+/// binary search (see the guard there).
+static __device__ __forceinline__ void plan_store_item(IvfItem * table, const uint32_t cap, const PlanListItems & g, const uint32_t i)
+{
+    if (g.work + i < cap)
+        table[g.work + i] = ivf_make_item(g.work + i, g.l, g.work, g.p0, g.p0 + g.c, g.b_lo, g.b_hi, g.seg_blocks, g.T, g.hb, g.lbeg, g.lend);
+}
+
+/// The records of list l, both tables, by one thread (the scatter launches: one record per list on a large batch).
+static __device__ __forceinline__ void plan_write_items(const IvfPlanParams & p, const uint32_t l, const uint32_t work_l, const uint32_t work2_l,
+                                                        const uint32_t p0, const uint32_t c, const uint32_t seg_blocks)
+{
+    const PlanListItems g = plan_list_items(p, false, l, work_l, p0, c, seg_blocks), g2 = plan_list_items(p, true, l, work2_l, p0, c, 0);
+    for (uint32_t i = 0; i < g.n; i++)
+        plan_store_item(p.items, p.items_cap, g, i);
+    for (uint32_t i = 0; i < g2.n; i++)
+        plan_store_item(p.items2, p.items2_cap, g2, i);
+}
+
+/// The records of the lists the 64 lanes of a wavefront hold (g.n = 0: none), spread over the lanes: record r of the wavefront goes
+/// to lane r % 64, which finds the lane that holds its list in the prefix sums of n (six shuffles) and fetches that list's fields.
+/// A small batch cuts its few lists into several segments each, a batch of a few hundred queries has a thousand lists of one record:
+/// either way every lane writes about one record, where one thread per list wrote a list's records one after the other, three
+/// integer divisions each, inside the one-block plan launch.  Every lane of the wavefront must call this.
+static __device__ __forceinline__ void plan_write_items_wave(IvfItem * table, const uint32_t cap, const PlanListItems & g)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t incl = g.n;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+        const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
+        if (lane >= (uint32_t)o)
+            incl += v;
+    }
+    const uint32_t excl = incl - g.n, total = (uint32_t)__shfl((int)incl, 63);
+    for (uint32_t base = 0; base < total; base += 64) // (a uniform trip count)
+    {
+        const uint32_t r = base + lane;
+        uint32_t j = 0; // the last lane whose records start at or before r: lanes without records share their successor's start
+#pragma unroll
+        for (int st = 32; st >= 1; st >>= 1)
+            if ((uint32_t)__shfl((int)excl, (int)(j + st)) <= r)
+                j += st;
+        PlanListItems b;
+        b.l = (uint32_t)__shfl((int)g.l, (int)j), b.work = (uint32_t)__shfl((int)g.work, (int)j), b.p0 = (uint32_t)__shfl((int)g.p0, (int)j);
+        b.c = (uint32_t)__shfl((int)g.c, (int)j), b.b_lo = (uint32_t)__shfl((int)g.b_lo, (int)j), b.b_hi = (uint32_t)__shfl((int)g.b_hi, (int)j);
+        b.seg_blocks = (uint32_t)__shfl((int)g.seg_blocks, (int)j), b.T = (uint32_t)__shfl((int)g.T, (int)j);
+        b.hb = (uint32_t)__shfl((int)g.hb, (int)j), b.lbeg = (uint32_t)__shfl((int)g.lbeg, (int)j), b.lend = (uint32_t)__shfl((int)g.lend, (int)j);
+        b.n = (uint32_t)__shfl((int)g.n, (int)j);
+        const uint32_t first = (uint32_t)__shfl((int)excl, (int)j);
+        if (r < total)
+            plan_store_item(table, cap, b, r - first);
+    }
+}
+
+/// ... by a launch that runs after the scans are final (the scatter launches): a grid-stride loop over the lists.
+static __device__ __forceinline__ void plan_write_items_grid(const IvfPlanParams & p)
+{
+    if (!p.items && !p.items2)
+        return;
+    const uint32_t seg_blocks = p.seg_out ? p.seg_out[0] : 0u;
+    for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < p.nlist; l += gridDim.x * blockDim.x)
+    {
+        const uint32_t p0 = p.pair_off[l];
+        plan_write_items(p, l, p.work_off[l], p.work_off2 ? p.work_off2[l] : 0u, p0, p.pair_off[l + 1] - p0, seg_blocks);
+    }
 }
 
 static __global__ void ivf_hist_kernel(const IvfPlanParams p)
@@ -766,6 +862,13 @@ static __global__ __launch_bounds__(1024) void ivf_plan_scan_kernel(const IvfPla
             if (p.work_off2)
                 p.work_off2[l] = cv + sv[cur][tid] - v;
         }
+        if (FUSED && (p.items || p.items2)) // (the whole plan is this launch: the list's offsets are final here; every thread of the block is here)
+        {
+            const bool has = l < p.nlist;
+            const uint32_t p0 = cp + sp[cur][tid] - c;
+            plan_write_items_wave(p.items, p.items_cap, plan_list_items(p, false, l, cw + sw[cur][tid] - w, p0, has ? c : 0u, seg_blocks));
+            plan_write_items_wave(p.items2, p.items2_cap, plan_list_items(p, true, l, cv + sv[cur][tid] - v, p0, has ? c : 0u, 0));
+        }
         __syncthreads();
         if (tid == 1023)
         {
@@ -808,6 +911,7 @@ static __global__ void ivf_scatter_kernel(const IvfPlanParams p)
         if (l >= 0 && (!p.whole_off || p.whole_off[l + 1] > p.whole_off[l]))
             p.pairs[p.pair_off[l] + atomicAdd(&p.fill[l], 1u)] = i;
     }
+    plan_write_items_grid(p);
 }
 
 // The same two passes with the per-pair atomics moved into LDS: a block takes PLAN_CHUNK consecutive pairs, counts them
@@ -863,6 +967,7 @@ static __global__ __launch_bounds__(256) void ivf_scatter_lds_kernel(const IvfPl
     for (uint32_t u = 0; u < PLAN_CHUNK / 256; u++)
         if (list[u] >= 0)
             p.pairs[h[list[u]] + rank[u]] = base + u * 256 + tid;
+    plan_write_items_grid(p);
 }
 
 /// A work item of a grouped plan (IvfPlanParams): the rows [row_begin, row_end) of segment `seg` of list `list` for the pairs
