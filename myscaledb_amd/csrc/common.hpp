@@ -224,6 +224,10 @@ struct Options
     double h8_pairs = 1;      // i8r list scan: the pair images by one wavefront per pair of the plan (h8_pairs_wave_kernel) for batches of more than 8192
                               // (query, probe) words; 0: always a workgroup per query (h8_prep_pairs_kernel); 2: always a wavefront per pair
     double h8_pairs_grid = 0; // ... its grid in workgroups of 4 wavefronts (0: 4 per CU; tests: a grid smaller than the pairs)
+    double h8_pairs_plan = 1; // ... built by extra workgroups of the three-launch plan's histogram and scatter launches, found by a sweep over the probe
+                              // words (ivf_hist_pairs_kernel, ivf_scatter_pairs_kernel); 0: by h8_pairs_wave_kernel after the plan
+    double h8_pairs_split = -1; // ... the first query of the scatter launch's share (the histogram launch takes those below it; -1: half of the batch;
+                                // tests: 0 and nq put every pair into one launch)
     double h16_prune = 1;     // shadow list scan (L2): drop (query, list) pairs that provably cannot hold one of the query's k nearest rows when the lists are probed by more than a tile of queries (0: off, 2: always)
     double coarse_gemm_tq = 64; // coarse_gemm_kernel: queries per workgroup tile (64 or 128)
     double coarse_gemm_tc = 128; // ... and centroids (64 or 128)

@@ -1,5 +1,6 @@
 // device_ops.hip -- kernel instantiation + launch dispatch for the scan / merge kernels.
 #include "device_ops.hpp"
+#include "h16_scan_kernels.hpp" // the pair role of launch_ivf_plan_pairs
 
 #include <atomic>
 #include <map>
@@ -277,6 +278,33 @@ void launch_ivf_plan(const IvfPlanParams & p, hipStream_t stream)
     MSVS_HIP(hipGetLastError());
 }
 
+bool ivf_plan_carries_pairs(const IvfPlanParams & p)
+{
+    return p.n_pairs != 0 && !ivf_plan_fused(p) && p.nlist <= PLAN_LDS_LISTS && options().plan_lds != 0 && options().h8_pairs_plan != 0;
+}
+
+void launch_ivf_plan_pairs(const IvfPlanParams & p, const H8PairsParams & a, uint32_t q_split, uint32_t pairs_grid, hipStream_t stream)
+{
+    ProfileScope prof("ivf_plan", stream);
+    const unsigned g = (unsigned)ceil_div(p.n_pairs, PLAN_CHUNK);
+    q_split = std::min(q_split, a.nq);
+    // (a launch whose share of the queries is empty is the plan's own kernel)
+    const unsigned g1 = h8_sweep_blocks(0, q_split, a.nprobe, pairs_grid), g2 = h8_sweep_blocks(q_split, a.nq, a.nprobe, pairs_grid);
+    with_int<1, 2>(h8_hold(a.nch8), [&](auto hold) {
+        constexpr int HOLD = decltype(hold)::value;
+        if (g1)
+            hipLaunchKernelGGL(ivf_hist_pairs_kernel<HOLD>, dim3(g + g1), dim3(256), 0, stream, p, a, (uint32_t)g, 0u, q_split);
+        else
+            hipLaunchKernelGGL(ivf_hist_lds_kernel, dim3(g), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL(ivf_plan_scan_kernel<false>, dim3(1), dim3(1024), 0, stream, p);
+        if (g2)
+            hipLaunchKernelGGL(ivf_scatter_pairs_kernel<HOLD>, dim3(g + g2), dim3(256), 0, stream, p, a, (uint32_t)g, q_split, a.nq);
+        else
+            hipLaunchKernelGGL(ivf_scatter_lds_kernel, dim3(g), dim3(256), 0, stream, p);
+    });
+    MSVS_HIP(hipGetLastError());
+}
+
 void GroupedPlan::run(const int32_t * probes, const int64_t * list_off, size_t n_pairs, uint32_t rows_per_block, uint32_t T, hipStream_t stream,
                       const int64_t * whole_off) const
 {
@@ -518,7 +546,7 @@ const OptionField g_option_fields[] = {
     {"h16_nocut", &Options::h16_nocut},     {"fb_cap", &Options::fb_cap},           {"rerank_second", &Options::rerank_second}, {"rerank_fused", &Options::rerank_fused},
     {"lat_path", &Options::lat_path},         {"filter_compact_below", &Options::filter_compact_below},
     {"bm25_wave", &Options::bm25_wave},     {"rerank_hint", &Options::rerank_hint}, {"rerank_chain", &Options::rerank_chain}, {"coarse_band", &Options::coarse_band}, {"coarse_tail", &Options::coarse_tail}, {"merge_small", &Options::merge_small}, {"route_streams", &Options::route_streams}, {"coarse_slow_inline", &Options::coarse_slow_inline}, {"coarse_slow_window", &Options::coarse_slow_window}, {"coarse_gemm_tq", &Options::coarse_gemm_tq}, {"coarse_gemm_tc", &Options::coarse_gemm_tc}, {"h16_prune", &Options::h16_prune}, {"h16_feedback", &Options::h16_feedback}, {"h16_group_appends", &Options::h16_group_appends}, {"h16_preprune", &Options::h16_preprune}, {"lat_prune", &Options::lat_prune}, {"lat_items", &Options::lat_items}, {"lat_hint", &Options::lat_hint},     {"bm25_posting", &Options::bm25_posting}, {"bm25_sub_docs", &Options::bm25_sub_docs}, {"bm25_dbg", &Options::bm25_dbg},
-    {"h8_pairs", &Options::h8_pairs}, {"h8_pairs_grid", &Options::h8_pairs_grid},
+    {"h8_pairs", &Options::h8_pairs}, {"h8_pairs_grid", &Options::h8_pairs_grid}, {"h8_pairs_plan", &Options::h8_pairs_plan}, {"h8_pairs_split", &Options::h8_pairs_split},
     {"h16_rho", &Options::h16_rho}, {"h16_form", &Options::h16_form}, {"h16_segs", &Options::h16_segs}, {"h16_stamps", &Options::h16_stamps}, {"h16_items", &Options::h16_items},   {"flat_h16", &Options::flat_h16},     {"flat_segb", &Options::flat_segb}, {"flat_rot", &Options::flat_rot}, {"flat_lazy_flush", &Options::flat_lazy_flush},   {"flat_ncb", &Options::flat_ncb},
     {"bm25_emit", &Options::bm25_emit},     {"bm25_cand_cap", &Options::bm25_cand_cap},
     {"flat_few", &Options::flat_few},

@@ -100,6 +100,12 @@ void launch_ivf_scan(int metric, ScanParams a, hipStream_t stream);
 void launch_ivf_plan(const IvfPlanParams & p, hipStream_t stream);
 /// ... in ONE launch (small batches: nothing to zero beforehand, p.zero cleared on the way)?
 bool ivf_plan_fused(const IvfPlanParams & p);
+/// The three-launch LDS form with the i8r pair images of an L2 batch (h16_scan_kernels.hpp: H8PairsParams, a.pairs / a.pair_off
+/// unused) built by extra workgroups of the histogram launch (queries below q_split) and of the scatter launch (the rest), at most
+/// pairs_grid workgroups each.  a.qmm must be zero before the first launch.  Only where ivf_plan_carries_pairs(p).
+struct H8PairsParams;
+bool ivf_plan_carries_pairs(const IvfPlanParams & p);
+void launch_ivf_plan_pairs(const IvfPlanParams & p, const H8PairsParams & a, uint32_t q_split, uint32_t pairs_grid, hipStream_t stream);
 /// Only the two exclusive scans again (pair_off, work_off) for another row range / work-item size of the same pairs.
 void launch_ivf_plan_rescan(const IvfPlanParams & p, hipStream_t stream);
 

@@ -565,12 +565,15 @@ struct H8PairsParams
 };
 
 // 16-element pieces per lane whose differences stay in registers between the reductions and the quantisation (32 VGPRs each): all
-// of them up to d = 2048; the pieces past that are loaded a second time.
+// of them up to d = 2048; the pieces past that are loaded a second time.  The L2 pair kernels take the count as a template argument
+// (h8_hold): ONE where a lane owns at most one piece (8 nch8 <= 64, d <= 1024) -- 150 instead of 176 VGPRs, a third wavefront per SIMD.
 constexpr int H8_HOLD = 2;
+inline int h8_hold(const uint32_t nch8) { return 8 * nch8 <= 64 ? 1 : 2; }
 
 /// One pair: the arithmetic of h8_prep_pairs_kernel's probe loop, lane-to-piece map (t = lane, lane + 64, ...) and reduction order
 /// included, over operands read once.  |q|^2 keeps its own sweep (float4 groups strided by 256 elements): folding it into the pieces
 /// would change the order of its f64 sum; its loads are in flight together with the pieces'.
+template <int HOLD>
 __device__ __forceinline__ void h8_pair_wave(const H8PairsParams & a, const uint32_t pair, const uint32_t lane)
 {
     const uint32_t qp = (uint32_t)__builtin_amdgcn_readfirstlane((int)pair); // (the same in every lane: scalar address arithmetic)
@@ -579,9 +582,9 @@ __device__ __forceinline__ void h8_pair_wave(const H8PairsParams & a, const uint
     const float * src = a.Q + (size_t)q * ld;
     const float * c = a.cents + (size_t)l * ld;
     const uint32_t npc = a.nch8 * 8;
-    double d[H8_HOLD][16];
+    double d[HOLD][16];
 #pragma unroll
-    for (int u = 0; u < H8_HOLD; u++)
+    for (int u = 0; u < HOLD; u++)
         if (lane + 64 * u < npc)
             h8_load_diff(src, c, 16 * (lane + 64 * u), ld, d[u]);
     double qq = 0.0;
@@ -592,7 +595,7 @@ __device__ __forceinline__ void h8_pair_wave(const H8PairsParams & a, const uint
     }
     double mx = 0.0, dd = 0.0;
 #pragma unroll
-    for (int u = 0; u < H8_HOLD; u++)
+    for (int u = 0; u < HOLD; u++)
         if (lane + 64 * u < npc)
         {
 #pragma unroll
@@ -602,7 +605,7 @@ __device__ __forceinline__ void h8_pair_wave(const H8PairsParams & a, const uint
                 dd += d[u][i] * d[u][i];
             }
         }
-    for (uint32_t t = lane + 64 * H8_HOLD; t < npc; t += 64)
+    for (uint32_t t = lane + 64 * HOLD; t < npc; t += 64)
     {
         double e[16];
         h8_load_diff(src, c, 16 * t, ld, e);
@@ -638,10 +641,10 @@ __device__ __forceinline__ void h8_pair_wave(const H8PairsParams & a, const uint
         out[(2 * ch + 1) * 8 + j] = h8_pack(vl);
     };
 #pragma unroll
-    for (int u = 0; u < H8_HOLD; u++)
+    for (int u = 0; u < HOLD; u++)
         if (lane + 64 * u < npc)
             quantise(lane + 64 * u, d[u]);
-    for (uint32_t t = lane + 64 * H8_HOLD; t < npc; t += 64)
+    for (uint32_t t = lane + 64 * HOLD; t < npc; t += 64)
     {
         double e[16];
         h8_load_diff(src, c, 16 * t, ld, e);
@@ -672,12 +675,13 @@ __device__ __forceinline__ void h8_pair_wave(const H8PairsParams & a, const uint
 /// dropped -- probed lists without rows: a shard's foreign lists, an empty list -- have no key, but h8_prep_pairs_kernel counts their
 /// C_p (0 or +inf: alpha = beta = 0) in the query's minimum and maximum: a sweep over the probe words finds them, 64 per
 /// wavefront and step, and gives each the same treatment.
+template <int HOLD>
 static __global__ __launch_bounds__(256) void h8_pairs_wave_kernel(const H8PairsParams a)
 {
     const uint32_t lane = threadIdx.x & 63, w0 = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
     const uint32_t npairs = a.pair_off[a.nlist];
     for (uint32_t i = w0; i < npairs; i += nw)
-        h8_pair_wave(a, a.pairs[i], lane);
+        h8_pair_wave<HOLD>(a, a.pairs[i], lane);
     const uint32_t nall = a.nq * a.nprobe;
     for (uint32_t base = w0 * 64; base < nall; base += nw * 64)
     {
@@ -685,10 +689,89 @@ static __global__ __launch_bounds__(256) void h8_pairs_wave_kernel(const H8Pairs
         uint64_t m = __ballot(l >= 0 && !(a.whole_off[l + 1] > a.whole_off[l]));
         while (m)
         {
-            h8_pair_wave(a, base + (uint32_t)__builtin_ctzll(m), lane);
+            h8_pair_wave<HOLD>(a, base + (uint32_t)__builtin_ctzll(m), lane);
             m &= m - 1;
         }
     }
+}
+
+// The same pairs WITHOUT the plan (option h8_pairs_plan): everything h8_pair_wave reads and writes is indexed by the probe word
+// qp = q * nprobe + p -- the plan's pair list only says which words survived, and the words say so themselves (l >= 0).  So the
+// pairs of the queries [q_lo, q_hi) are found by a sweep over their probe words, with or without rows in their lists (the two loops
+// above in one, every pair once), and the work needs nothing a plan launch writes: it rides in the plan's own launches as extra
+// workgroups (below), where 192 to 255 of the 256 CUs had nothing to run.
+//
+// Workgroup-to-word map: a workgroup takes the probe words of H8_SWEEP_QUERIES = 3 queries' worth (3 nprobe consecutive words, at
+// most 256: a thread each; the chunks do not care where a query begins), its threads append the surviving words to a list in LDS
+// (one LDS atomic each), and after a barrier wavefront w takes entries w, w + 4, ...  After the pre-pruning a query of the bench
+// step keeps ~1.05 of its 32 words, 5 % of the queries two or three, next to each other at the front of their probe list: three
+// queries are ~3.2 pairs for four wavefronts, five or more in about one workgroup of a hundred -- a wavefront walks ONE chain of
+// dependent reductions and the workgroups are full, where 64 words per wavefront would put two chains in series in every
+// wavefront.  The barriers cost an LDS round trip in front of a ~8 us chain.  Measured against a first form without the
+// compaction, 16 words per wavefront by a quarter-wave ballot (half of the wavefronts without a pair, the survivors of a query in
+// one wavefront): the same time at each form's best split (DESIGN 4.2 "Round 10"); this one balances an unpruned batch as well.
+// Any nprobe <= 64, any nq, any grid: the chunks are strided over the role's workgroups.
+constexpr uint32_t H8_SWEEP_QUERIES = 3;
+__host__ __device__ inline uint32_t h8_sweep_words(const uint32_t nprobe) { return nprobe * H8_SWEEP_QUERIES < 256u ? nprobe * H8_SWEEP_QUERIES : 256u; }
+
+/// The pairs of queries [q_lo, q_hi) by workgroup b0 of nb (256 threads, every one of them must call this); s_n / s_list: one word
+/// and 256 words of LDS.
+template <int HOLD>
+__device__ __forceinline__ void h8_pairs_sweep(const H8PairsParams & a, const uint32_t q_lo, const uint32_t q_hi, const uint32_t b0, const uint32_t nb,
+                                               uint32_t * s_n, uint32_t * s_list)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t lo = q_lo * a.nprobe, hi = q_hi * a.nprobe; // (nq * nprobe fits 32 bits: the plan's pair indices)
+    const uint32_t W = h8_sweep_words(a.nprobe), nchunks = (hi - lo + W - 1) / W;
+    for (uint32_t ch = b0; ch < nchunks; ch += nb) // (the same in every thread of the workgroup: the barriers are uniform)
+    {
+        if (tid == 0)
+            *s_n = 0;
+        __syncthreads();
+        const uint32_t word = lo + ch * W + tid;
+        if (tid < W && word < hi && a.probes[word] >= 0)
+            s_list[atomicAdd(s_n, 1u)] = word;
+        __syncthreads();
+        const uint32_t n = *s_n;
+        for (uint32_t i = wave; i < n; i += 4)
+            h8_pair_wave<HOLD>(a, s_list[i], lane);
+        __syncthreads(); // (the list is read: the next round may clear it)
+    }
+}
+
+/// Workgroups of a pair role for the queries [q_lo, q_hi): one per chunk, at most `grid` (>= 1).
+inline uint32_t h8_sweep_blocks(const uint32_t q_lo, const uint32_t q_hi, const uint32_t nprobe, const uint32_t grid)
+{
+    const uint64_t W = h8_sweep_words(nprobe), chunks = ((uint64_t)(q_hi - q_lo) * nprobe + W - 1) / W;
+    return (uint32_t)std::min<uint64_t>(chunks, grid);
+}
+
+/// TWO ROLES IN ONE LAUNCH: workgroups [0, g_plan) are the plan's histogram / scatter pass (scan_kernels.hpp; listed first, so
+/// dispatched first where the dispatcher goes in order -- for speed only), workgroups [g_plan, gridDim.x) build the pair images of
+/// the queries [q_lo, q_hi).  The roles share no data inside a launch -- the pair role reads the probe words, the queries and the
+/// centroids, all written by earlier launches; its stores and the plan's are read by later launches -- so there is no ticket, no
+/// fence and no spin, and nothing depends on dispatch order or placement.  Every index the plan body forms sees g_plan, not gridDim.x.
+/// The plan's 32 KB of LDS sit in the pair workgroups as well (still more workgroups per CU than the registers allow).
+template <int HOLD>
+static __global__ __launch_bounds__(256) void ivf_hist_pairs_kernel(const IvfPlanParams p, const H8PairsParams a, const uint32_t g_plan,
+                                                                    const uint32_t q_lo, const uint32_t q_hi)
+{
+    __shared__ uint32_t h[PLAN_LDS_LISTS];
+    if (blockIdx.x < g_plan) // (uniform per workgroup: the barriers of the plan body are its own)
+        plan_hist_lds(p, h, blockIdx.x);
+    else
+        h8_pairs_sweep<HOLD>(a, q_lo, q_hi, blockIdx.x - g_plan, gridDim.x - g_plan, h, h + 1);
+}
+
+template <int HOLD>
+static __global__ __launch_bounds__(256) void ivf_scatter_pairs_kernel(const IvfPlanParams p, const H8PairsParams a, const uint32_t g_plan,
+                                                                       const uint32_t q_lo, const uint32_t q_hi)
+{
+    __shared__ uint32_t h[PLAN_LDS_LISTS];
+    if (blockIdx.x < g_plan)
+        plan_scatter_lds(p, h, blockIdx.x, g_plan);
+    else
+        h8_pairs_sweep<HOLD>(a, q_lo, q_hi, blockIdx.x - g_plan, gridDim.x - g_plan, h, h + 1);
 }
 
 // ------------------------------------------------------------------------------------------ i8r under inner product and cosine

@@ -1390,58 +1390,27 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         pp.stat_first = prune2 ? 0 : 1;
     }
     pp.pairs_out = fb_out;
-    launch_ivf_plan(pp, stream);
-    pp.stat_rows = nullptr;
-    pp.pairs_out = nullptr;
-    IvfPlanParams pa = pp;
-    pa.work_off = pp.work_off2;
-    uint32_t * sample = scr.take<uint32_t>(nq * nprobe * H_ROWS);
-    uint32_t * qstate = scr.take<uint32_t>(2 * nq);
-    uint64_t * cand = scr.take<uint64_t>(nq * (size_t)pl.kc);
-    uint64_t * bound = scr.take<uint64_t>(nq);
-    uint32_t * failq = scr.take<uint32_t>(nq);
-    if (!prep_done)
-        prep(H16PrepAux{});
-    // i8r: the images of the (query, list) pairs the pre-pruning left, their constants and every query's error bound
+    // i8r: the images of the (query, list) pairs the pre-pruning left, their constants and every query's error bound.  The buffers are
+    // taken in front of the plan: where the batch takes the wavefront-per-pair form AND the plan its three LDS launches, the pairs are
+    // found by a sweep over the probe words and built by extra workgroups of the plan's histogram and scatter launches
+    // (launch_ivf_plan_pairs; option h8_pairs_plan = 0: by h8_pairs_wave_kernel after the plan, from the plan's pair list).
+    // INVARIANT: qmm is zero before the first plan launch -- the pair role's atomicMax words start there.  Every way to this point
+    // has cleared the counter block by now: the prepared counters (zeroed by the prep launch of the coarse stage), the prep launch
+    // above (aux.zero), or the memset; the fused plan, which clears them itself, never carries the pair role.
     uint4 * pimg = nullptr;
     float2 * pinfo = nullptr;
-    float * qbound = nullptr, * qoff = nullptr;
-    const float * pair_pc = nullptr;
-    H8Finish fin{};
+    float * qbound = nullptr, * qoff = nullptr, * pc = nullptr;
+    const bool per_query = ix.metric != MSVS_METRIC_L2; // inner product, cosine: one image per query, one constant per pair
+    H8PairsParams hp{};
     if (ix.h8)
     {
-        const bool per_query = ix.metric != MSVS_METRIC_L2; // inner product, cosine: one image per query, one constant per pair
         pimg = scr.take<uint4>((per_query ? nq : nq * nprobe) * (size_t)ix.h8_nch * 16 + 64);
         pinfo = scr.take<float2>(nq * nprobe);
         qbound = scr.take<float>(nq);
         qoff = scr.take<float>(nq);
-        float * pc = scr.take<float>(nq * nprobe);
-        ProfileScope prof("ivf_prep_pairs", stream);
-        if (per_query)
+        pc = scr.take<float>(nq * nprobe);
+        if (n_qmm)
         {
-            H8IpParams hp{};
-            hp.Q = dq; // (cosine: normalised by the caller)
-            hp.cents = ix.centroids.p;
-            hp.probes = plan_probes;
-            hp.whole_off = pp.whole_off;
-            hp.list_ab = ix.h8_list.p;
-            hp.nq = (uint32_t)nq;
-            hp.ld = ld;
-            hp.nprobe = (uint32_t)nprobe;
-            hp.nch8 = ix.h8_nch;
-            hp.lim = i8r_limit(ix.dim);
-            hp.xmax = ix.xnorm_max;
-            hp.img = pimg;
-            hp.pinfo = pinfo;
-            hp.pc = pc;
-            hp.qbound = qbound;
-            hp.qoff = qoff;
-            hipLaunchKernelGGL(h8_ip_prep_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, hp);
-        }
-        else if (n_qmm)
-        {
-            // one wavefront per pair of the plan; the cut kernel below finishes qbound / qoff (H8Finish)
-            H8PairsParams hp{};
             hp.Q = dq;
             hp.cents = ix.centroids.p;
             hp.probes = plan_probes;
@@ -1461,17 +1430,70 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
             hp.pc = pc;
             hp.qmm = qmm;
             hp.qxq = scr.take<double>(nq);
-            fin.qmm = qmm;
-            fin.qxq = hp.qxq;
-            fin.qbound = qbound;
-            fin.qoff = qoff;
-            const uint32_t pgrid = options().h8_pairs_grid >= 1 ? (uint32_t)options().h8_pairs_grid : device_cu_count() * 4;
-            hipLaunchKernelGGL(h8_pairs_wave_kernel, dim3(pgrid), dim3(256), 0, stream, hp);
         }
+    }
+    const uint32_t pgrid = options().h8_pairs_grid >= 1 ? (uint32_t)options().h8_pairs_grid : device_cu_count() * 4;
+    const bool pairs_in_plan = n_qmm != 0 && ivf_plan_carries_pairs(pp);
+    if (pairs_in_plan)
+    {
+        const double split = options().h8_pairs_split;
+        launch_ivf_plan_pairs(pp, hp, split >= 0 ? (uint32_t)std::min<double>(split, (double)nq) : (uint32_t)(nq / 2), pgrid, stream);
+    }
+    else
+        launch_ivf_plan(pp, stream);
+    pp.stat_rows = nullptr;
+    pp.pairs_out = nullptr;
+    IvfPlanParams pa = pp;
+    pa.work_off = pp.work_off2;
+    uint32_t * sample = scr.take<uint32_t>(nq * nprobe * H_ROWS);
+    uint32_t * qstate = scr.take<uint32_t>(2 * nq);
+    uint64_t * cand = scr.take<uint64_t>(nq * (size_t)pl.kc);
+    uint64_t * bound = scr.take<uint64_t>(nq);
+    uint32_t * failq = scr.take<uint32_t>(nq);
+    if (!prep_done)
+        prep(H16PrepAux{});
+    // i8r: the pairs' images, unless the plan's launches have built them
+    const float * pair_pc = nullptr;
+    H8Finish fin{};
+    if (n_qmm) // the cut kernel below finishes qbound / qoff (H8Finish)
+    {
+        fin.qmm = qmm;
+        fin.qxq = hp.qxq;
+        fin.qbound = qbound;
+        fin.qoff = qoff;
+        pair_pc = pc;
+    }
+    if (ix.h8 && !pairs_in_plan)
+    {
+        ProfileScope prof("ivf_prep_pairs", stream);
+        if (per_query)
+        {
+            H8IpParams ip{};
+            ip.Q = dq; // (cosine: normalised by the caller)
+            ip.cents = ix.centroids.p;
+            ip.probes = plan_probes;
+            ip.whole_off = pp.whole_off;
+            ip.list_ab = ix.h8_list.p;
+            ip.nq = (uint32_t)nq;
+            ip.ld = ld;
+            ip.nprobe = (uint32_t)nprobe;
+            ip.nch8 = ix.h8_nch;
+            ip.lim = i8r_limit(ix.dim);
+            ip.xmax = ix.xnorm_max;
+            ip.img = pimg;
+            ip.pinfo = pinfo;
+            ip.pc = pc;
+            ip.qbound = qbound;
+            ip.qoff = qoff;
+            hipLaunchKernelGGL(h8_ip_prep_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, ip);
+        }
+        else if (n_qmm) // one wavefront per pair of the plan
+            with_int<1, 2>(h8_hold(hp.nch8), [&](auto hold) {
+                hipLaunchKernelGGL(h8_pairs_wave_kernel<decltype(hold)::value>, dim3(pgrid), dim3(256), 0, stream, hp);
+            });
         else
             hipLaunchKernelGGL(h8_prep_pairs_kernel, dim3((unsigned)nq), dim3(256), 0, stream, dq, (uint32_t)nq, ld, ix.centroids.p, plan_probes,
                                (uint32_t)nprobe, ix.h8_nch, ix.h8_list.p, i8r_limit(ix.dim), ix.xnorm_max, pimg, pinfo, pc, qbound, qoff);
-        pair_pc = n_qmm ? pc : nullptr;
     }
     // (no fill of `sample`: the sample launch writes all 32 words of every pair whose list has rows, and the cut kernels
     // take a pair whose list is empty as 32 missing rows)

@@ -699,18 +699,21 @@ static __device__ __forceinline__ void plan_write_items_wave(IvfItem * table, co
     }
 }
 
-/// ... by a launch that runs after the scans are final (the scatter launches): a grid-stride loop over the lists.
-static __device__ __forceinline__ void plan_write_items_grid(const IvfPlanParams & p)
+/// ... by a launch that runs after the scans are final (the scatter launches): a grid-stride loop over the lists.  bid / nblocks:
+/// the workgroup's index among the launch's PLAN workgroups and their number (a launch may hold workgroups of another role behind
+/// them: ivf_scatter_pairs_kernel).
+static __device__ __forceinline__ void plan_write_items_grid(const IvfPlanParams & p, const uint32_t bid, const uint32_t nblocks)
 {
     if (!p.items && !p.items2)
         return;
     const uint32_t seg_blocks = p.seg_out ? p.seg_out[0] : 0u;
-    for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < p.nlist; l += gridDim.x * blockDim.x)
+    for (uint32_t l = bid * blockDim.x + threadIdx.x; l < p.nlist; l += nblocks * blockDim.x)
     {
         const uint32_t p0 = p.pair_off[l];
         plan_write_items(p, l, p.work_off[l], p.work_off2 ? p.work_off2[l] : 0u, p0, p.pair_off[l + 1] - p0, seg_blocks);
     }
 }
+static __device__ __forceinline__ void plan_write_items_grid(const IvfPlanParams & p) { plan_write_items_grid(p, blockIdx.x, gridDim.x); }
 
 static __global__ void ivf_hist_kernel(const IvfPlanParams p)
 {
@@ -919,14 +922,16 @@ static __global__ void ivf_scatter_kernel(const IvfPlanParams p)
 // 1024 lists, hot lists holding > 1000 pairs) the one-atomic-per-pair kernels spend 36 us each queueing on the hot
 // addresses; the scatter also hands every block ONE contiguous range per list (base from a single atomicAdd of the
 // block's count, rank inside the block from the LDS atomic).
-static __global__ __launch_bounds__(256) void ivf_hist_lds_kernel(const IvfPlanParams p)
+/// Both passes take the workgroup's index among the launch's plan workgroups (bid of nblocks) and its 32 KB of LDS counters from the
+/// kernel: the plan's own launches below, and the launches that carry a second role behind the plan's workgroups
+/// (h16_scan_kernels.hpp: ivf_hist_pairs_kernel, ivf_scatter_pairs_kernel).  256 threads.
+static __device__ __forceinline__ void plan_hist_lds(const IvfPlanParams & p, uint32_t * h, const uint32_t bid)
 {
-    __shared__ uint32_t h[PLAN_LDS_LISTS];
     const uint32_t tid = threadIdx.x;
     for (uint32_t l = tid; l < p.nlist; l += 256)
         h[l] = 0;
     __syncthreads();
-    const uint32_t base = blockIdx.x * PLAN_CHUNK, end = min(base + PLAN_CHUNK, p.n_pairs);
+    const uint32_t base = bid * PLAN_CHUNK, end = min(base + PLAN_CHUNK, p.n_pairs);
 #pragma unroll
     for (uint32_t u = 0; u < PLAN_CHUNK / 256; u++)
     {
@@ -940,14 +945,13 @@ static __global__ __launch_bounds__(256) void ivf_hist_lds_kernel(const IvfPlanP
             atomicAdd(&p.cnt[l], h[l]);
 }
 
-static __global__ __launch_bounds__(256) void ivf_scatter_lds_kernel(const IvfPlanParams p)
+static __device__ __forceinline__ void plan_scatter_lds(const IvfPlanParams & p, uint32_t * h, const uint32_t bid, const uint32_t nblocks)
 {
-    __shared__ uint32_t h[PLAN_LDS_LISTS];
     const uint32_t tid = threadIdx.x;
     for (uint32_t l = tid; l < p.nlist; l += 256)
         h[l] = 0;
     __syncthreads();
-    const uint32_t base = blockIdx.x * PLAN_CHUNK, end = min(base + PLAN_CHUNK, p.n_pairs);
+    const uint32_t base = bid * PLAN_CHUNK, end = min(base + PLAN_CHUNK, p.n_pairs);
     int32_t list[PLAN_CHUNK / 256];
     uint32_t rank[PLAN_CHUNK / 256];
 #pragma unroll
@@ -967,7 +971,19 @@ static __global__ __launch_bounds__(256) void ivf_scatter_lds_kernel(const IvfPl
     for (uint32_t u = 0; u < PLAN_CHUNK / 256; u++)
         if (list[u] >= 0)
             p.pairs[h[list[u]] + rank[u]] = base + u * 256 + tid;
-    plan_write_items_grid(p);
+    plan_write_items_grid(p, bid, nblocks);
+}
+
+static __global__ __launch_bounds__(256) void ivf_hist_lds_kernel(const IvfPlanParams p)
+{
+    __shared__ uint32_t h[PLAN_LDS_LISTS];
+    plan_hist_lds(p, h, blockIdx.x);
+}
+
+static __global__ __launch_bounds__(256) void ivf_scatter_lds_kernel(const IvfPlanParams p)
+{
+    __shared__ uint32_t h[PLAN_LDS_LISTS];
+    plan_scatter_lds(p, h, blockIdx.x, gridDim.x);
 }
 
 /// A work item of a grouped plan (IvfPlanParams): the rows [row_begin, row_end) of segment `seg` of list `list` for the pairs
