@@ -284,6 +284,68 @@ MSVS_API int msvs_pq_index_export(const msvs_pq_index_t * index, float * centroi
 MSVS_API int msvs_pq_index_serialize_io(const msvs_pq_index_t * index, const struct msvs_io * io);
 MSVS_API int msvs_pq_index_load_io(const struct msvs_io * io, msvs_pq_index_t ** out);
 
+/* Two-stage search -- the exact re-rank of a coded index's candidates (Faiss: IndexRefineFlat; the reference's index interface:
+ * computeTopDistanceSubset / supportTwoStageSearch).  IVFSQ and IVFPQ return labels with the quantiser's distances; scored again
+ * against the original f32 rows, the best k of kc candidates carry the canonical distances FLAT and IVFFLAT report.
+ *
+ * Row store (msvs_rows_*): an append-only table of f32 rows in which ROW i IS LABEL i -- part-local row offsets, the labels the coded
+ * indexes carry when add gets ids = NULL.  Row stride round_up(dim, 4) floats, zero padded.
+ *   create: 1 <= dim <= 8192 and placement MSVS_ROWS_DEVICE / MSVS_ROWS_HOST_PINNED (MSVS_ERR_INVALID_ARGUMENT otherwise);
+ *     capacity_rows is fixed here and <= 2^32 - 1 (MSVS_ERR_ID_RANGE otherwise).  normalize != 0 stores msvs_normalize_f32's rows
+ *     (the same arithmetic, the same skip of rows whose norm is below FLT_EPSILON), as msvs_block_upload does for cosine.
+ *     MSVS_ROWS_HOST_PINNED keeps the table in mapped, pinned host memory, which the kernel reads directly: only labels and queries
+ *     live in device memory, and the kernel is the same for both placements.
+ *   append: chunks of n dense rows, host or device (mem), like the indexes' add; beyond the capacity: MSVS_ERR_INVALID_ARGUMENT (and
+ *     nothing is appended).  Not concurrent with a refine; refines are re-entrant on a store that is no longer appended to.
+ *   num / dim / normalized: what the store holds (0 for NULL).  memory_usage: DEVICE bytes -- the table for MSVS_ROWS_DEVICE, 0 for
+ *     a pinned store.  There are no files: the rows are the part's column, the host feeds them again.
+ *
+ * refine (host pointers; stages, runs, copies back, synchronises) / refine_device (device pointers, enqueued on hip_stream without
+ * host synchronisation): queries nq * dim, cand nq * kc labels, ids / dis nq * k.  For each query:
+ *   - every candidate label c with 0 <= c < msvs_rows_num is scored against stored row c with the canonical scan arithmetic: 64
+ *     partial sums (accumulator e mod 64 for element e), multiply and add separately rounded, no fma, folded by the adjacent pairwise
+ *     tree -- the arithmetic of msvs_knn_f32 and the FLAT / IVFFLAT searches, bit for bit;
+ *   - labels < 0 (the first stage's padding) are skipped wherever they stand in the list, labels >= num too;
+ *   - a label that occurs twice is returned as often as it occurs;
+ *   - a candidate enters only if strictly better than the metric's neutral value (+-FLT_MAX); NaN never enters;
+ *   - order: (distance ascending -- descending for IP --, then label ascending); unfilled slots are -1 and the neutral value;
+ *   - cosine needs a store created with normalize=1, L2 and IP one with normalize=0 (MSVS_ERR_INVALID_ARGUMENT otherwise); cosine
+ *     normalises the queries, searches with IP and reports fl(1 - ip) in every slot, as the indexes do;
+ *   - k <= MSVS_MAX_K and kc <= MSVS_REFINE_MAX_CAND (MSVS_ERR_UNSUPPORTED_K beyond either); k may exceed kc, the rest are pads;
+ *     k = 0 or nq = 0 is a no-op; a metric outside L2 / IP / COSINE -> MSVS_ERR_NOT_IMPLEMENTED; null arguments ->
+ *     MSVS_ERR_INVALID_ARGUMENT.
+ *
+ * search_refine[_device] of the coded indexes: the index's own search[_device] with kc results (kc <= MSVS_MAX_K; params / nprobe
+ * and the filter apply here), the labels kept on the device, then refine_device with the index's metric -- no host round trip between
+ * the stages.  rows' dim must be the index's and normalized == (metric is cosine), and k <= kc: MSVS_ERR_INVALID_ARGUMENT otherwise.
+ * The result equals refine applied to search(kc)'s labels. */
+#define MSVS_REFINE_MAX_CAND 1024
+typedef struct msvs_rows msvs_rows_t;
+enum msvs_rows_placement { MSVS_ROWS_DEVICE = 0, MSVS_ROWS_HOST_PINNED = 1 };
+MSVS_API int msvs_rows_create(size_t dim, int normalize, int placement, size_t capacity_rows, msvs_rows_t ** out);
+MSVS_API int msvs_rows_append(msvs_rows_t * rows, const float * x, size_t n, int mem);
+MSVS_API size_t msvs_rows_num(const msvs_rows_t * rows);
+MSVS_API size_t msvs_rows_dim(const msvs_rows_t * rows);
+MSVS_API int msvs_rows_normalized(const msvs_rows_t * rows);
+MSVS_API size_t msvs_rows_memory_usage(const msvs_rows_t * rows);
+MSVS_API void msvs_rows_free(msvs_rows_t * rows);
+MSVS_API int msvs_refine(const msvs_rows_t * rows, int metric, const float * queries, size_t nq, const int64_t * cand, size_t kc,
+                         size_t k, int64_t * ids, float * dis);
+MSVS_API int msvs_refine_device(const msvs_rows_t * rows, int metric, const float * d_queries, size_t nq, const int64_t * d_cand,
+                                size_t kc, size_t k, int64_t * d_ids, float * d_dis, void * hip_stream);
+MSVS_API int msvs_sq_index_search_refine(const msvs_sq_index_t * index, const msvs_rows_t * rows, const float * queries, size_t nq,
+                                         size_t k, size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits,
+                                         int64_t * ids, float * dis);
+MSVS_API int msvs_sq_index_search_refine_device(const msvs_sq_index_t * index, const msvs_rows_t * rows, const float * d_queries,
+                                                size_t nq, size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits,
+                                                size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream);
+MSVS_API int msvs_pq_index_search_refine(const msvs_pq_index_t * index, const msvs_rows_t * rows, const float * queries, size_t nq,
+                                         size_t k, size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits,
+                                         int64_t * ids, float * dis);
+MSVS_API int msvs_pq_index_search_refine_device(const msvs_pq_index_t * index, const msvs_rows_t * rows, const float * d_queries,
+                                                size_t nq, size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits,
+                                                size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream);
+
 /* Resident blocks for the brute-force path: the GPU analogue of VICacheManager / VIWithMeta
  * (src/VectorIndex/Cache/VICacheObject.h:40-162) for the dense block a mark of a part turns into
  * (MergeTreeVSManager.cpp:1380-1392).  msvs_knn_f32 moves that block over PCIe on every query; here it is uploaded

@@ -15,6 +15,8 @@ METRIC_L2, METRIC_IP, METRIC_COSINE, METRIC_HAMMING, METRIC_JACCARD = 0, 1, 2, 3
 INDEX_FLAT, INDEX_IVFFLAT = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 MAX_K = 256
+REFINE_MAX_CAND = 1024  # MSVS_REFINE_MAX_CAND: candidates per query of refine()
+ROWS_DEVICE, ROWS_HOST_PINNED = 0, 1  # msvs_rows_placement
 MAX_K_ROUNDS = 4096  # MSVS_MAX_K_ROUNDS: the BM25, device-fusion and (non-sharded, non-binary) vector searches go this far in exact rounds
 METRICS = {"L2": METRIC_L2, "IP": METRIC_IP, "Cosine": METRIC_COSINE, "COSINE": METRIC_COSINE, "cosine": METRIC_COSINE}
 
@@ -47,6 +49,9 @@ SYMBOLS = [
     "msvs_pq_index_build", "msvs_pq_index_ready", "msvs_pq_index_num_data", "msvs_pq_index_num_lists", "msvs_pq_index_memory_usage",
     "msvs_pq_index_bit_size", "msvs_pq_index_query_tables", "msvs_pq_index_export_row_terms",
     "msvs_pq_index_search", "msvs_pq_index_search_device", "msvs_pq_index_export", "msvs_pq_index_serialize_io", "msvs_pq_index_load_io",
+    "msvs_rows_create", "msvs_rows_append", "msvs_rows_num", "msvs_rows_dim", "msvs_rows_normalized", "msvs_rows_memory_usage",
+    "msvs_rows_free", "msvs_refine", "msvs_refine_device", "msvs_sq_index_search_refine", "msvs_sq_index_search_refine_device",
+    "msvs_pq_index_search_refine", "msvs_pq_index_search_refine_device",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
     "msvs_comm_free", "msvs_comm_all_reduce_u64", "msvs_comm_rank", "msvs_comm_size", "msvs_shard_search_device", "msvs_shard_search_device_async", "msvs_shard_search_drain", "msvs_shard_search_routed_device",
@@ -361,6 +366,24 @@ class _CodedIndex:
                                          C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
                                          C.c_void_p(int(stream)) if stream else None))
 
+    def search_refine(self, rows, queries, k, kc, params="", alive=None, nbits=None):
+        """The two-stage search: search(kc)'s labels scored against `rows` (a Rows whose row i is label i), the best k with the
+        canonical distances.  params, alive and nbits are search's and apply to the first stage."""
+        q = _f32(queries).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), np.int64)
+        dis = np.empty((q.shape[0], k), np.float32)
+        bits = None if alive is None else pack_bits(alive)
+        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
+        _check(self._fn("search_refine")(self._h, rows._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), C.c_size_t(kc),
+                                         params.encode(), _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        return ids, dis
+
+    def search_refine_device(self, rows, d_queries, nq, k, kc, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """search_refine with raw device addresses (ints); enqueues both stages on `stream` and returns immediately."""
+        _check(self._fn("search_refine_device")(self._h, rows._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(kc),
+                                                C.c_size_t(nprobe), self._dev(d_alive), C.c_size_t(nbits), C.c_void_p(int(d_ids)),
+                                                C.c_void_p(int(d_dis)), self._dev(stream)))
+
     def serialize_io(self, store):
         """msvs_{sq,pq}_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""
         _check(self._fn("serialize_io")(self._h, C.byref(_DictIO(store).io)))
@@ -493,6 +516,74 @@ class PqIndex(_CodedIndex):
         query_tables from the loaded index; where given, they must agree with it (ValueError otherwise)."""
         h, (f_metric, f_dim, f_m) = cls._load(store, "pq_data", "<iQQ")
         return cls(f_metric, f_dim, _handle=h, _m=f_m)._agree("IVFPQ", metric=metric, dim=dim, m=m, bits=bits, query_tables=query_tables)
+
+
+class Rows:
+    """msvs_rows_t: the row store of a two-stage search -- an append-only table of f32 rows in which row i is label i, in device
+    memory (ROWS_DEVICE) or in mapped pinned host memory (ROWS_HOST_PINNED).  normalize=True stores normalize()'s rows (cosine)."""
+
+    def __init__(self, dim, capacity, normalize=False, placement=ROWS_DEVICE):
+        self.dim = int(dim)
+        self._h = C.c_void_p()
+        _check(lib().msvs_rows_create(C.c_size_t(dim), int(bool(normalize)), int(placement), C.c_size_t(capacity), C.byref(self._h)))
+        self.placement, self.capacity = int(placement), int(capacity)
+
+    def append(self, x, n=None, mem=MEM_HOST):
+        """mem=MEM_DEVICE: `x` is a raw device address (int) of n dense rows."""
+        if mem == MEM_DEVICE:
+            _check(lib().msvs_rows_append(self._h, C.c_void_p(int(x)) if x else None, C.c_size_t(n), mem))
+            return
+        x = _f32(x).reshape(-1, self.dim)
+        _check(lib().msvs_rows_append(self._h, _p(x, C.c_float), C.c_size_t(x.shape[0]), MEM_HOST))
+
+    def _size(self, name):
+        fn = getattr(lib(), "msvs_rows_" + name)
+        fn.restype, fn.argtypes = C.c_size_t, [C.c_void_p]
+        return fn(self._h)
+
+    @property
+    def num(self):
+        return self._size("num")
+
+    @property
+    def normalized(self):
+        fn = lib().msvs_rows_normalized
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        return bool(fn(self._h))
+
+    @property
+    def memory_usage(self):
+        """device bytes: the table of a ROWS_DEVICE store, 0 for a pinned one"""
+        return self._size("memory_usage")
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.msvs_rows_free.argtypes = [C.c_void_p]
+            _lib.msvs_rows_free.restype = None
+            _lib.msvs_rows_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def refine(rows, metric, queries, cand, k):
+    """msvs_refine: cand [nq, kc] labels (int64; < 0 and >= rows.num are skipped) scored against rows -> (ids [nq, k], dis [nq, k])."""
+    q = _f32(queries).reshape(-1, rows.dim)
+    cand = np.ascontiguousarray(cand, np.int64)
+    if cand.ndim != 2:
+        cand = cand.reshape(q.shape[0], -1)
+    ids = np.empty((q.shape[0], k), np.int64)
+    dis = np.empty((q.shape[0], k), np.float32)
+    _check(lib().msvs_refine(rows._h, int(metric), _p(q, C.c_float), C.c_size_t(q.shape[0]), _p(cand, C.c_int64), C.c_size_t(cand.shape[1]),
+                             C.c_size_t(k), _p(ids, C.c_int64), _p(dis, C.c_float)))
+    return ids, dis
+
+
+def refine_device(rows, metric, d_queries, nq, d_cand, kc, k, d_ids, d_dis, stream=0):
+    """msvs_refine_device: all buffers are raw device addresses (ints); enqueues on `stream` and returns immediately."""
+    _check(lib().msvs_refine_device(rows._h, int(metric), C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_void_p(int(d_cand)) if d_cand else None,
+                                    C.c_size_t(kc), C.c_size_t(k), C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
+                                    C.c_void_p(int(stream)) if stream else None))
 
 
 def normalize(x):

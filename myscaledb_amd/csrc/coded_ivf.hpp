@@ -4,6 +4,7 @@
 // callable (a lambda at the call site) or a plain argument; `name` is "IVFSQ" / "IVFPQ" for the messages.
 // Reused as they are: the k-means trainer (temporary IVFFLAT indexes), the assignment kernel, flat_search_device for the coarse
 // step, GroupedPlan, plan_segments, launch_ivf_merge, Scratch, normalize_device_rows, upload_rows, list_major_layout.
+// Also here: the two-stage search both indexes offer (search_refine_device: their own search, then refine.hip's exact re-rank).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -499,6 +500,39 @@ inline void search_host(const CodedIvf * ix, const char * name, const float * qu
     MSVS_HIP(hipMemcpyAsync(ids, d_ids, nq * k * 8, hipMemcpyDeviceToHost, stream));
     MSVS_HIP(hipMemcpyAsync(dis, d_dis, nq * k * 4, hipMemcpyDeviceToHost, stream));
     MSVS_HIP(hipStreamSynchronize(stream));
+}
+
+// ------------------------------------------------------------------------------------------- two-stage search
+
+/// msvs_refine_device (refine.hip): the candidates' labels scored against the row store's f32 rows, the best k; enqueued on `stream`
+void refine_device(const msvs_rows * rows, int metric, const float * d_queries, size_t nq, const int64_t * d_cand, size_t kc, size_t k,
+                   int64_t * d_ids, float * d_dis, hipStream_t stream);
+
+/// The composed entries: first(d_cand_ids, d_cand_dis) is the index's own device search with kc results (the filter applies
+/// there), its labels stay in an arena of their own on the same stream, then the refine step with the index's metric: no host round trip between.
+template <class FirstStage>
+inline void search_refine_device(const CodedIvf & ix, const char * name, const msvs_rows * rows, const float * d_queries, size_t nq, size_t k,
+                                 size_t kc, int64_t * d_ids, float * d_dis, hipStream_t stream, FirstStage first)
+{
+    if (!rows)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "null row store");
+    if (msvs_rows_dim(rows) != ix.dim || (msvs_rows_normalized(rows) != 0) != (ix.metric == MSVS_METRIC_COSINE))
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the row store (dim %zu, normalize=%d) does not fit the %s index (dim %zu, %s)", msvs_rows_dim(rows),
+             msvs_rows_normalized(rows), name, ix.dim, ix.metric == MSVS_METRIC_COSINE ? "cosine: normalize=1" : "L2 / IP: normalize=0");
+    check_k(kc);
+    if (k > kc)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "k = %zu exceeds kc = %zu, the first stage's results", k, kc);
+    check_built(ix, name);
+    if (nq == 0 || k == 0)
+        return;
+    if (!d_queries || !d_ids || !d_dis)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
+    Scratch & aux = aux_for(stream); // (the first stage and the refine step both take scratch_for)
+    aux.reserve(nq * kc * 12 + 2 * 256, stream);
+    int64_t * c_ids = aux.take<int64_t>(nq * kc);
+    float * c_dis = aux.take<float>(nq * kc);
+    first(c_ids, c_dis);
+    refine_device(rows, ix.metric, d_queries, nq, c_ids, kc, k, d_ids, d_dis, stream);
 }
 
 // ------------------------------------------------------------------------------------------- export and files

@@ -402,6 +402,33 @@ extern "C" int msvs_pq_index_search(const msvs_pq_index_t * ix, const float * qu
     });
 }
 
+extern "C" int msvs_pq_index_search_refine_device(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * d_queries, size_t nq,
+                                                  size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits, size_t nbits,
+                                                  int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return guarded([&] {
+        check_index(ix);
+        hipStream_t stream = as_stream(hip_stream);
+        search_refine_device(*ix, PQ, rows, d_queries, nq, k, kc, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
+            pq_search_device(*ix, d_queries, nq, kc, nprobe, d_alive_bits, nbits, c_ids, c_dis, stream);
+        });
+    });
+}
+
+extern "C" int msvs_pq_index_search_refine(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * queries, size_t nq, size_t k,
+                                           size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits, int64_t * ids,
+                                           float * dis)
+{
+    return guarded([&] {
+        search_host(ix, PQ, queries, nq, k, params, alive_bits, nbits, ids, dis,
+                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
+                        search_refine_device(*ix, PQ, rows, dq, nq, k, kc, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
+                            pq_search_device(*ix, dq, nq, kc, nprobe, d_alive, nbits, c_ids, c_dis, stream);
+                        });
+                    });
+    });
+}
+
 // ------------------------------------------------------------------------------------------- export and files
 
 /// bytes of a row's codes in the data file: they are the stored row's words, little endian, without the pad (8 bits: byte s is code
