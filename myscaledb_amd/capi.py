@@ -1120,7 +1120,7 @@ def debug_prune_stats():
 def debug_rerank_rows():
     """(candidate rows the re-rank's first stage evaluated, rows its second chance evaluated), cumulative -- counted only under
     rerank_stats = 1."""
-    out = (C.c_uint64 * 3)()
+    out = (C.c_uint64 * 4)()
     _check(lib().msvs_debug_rerank_rows(out))
     return int(out[0]), int(out[1])
 
@@ -1128,9 +1128,17 @@ def debug_rerank_rows():
 def debug_rerank_skipped_chunks():
     """Chunks of second-chance buffers the re-rank skipped whole because the first stage's hint left none of their keys
     (rerank_chain = 1), cumulative -- counted only under rerank_stats = 1."""
-    out = (C.c_uint64 * 3)()
+    out = (C.c_uint64 * 4)()
     _check(lib().msvs_debug_rerank_rows(out))
     return int(out[2])
+
+
+def debug_rerank_second_chance():
+    """Queries whose first certificate failed and that entered the second chance of the re-rank, cumulative -- counted only under
+    rerank_stats = 1."""
+    out = (C.c_uint64 * 4)()
+    _check(lib().msvs_debug_rerank_rows(out))
+    return int(out[3])
 
 
 def debug_scan_rows():

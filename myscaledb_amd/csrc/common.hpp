@@ -178,7 +178,7 @@ struct Options
     double coarse_h16_min_q = 192; // coarse quantiser through the centroid shadow from this many queries on (0: only with 128-query
                                    // tiles, ~1000 queries); measured on nlist 1024: 512 queries -6 %, 256 -2.6 %, 64 +10 % (ten launches)
     double h16_target = 0;    // rows of a query's probed lists the sample cut aims to keep (0: 15 k up to nprobe 64, 25 k beyond; 10 k beyond k = 40)
-    double h16_kc = 0;        // candidates re-ranked per query after the fp16-shadow list scan (0: 32 for k <= 12, else 64)
+    double h16_kc = 0;        // candidates re-ranked per query after the fp16-shadow list scan (0: for k <= 12 32 over the fp16 shadow, 48 over the int8 residual one; else 64)
     double coarse_kc = 0;     // ... after the centroid-shadow pass
     double fb_segs = 0;       // segments per list of the canonical fallback scan (0: automatic 4 / 16)
     double coarse_mfma = 1;   // same switch for the coarse quantiser ...

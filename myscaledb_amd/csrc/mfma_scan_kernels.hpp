@@ -993,7 +993,8 @@ struct RerankParams
     // (0: the loads where each step needs them, row pieces four at a time).  The rows read and the arithmetic are the same.
     int chain = 0;
     unsigned long long * stat_rows = nullptr; // nullable (option rerank_stats): [0] += rows the first stage evaluates, [1] += the second chance,
-                                              // [2] += chunks of a second chance's buffer skipped because the hint left none of their keys
+                                              // [2] += chunks of a second chance's buffer skipped because the hint left none of their keys,
+                                              // [3] += queries whose first certificate failed and that enter the second chance
 };
 
 /// |approximate value - canonical value| <= eps for every row of the table and this query (sx, sq: upper bounds of |x|, |q|;
@@ -1452,8 +1453,10 @@ __global__ __launch_bounds__(16 * G) void ivf_rerank_kernel(const RerankParams a
 /// SECOND CHANCE of a query whose certificate failed: the canonical distance of EVERY row in its candidate buffer (everything the
 /// pass kept below the query's cut: a few hundred rows, not the kc best of them), exact top-k by ranking, certificate against
 /// the cut itself -- the smallest approximate value a row outside the buffer can have.  The first certificate compares the
-/// k-th exact distance with the kc-th approximate one (32 candidates for k <= 12): on data whose distances concentrate
-/// (1024 blobs, sigma 0.3, in R^768: the 10th and the 32nd neighbour are 3 eps apart) a sixth of the queries fail it, and the
+/// k-th exact distance with the kc-th approximate one: on data whose distances concentrate (1024 blobs, sigma 0.3, in R^768,
+/// 1M rows, nprobe 32, k = 10) the 10th and the kc-th neighbour are a few eps apart, and how many queries fail it depends on the
+/// shadow's bound and on kc -- measured per 4096 queries (profiles/r11_rerank_notes.txt 1): int8 residual shadow 250 at 32
+/// candidates, 3.5 at 48, 3.0 at 64; fp16 shadow 1.4 at 32, 0.5 at 48 and 64 (hence plan_ivf's 48 for the former) -- and the
 /// canonical scan of all their probed lists costs 20 x the step.  Here the margin is cut - e_k (rank ~250 against rank k);
 /// only a query that fails this one too, or whose buffer overflowed, goes to the canonical scan (failq_out).
 /// Not every row of the buffer is evaluated: the first stage found k rows, so their k-th exact distance E0 (ek_in) bounds the
@@ -1498,6 +1501,8 @@ __device__ __forceinline__ bool rerank_all_query(const RerankParams & a, const R
     bool ok = cnt <= b.cap; // an overflowed buffer dropped rows below the cut: nothing to certify
     if (!(chain ? rq.finite : rerank_query_finite(a.qnorm[q])))
         ok = false;         // so did NaN approximate values (rerank_query_finite)
+    if (a.stat_rows && tid == 0)
+        atomicAdd(a.stat_rows + 3, 1ull);
     __syncthreads();        // whoever used the LDS arrays before is done with them
     if (!ok)
         return false;

@@ -220,7 +220,7 @@ static unsigned long long * prefilter_fail_counter()
     if (it != per_device.end())
         return it->second;
     unsigned long long * p = nullptr;
-    MSVS_HIP(hipMalloc(&p, 128));
+    MSVS_HIP(hipMalloc(&p, 128)); // 16 words, all taken: [0 .. 14] as the readers below lay them out, [15] = msvs_debug_rerank_rows' fourth
     MSVS_HIP(hipMemset(p, 0, 128));
     per_device[dev] = p;
     return p;
@@ -322,7 +322,12 @@ static IvfSearchPlan plan_ivf(const msvs_index & ix, size_t nq, size_t nprobe, u
             // (4096 q/step: 1.92 vs 1.70 ms, 16384: 6.01 vs 5.89 ms): kept as a knob only
             p.nqg = options().ivf_nqg == 2 ? 2 : 1;
             p.T = BG_TQ * p.nqg;
-            p.kc = k <= 12 ? 32 : k <= 40 ? 64 : 256;
+            // candidate depth by shadow form and k alone.  The first certificate compares the k-th exact distance with the kc-th
+            // approximate one, and the i8r bound is ~1.6 x the fp16 one: at 32 candidates 6 % of the headline's queries fail it and
+            // take the second chance, which reads their 32 rows again; at 48 one in a thousand.  The early exit keeps the 16 extra
+            // candidates' rows from being read unless they can matter (+0.6 % first-stage rows).  64 measured level with 48, the
+            // fp16 shadow level at all three: DESIGN 4.2 "Round 11".
+            p.kc = k <= 12 ? (ix.h8 ? 48 : 32) : k <= 40 ? 64 : 256;
             if (p.h16 && options().h16_kc >= k) // experiment knob: candidates per query of the shadow pass
                 p.kc = (uint32_t)std::min<double>(k <= 40 ? 64 : 256, options().h16_kc);
             // work item = 1 slice of a list for a tile of <= 128 queries, a grid of 4096 blocks: with the selection cheap,
@@ -2333,15 +2338,17 @@ extern "C" __attribute__((visibility("default"))) int msvs_debug_rerank_stats(ui
 
 /// Tests / measurement (not in msvs.h; needs rerank_stats = 1): candidate rows the re-rank of result passes evaluated canonically,
 /// cumulative -- out3[0] = by the first stage (ivf_rerank_kernel), out3[1] = by the second chance (rerank_all_query); out3[2] =
-/// chunks of second-chance buffers skipped whole because the hint left none of their keys (rerank_chain = 1 only).
-extern "C" __attribute__((visibility("default"))) int msvs_debug_rerank_rows(uint64_t * out3)
+/// chunks of second-chance buffers skipped whole because the hint left none of their keys (rerank_chain = 1 only); out4[3] = queries
+/// whose first certificate failed and that entered the second chance.  (Every word of msvs_debug_rerank_stats is taken: its [2],
+/// [3] and [5] count the coarse quantiser's passes.)
+extern "C" __attribute__((visibility("default"))) int msvs_debug_rerank_rows(uint64_t * out4)
 {
     return guarded([&] {
-        unsigned long long v[3];
+        unsigned long long v[4];
         MSVS_HIP(hipDeviceSynchronize());
-        MSVS_HIP(hipMemcpy(v, prefilter_fail_counter() + 12, 24, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 3; i++)
-            out3[i] = v[i];
+        MSVS_HIP(hipMemcpy(v, prefilter_fail_counter() + 12, 32, hipMemcpyDeviceToHost));
+        for (int i = 0; i < 4; i++)
+            out4[i] = v[i];
     });
 }
 
