@@ -1117,6 +1117,27 @@ def debug_prune_stats():
     return int(out[0]), int(out[1])
 
 
+def debug_prune_first(nq, nprobe):
+    """The pre-pruning of this thread's last IVFFLAT search (option coarse_prune_debug = 1) -> (have, probes [nq][nprobe] with -1 for a
+    dropped pair, upre [nq], flags [nq]: bit 0 = the coarse tail's prune-first path served the query, bit 1 = the tail's band formed,
+    bits 8 and up = the lists that path could not prune under the nearest list's bound).  have = False: that search had no pre-pruning."""
+    probes = np.full((nq, nprobe), -1, np.int32)
+    upre = np.full(nq, np.inf, np.float32)
+    flags = np.zeros(nq, np.uint32)
+    have = C.c_int(0)
+    fn = lib().msvs_debug_prune_first
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]
+    _check(fn(probes.ctypes.data, upre.ctypes.data, flags.ctypes.data, nq, nprobe, C.byref(have)))
+    return bool(have.value), probes, upre, flags
+
+
+def debug_prune_first_served():
+    """Queries the coarse tail's prune-first path has served, cumulative -- counted only under coarse_prune_debug = 1."""
+    out = C.c_uint64(0)
+    _check(lib().msvs_debug_prune_first_served(C.byref(out)))
+    return int(out.value)
+
+
 def debug_rerank_rows():
     """(candidate rows the re-rank's first stage evaluated, rows its second chance evaluated), cumulative -- counted only under
     rerank_stats = 1."""

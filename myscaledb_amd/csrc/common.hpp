@@ -233,6 +233,9 @@ struct Options
     double coarse_gemm_tc = 128; // ... and centroids (64 or 128)
     double coarse_slow_inline = 1; // coarse_tail_kernel: a query without a band computed exactly by its own wavefront while such queries are rare (0: always the queue + its three launches)
     double coarse_slow_window = 64; // ... rare = none in this many batched searches of the index
+    double coarse_prune_first = 1; // coarse_tail_kernel (L2): the pre-pruning decided first, on all the words -- a query whose pruned probe list follows from them
+                                   // skips the select and the band (0: select + band, then h16_preprune_kernel for every query)
+    double coarse_prune_debug = 0; // tests and experiments: the pre-pruning's lists, bounds and flags kept for msvs_debug_prune_first, served queries counted
     double route_streams = 1; // msvs_shard_search_routed_device_async: 1 = the exchanges in the compute stream's order; 2 = on their own stream (four event hand-overs
                               // per step, and -- FRONT(i) being enqueued ahead of BACK(i - 1) -- nothing they could overlap with: 0.70 against 0.63 ms on one rank)
     double merge_small = 1;   // msvs_merge_topk_device: nparts * k <= 256 keys per query merged by one wavefront (0: pack + block merge)

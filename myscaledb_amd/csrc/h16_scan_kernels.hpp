@@ -1977,7 +1977,66 @@ struct H16Prune
     int32_t * out_probes;      // [nq][nprobe]: the probes that survive (-1: dropped or absent)
     unsigned long long * stat; // nullable: [0] += pairs dropped, [1] += pairs
     int stat_all = 1;          // the second stage: 0 = a pre-pruning (here or on the rank the probes came from) has counted the pairs
+    const uint32_t * served = nullptr; // nullable [nq], pre-pruning only: bit 0 = coarse_tail_kernel's prune-first path has written this query's
+                                       // out_probes and upre already -- h16_preprune_kernel leaves it alone
 };
+
+/// The pre-pruning's L2 bounds from an approximate centroid word -- ONE definition for h16_preprune_kernel and the prune-first path of
+/// coarse_tail_kernel (their pruned lists and bounds are compared bit for bit).  Per query: the error bound of a word, the slack of the
+/// canonical row distances.
+struct PruneL2Query
+{
+    bool usable;  // finite norms: the bounds mean something
+    double eps_c; // |word's value - canonical centroid distance| <= 2 eps_c
+    double slack; // canonical vs real row distance, both sides
+};
+
+__device__ inline PruneL2Query h16_prune_l2_query(const H16Prune & pr, const uint32_t q)
+{
+    PruneL2Query c;
+    const float qn = pr.qnorm[q];
+    c.usable = pr.xmax < 1e30f && pr.cmax < 1e30f && qn < 1e30f;
+    const double sc = sqrt((double)pr.cmax * 1.001), sq = sqrt((double)qn * 1.001), sx = sqrt((double)pr.xmax * 1.001);
+    c.eps_c = 2.0 * pr.cd_c(q) * sc * sq + pr.c_norm * (sc * sc + sq * sq) + (pr.c_canon + 4e-7) * (sc + sq) * (sc + sq) + 1e-30;
+    c.slack = 2.0 * (pr.c_canon + 4e-7) * (sx + sq) * (sx + sq) + 0.0 * (1.0 + 1e-6) + 1e-30; // (no spread of the row norms under L2)
+    return c;
+}
+
+/// ub: the list's upper bound of the query's k-th best distance (1e300: none -- fewer than k rows, no radius); lb: lower bound of its
+/// rows' distances.  cw: the centroid's word (present), r: the list's radius, len: its rows.
+__device__ inline void h16_prune_l2_bounds(const PruneL2Query & c, const uint32_t cw, const float radius, const uint64_t len, const uint32_t k,
+                                           double & ub, double & lb)
+{
+    ub = 1e300;
+    lb = 0.0;
+    const double ac = (double)ord2f(cw), r = (double)radius;
+    const double hi2 = ac + 2.0 * c.eps_c, lo2 = ac - 2.0 * c.eps_c;
+    if (len >= k && r == r && hi2 == hi2)
+    {
+        const double hi = sqrt(hi2 > 0.0 ? hi2 : 0.0) * (1.0 + 1e-7) + r;
+        ub = hi * hi * (1.0 + 1e-7);
+    }
+    if (lo2 > 0.0)
+    {
+        const double lo = sqrt(lo2) * (1.0 - 1e-7);
+        if (lo > r)
+            lb = (lo - r) * (lo - r) * (1.0 - 1e-7);
+    }
+}
+
+/// U + slack as the list scan's second stage reads it: a float, rounded up (+inf: no bound).
+__device__ inline float h16_prune_upre(const bool usable, const double U, const double slack)
+{
+    float u = __uint_as_float(0x7f800000u);
+    if (usable && U < 1e299)
+    {
+        const double v = U + slack;
+        u = v < 3.0e38 ? (float)v : u;
+        if ((double)u < v)
+            u = nextafterf(u, __uint_as_float(0x7f800000u));
+    }
+    return u;
+}
 
 /// PRE-PRUNING (round 4; L2 indexes, no filter): before a single sample row is scored, the list radius alone rules most pairs
 /// out on data with cluster structure.  Every row of probed list p lies within ||q - c_p|| + r_p of the query, so a list with at
@@ -1993,9 +2052,12 @@ static __global__ __launch_bounds__(BLOCK) void h16_preprune_kernel(const int32_
     const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= nq)
         return;
+    if (pr.served && (pr.served[q] & 1u)) // coarse_tail_kernel's prune-first path has written this query's list and bound
+        return;
     const int32_t l = lane < nprobe ? probes[(size_t)q * nprobe + lane] : -1;
     double ub = 1e300, lb = 0.0; // this probe's upper bound of the k-th distance; lower bound of its rows' distances
     double sq = 0.0;             // an upper bound of |q|
+    double slack_l2 = -1.0;      // the L2 word form: its slack (h16_prune_l2_query)
     bool usable = pr.xmax < 1e30f && pr.cmax < 1e30f;
     const double sc = sqrt((double)pr.cmax * 1.001);
     double spread = 0.0; // cosine: how far the row norms are from each other
@@ -2085,26 +2147,11 @@ static __global__ __launch_bounds__(BLOCK) void h16_preprune_kernel(const int32_
     {
         const uint32_t cw = l >= 0 ? (pr.probe_words ? pr.probe_words[(size_t)q * nprobe + lane] : pr.coarse_words[(size_t)q * pr.npad + (uint32_t)l])
                                    : 0xFFFFFFFFu;
-        const float qn = pr.qnorm[q];
-        usable = usable && qn < 1e30f;
-        sq = sqrt((double)qn * 1.001);
+        const PruneL2Query c = h16_prune_l2_query(pr, q);
+        usable = c.usable;
+        slack_l2 = c.slack;
         if (usable && l >= 0 && cw != 0xFFFFFFFFu)
-        {
-            const double eps_c = 2.0 * pr.cd_c(q) * sc * sq + pr.c_norm * (sc * sc + sq * sq) + (pr.c_canon + 4e-7) * (sc + sq) * (sc + sq) + 1e-30;
-            const double ac = (double)ord2f(cw), r = (double)pr.radius[l];
-            const double hi2 = ac + 2.0 * eps_c, lo2 = ac - 2.0 * eps_c;
-            if ((uint64_t)(list_off[l + 1] - list_off[l]) >= pr.k && r == r && hi2 == hi2)
-            {
-                const double hi = sqrt(hi2 > 0.0 ? hi2 : 0.0) * (1.0 + 1e-7) + r;
-                ub = hi * hi * (1.0 + 1e-7);
-            }
-            if (lo2 > 0.0)
-            {
-                const double lo = sqrt(lo2) * (1.0 - 1e-7);
-                if (lo > r)
-                    lb = (lo - r) * (lo - r) * (1.0 - 1e-7);
-            }
-        }
+            h16_prune_l2_bounds(c, cw, pr.radius[l], (uint64_t)(list_off[l + 1] - list_off[l]), pr.k, ub, lb);
     }
     double U = ub;
 #pragma unroll
@@ -2115,23 +2162,14 @@ static __global__ __launch_bounds__(BLOCK) void h16_preprune_kernel(const int32_
     }
     bool keep = true;
     const double sx = sqrt((double)pr.xmax * 1.001);
-    const double slack = 2.0 * (pr.c_canon + 4e-7) * (sx + sq) * (sx + sq) + spread * (1.0 + 1e-6) + 1e-30; // canonical vs real distance, both sides
+    const double slack = slack_l2 >= 0.0 ? slack_l2
+                                         : 2.0 * (pr.c_canon + 4e-7) * (sx + sq) * (sx + sq) + spread * (1.0 + 1e-6) + 1e-30; // canonical vs real distance, both sides
     if (usable && l >= 0 && U < 1e299)
         keep = !(lb > U + slack);
     if (lane < nprobe)
         out_probes[(size_t)q * nprobe + lane] = keep ? l : -1;
     if (pr.upre && lane == 0)
-    {
-        float u = __uint_as_float(0x7f800000u);
-        if (usable && U < 1e299)
-        {
-            const double v = U + slack;
-            u = v < 3.0e38 ? (float)v : u;
-            if ((double)u < v)
-                u = nextafterf(u, __uint_as_float(0x7f800000u));
-        }
-        pr.upre[q] = u;
-    }
+        pr.upre[q] = h16_prune_upre(usable, U, slack);
     if (pr.stat)
     {
         // [0] pairs dropped, [1] pairs looked at: every probe of the query here; a second stage behind this one adds what IT drops only
@@ -3084,6 +3122,198 @@ __device__ inline void coarse_exact_rows(const RerankParams & a, const uint32_t 
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 
+/// Round 12 -- PRUNE FIRST.  On data with cluster structure the pre-pruning (h16_preprune_kernel) deletes all but one or two of the
+/// nprobe probes the tail has just selected and ordered exactly: the selection then only has to classify the handful of lists that
+/// are not provably prunable.  L2, one query per wavefront; -> true: the query's PRUNED probe list (pr.out_probes) and pr.upre are
+/// written and it needs neither the radix select nor the band; false: nothing is written, the caller goes on as before.
+/// Notation: a_l the approximate value of centroid l (its word), eps2 = 2 rerank_eps (the tail's), k' = nprobe; lb_l, ub_l, slack the
+/// pre-pruning's L2 expressions (h16_prune_l2_query / h16_prune_l2_bounds: one definition).
+///   1. U0 = ub of the centroid with the smallest word.  No U0 (unusable norms, the nearest list shorter than k): not served.
+///   2. S'' = every present centroid a conservative test cannot prune under U0.  The pre-pruning drops l iff lb_l > U0 + slack =: T, i.e.
+///      ((sqrt(lo2) (1 - 1e-7) - r_l)^2 (1 - 1e-7) > T with lo2 = a_l - 2 eps_c; a_l > ((sqrt(T) + r_l)^2 + 2 eps_c) (1 + 4e-6) implies
+///      it: then sqrt(lo2) > (sqrt(T) + r_l) (1 + 1.9e-6), (lo - r_l) > sqrt(T) (1 + 1.8e-6), lb_l > T (1 + 3e-6).  The right side is formed
+///      in f32 (five roundings, < 4e-7 relative) and compared with the word itself: no square root and no double per word.  A centroid
+///      wrongly KEPT costs time only.  The members are compacted one per lane; more than 64: not served.
+///   3. Each member is classified against ALL words by counting: certainly IN <=> #(words with value <= a_l + eps2) <= k' (the tail's
+///      `in` test, a + 2 eps < a_(k'+1), written as a count); certainly OUT <=> #(words with value < a_l - eps2) >= k' (a - 2 eps > a_(k')).
+///      Both are monotone in a_l: the members are ranked among themselves, the number of IN members is found by bisection and the
+///      first member that is not IN is tested for OUT (the later ones are then OUT too).  A member that is neither means not served;
+///      so does a nearest centroid that is not IN.
+///   4. U = min ub over the IN members.  That is the pre-pruning's minimum over the k' probes: its argmin p has lb_p <= ub_p <= U0, so p
+///      is in S'', a probe is not OUT, so p is IN -- and every IN member is a probe.  The survivors are the IN members with
+///      !(lb_l > U + slack), each at the slot of its approximate rank among all words (the tail's `rank`; an IN member has fewer than k'
+///      words below it); every other slot of the query's k' is -1; upre as the pre-pruning rounds it.
+///   5. Validity.  A list of the true top-k' that is dropped is either outside S'' (lb > U0 + slack >= U + slack) or an IN member that
+///      fails step 4's test: either way lb > U + slack for a bound U owned by a list that is certainly among the probes and has k rows.
+///      Every survivor is certainly a probe.  So the scan sees what it sees behind the select, the band and the pre-pruning; where the
+///      tail's band forms the list and upre are the same bit for bit, where it does not (the tail then re-reads exact words) only
+///      these intermediates may differ.
+template <int NW>
+__device__ inline bool coarse_prune_first_wave(const uint32_t * src, const uint32_t n_pad, const uint32_t n_rows, const uint32_t q, const uint32_t kp,
+                                               const double eps2, const H16Prune & pr, const int64_t * list_off, const uint32_t lane,
+                                               uint64_t * mem /* LDS [WAVE], this wavefront's */, uint32_t * slots /* LDS [WAVE] */,
+                                               uint32_t & members /* out, experiments: |S''| (0: left before step 2 was done) */)
+{
+    members = 0;
+    uint32_t w[NW];
+    float rad[NW];
+#pragma unroll
+    for (int u = 0; u < NW; u++)
+    {
+        const uint32_t i = u * WAVE + lane;
+        w[u] = i < n_pad ? src[i] : 0xFFFFFFFFu;
+        const float r = i < n_rows ? pr.radius[i] : 0.f;
+        rad[u] = r >= 0.f ? r : __uint_as_float(0x7f800000u); // (NaN: never pruned by step 2 -- the exact test of step 4 decides)
+    }
+    // 1. the nearest centroid (ties: the smaller slot, as the select's keys) and its bound
+    uint32_t bw = 0xFFFFFFFFu, bi = 0;
+#pragma unroll
+    for (int u = 0; u < NW; u++)
+        if (w[u] < bw)
+        {
+            bw = w[u];
+            bi = u * WAVE + lane;
+        }
+    unsigned long long best = (unsigned long long)bw << 32 | bi;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+    {
+        const unsigned long long other = __shfl_xor(best, o);
+        best = other < best ? other : best;
+    }
+    const uint32_t w0 = (uint32_t)(best >> 32), l0 = (uint32_t)best;
+    if (w0 == 0xFFFFFFFFu || !(eps2 < 1e300))
+        return false;
+    const PruneL2Query c = h16_prune_l2_query(pr, q);
+    if (!c.usable)
+        return false;
+    double ub0, lb0;
+    h16_prune_l2_bounds(c, w0, pr.radius[l0], (uint64_t)(list_off[l0 + 1] - list_off[l0]), pr.k, ub0, lb0);
+    if (!(ub0 < 1e299))
+        return false;
+    // 2. S''
+    const double T = ub0 + c.slack;
+    float sT = (float)sqrt(T), e2 = (float)(2.0 * c.eps_c);
+    sT = nextafterf(sT, __uint_as_float(0x7f800000u));
+    e2 = nextafterf(e2, __uint_as_float(0x7f800000u));
+    if (!(sT < 1e18f) || !(e2 < 1e30f))
+        return false;
+    uint32_t ns = 0;
+#pragma unroll
+    for (int u = 0; u < NW; u++)
+    {
+        const float t = __fadd_rn(sT, rad[u]);
+        const float thr = __fmul_rn(__fadd_rn(__fmul_rn(t, t), e2), 1.000004f); // (>= 0 or +inf: its ordered word is the bits | sign)
+        const bool member = w[u] <= (__float_as_uint(thr) | 0x80000000u);       // (an absent word, 0xFFFFFFFF, is above every threshold)
+        const uint64_t b = __ballot(member);
+        if (b)
+        {
+            if (member)
+            {
+                const uint32_t pos = ns + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+                if (pos < WAVE)
+                    mem[pos] = (uint64_t)w[u] << 32 | (uint32_t)(u * WAVE + lane);
+            }
+            ns += (uint32_t)__popcll(b);
+        }
+    }
+    members = ns;
+    if (ns > WAVE || ns == 0)
+        return false;
+    slots[lane] = 0xFFFFFFFFu;
+    bp_wave_lds_fence_h16();
+    // 3. rank the members among themselves, bisect for the IN / OUT boundaries
+    const uint64_t mine = lane < ns ? mem[lane] : KEY_NONE;
+    uint32_t sr = 0;
+    for (uint32_t j = 0; j < ns; j++)
+        sr += mem[j] < mine ? 1u : 0u;
+    auto count_le = [&](const uint32_t tw) -> uint32_t { // present words <= tw (tw < 0xFFFFFFFF)
+        uint32_t n = 0;
+#pragma unroll
+        for (int u = 0; u < NW; u++)
+            n += (uint32_t)__popcll(__ballot(w[u] <= tw));
+        return n;
+    };
+    // the words whose VALUE is <= x (strict: < x), x finite: the largest float at or below (below) x, +0 for either zero (-0 orders
+    // below +0 among the words and equals it as a value)
+    auto word_at = [&](const double x, const bool strict) -> uint32_t {
+        float f = (float)x;
+        if (strict ? (double)f >= x : (double)f > x)
+            f = nextafterf(f, __uint_as_float(0xff800000u));
+        if (f == 0.f)
+            f = 0.f;
+        return f2ord(f);
+    };
+    auto member_word = [&](const uint32_t t) -> uint32_t { // of the member of rank t (uniform)
+        const uint64_t m = __ballot(lane < ns && sr == t);
+        return (uint32_t)(readlane64(mine, __builtin_ctzll(m)) >> 32);
+    };
+    uint32_t lo = 0, hi = ns; // -> lo = the number of IN members
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi) >> 1;
+        const double x = (double)ord2f(member_word(mid)) + eps2;
+        if (x == x && count_le(word_at(x, false)) <= kp)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    const uint32_t n_in = lo;
+    if (n_in == 0)
+        return false;
+    hi = ns; // every member from n_in on must be OUT: the first of them is the one to test (OUT is monotone)
+    if (lo < hi)
+    {
+        const double y = (double)ord2f(member_word(lo)) - eps2;
+        if (!(y == y && count_le(word_at(y, true)) >= kp))
+            return false;
+    }
+    // 4. the bound over the IN members, the survivors at their approximate ranks
+    const bool in = lane < ns && sr < n_in;
+    double ub = 1e300, lb = 0.0;
+    const uint32_t l = (uint32_t)mine;
+    if (in && n_in == 1) // (the nearest centroid alone, the usual case: its bounds are step 1's -- no second trip to memory)
+    {
+        ub = ub0;
+        lb = lb0;
+    }
+    else if (in)
+        h16_prune_l2_bounds(c, (uint32_t)(mine >> 32), pr.radius[l], (uint64_t)(list_off[l + 1] - list_off[l]), pr.k, ub, lb);
+    double U = ub;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+    {
+        const double other = __shfl_xor(U, o);
+        U = other < U ? other : U;
+    }
+    const bool keep = in && !(lb > U + c.slack);
+    uint64_t todo = __ballot(keep);
+    while (todo)
+    {
+        const int src_lane = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const uint64_t key = readlane64(mine, src_lane);
+        const uint32_t kw = (uint32_t)(key >> 32), ks = (uint32_t)key;
+        uint32_t rank = 0; // among all words by (word, slot): the tail's `rank` (the nearest centroid's is 0)
+        if (key != (uint64_t)best)
+        {
+#pragma unroll
+            for (int u = 0; u < NW; u++)
+                rank += (uint32_t)__popcll(__ballot(w[u] < kw || (w[u] == kw && (uint32_t)(u * WAVE + lane) < ks)));
+        }
+        if (rank >= kp) // (cannot happen for an IN member: fewer than k' words at or below it)
+            return false;
+        if (lane == 0)
+            slots[rank] = ks;
+    }
+    bp_wave_lds_fence_h16();
+    if (lane < kp)
+        pr.out_probes[(size_t)q * kp + lane] = (int32_t)slots[lane];
+    if (pr.upre && lane == 0)
+        pr.upre[q] = h16_prune_upre(true, U, c.slack);
+    return true;
+}
+
 /// Round 6 -- the coarse quantiser's selection AND band re-rank in one launch, one WAVEFRONT per query, no workgroup barrier:
 /// coarse_select_kernel (15 us per 4096 queries) + ivf_rerank_kernel in band mode (33 us: a 256-thread block per query, eight
 /// barriers around three or four canonical rows) were two launches whose cost is the latency chain of a block, not work.
@@ -3099,7 +3329,9 @@ __device__ inline void coarse_exact_rows(const RerankParams & a, const uint32_t 
 template <int METRIC>
 __global__ __launch_bounds__(BLOCK) void coarse_tail_kernel(const uint32_t * sample, uint32_t nq, uint32_t n_pad, const RerankParams a,
                                                             uint64_t * cand, uint64_t * bound, uint32_t * slowq, uint32_t * nslow,
-                                                            uint32_t n_rows, uint32_t * slow_stamp, uint32_t seq, int slow_inline)
+                                                            uint32_t n_rows, uint32_t * slow_stamp, uint32_t seq, int slow_inline,
+                                                            const H16Prune pf, const int64_t * pf_list_off, uint32_t * pf_flags,
+                                                            unsigned long long * pf_count)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[BLOCK / WAVE][256];
     __shared__ uint64_t s_stage[BLOCK / WAVE][WAVE];
@@ -3111,6 +3343,36 @@ __global__ __launch_bounds__(BLOCK) void coarse_tail_kernel(const uint32_t * sam
     if (q >= nq)
         return;
     const uint32_t kc = a.kc, k = a.k, ld4 = a.ld4;
+    // round 12, prune first (pf.out_probes set: L2, every query leaves this launch with its probes -- slow_inline): a query whose pruned
+    // probe list can be decided from the words alone leaves here with it; pf_flags[q] bit 0 tells h16_preprune_kernel behind this launch
+    // (experiments and tests -- pf_count set: bit 1 = the band formed; bits 8 and up: the members of S'')
+    if (METRIC == M_L2 && pf.out_probes)
+    {
+        const float qn0 = a.qnorm[q];
+        bool served = false;
+        uint32_t members = 0;
+        if (qn0 < 1e30f && a.xmax < 1e30f)
+        {
+            const double eps2 = 2.0 * rerank_eps<METRIC>(a, sqrt((double)a.xmax * 1.001), sqrt((double)qn0 * 1.001), q);
+            const uint32_t * src0 = sample + (size_t)q * n_pad;
+            if (n_pad <= 4 * WAVE)
+                served = coarse_prune_first_wave<4>(src0, n_pad, n_rows, q, k, eps2, pf, pf_list_off, lane, s_keys[wave], s_band[wave], members);
+            else if (n_pad <= 8 * WAVE)
+                served = coarse_prune_first_wave<8>(src0, n_pad, n_rows, q, k, eps2, pf, pf_list_off, lane, s_keys[wave], s_band[wave], members);
+            else if (n_pad <= 16 * WAVE)
+                served = coarse_prune_first_wave<16>(src0, n_pad, n_rows, q, k, eps2, pf, pf_list_off, lane, s_keys[wave], s_band[wave], members);
+            else
+                served = coarse_prune_first_wave<32>(src0, n_pad, n_rows, q, k, eps2, pf, pf_list_off, lane, s_keys[wave], s_band[wave], members);
+        }
+        if (lane == 0)
+        {
+            pf_flags[q] = (served ? 1u : 0u) | members << 8;
+            if (served && pf_count)
+                atomicAdd(pf_count, 1ull);
+        }
+        if (served) // (uniform over the wavefront)
+            return;
+    }
     uint64_t * const cd = s_cand[wave];
     cd[lane] = KEY_NONE;
     bp_wave_lds_fence_h16();
@@ -3149,6 +3411,8 @@ __global__ __launch_bounds__(BLOCK) void coarse_tail_kernel(const uint32_t * sam
             band_ok = METRIC == M_L2 ? (al - eps2 > ak) : (al + eps2 < ak);
         }
     }
+    if (pf_count && lane == 0 && band_ok) // (experiments and tests: which queries' bands formed)
+        pf_flags[q] |= 2u;
     if (!band_ok) // (uniform over the wavefront)
     {
         // the host reads the stamp without synchronisation before its NEXT searches of this index: which form of the queue they take

@@ -220,8 +220,9 @@ static unsigned long long * prefilter_fail_counter()
     if (it != per_device.end())
         return it->second;
     unsigned long long * p = nullptr;
-    MSVS_HIP(hipMalloc(&p, 128)); // 16 words, all taken: [0 .. 14] as the readers below lay them out, [15] = msvs_debug_rerank_rows' fourth
-    MSVS_HIP(hipMemset(p, 0, 128));
+    // 32 words: [0 .. 14] as the readers below lay them out, [15] = msvs_debug_rerank_rows' fourth, [16] = msvs_debug_prune_first_served
+    MSVS_HIP(hipMalloc(&p, 256));
+    MSVS_HIP(hipMemset(p, 0, 256));
     per_device[dev] = p;
     return p;
 }
@@ -428,6 +429,7 @@ static size_t index_search_scratch(const msvs_index & ix, size_t nq, uint32_t k,
         + (5 * ix.nlist + 16 + nq * nprobe) * 4 + 32768
         + (4 * ix.nlist + 18) * 4 + 1024 + 1024 // the list scan's counters taken up front, the padded query images
         + 4 * nq * nprobe * 4 + nq * 4 + 2 * (ix.nlist + 1) * 4 + 8192 // probe pruning: surviving probes (two stages), the second plan
+        + nq * 4 + 512 // the coarse tail's prune-first flags
         + (ix.c_shadow_ready ? nq * ((size_t)ix.h_nch * 128 + 24 + round_up(ix.nlist, (size_t)H_ROWS) * 4 + ceil_div(ix.nlist, (size_t)H_ROWS) * 4) + 9216 : 0);
     if (p.mfma())
         need += nq * (p.h16 ? (size_t)p.h_cap : big_cand_cap(nprobe, p.seg_max)) * 8
@@ -492,6 +494,13 @@ struct TablePass
     float h16_rho = -1.f;  // measured rounding error of the table's shadow (set_error_model_h16; < 0: worst case)
     bool h16 = false; // the table is the centroid table and its fp16 shadow is usable: scan through h16_sample_kernel
     H16Queries * h16_out = nullptr; // h16: where the pass leaves the queries' fp16 images for the list scan that follows
+    // round 12, prune first (coarse_tail_kernel; probe lists of an L2 index): the pre-pruning that follows the pass, as far as the caller
+    // knows it -- radius, norms' bounds, k, out_probes, upre; the pass adds its words, norms and error model and hands it to the tail launch
+    const H16Prune * prune_first = nullptr;
+    const int64_t * pf_list_off = nullptr;   // the lists the radii belong to
+    uint32_t * pf_flags = nullptr;           // [nq]: bit 0 = served by the prune-first path (set with prune_first, or for pf_count alone)
+    unsigned long long * pf_count = nullptr; // nullable (option coarse_prune_debug): += queries served; the flags' bit 1 = band formed
+    bool * pf_ran = nullptr;                 // out: the tail launch took prune_first (the flags and the served queries' lists are written)
 };
 
 static uint32_t table_fallback_rpb(size_t n) { return (uint32_t)round_up(std::max<size_t>(256, ceil_div(n, (size_t)256)), 16); }
@@ -546,6 +555,7 @@ static void run_fallback_rounds(int metric, ScanParams c, IvfMergeParams fm, siz
 }
 
 static void set_error_model_h16(RerankParams & rp, size_t dim, float rho_table = -1.f, const float * qrho = nullptr);
+static void set_prune_error_model(H16Prune & pr, const msvs_index & ix, const float * qrho, bool remote_words = false, bool foreign_rows = false);
 
 HostSignal & host_signal()
 {
@@ -699,6 +709,19 @@ struct CoarseLast
     hipStream_t stream = nullptr;
 };
 static thread_local CoarseLast g_coarse_last;
+
+/// Tests and experiments (msvs_debug_prune_first; option coarse_prune_debug): what the pre-pruning of this host thread's last IVFFLAT
+/// search left -- the pruned probe lists, its bound per query and coarse_tail_kernel's flag words (valid until the thread's next search
+/// on that stream; nullptr: that search had none).
+struct PruneFirstLast
+{
+    const int32_t * probes = nullptr; // [nq][nprobe]
+    const float * upre = nullptr;     // [nq]
+    const uint32_t * flags = nullptr; // [nq]: bit 0 = served by the prune-first path, bit 1 = the tail's band formed, bits 8 and up = |S''|
+    uint32_t nq = 0, nprobe = 0;
+    hipStream_t stream = nullptr;
+};
+static thread_local PruneFirstLast g_prune_first_last;
 
 static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, const float * dq, size_t nq,
                                  const TablePass & t, hipStream_t stream)
@@ -926,9 +949,23 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
         {
             const RerankParams rp = table_rerank_params(ix, t, a, qn16, cand, bound, kc, failq, nfail, true, qrho);
             const dim3 tgrid((unsigned)ceil_div(nq, (size_t)(BLOCK / WAVE)));
+            // round 12: the pre-pruning decided first, on the words (coarse_prune_first_wave) -- only where every query leaves this launch
+            // with its probes (slow_inline) and the slots of the table are the list numbers
+            H16Prune pf{};
+            if (t.prune_first && t.pf_flags && slow_inline && m == MSVS_METRIC_L2 && !t.ids && t.h16_out && t.h16_out->coarse_words == sample)
+            {
+                pf = *t.prune_first;
+                set_prune_error_model(pf, ix, qrho, false, false);
+                pf.coarse_words = sample;
+                pf.npad = n_pad;
+                pf.qnorm = qn16;
+                if (t.pf_ran)
+                    *t.pf_ran = true;
+            }
             with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
                 hipLaunchKernelGGL((coarse_tail_kernel<decltype(mc)::value>), tgrid, dim3(BLOCK), 0, stream, sample, (uint32_t)nq, n_pad, rp, cand,
-                                   bound, failq2c, nslow, (uint32_t)t.n, slow_stamp, seq, slow_inline ? 1 : 0);
+                                   bound, failq2c, nslow, (uint32_t)t.n, slow_stamp, seq, slow_inline ? 1 : 0, pf, t.pf_list_off, t.pf_flags,
+                                   t.pf_flags ? t.pf_count : nullptr);
             });
         }
         else
@@ -1156,7 +1193,7 @@ static void set_error_model_i8r(RerankParams & rp, size_t dim, const float * qbo
 /// remote_words: the coarse words were computed by ANOTHER rank's centroid shadow and query images (ProbeWords::given): its measured
 /// rounding errors are not known here -- the worst-case model covers them.  foreign_rows: the bound speaks about rows of other ranks
 /// (the routed search's pre-pruning over the whole index): the worst-case row error instead of this shard's measured one.
-static void set_prune_error_model(H16Prune & pr, const msvs_index & ix, const float * qrho, bool remote_words = false, bool foreign_rows = false)
+static void set_prune_error_model(H16Prune & pr, const msvs_index & ix, const float * qrho, bool remote_words, bool foreign_rows)
 {
     RerankParams ex{}, ec{};
     set_error_model_h16(ex, ix.dim, foreign_rows ? -1.f : ix.h_rho, qrho); // (the query images of the row scan are this rank's own)
@@ -1874,6 +1911,12 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
     prepared.n_counters = (uint32_t)(4 * ix.nlist + 2 + 16 + h8_query_words(ix, nq, nprobe)); // the shadow list scan's counters (h16_list_scan)
     prepared.counters = scr.take<uint32_t>(prepared.n_counters);
     int32_t * d_probes = probes_only ? probes_only : scr.take<int32_t>(nq * nprobe);
+    // round 12 (prune first): the pre-pruning's outputs and the per-query flag words, taken before the coarse pass that may fill them
+    int32_t * pf_probes1 = nullptr;
+    float * pf_upre = nullptr;
+    uint32_t * pf_flags = nullptr;
+    bool pf_ran = false;
+    H16Prune pf0{};
     if (given_probes)
         MSVS_HIP(hipMemcpyAsync(d_probes, given_probes, nq * nprobe * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
     else if (table_pass_eligible(ix.nlist, ix.cnorm.p, ix.cnorm_max, nq, (uint32_t)nprobe, options().coarse_mfma)
@@ -1891,6 +1934,44 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         t.out_probes = d_probes;
         t.h16_out = &prepared;
         t.prof_name = "coarse_pass";
+        // round 12, prune first: where the pre-pruning below will run on this pass's words (the conditions of `preprune` that do not
+        // wait for the pass), the whole probe list is nobody's business (not a sharded entry) and nothing counts pairs -- the tail
+        // launch decides it on the words, for the queries it can (coarse_prune_first_wave).  Not while the last search of this shape
+        // kept more than a few pairs per query (the plan's feedback word: iid data -- nothing is prunable, the attempt is pure cost).
+        const bool pf_debug = options().coarse_prune_debug != 0;
+        bool pf_plan = options().coarse_prune_first != 0 && !probes_only && options().rerank_stats == 0 && options().h16_prune != 0
+            && options().h16_preprune != 0 && ix.metric == MSVS_METRIC_L2 && !d_alive && !view && ix.list_radius.p && nprobe <= 64 && nprobe >= 2
+            && ix.cnorm_max < 1e30f && ix.xnorm_max < 1e30f;
+        if (pf_plan && ix.plan_fb.pairs)
+        {
+            const uint32_t seen = *reinterpret_cast<volatile uint32_t *>(ix.plan_fb.pairs);
+            if (seen != 0xFFFFFFFFu && ix.plan_fb.nq != 0 && ix.plan_fb.nprobe == (uint32_t)nprobe && (uint64_t)seen > 4ull * ix.plan_fb.nq)
+                pf_plan = false;
+        }
+        if (pf_plan || pf_debug)
+        {
+            pf_probes1 = scr.take<int32_t>(nq * nprobe);
+            pf_upre = scr.take<float>(nq);
+            pf_flags = scr.take<uint32_t>(nq);
+            t.pf_flags = pf_flags;
+            t.pf_ran = &pf_ran;
+            if (pf_debug)
+            {
+                MSVS_HIP(hipMemsetAsync(pf_flags, 0, nq * sizeof(uint32_t), stream));
+                t.pf_count = prefilter_fail_counter() + 16;
+            }
+        }
+        if (pf_plan)
+        {
+            pf0.radius = ix.list_radius.p;
+            pf0.xmax = ix.xnorm_max;
+            pf0.cmax = ix.cnorm_max;
+            pf0.k = k;
+            pf0.upre = pf_upre;
+            pf0.out_probes = pf_probes1;
+            t.prune_first = &pf0;
+            t.pf_list_off = ix.list_off.p;
+        }
         table_candidate_pass(ix, scr, m, dq, nq, t, stream);
     }
     else
@@ -1946,7 +2027,8 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         }
         pr0.k = k;
         pr0.stat = options().rerank_stats != 0 ? prefilter_fail_counter() + 8 : nullptr;
-        pr0.upre = cosine_form || !keep_upre ? nullptr : scr.take<float>(nq); // (an L2 bound: the cosine scan's second stage compares inner products)
+        pr0.upre = cosine_form || !keep_upre ? nullptr : pf_upre ? pf_upre : scr.take<float>(nq); // (an L2 bound: the cosine scan's second stage compares inner products)
+        pr0.served = keep_upre && pf_ran ? pf_flags : nullptr; // (the tail launch has written these queries' lists and bounds: coarse_prune_first_wave)
         ProfileScope prof("ivf_plan", stream);
         hipLaunchKernelGGL(h16_preprune_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(BLOCK), 0, stream, in_probes, pr0, list_off,
                            (uint32_t)nq, (uint32_t)nprobe, out_probes);
@@ -1986,9 +2068,14 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
     const int32_t * all_probes = d_probes;
     (void)all_probes;
     {
-        int32_t * probes1 = scr.take<int32_t>(nq * nprobe);
-        if (preprune(d_probes, ix.list_radius.p, ix.list_off.p, probes1, true, ix.xnorm_max, ix.xnorm_min))
+        int32_t * probes1 = pf_probes1 ? pf_probes1 : scr.take<int32_t>(nq * nprobe);
+        const bool pruned = preprune(d_probes, ix.list_radius.p, ix.list_off.p, probes1, true, ix.xnorm_max, ix.xnorm_min);
+        if (pruned)
             d_probes = probes1;
+        else if (pf_ran) // (the served queries have no other probe list)
+            fail(MSVS_ERR_DEVICE, "the coarse tail pruned first, the pre-pruning behind it did not run");
+        if (options().coarse_prune_debug != 0) // msvs_debug_prune_first
+            g_prune_first_last = PruneFirstLast{pruned ? probes1 : nullptr, pruned ? prepared.upre : nullptr, pf_flags, (uint32_t)nq, (uint32_t)nprobe, stream};
     }
     // 2. scan the probed lists
     if (nq * nprobe > 0x7fffffffull)
@@ -2508,6 +2595,42 @@ extern "C" __attribute__((visibility("default"))) int msvs_debug_coarse_words(ui
         MSVS_HIP(hipStreamSynchronize(c.stream));
         MSVS_HIP(hipMemcpy(out, c.words, nq * npad * 4, hipMemcpyDeviceToHost));
         g_coarse_last = CoarseLast{};
+    });
+}
+
+/// Tests and experiments (not in msvs.h; option coarse_prune_debug = 1): the pre-pruning of this thread's last IVFFLAT search -- probes
+/// [nq][nprobe] (-1: dropped or absent), upre [nq], flags [nq] (bit 0: coarse_tail_kernel's prune-first path served the query, bit 1: the
+/// tail's band formed, bits 8 and up: the lists the path could not prune under the nearest list's bound -- |S''|, 0 = it left earlier).
+/// *have = 0: that search had no pre-pruning (probes and upre are left alone).
+extern "C" __attribute__((visibility("default"))) int msvs_debug_prune_first(int32_t * probes, float * upre, uint32_t * flags, size_t nq,
+                                                                             size_t nprobe, int * have)
+{
+    return guarded([&] {
+        const PruneFirstLast & p = g_prune_first_last;
+        if (p.nq != nq || p.nprobe != nprobe)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "no search of %zu queries x %zu probes on record (last: %u x %u)", nq, nprobe, p.nq, p.nprobe);
+        MSVS_HIP(hipStreamSynchronize(p.stream));
+        *have = p.probes ? 1 : 0;
+        if (p.probes)
+            MSVS_HIP(hipMemcpy(probes, p.probes, nq * nprobe * 4, hipMemcpyDeviceToHost));
+        if (p.probes && p.upre)
+            MSVS_HIP(hipMemcpy(upre, p.upre, nq * 4, hipMemcpyDeviceToHost));
+        if (p.flags)
+            MSVS_HIP(hipMemcpy(flags, p.flags, nq * 4, hipMemcpyDeviceToHost));
+        else
+            std::fill(flags, flags + nq, 0u);
+        g_prune_first_last = PruneFirstLast{};
+    });
+}
+
+/// ... and the queries the prune-first path has served on this device since the library was loaded (counted while coarse_prune_debug = 1).
+extern "C" __attribute__((visibility("default"))) int msvs_debug_prune_first_served(uint64_t * served)
+{
+    return guarded([&] {
+        unsigned long long v = 0;
+        MSVS_HIP(hipDeviceSynchronize());
+        MSVS_HIP(hipMemcpy(&v, prefilter_fail_counter() + 16, 8, hipMemcpyDeviceToHost));
+        *served = v;
     });
 }
 
