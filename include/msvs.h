@@ -166,6 +166,16 @@ MSVS_API int msvs_bin_index_export(const msvs_bin_index_t * index, uint8_t * cen
  * search (host pointers): params "nprobe=P" (default 1).  search_device: device pointers, enqueued on hip_stream without host
  *   synchronisation.  k <= MSVS_MAX_K and min(nprobe, nlist) <= MSVS_MAX_K (MSVS_ERR_UNSUPPORTED_K); k = 0 or nq = 0 is a no-op;
  *   before build: MSVS_ERR_NOT_READY.
+ * search_rounds / search_rounds_device: the same search and the same definition of its result with k <= MSVS_MAX_K_ROUNDS
+ *   (MSVS_ERR_UNSUPPORTED_K beyond); everything else as search / search_device, and for k <= MSVS_MAX_K the same bits.  Beyond
+ *   MSVS_MAX_K the list scan runs once per MSVS_MAX_K ranks for the whole batch, each time behind the last (distance, label) the
+ *   query has returned: two rows that carry the SAME label at the same distance are returned once when they straddle such a
+ *   boundary (labels are expected to be distinct).  search / search_device keep refusing k > MSVS_MAX_K.
+ * search_rounds / search_rounds_device: the same search and the same definition of its result with k <= MSVS_MAX_K_ROUNDS
+ *   (MSVS_ERR_UNSUPPORTED_K beyond); everything else as search / search_device, and for k <= MSVS_MAX_K the same bits.  Beyond
+ *   MSVS_MAX_K the list scan runs once per MSVS_MAX_K ranks for the whole batch, each time behind the last (distance, label) the
+ *   query has returned: two rows that carry the SAME label at the same distance are returned once when they straddle such a
+ *   boundary (labels are expected to be distinct).  search / search_device keep refusing k > MSVS_MAX_K.
  * export: centroids nlist * dim, vmin / vmax dim each, nlist + 1 offsets, codes n * dim in NATURAL column order, labels n; any
  *   output may be NULL.
  * memory_usage after build <= n * (round_up(dim, 16) + 8) + the centroids, quantiser and offsets + 4096 bytes.
@@ -188,6 +198,11 @@ MSVS_API int msvs_sq_index_search(const msvs_sq_index_t * index, const float * q
 MSVS_API int msvs_sq_index_search_device(const msvs_sq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t nprobe,
                                          const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
                                          void * hip_stream);
+MSVS_API int msvs_sq_index_search_rounds(const msvs_sq_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
+                                         const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_sq_index_search_rounds_device(const msvs_sq_index_t * index, const float * d_queries, size_t nq, size_t k,
+                                                size_t nprobe, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
+                                                float * d_dis, void * hip_stream);
 MSVS_API int msvs_sq_index_export(const msvs_sq_index_t * index, float * centroids, float * vmin, float * vmax, int64_t * list_off,
                                   uint8_t * codes, int64_t * ids);
 MSVS_API int msvs_sq_index_serialize_io(const msvs_sq_index_t * index, const struct msvs_io * io);
@@ -229,6 +244,16 @@ MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t **
  * search (host pointers): params "nprobe=P" (default 1).  search_device: device pointers, enqueued on hip_stream without host
  *   synchronisation.  k <= MSVS_MAX_K and min(nprobe, nlist) <= MSVS_MAX_K (MSVS_ERR_UNSUPPORTED_K); k = 0 or nq = 0 is a no-op;
  *   before build: MSVS_ERR_NOT_READY.
+ * search_rounds / search_rounds_device: the same search and the same definition of its result with k <= MSVS_MAX_K_ROUNDS
+ *   (MSVS_ERR_UNSUPPORTED_K beyond); everything else as search / search_device, and for k <= MSVS_MAX_K the same bits.  Beyond
+ *   MSVS_MAX_K the list scan runs once per MSVS_MAX_K ranks for the whole batch, each time behind the last (distance, label) the
+ *   query has returned: two rows that carry the SAME label at the same distance are returned once when they straddle such a
+ *   boundary (labels are expected to be distinct).  search / search_device keep refusing k > MSVS_MAX_K.
+ * search_rounds / search_rounds_device: the same search and the same definition of its result with k <= MSVS_MAX_K_ROUNDS
+ *   (MSVS_ERR_UNSUPPORTED_K beyond); everything else as search / search_device, and for k <= MSVS_MAX_K the same bits.  Beyond
+ *   MSVS_MAX_K the list scan runs once per MSVS_MAX_K ranks for the whole batch, each time behind the last (distance, label) the
+ *   query has returned: two rows that carry the SAME label at the same distance are returned once when they straddle such a
+ *   boundary (labels are expected to be distinct).  search / search_device keep refusing k > MSVS_MAX_K.
  * export: centroids nlist * dim, codebooks m * ksub * dsub, nlist + 1 offsets, codes n * m in NATURAL order, one code a byte in both
  *   forms (values < ksub), labels n; any output may be NULL.  bit_size: 4 or 8 (0 for NULL): what a host that loaded an index
  *   sizes export's codebook buffer by.
@@ -279,6 +304,11 @@ MSVS_API int msvs_pq_index_search(const msvs_pq_index_t * index, const float * q
 MSVS_API int msvs_pq_index_search_device(const msvs_pq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t nprobe,
                                          const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
                                          void * hip_stream);
+MSVS_API int msvs_pq_index_search_rounds(const msvs_pq_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
+                                         const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_pq_index_search_rounds_device(const msvs_pq_index_t * index, const float * d_queries, size_t nq, size_t k,
+                                                size_t nprobe, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
+                                                float * d_dis, void * hip_stream);
 MSVS_API int msvs_pq_index_export(const msvs_pq_index_t * index, float * centroids, float * codebooks, int64_t * list_off,
                                   uint8_t * codes, int64_t * ids);
 MSVS_API int msvs_pq_index_serialize_io(const msvs_pq_index_t * index, const struct msvs_io * io);
@@ -318,7 +348,10 @@ MSVS_API int msvs_pq_index_load_io(const struct msvs_io * io, msvs_pq_index_t **
  * search_refine[_device] of the coded indexes: the index's own search[_device] with kc results (kc <= MSVS_MAX_K; params / nprobe
  * and the filter apply here), the labels kept on the device, then refine_device with the index's metric -- no host round trip between
  * the stages.  rows' dim must be the index's and normalized == (metric is cosine), and k <= kc: MSVS_ERR_INVALID_ARGUMENT otherwise.
- * The result equals refine applied to search(kc)'s labels. */
+ * The result equals refine applied to search(kc)'s labels.
+ * search_refine_rounds[_device]: the same with search_rounds[_device] as the first stage: kc <= MSVS_REFINE_MAX_CAND and
+ * k <= MSVS_MAX_K (MSVS_ERR_UNSUPPORTED_K beyond either), k <= kc and the row store's fit as above; the result equals refine applied
+ * to search_rounds(kc)'s labels, and for kc <= MSVS_MAX_K search_refine's.  search_refine[_device] keep refusing kc > MSVS_MAX_K. */
 #define MSVS_REFINE_MAX_CAND 1024
 typedef struct msvs_rows msvs_rows_t;
 enum msvs_rows_placement { MSVS_ROWS_DEVICE = 0, MSVS_ROWS_HOST_PINNED = 1 };
@@ -339,12 +372,26 @@ MSVS_API int msvs_sq_index_search_refine(const msvs_sq_index_t * index, const ms
 MSVS_API int msvs_sq_index_search_refine_device(const msvs_sq_index_t * index, const msvs_rows_t * rows, const float * d_queries,
                                                 size_t nq, size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits,
                                                 size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream);
+MSVS_API int msvs_sq_index_search_refine_rounds(const msvs_sq_index_t * index, const msvs_rows_t * rows, const float * queries,
+                                                size_t nq, size_t k, size_t kc, const char * params, const uint64_t * alive_bits,
+                                                size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_sq_index_search_refine_rounds_device(const msvs_sq_index_t * index, const msvs_rows_t * rows,
+                                                       const float * d_queries, size_t nq, size_t k, size_t kc, size_t nprobe,
+                                                       const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                                       void * hip_stream);
 MSVS_API int msvs_pq_index_search_refine(const msvs_pq_index_t * index, const msvs_rows_t * rows, const float * queries, size_t nq,
                                          size_t k, size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits,
                                          int64_t * ids, float * dis);
 MSVS_API int msvs_pq_index_search_refine_device(const msvs_pq_index_t * index, const msvs_rows_t * rows, const float * d_queries,
                                                 size_t nq, size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits,
                                                 size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream);
+MSVS_API int msvs_pq_index_search_refine_rounds(const msvs_pq_index_t * index, const msvs_rows_t * rows, const float * queries,
+                                                size_t nq, size_t k, size_t kc, const char * params, const uint64_t * alive_bits,
+                                                size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * index, const msvs_rows_t * rows,
+                                                       const float * d_queries, size_t nq, size_t k, size_t kc, size_t nprobe,
+                                                       const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                                       void * hip_stream);
 
 /* Resident blocks for the brute-force path: the GPU analogue of VICacheManager / VIWithMeta
  * (src/VectorIndex/Cache/VICacheObject.h:40-162) for the dense block a mark of a part turns into

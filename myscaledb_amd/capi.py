@@ -52,6 +52,9 @@ SYMBOLS = [
     "msvs_rows_create", "msvs_rows_append", "msvs_rows_num", "msvs_rows_dim", "msvs_rows_normalized", "msvs_rows_memory_usage",
     "msvs_rows_free", "msvs_refine", "msvs_refine_device", "msvs_sq_index_search_refine", "msvs_sq_index_search_refine_device",
     "msvs_pq_index_search_refine", "msvs_pq_index_search_refine_device",
+    "msvs_sq_index_search_rounds", "msvs_sq_index_search_rounds_device", "msvs_sq_index_search_refine_rounds",
+    "msvs_sq_index_search_refine_rounds_device", "msvs_pq_index_search_rounds", "msvs_pq_index_search_rounds_device",
+    "msvs_pq_index_search_refine_rounds", "msvs_pq_index_search_refine_rounds_device",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
     "msvs_comm_free", "msvs_comm_all_reduce_u64", "msvs_comm_rank", "msvs_comm_size", "msvs_shard_search_device", "msvs_shard_search_device_async", "msvs_shard_search_drain", "msvs_shard_search_routed_device",
@@ -348,25 +351,25 @@ class _CodedIndex:
     def memory_usage(self):
         return self._size("memory_usage")
 
-    def search(self, queries, k, params="", alive=None, nbits=None):
+    def search(self, queries, k, params="", alive=None, nbits=None, _entry="search"):
         """params: "nprobe=P"; alive: bool over labels, nbits: how many of them the filter covers (default all of `alive`)."""
         q = _f32(queries).reshape(-1, self.dim)
         ids = np.empty((q.shape[0], k), np.int64)
         dis = np.empty((q.shape[0], k), np.float32)
         bits = None if alive is None else pack_bits(alive)
         nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
-        _check(self._fn("search")(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), params.encode(),
-                                  _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        _check(self._fn(_entry)(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), params.encode(),
+                                _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
         return ids, dis
 
-    def search_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+    def search_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0, _entry="search_device"):
         """All arguments are raw device addresses (ints); enqueues on `stream` and returns immediately."""
-        _check(self._fn("search_device")(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(nprobe),
-                                         C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
-                                         C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
-                                         C.c_void_p(int(stream)) if stream else None))
+        _check(self._fn(_entry)(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(nprobe),
+                                C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
+                                C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)),
+                                C.c_void_p(int(stream)) if stream else None))
 
-    def search_refine(self, rows, queries, k, kc, params="", alive=None, nbits=None):
+    def search_refine(self, rows, queries, k, kc, params="", alive=None, nbits=None, _entry="search_refine"):
         """The two-stage search: search(kc)'s labels scored against `rows` (a Rows whose row i is label i), the best k with the
         canonical distances.  params, alive and nbits are search's and apply to the first stage."""
         q = _f32(queries).reshape(-1, self.dim)
@@ -374,15 +377,33 @@ class _CodedIndex:
         dis = np.empty((q.shape[0], k), np.float32)
         bits = None if alive is None else pack_bits(alive)
         nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
-        _check(self._fn("search_refine")(self._h, rows._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), C.c_size_t(kc),
-                                         params.encode(), _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        _check(self._fn(_entry)(self._h, rows._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), C.c_size_t(kc),
+                                params.encode(), _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
         return ids, dis
 
-    def search_refine_device(self, rows, d_queries, nq, k, kc, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+    def search_refine_device(self, rows, d_queries, nq, k, kc, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0,
+                             _entry="search_refine_device"):
         """search_refine with raw device addresses (ints); enqueues both stages on `stream` and returns immediately."""
-        _check(self._fn("search_refine_device")(self._h, rows._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(kc),
-                                                C.c_size_t(nprobe), self._dev(d_alive), C.c_size_t(nbits), C.c_void_p(int(d_ids)),
-                                                C.c_void_p(int(d_dis)), self._dev(stream)))
+        _check(self._fn(_entry)(self._h, rows._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(kc),
+                                C.c_size_t(nprobe), self._dev(d_alive), C.c_size_t(nbits), C.c_void_p(int(d_ids)),
+                                C.c_void_p(int(d_dis)), self._dev(stream)))
+
+    def search_rounds(self, queries, k, params="", alive=None, nbits=None):
+        """search with k <= MAX_K_ROUNDS: beyond MAX_K the list scan runs once per MAX_K ranks (msvs_*_index_search_rounds)."""
+        return self.search(queries, k, params, alive, nbits, _entry="search_rounds")
+
+    def search_rounds_device(self, d_queries, nq, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """search_device with k <= MAX_K_ROUNDS."""
+        self.search_device(d_queries, nq, k, nprobe, d_ids, d_dis, stream, d_alive, nbits, _entry="search_rounds_device")
+
+    def search_refine_rounds(self, rows, queries, k, kc, params="", alive=None, nbits=None):
+        """search_refine with kc <= REFINE_MAX_CAND: the first stage is search_rounds(kc)."""
+        return self.search_refine(rows, queries, k, kc, params, alive, nbits, _entry="search_refine_rounds")
+
+    def search_refine_rounds_device(self, rows, d_queries, nq, k, kc, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """search_refine_device with kc <= REFINE_MAX_CAND."""
+        self.search_refine_device(rows, d_queries, nq, k, kc, nprobe, d_ids, d_dis, stream, d_alive, nbits,
+                                  _entry="search_refine_rounds_device")
 
     def serialize_io(self, store):
         """msvs_{sq,pq}_index_serialize_io through stream callbacks; `store` = dict NAME -> bytearray (filled in)."""

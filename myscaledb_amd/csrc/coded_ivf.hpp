@@ -350,6 +350,9 @@ struct ScanRound
     size_t nq = 0;                   // queries of the round
     const float * probe_dis = nullptr; // [query][probe] the canonical distance / inner product to every probe's centroid
     void * extra = nullptr;          // nq * RoundExtra::bytes_per_q bytes of the search's arena, 256-byte aligned
+    // a later rank round of a search with k > MSVS_MAX_K (null otherwise): [query] the last key the query has returned; the scan
+    // offers only rows whose key is strictly greater (its AFTER form)
+    const uint64_t * after = nullptr;
 };
 
 /// What an index wants of a round beside the common buffers: scratch bytes per query of its own, the coarse step's distances.
@@ -376,6 +379,38 @@ inline void fill_scan_params(Params & a, const CodedIvf & ix, const ScanRound & 
     a.pair_off = r.plan.pair_off;
     a.work_off = r.plan.work_off;
     a.pairs = r.plan.pairs;
+    a.after = r.after;
+}
+
+/// One rank round of a search with k > MSVS_MAX_K: the round's merged keys, [nq][kr] ascending and KEY_NONE-padded (launch_ivf_merge's
+/// out_keys), go to columns [col0, col0 + kr) of the [nq][k] outputs as the one-round merge writes them (label or -1; the key's value,
+/// fl(1 - v) for cosine in every slot), and a full round's LAST key becomes the query's continuation key -- KEY_NONE when the round
+/// came back short: the query is finished, later rounds offer nothing and its tail stays padded.  (kr < MSVS_MAX_K: the last round.)
+template <int METRIC>
+static __global__ __launch_bounds__(MSVS_MAX_K) void coded_round_scatter_kernel(const uint64_t * keys, uint32_t kr, uint32_t k, uint32_t col0,
+                                                                               int cosine, int64_t * out_ids, float * out_dis, uint64_t * after)
+{
+    const uint32_t q = blockIdx.x, i = threadIdx.x;
+    const uint64_t key = i < kr ? keys[(size_t)q * kr + i] : KEY_NONE;
+    if (i < kr)
+    {
+        const size_t o = (size_t)q * k + col0 + i;
+        out_ids[o] = key == KEY_NONE ? -1 : (int64_t)(uint32_t)key;
+        const float v = key_value<METRIC>(key);
+        out_dis[o] = cosine ? __fsub_rn(1.0f, v) : v;
+    }
+    if (i == MSVS_MAX_K - 1)
+        after[q] = key;
+}
+
+inline void launch_round_scatter(int metric, const uint64_t * keys, size_t nq, size_t kr, size_t k, size_t col0, bool cosine, int64_t * out_ids,
+                                 float * out_dis, uint64_t * after, hipStream_t stream)
+{
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        hipLaunchKernelGGL((coded_round_scatter_kernel<decltype(m)::value>), dim3((unsigned)nq), dim3(MSVS_MAX_K), 0, stream, keys, (uint32_t)kr,
+                           (uint32_t)k, (uint32_t)col0, cosine ? 1 : 0, out_ids, out_dis, after);
+    });
+    MSVS_HIP(hipGetLastError());
 }
 
 /// Everything on the device, enqueued on `stream`: queries padded (and normalised for cosine) into scratch, the canonical coarse
@@ -383,12 +418,17 @@ inline void fill_scan_params(Params & a, const CodedIvf & ix, const ScanRound & 
 /// row_step rows (rpb_knob: the index's option); pick_T(n_pairs, k) is the round's query tile, scan(T, grid, round) its launch.
 /// extra: what the index wants beside (RoundExtra); prepare(round) enqueues its per-query work of a round, after the queries are
 /// padded and normalised and before the plan (its round has no plan-dependent field to read: T, grid and the scan come later).
+/// k_max: MSVS_MAX_K, or MSVS_MAX_K_ROUNDS for the entries that search in rank rounds.  k > MSVS_MAX_K: everything up to the plan
+/// once per chunk of queries as ever, then ceil(k / MSVS_MAX_K) times the scan (k_round = min(MSVS_MAX_K, k - done) ranks, from the
+/// second round on only rows whose key is strictly greater than the query's continuation key: ScanRound::after), the merge to keys
+/// and launch_round_scatter.  All queries of the chunk advance together and nothing waits for the host: a query that has
+/// finished rides through the later rounds admitting nothing.  Segments, tile, LDS and partial lists are sized by min(k, MSVS_MAX_K).
 template <class PickT, class Prepare, class Scan>
 inline void search_device(const CodedIvf & ix, const char * name, const char * prof_name, const float * d_queries, size_t nq, size_t k,
-                          size_t nprobe, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream,
+                          size_t k_max, size_t nprobe, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream,
                           size_t row_step, double rpb_knob, RoundExtra extra, PickT pick_T, Prepare prepare, Scan scan)
 {
-    check_k(k);
+    check_k(k, k_max);
     check_built(ix, name);
     if (nprobe < 1)
         fail(MSVS_ERR_INVALID_ARGUMENT, "nprobe must be >= 1");
@@ -401,21 +441,27 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
         fail(MSVS_ERR_UNSUPPORTED_K, "min(nprobe, nlist) = %zu exceeds the coarse quantiser's top-k limit %d", P, MSVS_MAX_K);
     const uint32_t ld = ix.ld;
     const int m = scan_metric(ix.metric);
-    // per query of a round: its padded row, its probes and pairs
-    const SegmentPlan sp = plan_segments(ix.max_list_len, rpb_knob, row_step, P, k,
-                                         (size_t)ld * 4 + P * 8 + 64 + extra.bytes_per_q + (extra.probe_dis ? P * 4 : 0), nq);
+    const bool rounds = k > MSVS_MAX_K;
+    const size_t kl = std::min<size_t>(k, MSVS_MAX_K); // ranks of one scan
+    // per query of a round: its padded row, its probes and pairs (rounds: a round's merged keys and the continuation key)
+    const SegmentPlan sp = plan_segments(ix.max_list_len, rpb_knob, row_step, P, kl,
+                                         (size_t)ld * 4 + P * 8 + 64 + extra.bytes_per_q + (extra.probe_dis ? P * 4 : 0)
+                                             + (rounds ? (size_t)(MSVS_MAX_K + 1) * 8 : 0),
+                                         nq);
     const uint32_t rpb = sp.rpb;
     const size_t seg_max = sp.seg_max, per_q = sp.per_q, chunk = sp.chunk;
     const size_t last = nq % chunk;
     const size_t coarse = std::max(flat_scratch_bytes(nlist, chunk, (uint32_t)P, ld), last ? flat_scratch_bytes(nlist, last, (uint32_t)P, ld) : 0);
     Scratch & scr = scratch_for(stream);
-    scr.reserve(chunk * per_q + coarse + (nlist + 1) * 16 + 18 * 256, stream);
+    scr.reserve(chunk * per_q + coarse + (nlist + 1) * 16 + 20 * 256, stream);
     float * dq = scr.take<float>(chunk * ld);
     int32_t * probes = scr.take<int32_t>(chunk * P);
     float * probe_dis = extra.probe_dis ? scr.take<float>(chunk * P) : nullptr;
     void * extra_buf = extra.bytes_per_q ? scr.take<unsigned char>(chunk * extra.bytes_per_q) : nullptr;
     const GroupedPlan plan(scr, nlist, chunk * P);
-    uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * k);
+    uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * kl);
+    uint64_t * round_keys = rounds ? scr.take<uint64_t>(chunk * MSVS_MAX_K) : nullptr;
+    uint64_t * after = rounds ? scr.take<uint64_t>(chunk) : nullptr;
     const size_t mark = scr.used;
     for (size_t q0 = 0; q0 < nq; q0 += chunk)
     {
@@ -430,56 +476,64 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
         co.out_probes = probes;
         co.out_probe_dis = probe_dis;
         flat_search_device(scr, m, ix.centroids.p, nullptr, nlist, ld, dq, nqc, (uint32_t)P, nullptr, 0, co, stream);
-        const ScanRound round{dq, probes, plan, partial, d_alive, nbits, k, P, seg_max, rpb, m, nqc, probe_dis, extra_buf};
-        prepare(round);
+        const ScanRound first{dq, probes, plan, partial, d_alive, nbits, kl, P, seg_max, rpb, m, nqc, probe_dis, extra_buf};
+        prepare(first);
         MSVS_HIP(hipGetLastError());
         // 2. (query, list) pairs grouped by list -> (list, query tile, row segment) items
         const size_t n_pairs = nqc * P;
-        const uint32_t T = pick_T(n_pairs, k);
+        const uint32_t T = pick_T(n_pairs, kl);
         plan.run(probes, ix.list_off.p, n_pairs, rpb, T, stream);
-        // 3. the list scan over the codes
+        for (size_t done = 0; done < k; done += MSVS_MAX_K) // (one pass unless `rounds`)
         {
-            ProfileScope prof(prof_name, stream);
-            const uint32_t grid = (uint32_t)std::min<size_t>(2048, n_pairs * seg_max);
-            scan(T, grid, round);
-            MSVS_HIP(hipGetLastError());
+            const size_t kr = std::min<size_t>(MSVS_MAX_K, k - done);
+            const ScanRound round{dq, probes, plan, partial, d_alive, nbits, kr, P, seg_max, rpb, m, nqc, probe_dis, extra_buf, done ? after : nullptr};
+            // 3. the list scan over the codes
+            {
+                ProfileScope prof(prof_name, stream);
+                const uint32_t grid = (uint32_t)std::min<size_t>(2048, n_pairs * seg_max);
+                scan(T, grid, round);
+                MSVS_HIP(hipGetLastError());
+            }
+            // 4. per-query top-k over the valid segments of its probed lists
+            IvfMergeParams im{};
+            im.partial = partial;
+            im.probes = probes;
+            im.list_off = ix.list_off.p;
+            im.nprobe = (uint32_t)P;
+            im.seg_max = (uint32_t)seg_max;
+            im.rows_per_block = rpb;
+            im.k = (uint32_t)kr;
+            im.out_ids = d_ids + q0 * k;
+            im.out_dis = d_dis + q0 * k;
+            im.cosine = ix.metric == MSVS_METRIC_COSINE;
+            im.out_keys = round_keys;
+            launch_ivf_merge(m, im, (uint32_t)nqc, stream);
+            if (rounds)
+                launch_round_scatter(m, round_keys, nqc, kr, k, done, ix.metric == MSVS_METRIC_COSINE, d_ids + q0 * k, d_dis + q0 * k, after, stream);
         }
-        // 4. per-query top-k over the valid segments of its probed lists
-        IvfMergeParams im{};
-        im.partial = partial;
-        im.probes = probes;
-        im.list_off = ix.list_off.p;
-        im.nprobe = (uint32_t)P;
-        im.seg_max = (uint32_t)seg_max;
-        im.rows_per_block = rpb;
-        im.k = (uint32_t)k;
-        im.out_ids = d_ids + q0 * k;
-        im.out_dis = d_dis + q0 * k;
-        im.cosine = ix.metric == MSVS_METRIC_COSINE;
-        launch_ivf_merge(m, im, (uint32_t)nqc, stream);
     }
 }
 
 /// ... for an index that wants nothing beside
 template <class PickT, class Scan>
 inline void search_device(const CodedIvf & ix, const char * name, const char * prof_name, const float * d_queries, size_t nq, size_t k,
-                          size_t nprobe, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream,
+                          size_t k_max, size_t nprobe, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream,
                           size_t row_step, double rpb_knob, PickT pick_T, Scan scan)
 {
-    search_device(ix, name, prof_name, d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, row_step, rpb_knob, RoundExtra{}, pick_T,
+    search_device(ix, name, prof_name, d_queries, nq, k, k_max, nprobe, d_alive, nbits, d_ids, d_dis, stream, row_step, rpb_knob, RoundExtra{}, pick_T,
                   [](const ScanRound &) {}, scan);
 }
 
 /// The host-pointer entry: queries and filter staged to the device, dev(d_queries, nprobe, d_alive, d_ids, d_dis, stream) is the
-/// index's device search, results copied back; synchronises.
+/// index's device search, results copied back; synchronises.  k_max: the entry's limit of k.
 template <class DeviceSearch>
-inline void search_host(const CodedIvf * ix, const char * name, const float * queries, size_t nq, size_t k, const char * params,
+inline void search_host(const CodedIvf * ix, const char * name, const float * queries, size_t nq, size_t k, size_t k_max, const char * params,
                         const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis, DeviceSearch dev)
 {
     DeviceGuard on_device(ix ? ix->device : -1);
     check_index(ix);
     const size_t nprobe = parse_nprobe(params);
-    check_k(k);
+    check_k(k, k_max);
     check_built(*ix, name);
     if (nq == 0 || k == 0)
         return;
@@ -510,18 +564,20 @@ void refine_device(const msvs_rows * rows, int metric, const float * d_queries, 
 
 /// The composed entries: first(d_cand_ids, d_cand_dis) is the index's own device search with kc results (the filter applies
 /// there), its labels stay in an arena of their own on the same stream, then the refine step with the index's metric: no host round trip between.
+/// kc_max: MSVS_MAX_K, or MSVS_REFINE_MAX_CAND for the entries whose first stage searches in rank rounds.
 template <class FirstStage>
 inline void search_refine_device(const CodedIvf & ix, const char * name, const msvs_rows * rows, const float * d_queries, size_t nq, size_t k,
-                                 size_t kc, int64_t * d_ids, float * d_dis, hipStream_t stream, FirstStage first)
+                                 size_t kc, size_t kc_max, int64_t * d_ids, float * d_dis, hipStream_t stream, FirstStage first)
 {
     if (!rows)
         fail(MSVS_ERR_INVALID_ARGUMENT, "null row store");
     if (msvs_rows_dim(rows) != ix.dim || (msvs_rows_normalized(rows) != 0) != (ix.metric == MSVS_METRIC_COSINE))
         fail(MSVS_ERR_INVALID_ARGUMENT, "the row store (dim %zu, normalize=%d) does not fit the %s index (dim %zu, %s)", msvs_rows_dim(rows),
              msvs_rows_normalized(rows), name, ix.dim, ix.metric == MSVS_METRIC_COSINE ? "cosine: normalize=1" : "L2 / IP: normalize=0");
-    check_k(kc);
+    check_k(kc, kc_max);
     if (k > kc)
         fail(MSVS_ERR_INVALID_ARGUMENT, "k = %zu exceeds kc = %zu, the first stage's results", k, kc);
+    check_k(k); // (kc_max > MSVS_MAX_K: the refine step's own limit)
     check_built(ix, name);
     if (nq == 0 || k == 0)
         return;

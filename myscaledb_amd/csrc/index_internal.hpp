@@ -166,6 +166,12 @@ inline void check_k(size_t k)
     if (k > MSVS_MAX_K)
         fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the device top-k limit %d", k, MSVS_MAX_K);
 }
+/// ... for an entry whose limit is k_max (MSVS_MAX_K, MSVS_MAX_K_ROUNDS, MSVS_REFINE_MAX_CAND)
+inline void check_k(size_t k, size_t k_max)
+{
+    if (k > k_max)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the limit %zu", k, k_max);
+}
 
 /// Exhaustive top-k of device queries (nq x ld) against device rows (n x ld) -> device ids / distances (msvs_capi.hip).
 /// `scr` must have been reserved by the caller for flat_scratch_bytes().

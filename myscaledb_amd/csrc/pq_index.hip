@@ -290,10 +290,10 @@ extern "C" int msvs_pq_index_query_tables(const msvs_pq_index_t * ix) { return i
 
 // ------------------------------------------------------------------------------------------- search
 
-template <int BITS, int METRIC, int T, int R, int FORM>
+template <int BITS, int METRIC, int T, int R, int FORM, int AFTER = 0>
 static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStream_t stream)
 {
-    constexpr auto kernel = &pq_ivf_scan_kernel<BITS, METRIC, T, R, FORM>;
+    constexpr auto kernel = &pq_ivf_scan_kernel<BITS, METRIC, T, R, FORM, AFTER>;
     // more than 64 KiB of dynamic LDS needs the attribute raised once per kernel
     static std::once_flag once;
     std::call_once(once, [] {
@@ -307,7 +307,9 @@ static void pq_launch(uint32_t grid, size_t lds, const PqIvfParams & a, hipStrea
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, stream, a);
 }
 
-/// tiles of 1, 2, 4 or 8 queries; 256- or 16-entry tables; built per (query, list) pair or copied from the query's (form)
+/// tiles of 1, 2, 4 or 8 queries; 256- or 16-entry tables; built per (query, list) pair or copied from the query's (form).
+/// A later rank round (a.after) takes the AFTER form, which exists with four top-k registers per lane only: such a round
+/// follows one of MSVS_MAX_K ranks, and its own k is the search's remainder
 static void launch_pq_ivf_scan(size_t bits, int form, int metric, uint32_t T, uint32_t grid, const PqIvfParams & a, hipStream_t stream)
 {
     const size_t lds = pq_lds_bytes(bits, T, a.m, a.ld, a.k, form);
@@ -315,10 +317,13 @@ static void launch_pq_ivf_scan(size_t bits, int form, int metric, uint32_t T, ui
         with_int<8, 4>((int)bits, [&](auto b) {
             with_int<M_IP, M_L2>(metric, [&](auto m) {
                 with_int<1, 2, 4, 8>(T, [&](auto t) {
-                    with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
-                        pq_launch<decltype(b)::value, decltype(m)::value, decltype(t)::value, decltype(r)::value, decltype(f)::value>(grid, lds, a,
-                                                                                                                                      stream);
-                    });
+                    if (a.after)
+                        pq_launch<decltype(b)::value, decltype(m)::value, decltype(t)::value, 4, decltype(f)::value, 1>(grid, lds, a, stream);
+                    else
+                        with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                            pq_launch<decltype(b)::value, decltype(m)::value, decltype(t)::value, decltype(r)::value, decltype(f)::value>(
+                                grid, lds, a, stream);
+                        });
                 });
             });
         });
@@ -341,8 +346,8 @@ static void launch_pq_query_tables(const msvs_pq_index & ix, const float * dq, s
 /// search_device of coded_ivf.hpp with this index's shapes: row segments of whole 256-row steps (a segment rebuilds its tile's
 /// tables, or copies them in form 1); the tile by the pairs per list, 1 to 8 queries, halved until its tables fit.  Form 1 takes the
 /// probes' distances from the coarse step and 4 * ksub * m bytes per query of the round for the query tables, from the same arena
-static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, size_t nq, size_t k, size_t nprobe, const uint64_t * d_alive,
-                             size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, size_t nq, size_t k, size_t k_max, size_t nprobe,
+                             const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
 {
     if (ix.ready && ix.keeps_row_terms() && !ix.row_w.p)
         fail(MSVS_ERR_NOT_READY, "the IVFPQ index has no row terms: its build did not finish");
@@ -350,7 +355,7 @@ static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, 
     extra.bytes_per_q = ix.form ? ix.m * ix.ksub * 4 : 0;
     extra.probe_dis = ix.form != 0;
     search_device(
-        ix, PQ, "pq_ivf_scan", d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, BLOCK, options().pq_ivf_rpb, extra,
+        ix, PQ, "pq_ivf_scan", d_queries, nq, k, k_max, nprobe, d_alive, nbits, d_ids, d_dis, stream, BLOCK, options().pq_ivf_rpb, extra,
         [&](size_t n_pairs, size_t k_) {
             const size_t nlist = ix.nlist;
             uint32_t T = n_pairs >= 16 * nlist ? 8 : (n_pairs >= 2 * nlist ? 4 : (n_pairs >= nlist ? 2 : 1));
@@ -382,51 +387,107 @@ static void pq_search_device(const msvs_pq_index & ix, const float * d_queries, 
         });
 }
 
-extern "C" int msvs_pq_index_search_device(const msvs_pq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t nprobe,
-                                           const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+// The C entries come in two forms that differ in their limits alone: the one-round form (k, kc <= MSVS_MAX_K) and the rounds form
+// (k <= MSVS_MAX_K_ROUNDS; kc <= MSVS_REFINE_MAX_CAND).
+
+static int pq_search_device_entry(const msvs_pq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t k_max, size_t nprobe,
+                                  const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
 {
     return guarded([&] {
         check_index(ix);
-        pq_search_device(*ix, d_queries, nq, k, nprobe, d_alive_bits, nbits, d_ids, d_dis, as_stream(hip_stream));
+        pq_search_device(*ix, d_queries, nq, k, k_max, nprobe, d_alive_bits, nbits, d_ids, d_dis, as_stream(hip_stream));
     });
+}
+
+static int pq_search_entry(const msvs_pq_index_t * ix, const float * queries, size_t nq, size_t k, size_t k_max, const char * params,
+                           const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return guarded([&] {
+        search_host(ix, PQ, queries, nq, k, k_max, params, alive_bits, nbits, ids, dis,
+                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
+                        pq_search_device(*ix, dq, nq, k, k_max, nprobe, d_alive, nbits, d_ids, d_dis, stream);
+                    });
+    });
+}
+
+static int pq_search_refine_device_entry(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * d_queries, size_t nq, size_t k,
+                                         size_t kc, size_t kc_max, size_t nprobe, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
+                                         float * d_dis, void * hip_stream)
+{
+    return guarded([&] {
+        check_index(ix);
+        hipStream_t stream = as_stream(hip_stream);
+        search_refine_device(*ix, PQ, rows, d_queries, nq, k, kc, kc_max, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
+            pq_search_device(*ix, d_queries, nq, kc, kc_max, nprobe, d_alive_bits, nbits, c_ids, c_dis, stream);
+        });
+    });
+}
+
+static int pq_search_refine_entry(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * queries, size_t nq, size_t k, size_t kc,
+                                  size_t kc_max, const char * params, const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return guarded([&] {
+        search_host(ix, PQ, queries, nq, k, MSVS_MAX_K, params, alive_bits, nbits, ids, dis,
+                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
+                        search_refine_device(*ix, PQ, rows, dq, nq, k, kc, kc_max, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
+                            pq_search_device(*ix, dq, nq, kc, kc_max, nprobe, d_alive, nbits, c_ids, c_dis, stream);
+                        });
+                    });
+    });
+}
+
+extern "C" int msvs_pq_index_search_device(const msvs_pq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t nprobe,
+                                           const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return pq_search_device_entry(ix, d_queries, nq, k, MSVS_MAX_K, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
+}
+
+extern "C" int msvs_pq_index_search_rounds_device(const msvs_pq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t nprobe,
+                                                  const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                                  void * hip_stream)
+{
+    return pq_search_device_entry(ix, d_queries, nq, k, MSVS_MAX_K_ROUNDS, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
 }
 
 extern "C" int msvs_pq_index_search(const msvs_pq_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
                                     const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
 {
-    return guarded([&] {
-        search_host(ix, PQ, queries, nq, k, params, alive_bits, nbits, ids, dis,
-                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
-                        pq_search_device(*ix, dq, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream);
-                    });
-    });
+    return pq_search_entry(ix, queries, nq, k, MSVS_MAX_K, params, alive_bits, nbits, ids, dis);
+}
+
+extern "C" int msvs_pq_index_search_rounds(const msvs_pq_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
+                                           const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return pq_search_entry(ix, queries, nq, k, MSVS_MAX_K_ROUNDS, params, alive_bits, nbits, ids, dis);
 }
 
 extern "C" int msvs_pq_index_search_refine_device(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * d_queries, size_t nq,
                                                   size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits, size_t nbits,
                                                   int64_t * d_ids, float * d_dis, void * hip_stream)
 {
-    return guarded([&] {
-        check_index(ix);
-        hipStream_t stream = as_stream(hip_stream);
-        search_refine_device(*ix, PQ, rows, d_queries, nq, k, kc, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
-            pq_search_device(*ix, d_queries, nq, kc, nprobe, d_alive_bits, nbits, c_ids, c_dis, stream);
-        });
-    });
+    return pq_search_refine_device_entry(ix, rows, d_queries, nq, k, kc, MSVS_MAX_K, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
+}
+
+extern "C" int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * d_queries,
+                                                         size_t nq, size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits,
+                                                         size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return pq_search_refine_device_entry(ix, rows, d_queries, nq, k, kc, MSVS_REFINE_MAX_CAND, nprobe, d_alive_bits, nbits, d_ids, d_dis,
+                                         hip_stream);
 }
 
 extern "C" int msvs_pq_index_search_refine(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * queries, size_t nq, size_t k,
                                            size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits, int64_t * ids,
                                            float * dis)
 {
-    return guarded([&] {
-        search_host(ix, PQ, queries, nq, k, params, alive_bits, nbits, ids, dis,
-                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
-                        search_refine_device(*ix, PQ, rows, dq, nq, k, kc, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
-                            pq_search_device(*ix, dq, nq, kc, nprobe, d_alive, nbits, c_ids, c_dis, stream);
-                        });
-                    });
-    });
+    return pq_search_refine_entry(ix, rows, queries, nq, k, kc, MSVS_MAX_K, params, alive_bits, nbits, ids, dis);
+}
+
+extern "C" int msvs_pq_index_search_refine_rounds(const msvs_pq_index_t * ix, const msvs_rows_t * rows, const float * queries, size_t nq,
+                                                  size_t k, size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits,
+                                                  int64_t * ids, float * dis)
+{
+    return pq_search_refine_entry(ix, rows, queries, nq, k, kc, MSVS_REFINE_MAX_CAND, params, alive_bits, nbits, ids, dis);
 }
 
 // ------------------------------------------------------------------------------------------- export and files

@@ -290,6 +290,7 @@ struct PqIvfParams
     const float * qtab;   // [query of the round][s * ksub + j]: pq_query_table_kernel's P
     const float * pair_b; // [query][probe], indexed like pairs: the canonical distance / inner product of the query to the probe's centroid
     const float * row_w;  // [row]: pq_row_terms_kernel's w (L2 indexes)
+    const uint64_t * after; // AFTER 1 only: [query of the round] continuation keys (search in rounds, coded_ivf.hpp)
 };
 
 /// LDS bytes of a scan block: the tile's look-up tables (4 * ksub bytes per query and sub-space), its queries, the list's centroid,
@@ -307,7 +308,9 @@ inline size_t pq_lds_bytes(size_t bits, uint32_t T, uint32_t m, uint32_t ld, uin
 /// FORM 1 (query_tables=1; dynamic LDS pq_lds_bytes(BITS, T, m, ld, k, 1)): the prologue stages no query and no centroid and computes
 /// nothing -- it copies the table P of each tile query (pq_query_table_kernel) into lut and the pairs' terms b into bs; the row loop
 /// sums the same look-ups and the row's score is fl(fl(b + w[r]) - fl(2 * acc)) (L2) or fl(b + acc) (IP, cosine).
-template <int BITS, int METRIC, int T, int R, int FORM = 0>
+/// AFTER 1: as in sq_ivf_scan_kernel -- a row is offered to tile query t only if its key is strictly greater than
+/// a.after[query of t], read once per work item into scalar registers.  AFTER 0 never reads a.after.
+template <int BITS, int METRIC, int T, int R, int FORM = 0, int AFTER = 0>
 __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
 {
     constexpr uint32_t KSUB = 1u << BITS;  // entries of a table
@@ -332,6 +335,7 @@ __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
         const IvfWorkItem it = ivf_work_item<T>(w, a.work_off, a.pair_off, a.list_off, a.nlist, a.rows_per_block);
         const uint32_t l = it.list, seg = it.seg, row_begin = it.row_begin, row_end = it.row_end;
         uint64_t * out[T];
+        uint64_t floor_key[T];
         __syncthreads(); // the previous item is done with the LDS
 #pragma unroll
         for (int t = 0; t < T; t++)
@@ -339,6 +343,7 @@ __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
             const uint32_t pi = min(it.pair_begin + t, it.pair_end - 1); // short tiles repeat their last pair (same slot, same values)
             const uint32_t qp = a.pairs[pi];
             out[t] = a.partial + ((size_t)qp * a.seg_max + seg) * k;
+            floor_key[t] = AFTER ? uniform_key(a.after[qp / a.nprobe]) : 0;
             if (FORM)
             {
                 // the query's table, four entries a load (m * KSUB is a multiple of 16, a table is 64-byte aligned): i4 < m * KSUB / 4
@@ -478,7 +483,12 @@ __global__ __launch_bounds__(BLOCK) void pq_ivf_scan_kernel(const PqIvfParams a)
                 }
 #pragma unroll
                 for (int t = 0; t < T; t++)
-                    top[t].offer(ok ? make_key<METRIC>(dis[t], id) : KEY_NONE, k, lane);
+                {
+                    uint64_t key = ok ? make_key<METRIC>(dis[t], id) : KEY_NONE;
+                    if (AFTER)
+                        key = key > floor_key[t] ? key : KEY_NONE;
+                    top[t].offer(key, k, lane);
+                }
             }
         }
 

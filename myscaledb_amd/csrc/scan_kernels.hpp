@@ -72,6 +72,13 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane)
     return (uint64_t)hi << 32 | lo;
 }
 
+/// A value that is the same in every lane, moved into scalar registers.
+__device__ __forceinline__ uint64_t uniform_key(uint64_t v)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return (uint64_t)hi << 32 | lo;
+}
+
 /// Lane i gets lane i-1's value (lane 0: unspecified).  DPP wave_shr:1 -- a register move, against the ds_bpermute
 /// round trip through the LDS crossbar that __shfl_up costs; this sits on the serial path of every top-k insertion.
 __device__ __forceinline__ uint64_t shfl_up64(uint64_t v)

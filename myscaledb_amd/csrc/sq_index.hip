@@ -185,26 +185,31 @@ extern "C" size_t msvs_sq_index_memory_usage(const msvs_sq_index_t * ix)
 
 // ------------------------------------------------------------------------------------------- search
 
-/// tiles of 2, 4 or 8 queries (no T = 1)
+/// tiles of 2, 4 or 8 queries (no T = 1).  A later rank round (a.after) takes the AFTER form, which exists with four top-k
+/// registers per lane only: such a round follows one of MSVS_MAX_K ranks, and its own k is the search's remainder
 static void launch_sq_ivf_scan(int metric, uint32_t T, uint32_t grid, const SqIvfParams & a, hipStream_t stream)
 {
     with_int<M_IP, M_L2>(metric, [&](auto m) {
         with_int<2, 4, 8>(T, [&](auto t) {
-            with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
-                constexpr int METRIC = decltype(m)::value, TQ = decltype(t)::value, R = decltype(r)::value;
-                hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, TQ, R>), dim3(grid), dim3(BLOCK), sq_lds_bytes(TQ, a.ld4, a.k), stream, a);
-            });
+            constexpr int METRIC = decltype(m)::value, TQ = decltype(t)::value;
+            if (a.after)
+                hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, TQ, 4, 1>), dim3(grid), dim3(BLOCK), sq_lds_bytes(TQ, a.ld4, a.k), stream, a);
+            else
+                with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
+                    constexpr int R = decltype(r)::value;
+                    hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, TQ, R>), dim3(grid), dim3(BLOCK), sq_lds_bytes(TQ, a.ld4, a.k), stream, a);
+                });
         });
     });
 }
 
 /// search_device of coded_ivf.hpp with this index's shapes: row segments of whole 16-row steps, tiles of 2, 4 or 8 queries
-static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, size_t nq, size_t k, size_t nprobe, const uint64_t * d_alive,
-                             size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, size_t nq, size_t k, size_t k_max, size_t nprobe,
+                             const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
 {
     const uint32_t ld4 = ix.ld / 4;
     search_device(
-        ix, SQ, "sq_ivf_scan", d_queries, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream, 16, options().sq_ivf_rpb,
+        ix, SQ, "sq_ivf_scan", d_queries, nq, k, k_max, nprobe, d_alive, nbits, d_ids, d_dis, stream, 16, options().sq_ivf_rpb,
         [&](size_t n_pairs, size_t k_) {
             uint32_t T = n_pairs >= 16 * ix.nlist ? 8 : (n_pairs >= 2 * ix.nlist ? 4 : 2);
             while (T > 2 && sq_lds_bytes(T, ld4, (uint32_t)k_) > SCAN_LDS_BUDGET)
@@ -224,51 +229,107 @@ static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, 
         });
 }
 
-extern "C" int msvs_sq_index_search_device(const msvs_sq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t nprobe,
-                                           const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+// The C entries come in two forms that differ in their limits alone: the one-round form (k, kc <= MSVS_MAX_K) and the rounds form
+// (k <= MSVS_MAX_K_ROUNDS; kc <= MSVS_REFINE_MAX_CAND).
+
+static int sq_search_device_entry(const msvs_sq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t k_max, size_t nprobe,
+                                  const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
 {
     return guarded([&] {
         check_index(ix);
-        sq_search_device(*ix, d_queries, nq, k, nprobe, d_alive_bits, nbits, d_ids, d_dis, as_stream(hip_stream));
+        sq_search_device(*ix, d_queries, nq, k, k_max, nprobe, d_alive_bits, nbits, d_ids, d_dis, as_stream(hip_stream));
     });
+}
+
+static int sq_search_entry(const msvs_sq_index_t * ix, const float * queries, size_t nq, size_t k, size_t k_max, const char * params,
+                           const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return guarded([&] {
+        search_host(ix, SQ, queries, nq, k, k_max, params, alive_bits, nbits, ids, dis,
+                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
+                        sq_search_device(*ix, dq, nq, k, k_max, nprobe, d_alive, nbits, d_ids, d_dis, stream);
+                    });
+    });
+}
+
+static int sq_search_refine_device_entry(const msvs_sq_index_t * ix, const msvs_rows_t * rows, const float * d_queries, size_t nq, size_t k,
+                                         size_t kc, size_t kc_max, size_t nprobe, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
+                                         float * d_dis, void * hip_stream)
+{
+    return guarded([&] {
+        check_index(ix);
+        hipStream_t stream = as_stream(hip_stream);
+        search_refine_device(*ix, SQ, rows, d_queries, nq, k, kc, kc_max, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
+            sq_search_device(*ix, d_queries, nq, kc, kc_max, nprobe, d_alive_bits, nbits, c_ids, c_dis, stream);
+        });
+    });
+}
+
+static int sq_search_refine_entry(const msvs_sq_index_t * ix, const msvs_rows_t * rows, const float * queries, size_t nq, size_t k, size_t kc,
+                                  size_t kc_max, const char * params, const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return guarded([&] {
+        search_host(ix, SQ, queries, nq, k, MSVS_MAX_K, params, alive_bits, nbits, ids, dis,
+                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
+                        search_refine_device(*ix, SQ, rows, dq, nq, k, kc, kc_max, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
+                            sq_search_device(*ix, dq, nq, kc, kc_max, nprobe, d_alive, nbits, c_ids, c_dis, stream);
+                        });
+                    });
+    });
+}
+
+extern "C" int msvs_sq_index_search_device(const msvs_sq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t nprobe,
+                                           const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return sq_search_device_entry(ix, d_queries, nq, k, MSVS_MAX_K, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
+}
+
+extern "C" int msvs_sq_index_search_rounds_device(const msvs_sq_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t nprobe,
+                                                  const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                                  void * hip_stream)
+{
+    return sq_search_device_entry(ix, d_queries, nq, k, MSVS_MAX_K_ROUNDS, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
 }
 
 extern "C" int msvs_sq_index_search(const msvs_sq_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
                                     const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
 {
-    return guarded([&] {
-        search_host(ix, SQ, queries, nq, k, params, alive_bits, nbits, ids, dis,
-                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
-                        sq_search_device(*ix, dq, nq, k, nprobe, d_alive, nbits, d_ids, d_dis, stream);
-                    });
-    });
+    return sq_search_entry(ix, queries, nq, k, MSVS_MAX_K, params, alive_bits, nbits, ids, dis);
+}
+
+extern "C" int msvs_sq_index_search_rounds(const msvs_sq_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
+                                           const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return sq_search_entry(ix, queries, nq, k, MSVS_MAX_K_ROUNDS, params, alive_bits, nbits, ids, dis);
 }
 
 extern "C" int msvs_sq_index_search_refine_device(const msvs_sq_index_t * ix, const msvs_rows_t * rows, const float * d_queries, size_t nq,
                                                   size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits, size_t nbits,
                                                   int64_t * d_ids, float * d_dis, void * hip_stream)
 {
-    return guarded([&] {
-        check_index(ix);
-        hipStream_t stream = as_stream(hip_stream);
-        search_refine_device(*ix, SQ, rows, d_queries, nq, k, kc, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
-            sq_search_device(*ix, d_queries, nq, kc, nprobe, d_alive_bits, nbits, c_ids, c_dis, stream);
-        });
-    });
+    return sq_search_refine_device_entry(ix, rows, d_queries, nq, k, kc, MSVS_MAX_K, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
+}
+
+extern "C" int msvs_sq_index_search_refine_rounds_device(const msvs_sq_index_t * ix, const msvs_rows_t * rows, const float * d_queries,
+                                                         size_t nq, size_t k, size_t kc, size_t nprobe, const uint64_t * d_alive_bits,
+                                                         size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return sq_search_refine_device_entry(ix, rows, d_queries, nq, k, kc, MSVS_REFINE_MAX_CAND, nprobe, d_alive_bits, nbits, d_ids, d_dis,
+                                         hip_stream);
 }
 
 extern "C" int msvs_sq_index_search_refine(const msvs_sq_index_t * ix, const msvs_rows_t * rows, const float * queries, size_t nq, size_t k,
                                            size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits, int64_t * ids,
                                            float * dis)
 {
-    return guarded([&] {
-        search_host(ix, SQ, queries, nq, k, params, alive_bits, nbits, ids, dis,
-                    [&](const float * dq, size_t nprobe, const uint64_t * d_alive, int64_t * d_ids, float * d_dis, hipStream_t stream) {
-                        search_refine_device(*ix, SQ, rows, dq, nq, k, kc, d_ids, d_dis, stream, [&](int64_t * c_ids, float * c_dis) {
-                            sq_search_device(*ix, dq, nq, kc, nprobe, d_alive, nbits, c_ids, c_dis, stream);
-                        });
-                    });
-    });
+    return sq_search_refine_entry(ix, rows, queries, nq, k, kc, MSVS_MAX_K, params, alive_bits, nbits, ids, dis);
+}
+
+extern "C" int msvs_sq_index_search_refine_rounds(const msvs_sq_index_t * ix, const msvs_rows_t * rows, const float * queries, size_t nq,
+                                                  size_t k, size_t kc, const char * params, const uint64_t * alive_bits, size_t nbits,
+                                                  int64_t * ids, float * dis)
+{
+    return sq_search_refine_entry(ix, rows, queries, nq, k, kc, MSVS_REFINE_MAX_CAND, params, alive_bits, nbits, ids, dis);
 }
 
 // ------------------------------------------------------------------------------------------- export and files

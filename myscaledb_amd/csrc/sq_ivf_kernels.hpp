@@ -110,6 +110,7 @@ struct SqIvfParams
     uint32_t nlist, rows_per_block, seg_max;
     const int64_t * list_off; // [nlist + 1]
     const uint32_t * pair_off, * work_off, * pairs; // the plan (IvfPlanParams)
+    const uint64_t * after;  // AFTER 1 only: [query of the round] continuation keys (search in rounds, coded_ivf.hpp)
 };
 
 /// LDS bytes of a scan block: the tile's queries, the list's centroid, vmin, step, and the merge lists.
@@ -117,7 +118,10 @@ inline size_t sq_lds_bytes(uint32_t T, uint32_t ld4, uint32_t k) { return (size_
 
 /// grid: any size; slot -> work item (list, query tile, row segment) as in ivf_batched_scan_kernel (an XCD walks one contiguous range).
 /// dynamic LDS: sq_lds_bytes(T, ld4, k).
-template <int METRIC, int T, int R>
+/// AFTER 1 (a later round of a search with k > MSVS_MAX_K): a row is offered to tile query t only if its key is strictly greater
+/// than a.after[query of t], the last key the query has returned; KEY_NONE there admits nothing.  The floor is read once per work
+/// item and is uniform over the workgroup (scalar registers).  AFTER 0 never reads a.after.
+template <int METRIC, int T, int R, int AFTER = 0>
 __global__ __launch_bounds__(BLOCK) void sq_ivf_scan_kernel(const SqIvfParams a)
 {
     const uint32_t ld4 = a.ld4, k = a.k;
@@ -174,6 +178,7 @@ __global__ __launch_bounds__(BLOCK) void sq_ivf_scan_kernel(const SqIvfParams a)
         const IvfWorkItem it = ivf_work_item<T>(w, a.work_off, a.pair_off, a.list_off, a.nlist, a.rows_per_block);
         const uint32_t l = it.list, seg = it.seg, row_begin = it.row_begin, row_end = it.row_end;
         uint64_t * out[T];
+        uint64_t floor_key[T];
         __syncthreads(); // the previous item is done with the LDS
 #pragma unroll
         for (int t = 0; t < T; t++)
@@ -181,6 +186,7 @@ __global__ __launch_bounds__(BLOCK) void sq_ivf_scan_kernel(const SqIvfParams a)
             const uint32_t pi = min(it.pair_begin + t, it.pair_end - 1); // short tiles repeat their last pair (same slot, same values)
             const uint32_t qp = a.pairs[pi];
             out[t] = a.partial + ((size_t)qp * a.seg_max + seg) * k;
+            floor_key[t] = AFTER ? uniform_key(a.after[qp / a.nprobe]) : 0;
             const float4 * src = a.Q + (size_t)(qp / a.nprobe) * ld4;
             for (uint32_t c = tid; c < ld4; c += BLOCK)
                 qs[t * ld4 + c] = src[c];
@@ -260,7 +266,10 @@ __global__ __launch_bounds__(BLOCK) void sq_ivf_scan_kernel(const SqIvfParams a)
             {
                 float sum = __fadd_rn(__fadd_rn(acc[t].x, acc[t].y), __fadd_rn(acc[t].z, acc[t].w));
                 sum = row16_tree_sum(sum);
-                top[t].offer(ok ? make_key<METRIC>(sum, id) : KEY_NONE, k, lane);
+                uint64_t key = ok ? make_key<METRIC>(sum, id) : KEY_NONE;
+                if (AFTER)
+                    key = key > floor_key[t] ? key : KEY_NONE;
+                top[t].offer(key, k, lane);
             }
         }
 

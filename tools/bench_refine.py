@@ -10,12 +10,14 @@ of the device entries on one stream (median of --reps), and the legs that are co
   - the whole two-stage step: search_refine_device(k, kc) of the PQ index over either store beside search_device(k) of the IVFFLAT
     index and the PQ index's own first stage at k and at kc, same nprobe; recall@k of each against an exact scan of the rows on
     the first 256 queries;
+  - first stages beyond 256 candidates (--kcs, default 256, 512 and 1024): search_rounds_device(kc) alone and
+    search_refine_rounds_device(k, kc) over the device store, with the recall@k of the latter;
   - device bytes (memory_usage) of the three configurations: PQ + device rows, PQ + pinned rows, IVFFLAT.
 
 Writes one JSON file (default profiles/refine.json) and prints it.
 
     python -m tools.bench_refine [--rows N] [--dim D] [--nlist L] [--m M] [--batch 4096] [--nprobe P] [--k 10] [--kc 100] [--reps R]
-                                 [--no-pinned] [--query-tables] [--out FILE]
+                                 [--kcs 256,512,1024] [--no-pinned] [--query-tables] [--out FILE]
 """
 import argparse
 import json
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--nprobe", type=int, default=32)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--kc", type=int, default=100)
+    ap.add_argument("--kcs", default="256,512,1024", help="first stages in rank rounds (search_rounds_device), comma separated; empty: none")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--no-pinned", action="store_true", help="leave the pinned store out")
     ap.add_argument("--query-tables", action="store_true", help="the PQ index in the query-table form (query_tables=1)")
@@ -131,6 +134,25 @@ def main():
     out["two_stage"] = {"queries": nq, "times": summary(timed(legs, a.reps)), "recall_at_k": {n: recall(r) for n, r in results.items()}}
     if "pinned" in stores:
         out["two_stage"]["device_and_pinned_agree"] = bool((results["pq_search_refine_device"] == results["pq_search_refine_pinned"]).all())
+    # first stages beyond one round of 256 ranks (search_rounds_device: the list scan once per 256 ranks, coarse step and plan once):
+    # the first stage alone and the whole step over the device store at every kc of --kcs, recall@k of the whole step
+    kcs = [int(v) for v in a.kcs.split(",") if v]
+    if kcs:
+        d_cand2 = torch.empty((nq, max(kcs)), device=dev, dtype=torch.int64)
+        d_cdis2 = torch.empty((nq, max(kcs)), device=dev, dtype=torch.float32)
+        legs, results = {}, {}
+        for c in kcs:
+            legs["pq_first_stage_rounds_kc%d" % c] = (lambda c: lambda: pq.search_rounds_device(dq.data_ptr(), nq, c, a.nprobe, d_cand2.data_ptr(),
+                                                                                                d_cdis2.data_ptr(), stream))(c)
+            legs["pq_search_refine_rounds_device_kc%d" % c] = (lambda c: lambda: pq.search_refine_rounds_device(
+                stores["device"], dq.data_ptr(), nq, k, c, a.nprobe, d_ids.data_ptr(), d_dis.data_ptr(), stream))(c)
+        for n, fn in legs.items():
+            if "refine" in n:
+                fn()
+                torch.cuda.synchronize()
+                results[n] = d_ids.cpu().numpy()
+        out["large_first_stage"] = {"queries": nq, "kcs": kcs, "times": summary(timed(legs, a.reps)),
+                                    "recall_at_k": {n: recall(r) for n, r in results.items()}}
     out["device_bytes"] = {"pq": pq.memory_usage, "ivfflat": flat.memory_usage,
                            "pq_plus_rows_" + "device": pq.memory_usage + stores["device"].memory_usage}
     if "pinned" in stores:
