@@ -229,8 +229,6 @@ struct Options
     double h8_pairs_split = -1; // ... the first query of the scatter launch's share (the histogram launch takes those below it; -1: half of the batch;
                                 // tests: 0 and nq put every pair into one launch)
     double h16_prune = 1;     // shadow list scan (L2): drop (query, list) pairs that provably cannot hold one of the query's k nearest rows when the lists are probed by more than a tile of queries (0: off, 2: always)
-    double coarse_gemm_tq = 64; // coarse_gemm_kernel: queries per workgroup tile (64 or 128)
-    double coarse_gemm_tc = 128; // ... and centroids (64 or 128)
     double coarse_slow_inline = 1; // coarse_tail_kernel: a query without a band computed exactly by its own wavefront while such queries are rare (0: always the queue + its three launches)
     double coarse_slow_window = 64; // ... rare = none in this many batched searches of the index
     double coarse_prune_first = 1; // coarse_tail_kernel (L2): the pre-pruning decided first, on all the words -- a query whose pruned probe list follows from them

@@ -113,7 +113,23 @@ struct msvs_index
     struct PlanFeedback
     {
         uint32_t * pairs = nullptr; // pinned host memory, 0xFFFFFFFF: nothing yet
-        mutable uint32_t nq = 0, nprobe = 0;
+        mutable std::atomic<uint64_t> shape{0}; // nq << 32 | nprobe of the search that armed the word last (one word: a reader never sees half a shape)
+        /// The pair count the last plan left and the batch size it belongs to -> false: none yet, or it was counted for another nprobe.
+        bool last(size_t nprobe, uint32_t & seen, uint32_t & nq) const
+        {
+            if (!pairs)
+                return false;
+            seen = *reinterpret_cast<volatile uint32_t *>(pairs);
+            const uint64_t s = shape.load(std::memory_order_relaxed);
+            nq = (uint32_t)(s >> 32);
+            return seen != 0xFFFFFFFFu && nq != 0 && (uint32_t)s == (uint32_t)nprobe;
+        }
+        /// This search's plan will count its pairs: note its shape -> the pinned word for the plan kernel.
+        uint32_t * note(size_t nq, size_t nprobe) const
+        {
+            shape.store((uint64_t)nq << 32 | (uint32_t)nprobe, std::memory_order_relaxed);
+            return pairs;
+        }
         // pairs[1], pairs[2]: the sequence number (`seq`) of the last batched search whose coarse stage met a query without a band, and
         // whether there has been one at all (coarse_tail_kernel writes them; table_candidate_pass picks the form of the queue by them)
         mutable std::atomic<uint32_t> seq{0};

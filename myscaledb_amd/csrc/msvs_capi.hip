@@ -543,17 +543,6 @@ static size_t fallback_cap(size_t nq, size_t nprobe, size_t seg_max, uint32_t k)
     return std::min(nq, std::max<size_t>(64, ((size_t)256 << 20) / per_query));
 }
 
-static void run_fallback_rounds(int metric, ScanParams c, IvfMergeParams fm, size_t nq, size_t cap, uint32_t slots, hipStream_t stream)
-{
-    for (size_t base = 0; base < nq; base += cap)
-    {
-        c.slot_base = fm.slot_base = (uint32_t)base;
-        c.slot_cap = fm.slot_cap = (uint32_t)cap;
-        launch_ivf_scan_subset(metric, c, slots, stream);
-        launch_ivf_merge_subset(metric, fm, slots, stream);
-    }
-}
-
 static void set_error_model_h16(RerankParams & rp, size_t dim, float rho_table = -1.f, const float * qrho = nullptr);
 static void set_prune_error_model(H16Prune & pr, const msvs_index & ix, const float * qrho, bool remote_words = false, bool foreign_rows = false);
 
@@ -601,103 +590,159 @@ static bool host_signal_round(HostSignal & hs, const uint32_t * nfail, hipStream
     return __atomic_load_n(hs.nfail, __ATOMIC_ACQUIRE) == 0;
 }
 
-/// Second half of a table pass, whatever produced the candidates: canonical re-rank + certificate, then the canonical scan
-/// of the table for the queries on the fail list.
-static RerankParams table_rerank_params(const msvs_index & ix, const TablePass & t, const ScanParams & a, const float * qnorm,
-                                        const uint64_t * cand, const uint64_t * bound, uint32_t kc, uint32_t * failq, uint32_t * nfail,
-                                        bool h16, const float * qrho);
-static void table_pass_fallback(int m, const TablePass & t, const ScanParams & a, size_t nq, uint32_t * failq, uint32_t * nfail,
-                                uint64_t * partial1, size_t fb_cap, uint32_t rpb1, uint32_t seg_max1, const int32_t * probes0,
-                                const int64_t * list_off, hipStream_t stream);
-
-/// slowq / nslow (nullable): the coarse quantiser's selection + band ran in coarse_tail_kernel; the re-rank launch serves only the
-/// queries it queued.
-static void table_pass_tail(const msvs_index & ix, int m, const TablePass & t, const ScanParams & a, size_t nq, const float * qnorm,
-                            const uint64_t * cand, const uint64_t * bound, uint32_t kc, uint32_t * failq, uint32_t * nfail,
-                            uint64_t * partial1, size_t fb_cap, uint32_t rpb1, uint32_t seg_max1, const int32_t * probes0,
-                            const int64_t * list_off, bool h16, const float * qrho, hipStream_t stream, const uint32_t * slowq = nullptr,
-                            const uint32_t * nslow = nullptr)
+static void run_fallback_rounds(int metric, ScanParams c, IvfMergeParams fm, size_t nq, size_t cap, uint32_t slots, hipStream_t stream)
 {
-    RerankParams rp = table_rerank_params(ix, t, a, qnorm, cand, bound, kc, failq, nfail, h16, qrho);
-    rp.qmap = slowq;
-    rp.qcount = nslow;
-    if (t.out_probes)
-        g_coarse_queries.fetch_add(nq, std::memory_order_relaxed);
-    launch_ivf_rerank(scan_metric(m), rp, (uint32_t)nq, stream);
-    table_pass_fallback(m, t, a, nq, failq, nfail, partial1, fb_cap, rpb1, seg_max1, probes0, list_off, stream);
+    for (size_t base = 0; base < nq; base += cap)
+    {
+        c.slot_base = fm.slot_base = (uint32_t)base;
+        c.slot_cap = fm.slot_cap = (uint32_t)cap;
+        launch_ivf_scan_subset(metric, c, slots, stream);
+        launch_ivf_merge_subset(metric, fm, slots, stream);
+    }
 }
 
-static RerankParams table_rerank_params(const msvs_index & ix, const TablePass & t, const ScanParams & a, const float * qnorm,
-                                        const uint64_t * cand, const uint64_t * bound, uint32_t kc, uint32_t * failq, uint32_t * nfail,
-                                        bool h16, const float * qrho)
+/// The top-k merge over the partial lists a canonical scan left: `seg_max` lists of k keys per (query, probe), segments of `rpb` rows.
+static IvfMergeParams ivf_merge_params(const uint64_t * partial, const int32_t * probes, const int64_t * list_off, size_t nprobe, uint32_t seg_max,
+                                       uint32_t rpb, uint32_t k, int64_t * out_ids, float * out_dis, bool cosine)
 {
-    RerankParams rp{};
-    rp.Y = a.Y;
-    rp.ids = t.ids;
-    rp.Q = a.Q;
-    rp.qnorm = qnorm;
-    rp.cand = cand;
-    rp.bound = bound;
-    rp.kc = kc;
-    rp.k = t.k;
-    rp.ld4 = a.ld4;
-    rp.out_probes = t.out_probes;
-    rp.out_ids = t.out_ids;
-    rp.out_dis = t.out_dis;
-    rp.cosine = t.cosine;
-    if (h16)
-        set_error_model_h16(rp, ix.dim, t.h16_rho, qrho);
-    else
-        set_error_model(rp, ix.dim);
-    rp.xmax = t.norm_max;
-    rp.failq = failq;
-    rp.nfail = nfail;
-    rp.early_exit = options().rerank_early != 0 && !t.out_probes ? 1 : 0; // result passes only: the centroid table gains nothing
-    rp.band = t.out_probes && h16 && options().coarse_band != 0 ? 1 : 0;
-    rp.stat_fail = prefilter_fail_counter() + (t.out_probes ? 1 : 0); // msvs_prefilter_stats / msvs_coarse_stats
-    rp.stat_skip = options().rerank_stats != 0 ? prefilter_fail_counter() + (t.out_probes ? 4 : 2) : nullptr;
-    rp.stat_rows = options().rerank_stats != 0 && !t.out_probes ? prefilter_fail_counter() + 12 : nullptr; // msvs_debug_rerank_rows
+    IvfMergeParams im{};
+    im.partial = partial;
+    im.probes = probes;
+    im.list_off = list_off;
+    im.nprobe = (uint32_t)nprobe;
+    im.seg_max = seg_max;
+    im.rows_per_block = rpb;
+    im.k = k;
+    im.out_ids = out_ids;
+    im.out_dis = out_dis;
+    im.cosine = cosine;
+    return im;
+}
+
+/// What a candidate pass hands to certified_tail: the rows and queries, its finished candidates and error model, where the results go,
+/// and every point in which the passes differ (the coarse table pass, a FLAT table's result pass, the shadow and the split-bf16 list scan).
+struct CertifiedTail
+{
+    const float4 * Y = nullptr;      // the rows the candidates' low words index, ld4 float4 each ...
+    const uint32_t * ids = nullptr;  // ... their ids (nullable: the position) ...
+    float xmax = 0.f;                // ... and the largest |row|^2
+    const uint64_t * alive = nullptr; // the filter over the ids (the fallback's scan applies it again)
+    uint32_t nbits = 0;
+    const float4 * Q = nullptr;
+    const float * qnorm = nullptr;
+    uint32_t ld4 = 0, k = 0;
+    const uint64_t * cand = nullptr;  // [nq][kc], ascending
+    const uint64_t * bound = nullptr; // [nq]: the smallest key the pass may have dropped
+    uint32_t kc = 0;
+    uint32_t * failq = nullptr, * nfail = nullptr; // the re-rank's fail list (nfail zeroed by the pass)
+    int32_t * out_probes = nullptr; // either the probe lists (the coarse table pass) ...
+    int64_t * out_ids = nullptr;    // ... or (ids, distances)
+    float * out_dis = nullptr;
+    bool cosine = false;
+    RerankParams model{}; // the pass's error model and nothing else (set_error_model / _h16 / _i8r)
+    bool early_exit = false; // result passes: the centroid table gains nothing
+    bool band = false;       // the coarse pass over the centroid shadow
+    const uint32_t * qmap = nullptr, * qcount = nullptr; // ... whose re-rank launch serves only the queries coarse_tail_kernel queued
+    unsigned long long * stat_fail = nullptr, * stat_skip = nullptr, * stat_rows = nullptr; // words of prefilter_fail_counter(), nullable
+    std::atomic<unsigned long long> * queries = nullptr; // += nq: g_coarse_queries or g_prefilter_queries
+    // second chance (the shadow list scan; ra.partial set = on): the pass fills partial / qcnt / qthr / cap / nfail_out, the tail the rest
+    RerankAllParams ra{};
+    bool fused = false;  // ... inside the re-rank launch
+    bool signal = false; // a host-pointer call's armed signal (HostSignal) is this pass's to use: the passes that leave the RESULTS
+    // canonical fallback of the queries still without a certificate: the lists it scans, in segments of rpb1 rows
+    const int32_t * probes = nullptr;
+    const int64_t * list_off = nullptr;
+    uint32_t nprobe = 0, rpb1 = 0, seg_max1 = 0, slots = 0;
+};
+
+static RerankParams rerank_params(const CertifiedTail & in)
+{
+    RerankParams rp = in.model;
+    rp.Y = in.Y;
+    rp.ids = in.ids;
+    rp.Q = in.Q;
+    rp.qnorm = in.qnorm;
+    rp.cand = in.cand;
+    rp.bound = in.bound;
+    rp.kc = in.kc;
+    rp.k = in.k;
+    rp.ld4 = in.ld4;
+    rp.out_probes = in.out_probes;
+    rp.out_ids = in.out_ids;
+    rp.out_dis = in.out_dis;
+    rp.cosine = in.cosine;
+    rp.xmax = in.xmax;
+    rp.failq = in.failq;
+    rp.nfail = in.nfail;
+    rp.early_exit = in.early_exit ? 1 : 0;
+    rp.band = in.band ? 1 : 0;
+    rp.qmap = in.qmap;
+    rp.qcount = in.qcount;
+    rp.stat_fail = in.stat_fail; // msvs_prefilter_stats / msvs_coarse_stats
+    rp.stat_skip = in.stat_skip;
+    rp.stat_rows = in.stat_rows; // msvs_debug_rerank_rows
     return rp;
 }
 
-static void table_pass_fallback(int m, const TablePass & t, const ScanParams & a, size_t nq, uint32_t * failq, uint32_t * nfail,
-                                uint64_t * partial1, size_t fb_cap, uint32_t rpb1, uint32_t seg_max1, const int32_t * probes0,
-                                const int64_t * list_off, hipStream_t stream)
+/// Second half of every candidate pass, whatever produced the candidates: canonical re-rank + certificate, the second chance of the
+/// queries without one (every row of their candidate buffers, certified against the cut), then the canonical scan of their lists
+/// for those still on the fail list (one query per block; normally nobody).
+static void certified_tail(Scratch & scr, int metric, CertifiedTail in, size_t nq, hipStream_t stream)
 {
-    // queries without a certificate: canonical scan of the table
-    ScanParams c = a;
-    c.k = t.k;
-    c.partial = partial1;
-    c.rows_per_block = rpb1;
-    c.seg_max = seg_max1;
-    c.qmap = failq;
-    c.qcount = nfail;
-    const uint32_t slots = (uint32_t)std::min<size_t>(nq, 8);
-    IvfMergeParams fm{};
-    fm.partial = partial1;
-    fm.probes = probes0;
-    fm.list_off = list_off;
-    fm.nprobe = 1;
-    fm.seg_max = seg_max1;
-    fm.rows_per_block = rpb1;
-    fm.k = t.k;
-    fm.out_probes = t.out_probes;
-    fm.out_ids = t.out_ids;
-    fm.out_dis = t.out_dis;
-    fm.cosine = t.cosine;
-    fm.qmap = failq;
-    fm.qcount = nfail;
-    HostSignal & hs = host_signal();
-    if (hs.armed && t.flat_h16 && !t.out_probes)
+    RerankParams rp = rerank_params(in);
+    const bool second = in.ra.partial != nullptr;
+    uint32_t * failq = in.failq, * nfail = in.nfail; // who reaches the fallback
+    if (second)
     {
-        // host-pointer call of a few queries: tell the host, let it decide about the fallback
-        if (host_signal_round(hs, nfail, stream))
-            return;
-        run_fallback_rounds(scan_metric(m), c, fm, nq, fb_cap, slots, stream);
-        MSVS_HIP(hipStreamSynchronize(stream));
-        return;
+        rp.ek_out = options().rerank_hint != 0 ? scr.take<uint64_t>(nq) : nullptr; // written for failing queries only
+        in.ra.failq_in = in.failq;
+        in.ra.nfail_in = in.nfail;
+        in.ra.failq_out = failq = scr.take<uint32_t>(nq);
+        nfail = in.ra.nfail_out;
+        in.ra.stat_fail = prefilter_fail_counter();
+        in.ra.ek_in = rp.ek_out;
+        if (in.fused)
+        {
+            rp.fuse_second = 1;
+            rp.ra = in.ra;
+        }
     }
-    run_fallback_rounds(scan_metric(m), c, fm, nq, fb_cap, slots, stream);
+    if (in.queries)
+        in.queries->fetch_add(nq, std::memory_order_relaxed);
+    launch_ivf_rerank(metric, rp, (uint32_t)nq, stream);
+    // a small batch through msvs_index_search (search_entry.hip: the pinned form): the host learns how many queries are without a
+    // certificate and enqueues the second chance and the fallback rounds -- three launches that normally find nothing to do, ~14 of
+    // the batch's ~138 us -- only when somebody is; the results are in pinned memory at its return either way
+    HostSignal & hs = host_signal();
+    const bool signalled = in.signal && hs.armed;
+    if (signalled && host_signal_round(hs, in.fused ? nfail : in.nfail, stream))
+        return;
+    if (second && !in.fused)
+        launch_ivf_rerank_all(metric, rp, in.ra, (uint32_t)nq, stream);
+    const size_t fb_cap = fallback_cap(nq, in.nprobe, in.seg_max1, in.k);
+    uint64_t * partial1 = scr.take<uint64_t>(fb_cap * in.nprobe * (size_t)in.seg_max1 * in.k);
+    ScanParams c{};
+    c.Y = in.Y;
+    c.ids = in.ids;
+    c.alive = in.alive;
+    c.nbits = in.nbits;
+    c.Q = in.Q;
+    c.ld4 = in.ld4;
+    c.nq = (uint32_t)nq;
+    c.probes = in.probes;
+    c.list_off = in.list_off;
+    c.nprobe = in.nprobe;
+    c.k = in.k;
+    c.partial = partial1;
+    c.rows_per_block = in.rpb1;
+    c.seg_max = in.seg_max1;
+    IvfMergeParams fm = ivf_merge_params(partial1, in.probes, in.list_off, in.nprobe, in.seg_max1, in.rpb1, in.k, in.out_ids, in.out_dis, in.cosine);
+    fm.out_probes = in.out_probes;
+    c.qmap = fm.qmap = failq;
+    c.qcount = fm.qcount = nfail;
+    run_fallback_rounds(metric, c, fm, nq, fb_cap, in.slots, stream);
+    if (signalled)
+        MSVS_HIP(hipStreamSynchronize(stream));
 }
 
 /// Tests (msvs_debug_coarse_words): where this host thread's last centroid-shadow pass left its words (valid until the thread's
@@ -722,6 +767,14 @@ struct PruneFirstLast
     hipStream_t stream = nullptr;
 };
 static thread_local PruneFirstLast g_prune_first_last;
+
+/// The queries' norms, fp16 images and their measured rounding errors; `aux`: what the launch plans and clears on its way (H16PrepAux).
+static void launch_h16_prep(const msvs_index & ix, int m, const float * dq, size_t nq, uint4 * qh, float2 * qinfo, float * qnorm, float * qrho,
+                            const H16PrepAux & aux, hipStream_t stream)
+{
+    hipLaunchKernelGGL(h16_prep_queries_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, dq, (uint32_t)nq, ix.ld, ix.h_nch,
+                       ix.h_inv_scale, m == MSVS_METRIC_L2 ? 0 : 1, qh, qinfo, qnorm, 1, aux, qrho);
+}
 
 static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, const float * dq, size_t nq,
                                  const TablePass & t, hipStream_t stream)
@@ -748,22 +801,17 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
     uint64_t * cand = scr.take<uint64_t>(nq * (size_t)kc);
     uint64_t * bound = scr.take<uint64_t>(nq);
     uint32_t * failq = scr.take<uint32_t>(nq);
-    const uint32_t rpb1 = table_fallback_rpb(t.n), seg_max1 = (uint32_t)ceil_div(t.n, (size_t)rpb1);
-    const size_t fb_cap = fallback_cap(nq, 1, seg_max1, t.k);
-    uint64_t * partial1 = scr.take<uint64_t>(fb_cap * (size_t)seg_max1 * t.k);
     uint32_t * nfail = small + 2;
     const uint32_t rpb = BG_ROWS; // work item = 1 slice (see plan_ivf)
-    if (!t.h16 && !t.flat_h16) // (the shadow passes' query preparation kernel does the rest)
+    const bool shadow = t.h16 || t.flat_h16;
+    float4 * qsplit = nullptr;
+    if (!shadow) // (the shadow passes' query preparation kernel does the rest)
     {
         MSVS_HIP(hipMemsetAsync(small, 0, 9 * sizeof(uint32_t), stream));
         MSVS_HIP(hipMemsetAsync(qstate, 0xFF, nq * sizeof(uint32_t), stream));
         MSVS_HIP(hipMemsetAsync(qstate + nq, 0, nq * sizeof(uint32_t), stream));
         // plan 0: the whole table (also what the fallback scans)
         launch_single_list_plan((uint32_t)nq, 0, nrows, rpb, tq, pairs, probes0, list_off, small, small + 3, stream);
-    }
-    float4 * qsplit = nullptr;
-    if (!t.h16 && !t.flat_h16)
-    {
         launch_row_sqnorm(dq, qnorm, nq, ld / 4, nullptr, stream);
         qsplit = scr.take<float4>(nq * (size_t)ceil_div((size_t)ld / 4, (size_t)8) * 8);
         launch_split_queries(dq, (uint32_t)nq, ld / 4, qsplit, stream);
@@ -774,7 +822,7 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
     const uint32_t sample = two_phase
         ? (uint32_t)std::min<size_t>(t.n / 2, round_up(std::max<size_t>(32768, t.n / 32), (size_t)rpb))
         : 0;
-    if (two_phase && !t.h16 && !t.flat_h16) // (the shadow passes sample their own way)
+    if (two_phase && !shadow) // (the shadow passes sample their own way)
     {
         launch_single_list_plan((uint32_t)nq, 0, sample, rpb, tq, pairs, probes0, list_off + 2, small, small + 5,
                                 stream);
@@ -809,6 +857,53 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
     a.tile_q = tq;
     a.Qsplit = qsplit;
     const size_t tiles = ceil_div(nq, (size_t)tq);
+    // the second half, whatever produces the candidates below; its fallback scans the table as the one list of plan 0
+    const bool stats = options().rerank_stats != 0;
+    CertifiedTail ct{};
+    ct.Y = a.Y;
+    ct.ids = t.ids;
+    ct.xmax = t.norm_max;
+    ct.alive = t.alive;
+    ct.nbits = a.nbits;
+    ct.Q = a.Q;
+    ct.qnorm = qnorm;
+    ct.ld4 = a.ld4;
+    ct.k = t.k;
+    ct.cand = cand;
+    ct.bound = bound;
+    ct.kc = kc;
+    ct.failq = failq;
+    ct.nfail = nfail;
+    ct.out_probes = t.out_probes;
+    ct.out_ids = t.out_ids;
+    ct.out_dis = t.out_dis;
+    ct.cosine = t.cosine;
+    ct.early_exit = options().rerank_early != 0 && !t.out_probes;
+    ct.band = t.out_probes && shadow && options().coarse_band != 0;
+    ct.stat_fail = prefilter_fail_counter() + (t.out_probes ? 1 : 0);
+    ct.stat_skip = stats ? prefilter_fail_counter() + (t.out_probes ? 4 : 2) : nullptr;
+    ct.stat_rows = stats && !t.out_probes ? prefilter_fail_counter() + 12 : nullptr;
+    ct.queries = t.out_probes ? &g_coarse_queries : &g_prefilter_queries;
+    ct.signal = t.flat_h16 && !t.out_probes; // (a coarse pass leaves an armed signal to the list scan behind it)
+    ct.probes = probes0;
+    ct.list_off = list_off;
+    ct.nprobe = 1;
+    ct.rpb1 = table_fallback_rpb(t.n);
+    ct.seg_max1 = (uint32_t)ceil_div(t.n, (size_t)ct.rpb1);
+    ct.slots = (uint32_t)std::min<size_t>(nq, 8);
+    if (!shadow)
+        set_error_model(ct.model, ix.dim);
+    // the shadow passes' preparation launch also makes plan 0 and clears this pass's fail counter
+    H16PrepAux aux{};
+    aux.pairs = pairs;
+    aux.probes0 = probes0;
+    aux.list_off = list_off;
+    aux.pair_off = small;
+    aux.work_off = small + 3;
+    aux.nfail = nfail;
+    aux.row_end = nrows;
+    aux.rows_per_block = rpb;
+    aux.tq = tq;
     ProfileScope prof(t.prof_name, stream);
     if (t.h16)
     {
@@ -826,16 +921,6 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
         uint32_t * nslow = t.out_probes ? scr.take<uint32_t>(1) : nullptr;    // ... and their count (cleared by the preparation kernel)
         // one launch: norms, fp16 images, the one-list plan of this pass (what its fallback scans), its fail counter, and the
         // zeroed counters of the list scan that follows
-        H16PrepAux aux{};
-        aux.pairs = pairs;
-        aux.probes0 = probes0;
-        aux.list_off = list_off;
-        aux.pair_off = small;
-        aux.work_off = small + 3;
-        aux.nfail = nfail;
-        aux.row_end = nrows;
-        aux.rows_per_block = rpb;
-        aux.tq = tq;
         if (t.h16_out && t.h16_out->counters)
         {
             aux.zero[0] = t.h16_out->counters;
@@ -846,8 +931,8 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
             aux.zero[1] = nslow;
             aux.nzero[1] = 1;
         }
-        hipLaunchKernelGGL(h16_prep_queries_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, dq, (uint32_t)nq, ld,
-                           ix.h_nch, ix.h_inv_scale, m == MSVS_METRIC_L2 ? 0 : 1, qh, qinfo, qn16, 1, aux, qrho);
+        launch_h16_prep(ix, m, dq, nq, qh, qinfo, qn16, qrho, aux, stream);
+        set_error_model_h16(ct.model, ix.dim, t.h16_rho, qrho);
         if (t.h16_out)
         {
             t.h16_out->qrho = qrho;
@@ -868,19 +953,13 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
             const uint32_t cgrid = (uint32_t)std::min<size_t>(ceil_div((size_t)items, (size_t)4), (size_t)device_cu_count() * 2);
             if (options().coarse_h16 != 3 && nq >= 256)
             {
-                // round 6: 128 x 128 workgroup tiles, both operands through LDS (coarse_gemm_kernel)
+                // round 6: workgroup tiles of 64 queries x 128 centroids, both operands through LDS (coarse_gemm_kernel<METRIC, 1, 2>)
                 // (smaller tiles than 128 x 128: several workgroups per CU in different phases -- the launch is its prologue, epilogue
                 // and stores, not its loop)
-                const int nt = options().coarse_gemm_tq == 128 ? 2 : 1, ns = options().coarse_gemm_tc == 128 ? 2 : 1;
-                const dim3 ggrid((unsigned)ceil_div(nq, (size_t)(64 * nt)), (unsigned)ceil_div((size_t)G, (size_t)(2 * ns)));
+                const dim3 ggrid((unsigned)ceil_div(nq, (size_t)64), (unsigned)ceil_div((size_t)G, (size_t)4));
                 with_int<M_IP, M_L2>(scan_metric(m), [&](auto mc) {
-                    with_int<2, 1>(nt, [&](auto ntc) {
-                        with_int<2, 1>(ns, [&](auto nsc) {
-                            constexpr int METRIC = decltype(mc)::value, NT = decltype(ntc)::value, NS = decltype(nsc)::value;
-                            hipLaunchKernelGGL((coarse_gemm_kernel<METRIC, NT, NS>), ggrid, dim3(256), 0, stream, ix.c_shadow.p, ix.h_nch, qh, qinfo,
-                                               t.norms, (uint32_t)t.n, (uint32_t)nq, sample);
-                        });
-                    });
+                    hipLaunchKernelGGL((coarse_gemm_kernel<decltype(mc)::value, 1, 2>), ggrid, dim3(256), 0, stream, ix.c_shadow.p, ix.h_nch, qh, qinfo,
+                                       t.norms, (uint32_t)t.n, (uint32_t)nq, sample);
                 });
             }
             else
@@ -947,7 +1026,7 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
         }
         if (tail)
         {
-            const RerankParams rp = table_rerank_params(ix, t, a, qn16, cand, bound, kc, failq, nfail, true, qrho);
+            const RerankParams rp = rerank_params(ct); // (every query: the queue is this launch's to fill)
             const dim3 tgrid((unsigned)ceil_div(nq, (size_t)(BLOCK / WAVE)));
             // round 12: the pre-pruning decided first, on the words (coarse_prune_first_wave) -- only where every query leaves this launch
             // with its probes (slow_inline) and the slots of the table are the list numbers
@@ -977,8 +1056,9 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
             g_coarse_queries.fetch_add(nq, std::memory_order_relaxed);
             return;
         }
-        table_pass_tail(ix, m, t, a, nq, qn16, cand, bound, kc, failq, nfail, partial1, fb_cap, rpb1, seg_max1, probes0, list_off, true, qrho,
-                        stream, tail ? failq2c : nullptr, tail ? nslow : nullptr);
+        ct.qmap = tail ? failq2c : nullptr;
+        ct.qcount = tail ? nslow : nullptr;
+        certified_tail(scr, scan_metric(m), ct, nq, stream);
         return;
     }
     if (t.flat_h16)
@@ -992,20 +1072,10 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
         float * qrho = scr.take<float>(nq);
         uint32_t * sample = scr.take<uint32_t>(nq * (size_t)n_pad);
         uint32_t * sched = scr.take<uint32_t>(9); // 8 item cursors of the scan + the sample's ticket
-        H16PrepAux aux{};
-        aux.pairs = pairs;
-        aux.probes0 = probes0;
-        aux.list_off = list_off;
-        aux.pair_off = small;
-        aux.work_off = small + 3;
-        aux.nfail = nfail;
-        aux.row_end = nrows;
-        aux.rows_per_block = rpb;
-        aux.tq = tq;
         aux.zero[0] = sched;
         aux.nzero[0] = 9;
-        hipLaunchKernelGGL(h16_prep_queries_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, dq, (uint32_t)nq, ld,
-                           ix.h_nch, ix.h_inv_scale, m == MSVS_METRIC_L2 ? 0 : 1, qh, qinfo, qnorm, 1, aux, qrho);
+        launch_h16_prep(ix, m, dq, nq, qh, qinfo, qnorm, qrho, aux, stream);
+        set_error_model_h16(ct.model, ix.dim, t.h16_rho, qrho);
         // ~target rows of the whole table below the cut: the m-th smallest of the S sample rows, m = target S / n (the sample is a
         // 1 / blk_stride share of the table), at least 4 (the certificate fails when fewer than k rows lie below the cut)
         const size_t target = std::max<size_t>(64, 25 * (size_t)t.k);
@@ -1078,8 +1148,7 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
         h16_flat_dispatch(scan_metric(m), ncb, shape, fgrid, lds, h, f, stream);
         MSVS_HIP(hipGetLastError());
         launch_cand_select(candbuf, h.qcnt, h.qthr, cap, (uint32_t)nq, kc, cand, bound, stream);
-        table_pass_tail(ix, m, t, a, nq, qnorm, cand, bound, kc, failq, nfail, partial1, fb_cap, rpb1, seg_max1, probes0, list_off, true, qrho,
-                        stream);
+        certified_tail(scr, scan_metric(m), ct, nq, stream);
         return;
     }
     if (two_phase)
@@ -1107,8 +1176,7 @@ static void table_candidate_pass(const msvs_index & ix, Scratch & scr, int m, co
                              (uint32_t)std::min<size_t>(tiles * ceil_div(t.n, (size_t)rpb), 4096 / nqg), a, stream,
                              "table_scan", false);
     launch_cand_select(candbuf, a.qcnt, a.qthr, cap, (uint32_t)nq, kc, cand, bound, stream);
-    table_pass_tail(ix, m, t, a, nq, qnorm, cand, bound, kc, failq, nfail, partial1, fb_cap, rpb1, seg_max1, probes0, list_off, false, nullptr,
-                    stream);
+    certified_tail(scr, scan_metric(m), ct, nq, stream);
 }
 
 /// Error model of the fp16 shadow pass (h16_scan_kernels.hpp), u = 2^-11:
@@ -1206,6 +1274,36 @@ static void set_prune_error_model(H16Prune & pr, const msvs_index & ix, const fl
     pr.qrho_x = ex.qrho;
     pr.qrho_scale = ex.qrho_scale;
     pr.qrho_scale_c = ec.qrho_scale;
+}
+
+/// What a pruning stage knows of a probe's centroid distance, the best source the coarse stage left: its approximate word of every
+/// (query, centroid), else the words that came with given probes (a sharded search), else the canonical distances of a small batch.
+static void set_prune_words(H16Prune & pr, const H16Queries & prepared, const float * qnorm)
+{
+    pr.coarse_words = prepared.coarse_words;
+    pr.npad = prepared.coarse_npad;
+    pr.probe_words = prepared.coarse_words ? nullptr : prepared.probe_words;
+    pr.probe_dis = prepared.coarse_words || prepared.probe_words ? nullptr : prepared.probe_dis;
+    pr.qnorm = qnorm; // (the words are distances between fp16 images: their bound needs |q|)
+}
+
+/// ... and of the lists: their radii (this index's, or the whole sharded index's), the norms' bounds, and the k it prunes for.
+static H16Prune prune_for(const msvs_index & ix, const float * radius, float xmax, uint32_t k)
+{
+    H16Prune pr{};
+    pr.radius = radius;
+    pr.xmax = xmax;
+    pr.cmax = ix.cnorm_max;
+    pr.k = k;
+    return pr;
+}
+
+/// The pre-pruning's conditions that do not wait for the coarse pass: L2 and cosine indexes, unfiltered searches over the stored
+/// lists whose radii are known, 2 .. 64 probes, finite norm bounds.
+static bool preprune_applies(const msvs_index & ix, size_t nprobe, const uint64_t * d_alive, const SearchView * view, const float * radius, float xmax)
+{
+    return options().h16_prune != 0 && options().h16_preprune != 0 && (ix.metric == MSVS_METRIC_L2 || ix.metric == MSVS_METRIC_COSINE) && !d_alive
+        && !view && radius && nprobe <= 64 && nprobe >= 2 && ix.cnorm_max < 1e30f && xmax < 1e30f;
 }
 
 template <int METRIC, int NCB, bool I8 = false>
@@ -1359,8 +1457,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     bool prep_done = prepared.qh != nullptr;
     auto prep = [&](const H16PrepAux & aux) {
         ProfileScope prof("ivf_prep", stream);
-        hipLaunchKernelGGL(h16_prep_queries_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, dq,
-                           (uint32_t)nq, ld, ix.h_nch, ix.h_inv_scale, m == MSVS_METRIC_L2 ? 0 : 1, qh, qinfo, qnorm, 1, aux, qrho);
+        launch_h16_prep(ix, m, dq, nq, qh, qinfo, qnorm, qrho, aux, stream);
         prep_done = true;
     };
     if (!zeroed)
@@ -1399,14 +1496,12 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     uint32_t * fb_out = nullptr;
     if (prepared.prepruned && ix.plan_fb.pairs && options().h16_prune != 2 && options().h16_feedback != 0)
     {
-        const uint32_t seen = *reinterpret_cast<volatile uint32_t *>(ix.plan_fb.pairs);
         // (the same nprobe; another batch size scales the count: the searching side of a routed step sees a few queries more or less
         // every time)
-        if (seen != 0xFFFFFFFFu && ix.plan_fb.nq != 0 && ix.plan_fb.nprobe == (uint32_t)nprobe)
-            eff_pairs = std::min(eff_pairs, 1.25 * (double)seen * ((double)nq / (double)ix.plan_fb.nq) + 64.0);
-        ix.plan_fb.nq = (uint32_t)nq;
-        ix.plan_fb.nprobe = (uint32_t)nprobe;
-        fb_out = ix.plan_fb.pairs;
+        uint32_t seen = 0, seen_nq = 0;
+        if (ix.plan_fb.last(nprobe, seen, seen_nq))
+            eff_pairs = std::min(eff_pairs, 1.25 * (double)seen * ((double)nq / (double)seen_nq) + 64.0);
+        fb_out = ix.plan_fb.note(nq, nprobe);
     }
     const bool prune_pays = options().h16_prune == 2 || eff_pairs > (double)ix.nlist * (double)pp.T || pair_bytes >= 2.5e6;
     const bool prune2 = options().h16_prune != 0 && prune_pays && (prepared.coarse_words || prepared.probe_words || prepared.probe_dis)
@@ -1444,6 +1539,22 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     float * qbound = nullptr, * qoff = nullptr, * pc = nullptr;
     const bool per_query = ix.metric != MSVS_METRIC_L2; // inner product, cosine: one image per query, one constant per pair
     H8PairsParams hp{};
+    auto h8_common = [&](auto & p) { // what the L2 pair kernel and the inner-product query kernel both read
+        p.Q = dq; // (cosine: normalised by the caller)
+        p.cents = ix.centroids.p;
+        p.probes = plan_probes;
+        p.whole_off = pp.whole_off;
+        p.list_ab = ix.h8_list.p;
+        p.nq = (uint32_t)nq;
+        p.ld = ld;
+        p.nprobe = (uint32_t)nprobe;
+        p.nch8 = ix.h8_nch;
+        p.lim = i8r_limit(ix.dim);
+        p.xmax = ix.xnorm_max;
+        p.img = pimg;
+        p.pinfo = pinfo;
+        p.pc = pc;
+    };
     if (ix.h8)
     {
         pimg = scr.take<uint4>((per_query ? nq : nq * nprobe) * (size_t)ix.h8_nch * 16 + 64);
@@ -1453,23 +1564,10 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         pc = scr.take<float>(nq * nprobe);
         if (n_qmm)
         {
-            hp.Q = dq;
-            hp.cents = ix.centroids.p;
-            hp.probes = plan_probes;
+            h8_common(hp);
             hp.pairs = pp.pairs;
             hp.pair_off = pp.pair_off;
-            hp.whole_off = pp.whole_off;
-            hp.list_ab = ix.h8_list.p;
-            hp.nq = (uint32_t)nq;
-            hp.ld = ld;
-            hp.nprobe = (uint32_t)nprobe;
             hp.nlist = (uint32_t)ix.nlist;
-            hp.nch8 = ix.h8_nch;
-            hp.lim = i8r_limit(ix.dim);
-            hp.xmax = ix.xnorm_max;
-            hp.img = pimg;
-            hp.pinfo = pinfo;
-            hp.pc = pc;
             hp.qmm = qmm;
             hp.qxq = scr.take<double>(nq);
         }
@@ -1511,20 +1609,7 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
         if (per_query)
         {
             H8IpParams ip{};
-            ip.Q = dq; // (cosine: normalised by the caller)
-            ip.cents = ix.centroids.p;
-            ip.probes = plan_probes;
-            ip.whole_off = pp.whole_off;
-            ip.list_ab = ix.h8_list.p;
-            ip.nq = (uint32_t)nq;
-            ip.ld = ld;
-            ip.nprobe = (uint32_t)nprobe;
-            ip.nch8 = ix.h8_nch;
-            ip.lim = i8r_limit(ix.dim);
-            ip.xmax = ix.xnorm_max;
-            ip.img = pimg;
-            ip.pinfo = pinfo;
-            ip.pc = pc;
+            h8_common(ip);
             ip.qbound = qbound;
             ip.qoff = qoff;
             hipLaunchKernelGGL(h8_ip_prep_kernel, dim3((unsigned)ceil_div(nq, (size_t)4)), dim3(256), 0, stream, ip);
@@ -1592,6 +1677,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
             // below that the second plan and the looser cut cost more than the dropped pairs save: sigma-0.3 blobs at nprobe 2)
             if (prune2)
             {
+                pr = prune_for(ix, ix.list_radius.p, ix.xnorm_max, k);
+                set_prune_words(pr, prepared, qnorm);
                 set_prune_error_model(pr, ix, qrho, !prepared.coarse_words && prepared.probe_words != nullptr);
                 if (ix.h8)
                 {
@@ -1603,17 +1690,8 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
                     pr.qrho_scale = ex.qrho_scale;
                     pr.qoff = qoff;
                 }
-                pr.coarse_words = prepared.coarse_words;
-                pr.npad = prepared.coarse_npad;
-                pr.probe_words = prepared.coarse_words ? nullptr : prepared.probe_words;
-                pr.probe_dis = prepared.coarse_words || prepared.probe_words ? nullptr : prepared.probe_dis;
-                pr.radius = ix.list_radius.p;
                 pr.cnorm = ix.cnorm.p;
                 pr.ip = ix.metric == MSVS_METRIC_COSINE ? 1 : ix.metric == MSVS_METRIC_IP ? 2 : 0;
-                pr.qnorm = qnorm;
-                pr.xmax = ix.xnorm_max;
-                pr.cmax = ix.cnorm_max;
-                pr.k = k;
                 pr.out_probes = scr.take<int32_t>(nq * nprobe);
                 pr.upre = prepared.upre; // (null without the pre-pruning)
                 pr.stat = options().rerank_stats != 0 ? prefilter_fail_counter() + 8 : nullptr;
@@ -1697,108 +1775,52 @@ static void h16_list_scan(const msvs_index & ix, Scratch & scr, int m, const flo
     g_h16_last = H16Last{partial, qstate + nq, pl.h_cap, nq, stream, qbound, pp.work_off, pp.pair_off, pp.seg_out, pa.work_off, pa.pair_off,
                          a.items, pa.items2, a.items_cap, pa.items2_cap, (uint32_t)ix.nlist};
     launch_cand_select(partial, qstate + nq, qstate, pl.h_cap, (uint32_t)nq, pl.kc, cand, bound, stream);
-    RerankParams rp{};
-    rp.Y = reinterpret_cast<const float4 *>(ix.vecs.p);
-    rp.ids = ix.row_ids.p;
-    rp.Q = reinterpret_cast<const float4 *>(dq);
-    rp.qnorm = qnorm;
-    rp.cand = cand;
-    rp.bound = bound;
-    rp.kc = pl.kc;
-    rp.k = k;
-    rp.ld4 = ld / 4;
-    rp.out_ids = d_ids;
-    rp.out_dis = d_dis;
-    rp.cosine = ix.metric == MSVS_METRIC_COSINE;
+    const bool second = options().rerank_second != 0 && k <= RA_KMAX, stats = options().rerank_stats != 0;
+    CertifiedTail ct{};
+    ct.Y = reinterpret_cast<const float4 *>(ix.vecs.p);
+    ct.ids = ix.row_ids.p;
+    ct.xmax = ix.xnorm_max;
+    ct.alive = d_alive;
+    ct.nbits = a.nbits;
+    ct.Q = reinterpret_cast<const float4 *>(dq);
+    ct.qnorm = qnorm;
+    ct.ld4 = ld / 4;
+    ct.k = k;
+    ct.cand = cand;
+    ct.bound = bound;
+    ct.kc = pl.kc;
+    ct.failq = failq;
+    ct.nfail = nfail;
+    ct.out_ids = d_ids;
+    ct.out_dis = d_dis;
+    ct.cosine = ix.metric == MSVS_METRIC_COSINE;
     if (ix.h8)
-        set_error_model_i8r(rp, ix.dim, qbound);
+        set_error_model_i8r(ct.model, ix.dim, qbound);
     else
-        set_error_model_h16(rp, ix.dim, ix.h_rho, qrho);
-    rp.xmax = ix.xnorm_max;
-    rp.failq = failq;
-    rp.nfail = nfail;
-    rp.early_exit = options().rerank_early != 0 ? 1 : 0;
-    const bool second = options().rerank_second != 0 && k <= RA_KMAX;
-    uint64_t * ek_hint = second && options().rerank_hint != 0 ? scr.take<uint64_t>(nq) : nullptr; // written for failing queries only
-    rp.ek_out = ek_hint;
-    rp.stat_fail = second ? nullptr : prefilter_fail_counter(); // the statistic counts queries that reach the canonical scan
-    rp.stat_skip = options().rerank_stats != 0 ? prefilter_fail_counter() + 2 : nullptr;
-    rp.stat_rows = options().rerank_stats != 0 ? prefilter_fail_counter() + 12 : nullptr; // msvs_debug_rerank_rows
-    // the second chance inside the re-rank launch (256-thread blocks: every shape but the rerank_groups = 32 experiment)
-    const bool fused = second && options().rerank_fused != 0 && (pl.kc > 64 || options().rerank_groups != 32);
-    uint32_t * failq2 = failq;
-    uint32_t * nfail_final = nfail;
-    RerankAllParams ra{};
+        set_error_model_h16(ct.model, ix.dim, ix.h_rho, qrho);
+    ct.early_exit = options().rerank_early != 0;
+    ct.stat_fail = second ? nullptr : prefilter_fail_counter(); // the statistic counts queries that reach the canonical scan
+    ct.stat_skip = stats ? prefilter_fail_counter() + 2 : nullptr;
+    ct.stat_rows = stats ? prefilter_fail_counter() + 12 : nullptr;
+    ct.queries = &g_prefilter_queries;
     if (second)
     {
-        failq2 = scr.take<uint32_t>(nq);
-        nfail_final = nfail2;
-        ra.partial = partial;
-        ra.qcnt = qstate + nq;
-        ra.qthr = qstate;
-        ra.cap = pl.h_cap;
-        ra.failq_in = failq;
-        ra.nfail_in = nfail;
-        ra.failq_out = failq2;
-        ra.nfail_out = nfail2;
-        ra.stat_fail = prefilter_fail_counter();
-        ra.ek_in = ek_hint;
-        if (fused)
-        {
-            rp.fuse_second = 1;
-            rp.ra = ra;
-        }
+        ct.ra.partial = partial;
+        ct.ra.qcnt = qstate + nq;
+        ct.ra.qthr = qstate;
+        ct.ra.cap = pl.h_cap;
+        ct.ra.nfail_out = nfail2; // queries still without a certificate after it
+        // inside the re-rank launch (256-thread blocks: every shape but the rerank_groups = 32 experiment)
+        ct.fused = options().rerank_fused != 0 && (pl.kc > 64 || options().rerank_groups != 32);
     }
-    launch_ivf_rerank(scan_metric(m), rp, (uint32_t)nq, stream);
-    rp.fuse_second = 0;
-    g_prefilter_queries.fetch_add(nq, std::memory_order_relaxed);
-    // a small batch through msvs_index_search (search_entry.hip: the pinned form): the host learns how many queries are without a
-    // certificate and enqueues the second chance and the fallback rounds -- three launches that normally find nothing to do, ~14 of
-    // the batch's ~138 us -- only when somebody is; the results are in pinned memory at its return either way
-    HostSignal & hs = host_signal();
-    const bool signalled = hs.armed;
-    if (signalled && host_signal_round(hs, fused ? nfail2 : nfail, stream))
-        return;
-    // second chance of the queries without a certificate: every row of their candidate buffers, certified against the cut
-    if (second && !fused)
-        launch_ivf_rerank_all(scan_metric(m), rp, ra, (uint32_t)nq, stream);
-    // queries without a certificate: canonical scan, one query per block (normally zero of them)
-    const size_t fb_cap = fallback_cap(nq, nprobe, pl.seg_max1, k);
-    uint64_t * partial1 = scr.take<uint64_t>(fb_cap * nprobe * (size_t)pl.seg_max1 * k);
-    ScanParams c{};
-    c.Y = rp.Y;
-    c.ids = ix.row_ids.p;
-    c.alive = d_alive;
-    c.nbits = a.nbits;
-    c.Q = rp.Q;
-    c.ld4 = ld / 4;
-    c.nq = (uint32_t)nq;
-    c.probes = plan_probes; // (the lists the pre-pruning dropped provably hold none of the k nearest rows: not for the fallback either)
-    c.list_off = ix.list_off.p;
-    c.nprobe = (uint32_t)nprobe;
-    c.nlist = (uint32_t)ix.nlist;
-    c.k = k;
-    c.partial = partial1;
-    c.rows_per_block = pl.rpb1;
-    c.seg_max = pl.seg_max1;
-    c.qmap = failq2;
-    c.qcount = nfail_final;
-    IvfMergeParams fm{};
-    fm.partial = partial1;
-    fm.probes = plan_probes;
-    fm.list_off = ix.list_off.p;
-    fm.nprobe = (uint32_t)nprobe;
-    fm.seg_max = pl.seg_max1;
-    fm.rows_per_block = pl.rpb1;
-    fm.k = k;
-    fm.out_ids = d_ids;
-    fm.out_dis = d_dis;
-    fm.cosine = ix.metric == MSVS_METRIC_COSINE;
-    fm.qmap = failq2;
-    fm.qcount = nfail_final;
-    run_fallback_rounds(scan_metric(m), c, fm, nq, fb_cap, pl.fb_slots, stream);
-    if (signalled)
-        MSVS_HIP(hipStreamSynchronize(stream));
+    ct.signal = true;
+    ct.probes = plan_probes; // (the lists the pre-pruning dropped provably hold none of the k nearest rows: not for the fallback either)
+    ct.list_off = ix.list_off.p;
+    ct.nprobe = (uint32_t)nprobe;
+    ct.rpb1 = pl.rpb1;
+    ct.seg_max1 = pl.seg_max1;
+    ct.slots = pl.fb_slots;
+    certified_tail(scr, scan_metric(m), ct, nq, stream);
 }
 
 /// given_probes (nullable): [nq][nprobe] list ids computed elsewhere (another rank's share of the coarse quantiser):
@@ -1900,7 +1922,6 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
             t.h16_rho = ix.h_rho;
             t.prof_name = "flat_pass";
             table_candidate_pass(ix, scr, m, dq, nq, t, stream);
-            g_prefilter_queries.fetch_add(nq, std::memory_order_relaxed);
             return;
         }
         flat_search_device(scr, m, ix.vecs.p, ix.row_ids.p, ix.n, ld, dq, nq, k, d_alive, nbits, out, stream, view);
@@ -1939,15 +1960,11 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         // launch decides it on the words, for the queries it can (coarse_prune_first_wave).  Not while the last search of this shape
         // kept more than a few pairs per query (the plan's feedback word: iid data -- nothing is prunable, the attempt is pure cost).
         const bool pf_debug = options().coarse_prune_debug != 0;
-        bool pf_plan = options().coarse_prune_first != 0 && !probes_only && options().rerank_stats == 0 && options().h16_prune != 0
-            && options().h16_preprune != 0 && ix.metric == MSVS_METRIC_L2 && !d_alive && !view && ix.list_radius.p && nprobe <= 64 && nprobe >= 2
-            && ix.cnorm_max < 1e30f && ix.xnorm_max < 1e30f;
-        if (pf_plan && ix.plan_fb.pairs)
-        {
-            const uint32_t seen = *reinterpret_cast<volatile uint32_t *>(ix.plan_fb.pairs);
-            if (seen != 0xFFFFFFFFu && ix.plan_fb.nq != 0 && ix.plan_fb.nprobe == (uint32_t)nprobe && (uint64_t)seen > 4ull * ix.plan_fb.nq)
-                pf_plan = false;
-        }
+        bool pf_plan = options().coarse_prune_first != 0 && !probes_only && options().rerank_stats == 0 && ix.metric == MSVS_METRIC_L2
+            && preprune_applies(ix, nprobe, d_alive, view, ix.list_radius.p, ix.xnorm_max);
+        uint32_t seen = 0, seen_nq = 0;
+        if (pf_plan && ix.plan_fb.last(nprobe, seen, seen_nq) && (uint64_t)seen > 4ull * seen_nq)
+            pf_plan = false;
         if (pf_plan || pf_debug)
         {
             pf_probes1 = scr.take<int32_t>(nq * nprobe);
@@ -1963,10 +1980,7 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         }
         if (pf_plan)
         {
-            pf0.radius = ix.list_radius.p;
-            pf0.xmax = ix.xnorm_max;
-            pf0.cmax = ix.cnorm_max;
-            pf0.k = k;
+            pf0 = prune_for(ix, ix.list_radius.p, ix.xnorm_max, k);
             pf0.upre = pf_upre;
             pf0.out_probes = pf_probes1;
             t.prune_first = &pf0;
@@ -1997,25 +2011,13 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
     // radius / list_off: the index's own lists, or (the routed sharded search) those of the whole index.
     auto preprune = [&](const int32_t * in_probes, const float * radius, const int64_t * list_off, int32_t * out_probes, bool keep_upre, float xmax,
                         float xmin) -> bool {
-        if (!(options().h16_prune != 0 && options().h16_preprune != 0 && (ix.metric == MSVS_METRIC_L2 || ix.metric == MSVS_METRIC_COSINE) && !d_alive
-              && !view && radius && nprobe <= 64 && nprobe >= 2 && ix.cnorm_max < 1e30f && xmax < 1e30f
+        if (!(preprune_applies(ix, nprobe, d_alive, view, radius, xmax)
               && (prepared.probe_dis || ((prepared.coarse_words || prepared.probe_words) && prepared.qnorm))))
             return false;
-        H16Prune pr0{};
+        H16Prune pr0 = prune_for(ix, radius, xmax, k);
+        set_prune_words(pr0, prepared, prepared.qnorm);
         set_prune_error_model(pr0, ix, prepared.qh ? prepared.qrho : nullptr, !prepared.coarse_words && prepared.probe_words != nullptr,
                               radius != ix.list_radius.p);
-        if (prepared.coarse_words || prepared.probe_words)
-        {
-            pr0.coarse_words = prepared.coarse_words;
-            pr0.npad = prepared.coarse_npad;
-            pr0.probe_words = prepared.coarse_words ? nullptr : prepared.probe_words;
-            pr0.qnorm = prepared.qnorm;
-        }
-        else
-            pr0.probe_dis = prepared.probe_dis;
-        pr0.radius = radius;
-        pr0.xmax = xmax;
-        pr0.cmax = ix.cnorm_max;
         const bool cosine_form = ix.metric == MSVS_METRIC_COSINE;
         if (cosine_form)
         {
@@ -2025,7 +2027,6 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
             pr0.Q = dq; // (normalised above)
             pr0.ldq = ld;
         }
-        pr0.k = k;
         pr0.stat = options().rerank_stats != 0 ? prefilter_fail_counter() + 8 : nullptr;
         pr0.upre = cosine_form || !keep_upre ? nullptr : pf_upre ? pf_upre : scr.take<float>(nq); // (an L2 bound: the cosine scan's second stage compares inner products)
         pr0.served = keep_upre && pf_ran ? pf_flags : nullptr; // (the tail launch has written these queries' lists and bounds: coarse_prune_first_wave)
@@ -2065,8 +2066,6 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         prepared.probe_words = words.given;
         prepared.prepruned = words.given_pruned; // (a routed search: the sending rank dropped what it could; the plan's own count tells the next search)
     }
-    const int32_t * all_probes = d_probes;
-    (void)all_probes;
     {
         int32_t * probes1 = pf_probes1 ? pf_probes1 : scr.take<int32_t>(nq * nprobe);
         const bool pruned = preprune(d_probes, ix.list_radius.p, ix.list_off.p, probes1, true, ix.xnorm_max, ix.xnorm_min);
@@ -2179,55 +2178,36 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         a.work_off = pp.work_off;
         launch_ivf_mfma_scan(scan_metric(m), pl.nqg, pl.grid, a, stream);
         launch_cand_select(partial, a.qcnt, a.qthr, a.cand_cap, (uint32_t)nq, pl.kc, cand, bound, stream);
-        uint32_t * failq = scr.take<uint32_t>(nq);
-        RerankParams rp{};
-        rp.Y = a.Y;
-        rp.ids = ix.row_ids.p;
-        rp.Q = a.Q;
-        rp.qnorm = qnorm;
-        rp.cand = cand;
-        rp.bound = bound;
-        rp.kc = pl.kc;
-        rp.k = k;
-        rp.ld4 = ld / 4;
-        rp.out_ids = d_ids;
-        rp.out_dis = d_dis;
-        rp.cosine = ix.metric == MSVS_METRIC_COSINE;
-        set_error_model(rp, ix.dim);
-        rp.xmax = ix.xnorm_max;
-        rp.failq = failq;
-        rp.nfail = nfail;
-        rp.early_exit = options().rerank_early != 0 ? 1 : 0;
-        rp.stat_fail = prefilter_fail_counter();
-        rp.stat_rows = options().rerank_stats != 0 ? prefilter_fail_counter() + 12 : nullptr; // msvs_debug_rerank_rows
-        launch_ivf_rerank(scan_metric(m), rp, (uint32_t)nq, stream);
-        g_prefilter_queries.fetch_add(nq, std::memory_order_relaxed);
-        // queries without a certificate: canonical scan, one query per block (normally zero of them)
-        const size_t fb_cap = fallback_cap(nq, nprobe, pl.seg_max1, k);
-        uint64_t * partial1 = scr.take<uint64_t>(fb_cap * nprobe * (size_t)pl.seg_max1 * k);
-        ScanParams c = a;
-        c.list_off = ix.list_off.p; // the fallback scans whole lists
-        c.list_end = nullptr;
-        c.k = k;
-        c.partial = partial1;
-        c.rows_per_block = pl.rpb1;
-        c.seg_max = pl.seg_max1;
-        c.qmap = failq;
-        c.qcount = nfail;
-        IvfMergeParams fm{};
-        fm.partial = partial1;
-        fm.probes = d_probes;
-        fm.list_off = ix.list_off.p;
-        fm.nprobe = (uint32_t)nprobe;
-        fm.seg_max = pl.seg_max1;
-        fm.rows_per_block = pl.rpb1;
-        fm.k = k;
-        fm.out_ids = d_ids;
-        fm.out_dis = d_dis;
-        fm.cosine = ix.metric == MSVS_METRIC_COSINE;
-        fm.qmap = failq;
-        fm.qcount = nfail;
-        run_fallback_rounds(scan_metric(m), c, fm, nq, fb_cap, pl.fb_slots, stream);
+        CertifiedTail ct{};
+        ct.Y = a.Y;
+        ct.ids = ix.row_ids.p;
+        ct.xmax = ix.xnorm_max;
+        ct.alive = d_alive;
+        ct.nbits = a.nbits;
+        ct.Q = a.Q;
+        ct.qnorm = qnorm;
+        ct.ld4 = ld / 4;
+        ct.k = k;
+        ct.cand = cand;
+        ct.bound = bound;
+        ct.kc = pl.kc;
+        ct.failq = scr.take<uint32_t>(nq);
+        ct.nfail = nfail;
+        ct.out_ids = d_ids;
+        ct.out_dis = d_dis;
+        ct.cosine = ix.metric == MSVS_METRIC_COSINE;
+        set_error_model(ct.model, ix.dim);
+        ct.early_exit = options().rerank_early != 0;
+        ct.stat_fail = prefilter_fail_counter();
+        ct.stat_rows = options().rerank_stats != 0 ? prefilter_fail_counter() + 12 : nullptr;
+        ct.queries = &g_prefilter_queries;
+        ct.probes = d_probes;
+        ct.list_off = ix.list_off.p; // the fallback scans whole lists
+        ct.nprobe = (uint32_t)nprobe;
+        ct.rpb1 = pl.rpb1;
+        ct.seg_max1 = pl.seg_max1;
+        ct.slots = pl.fb_slots;
+        certified_tail(scr, scan_metric(m), ct, nq, stream);
         return;
     }
     if (pl.T == 1)
@@ -2255,18 +2235,8 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         launch_ivf_batched_scan(scan_metric(m), pl.T, pl.grid, a, stream);
     }
     // 3. per-query top-k over the valid segments of its probed lists
-    IvfMergeParams im{};
-    im.partial = partial;
-    im.probes = d_probes;
-    im.list_off = list_off;
-    im.nprobe = (uint32_t)nprobe;
-    im.seg_max = pl.seg_max;
-    im.rows_per_block = pl.rpb;
-    im.k = k;
-    im.out_ids = d_ids;
-    im.out_dis = d_dis;
-    im.cosine = ix.metric == MSVS_METRIC_COSINE;
-    launch_ivf_merge(scan_metric(m), im, (uint32_t)nq, stream);
+    launch_ivf_merge(scan_metric(m), ivf_merge_params(partial, d_probes, list_off, nprobe, pl.seg_max, pl.rpb, k, d_ids, d_dis, ix.metric == MSVS_METRIC_COSINE),
+                     (uint32_t)nq, stream);
 }
 
 }

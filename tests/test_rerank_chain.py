@@ -174,6 +174,41 @@ def test_forced_failures_take_the_same_route_in_both_forms(knobs, forced, opt):
         assert first["0"][0] >= NQ // 4, "the scale was meant to fail many first certificates"
 
 
+SIGNAL_NQ = 200  # at most 256 queries through the host entry: the shadow list scan ends with the armed host signal
+SIGNAL_SETTINGS = [{"ivf_eps_scale": EPS_SECOND_CHANCE}, {"ivf_eps_scale": EPS_SECOND_CHANCE, "rerank_fused": "0"}, {"ivf_eps_scale": "1e12"}]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knobs", SIGNAL_SETTINGS, ids=lambda kn: ",".join("%s=%s" % it for it in kn.items()))
+def test_armed_host_signal_that_comes_back_with_failures(knobs, forced, opt):
+    """A host-pointer call of 200 queries arms the signal (`forced`'s 300 never do): the host hears how many queries are without
+    a certificate -- after the fused second chance, or in front of the one that is a launch of its own -- and only then enqueues
+    what is left of the chain.  With certificates made to fail the count it hears is not zero: the second chance serves most of
+    the queries at EPS_SECOND_CHANCE, the canonical fallback all of them at 1e12.  The results are the oracle's and the same
+    number of queries reaches the fallback as with every launch enqueued blindly (host_signal_batch = 0)."""
+    ix, q, oi, od = forced
+    q, oi, od = q[:SIGNAL_NQ], oi[:SIGNAL_NQ], od[:SIGNAL_NQ]
+    for kn, v in knobs.items():
+        opt(kn, v)
+    opt("rerank_stats", "1")
+    counts = {}
+    for signal in ("1", "0"):
+        opt("host_signal_batch", signal)
+        p0, r0 = capi.prefilter_stats(), capi.debug_rerank_rows()
+        ids, dis = ix.search(q, 10, "nprobe=%d" % NPROBE)
+        p1, r1 = capi.prefilter_stats(), capi.debug_rerank_rows()
+        assert p1[0] - p0[0] == SIGNAL_NQ, "host_signal_batch=%s: the candidate pass did not run for all queries" % signal
+        same(ids, dis, oi, od)
+        counts[signal] = (p1[1] - p0[1], r1[1] - r0[1])
+    print("%s (fallbacks, rows second) signal armed: %s every launch enqueued: %s" % (knobs, counts["1"], counts["0"]))
+    assert counts["1"][0] == counts["0"][0], "the armed signal changed how many queries reach the canonical fallback: %s" % (counts,)
+    if knobs["ivf_eps_scale"] == "1e12":
+        assert counts["1"][0] == SIGNAL_NQ  # nobody has a certificate
+    else:
+        assert counts["1"][1] > 0, "no query took the second chance at this ivf_eps_scale"
+        assert counts["1"][0] <= SIGNAL_NQ // 10, "the second chance was meant to serve the queries whose first certificate fails"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("fused", ["1", "0"])
 def test_second_chance_skips_the_chunks_the_hint_empties(fused, forced, opt):
