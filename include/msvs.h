@@ -647,7 +647,17 @@ MSVS_API int msvs_shard_search_drain(const msvs_comm_t * comm, void * hip_stream
 /* Multi-part / multi-GPU merge of partial top-k lists with the canonical total order -- the
  * device-side analogue of MergeTreeBaseSearchManager::getTotalTopSearchResultImpl
  * (src/VectorIndex/Storages/MergeTreeBaseSearchManager.cpp:207-299) for lists that share one id space.
- * ids/dis: [nparts][nq][k] (HOST), out: [nq][k]. */
+ * ids/dis: [nparts][nq][k] (HOST), out: [nq][k].
+ *   metric: MSVS_METRIC_L2 (ascending distances; also for cosine distances) or MSVS_METRIC_IP (descending), anything else
+ *   MSVS_ERR_NOT_IMPLEMENTED; k <= MSVS_MAX_K (MSVS_ERR_UNSUPPORTED_K); nq = 0 or k = 0 is a no-op; nparts = 0 writes nq * k empty slots.
+ *   An entry counts when its id is >= 0 and its distance is strictly better than the neutral value: < FLT_MAX, IP: > -FLT_MAX,
+ *   never NaN.  Order: the distance as a FLOAT (-0 and +0 tie; a -0 is reported as +0), then the ascending id; every copy of a
+ *   (distance, id) that several parts hold keeps a slot.  Unfilled slots: id -1 at the neutral value.
+ *   Ids lie in [0, 2^32 - 1) like every id of the library (the keys carry 32 bits).  msvs_merge_topk refuses a larger one with
+ *   MSVS_ERR_ID_RANGE; the device forms cannot look without a synchronisation and return such an id truncated.
+ *   PRECONDITION: every part's [k] list is in that order, best first, with its entries that do not count (id -1) at the END --
+ *   what every search entry writes.  Between 257 and 6144 keys per query the merge walks the lists from their heads and relies
+ *   on it; the result for other input is unspecified (never out of bounds). */
 MSVS_API int msvs_merge_topk(const int64_t * ids, const float * dis, size_t nparts, size_t nq, size_t k, int metric,
                              int64_t * out_ids, float * out_dis);
 MSVS_API int msvs_merge_topk_device(const int64_t * d_ids, const float * d_dis, size_t nparts, size_t nq, size_t k,

@@ -96,7 +96,10 @@ MSVS_HOST_API size_t msvs_host_fusion_transform(int fusion_type, const float * s
                                                 int vector_scan_direction, uint64_t * out_rows, float * out_scores);
 
 /* Canonical merge of per-shard top-k lists that share one id space (the multi-GPU exchange step when the merge is
- * done on the host): ids/dis [nparts][nq][k] -> [nq][k]; order (dist asc | desc for IP, id asc), -1 ids ignored. */
+ * done on the host): ids/dis [nparts][nq][k] -> [nq][k]; order (dist asc | desc for IP, id asc; distances compare as floats, so
+ * -0 and +0 tie).  An entry counts when its id is >= 0 and its distance is strictly better than the neutral value (< FLT_MAX,
+ * IP: > -FLT_MAX; never NaN), as in msvs_merge_topk; unfilled slots are id -1 at that value.  The lists may be in any order, and
+ * ids keep all 64 bits (the device forms carry 32).  L2 or IP, anything else MSVS_ERR_NOT_IMPLEMENTED. */
 MSVS_HOST_API int msvs_host_merge_topk(const int64_t * ids, const float * dis, size_t nparts, size_t nq, size_t k,
                                        int metric, int64_t * out_ids, float * out_dis);
 

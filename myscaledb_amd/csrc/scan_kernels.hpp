@@ -1345,7 +1345,8 @@ __global__ __launch_bounds__(BLOCK) void merge_kernel(const MergeParams a)
 
     if (total <= HEADS_CAP)
     {
-        // Fast path: stage all lists in LDS and run the heads merge (see wave_heads_merge)
+        // Fast path: stage all lists in LDS and run the heads merge (see wave_heads_merge).  It reads the lists from their heads, so
+        // every list must be sorted ascending by key with its KEY_NONE entries at the end; the path below is order-free.
         uint64_t * keys = lds;
         uint64_t * outk = lds + HEADS_CAP;
         uint16_t * idx = reinterpret_cast<uint16_t *>(outk + k);
@@ -1417,6 +1418,15 @@ __global__ __launch_bounds__(BLOCK) void merge_kernel(const MergeParams a)
     }
 }
 
+/// The key of one (id, distance) entry of a merge input (merge_small_kernel, pack_keys_kernel).  -0 is taken as +0: the canonical
+/// order compares distances as floats, so -0 and +0 tie and the id decides, while make_key orders the bit patterns, -0 first.
+/// (The scans' make_key stays as it is: their sums start at +0 and never come out as -0.)
+template <int METRIC>
+__device__ __forceinline__ uint64_t merge_entry_key(int64_t id, float d)
+{
+    return id < 0 ? KEY_NONE : make_key<METRIC>(d == 0.0f ? 0.0f : d, (uint32_t)id);
+}
+
 /// The merge of a FEW short lists (nparts * k <= 256: the result exchange of a sharded search, the per-part lists of a multi-part
 /// search) straight from the (ids, dis) arrays, one WAVEFRONT per query: every key ranks itself among the others through a
 /// wave-private LDS slab and writes itself to its output slot -- no packing pass, no block per query (the general pair of launches costs
@@ -1446,7 +1456,7 @@ __global__ __launch_bounds__(BLOCK) void merge_small_kernel(const int64_t * ids,
             const size_t rem = (size_t)q * k + j;
             const int64_t id = ids[p * ids_stride + rem];
             const float d = dis[p * dis_stride + rem];
-            key = id < 0 ? KEY_NONE : make_key<METRIC>(d, (uint32_t)id);
+            key = merge_entry_key<METRIC>(id, d);
         }
         mine[u] = key;
         s_keys[wave][i] = key;
@@ -1495,7 +1505,7 @@ __global__ void pack_keys_kernel(const int64_t * ids, size_t ids_stride, const f
     const uint32_t q = (uint32_t)(rem / k), j = (uint32_t)(rem - (size_t)q * k);
     const int64_t id = ids[p * ids_stride + rem];
     const float d = dis[p * dis_stride + rem];
-    keys[((size_t)q * nparts + p) * k + j] = id < 0 ? KEY_NONE : make_key<METRIC>(d, (uint32_t)id);
+    keys[((size_t)q * nparts + p) * k + j] = merge_entry_key<METRIC>(id, d);
 }
 
 // ------------------------------------------------------------------------------------------ normalisation

@@ -38,10 +38,11 @@ void merge_topk_device(const int64_t * d_ids, size_t ids_stride, const float * d
     const size_t total = nparts * nq * k;
     scr.reserve(total * 8 + 8192, stream);
     uint64_t * keys_q = scr.take<uint64_t>(total); // [nq][nparts][k]
-    with_int<M_IP, M_L2>(scan_metric(metric), [&](auto m) { // (L2 or IP only, see above)
-        hipLaunchKernelGGL((pack_keys_kernel<decltype(m)::value>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream, d_ids,
-                           ids_stride, d_dis, dis_stride, keys_q, (uint32_t)nparts, (uint32_t)nq, (uint32_t)k);
-    });
+    if (total) // (no parts: nothing to pack, and an empty grid is no launch; merge_kernel writes the empty slots)
+        with_int<M_IP, M_L2>(scan_metric(metric), [&](auto m) { // (L2 or IP only, see above)
+            hipLaunchKernelGGL((pack_keys_kernel<decltype(m)::value>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream, d_ids,
+                               ids_stride, d_dis, dis_stride, keys_q, (uint32_t)nparts, (uint32_t)nq, (uint32_t)k);
+        });
     MSVS_HIP(hipGetLastError());
     MergeParams m{};
     m.partial = keys_q;
@@ -82,11 +83,25 @@ extern "C" int msvs_merge_topk(const int64_t * ids, const float * dis, size_t np
                                int64_t * out_ids, float * out_dis)
 {
     return guarded([&] {
-        if (nparts == 0 || nq == 0 || k == 0)
+        if (metric != MSVS_METRIC_L2 && metric != MSVS_METRIC_IP)
+            fail(MSVS_ERR_NOT_IMPLEMENTED, "merge supports L2 / IP ordering (cosine distances are ascending: use L2)");
+        if (nq == 0 || k == 0)
             return;
-        if (!ids || !dis || !out_ids || !out_dis)
+        check_k(k);
+        if (!out_ids || !out_dis || (nparts && (!ids || !dis)))
             fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
+        if (nparts == 0)
+        {
+            // no lists: every slot is empty, as the device forms write it
+            std::fill(out_ids, out_ids + nq * k, (int64_t)-1);
+            std::fill(out_dis, out_dis + nq * k, metric == MSVS_METRIC_IP ? -3.402823466e+38f : 3.402823466e+38f);
+            return;
+        }
         const size_t total = nparts * nq * k;
+        // the keys carry 32 bits of id: a larger one would come back truncated (ids < 0 are holes whatever their value)
+        for (size_t i = 0; i < total; i++)
+            if (ids[i] >= 0xFFFFFFFFll)
+                fail(MSVS_ERR_ID_RANGE, "merge id %lld outside [0, 2^32 - 1)", (long long)ids[i]);
         DevBuf<int64_t> d_ids(total), d_oi(nq * k);
         DevBuf<float> d_dis(total), d_od(nq * k);
         MSVS_HIP(hipMemcpy(d_ids.p, ids, total * 8, hipMemcpyHostToDevice));

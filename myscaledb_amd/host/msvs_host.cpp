@@ -860,7 +860,10 @@ extern "C" int msvs_host_merge_topk(const int64_t * ids, const float * dis, size
             for (size_t j = 0; j < k; j++)
             {
                 const size_t o = (p * nq + q) * k + j;
-                if (ids[o] >= 0)
+                // admitted like everywhere else: strictly better than the neutral value, which a NaN never is (and a NaN
+                // among the entries would leave the comparator below without a strict weak order)
+                const bool better = desc ? dis[o] > -std::numeric_limits<float>::max() : dis[o] < std::numeric_limits<float>::max();
+                if (ids[o] >= 0 && better)
                     all.emplace_back(dis[o], ids[o]);
             }
         std::sort(all.begin(), all.end(), [desc](const auto & a, const auto & b) {
