@@ -52,6 +52,10 @@ size_t flat_scratch_bytes(size_t n, size_t nq, uint32_t k, uint32_t ld)
 }
 
 
+/// Tests only (msvs_debug_planned_tiles): the query tile of this host thread's last canonical table scan (plan_flat) and of its
+/// last canonical list scan (plan_ivf: 1 = ivf_scan_kernel, 2 / 4 / 8 = the list-batched kernel); 0: none yet.
+static thread_local uint32_t g_planned_tiles[2] = {0, 0};
+
 void flat_search_device(Scratch & scr, int metric, const float * d_rows, const uint32_t * d_row_ids, size_t n, uint32_t ld,
                         const float * d_q, size_t nq, uint32_t k, const uint64_t * d_alive, size_t nbits, MergeParams out,
                         hipStream_t stream, const SearchView * view)
@@ -59,6 +63,7 @@ void flat_search_device(Scratch & scr, int metric, const float * d_rows, const u
     if (view)
         n = std::max<size_t>(1, std::min(n, view->n_upper));
     FlatPlan p = plan_flat(n, nq, ld / 4, k);
+    g_planned_tiles[0] = p.T;
     uint64_t * partial = scr.take<uint64_t>(flat_partial_keys(p, nq, k));
     ScanParams a{};
     a.Y = reinterpret_cast<const float4 *>(d_rows);
@@ -2210,6 +2215,7 @@ static void index_search_device_one(const msvs_index & ix, const float * d_queri
         certified_tail(scr, scan_metric(m), ct, nq, stream);
         return;
     }
+    g_planned_tiles[1] = pl.T;
     if (pl.T == 1)
     {
         // few queries: one (query, list, segment) per block, no grouping pass
@@ -2601,6 +2607,18 @@ extern "C" __attribute__((visibility("default"))) int msvs_debug_prune_first_ser
         MSVS_HIP(hipDeviceSynchronize());
         MSVS_HIP(hipMemcpy(&v, prefilter_fail_counter() + 16, 8, hipMemcpyDeviceToHost));
         *served = v;
+    });
+}
+
+/// Tests only (not in msvs.h): out2[0] = the query tile plan_flat gave this thread's last canonical table scan (msvs_knn_f32, a FLAT
+/// index, the canonical coarse quantiser), out2[1] = the tile plan_ivf gave its last canonical list scan; 0: none yet.  A read
+/// resets both, so that a search that takes another path is not mistaken for the one before it.
+extern "C" __attribute__((visibility("default"))) int msvs_debug_planned_tiles(uint32_t * out2)
+{
+    return guarded([&] {
+        out2[0] = g_planned_tiles[0];
+        out2[1] = g_planned_tiles[1];
+        g_planned_tiles[0] = g_planned_tiles[1] = 0;
     });
 }
 

@@ -1445,7 +1445,8 @@ ADVERSARIAL = {
 
 
 @pytest.mark.parametrize("name", sorted(ADVERSARIAL))
-@pytest.mark.parametrize("metric,d", [(capi.METRIC_L2, 768), (capi.METRIC_IP, 768), (capi.METRIC_L2, 1024), (capi.METRIC_L2, 100)])
+@pytest.mark.parametrize("metric,d", [(capi.METRIC_L2, 768), (capi.METRIC_IP, 768), (capi.METRIC_L2, 1024), (capi.METRIC_L2, 100),
+                                      (capi.METRIC_L2, 2432), (capi.METRIC_IP, 2432)])  # 2432: the largest d the shadow pass serves
 def test_mfma_accumulation_error_bound_on_hardware(name, metric, d, opt):
     """The certificate (mfma_scan_kernels.hpp / h16_scan_kernels.hpp) rests on a per-pair bound of what the fp16-shadow
     MFMA pass computes: |approximate - true| <= 2 c_dot |x||q| + c_norm (|x|^2 + |q|^2) for L2, c_dot |x||q| for IP, with
@@ -1454,7 +1455,7 @@ def test_mfma_accumulation_error_bound_on_hardware(name, metric, d, opt):
     import ctypes as C
 
     rng = np.random.default_rng(sorted(ADVERSARIAL).index(name) * 100 + metric * 10 + d)
-    n, nlist, nq = 2048, 4, 64
+    n, nlist, nq = (2048 if d <= 1024 else 1024), 4, 64  # (d = 2432: 38 chunks a row; fewer rows keep the f64 reference in seconds)
     keys0 = np.zeros((nq, 1), np.uint64)
     capi.lib().msvs_debug_h16_keys(keys0.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_size_t(1), np.zeros(nq, np.uint32).ctypes.data_as(
         C.POINTER(C.c_uint32)), C.c_size_t(nq))  # drop the record of an earlier pass

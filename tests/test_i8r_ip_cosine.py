@@ -152,7 +152,7 @@ ADVERSARIAL = ["blobs", "one_huge_element", "residuals_near_zero", "queries_with
 
 
 @pytest.mark.parametrize("name", ADVERSARIAL)
-@pytest.mark.parametrize("d", [768, 100, 200])
+@pytest.mark.parametrize("d", [768, 100, 200, 2432])  # 2432: the largest d whose query tile the list scan holds in LDS (1024 rows there)
 @pytest.mark.parametrize("metric", ["ip", "cosine"])
 def test_i8r_ip_error_bound_on_hardware(metric, name, d, opt):
     """The kernels' own keys (every row of every list: no cut, no pruning) against f64 products: exact <= approx + eps with eps the
@@ -161,7 +161,7 @@ def test_i8r_ip_error_bound_on_hardware(metric, name, d, opt):
     alone, which puts the model's rounding constants to the test."""
     m = METRICS[metric]
     rng = np.random.default_rng(ADVERSARIAL.index(name) * 1000 + d)
-    nlist, n, nq = 8, 4096, 64
+    nlist, n, nq = 8, (4096 if d <= 1024 else 1024), 64
     x, q = blobs(rng, nlist, n, nq, d)
     if name == "one_huge_element":
         hit = rng.random(n) < 0.1

@@ -72,10 +72,11 @@ def lists_of_keys(ix, keys, cnt):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("d", DIMS + [2100])
+@pytest.mark.parametrize("d", DIMS + [2100, 2432])
 def test_every_pair_survives(d, opt):
     """No pruning: 64 x 8 = 512 pairs, eight per query through the atomics.  A grid of 8 workgroups (32 wavefronts) walks them in 16
-    rounds of its grid-stride loop; the default grid has more wavefronts than pairs."""
+    rounds of its grid-stride loop; the default grid has more wavefronts than pairs.  d = 2432 (19 chunks a pair, 152 pieces): the
+    largest dimension the i8r list scan serves."""
     rng = np.random.default_rng(d)
     x, q = blobs(rng, NLIST, N, 64, d)
     ix = i8r_index(x, opt)

@@ -115,14 +115,16 @@ ADVERSARIAL = ["blobs", "one_huge_element", "residuals_near_zero", "queries_far_
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ADVERSARIAL)
-@pytest.mark.parametrize("d", [768, 100, 200])
+@pytest.mark.parametrize("d", [768, 100, 200, 2432])
 def test_i8r_error_bound_on_hardware(name, d, opt):
     """The kernels' OWN approximate keys (every probed row of every list: h16_nocut, no pruning) against f64 exact distances:
     approx - eps <= exact with eps = 2 c_dot(q) |x||q| + c_norm (|x|^2 + |q|^2), c_dot(q) the per-query bound of
     set_error_model_i8r -- the lower bound every consumer of the keys relies on (the keys of a query's farther lists are lowered
-    on purpose, so the band is one-sided there).  d = 100, 200: not multiples of 64 / 128 (zero padding of the last chunk)."""
+    on purpose, so the band is one-sided there).  d = 100, 200: not multiples of 64 / 128 (zero padding of the last chunk);
+    d = 2432: 19 chunks, the largest dimension whose query tile the list scan holds in LDS (1024 rows there: the f64 reference
+    stays in seconds)."""
     rng = np.random.default_rng(ADVERSARIAL.index(name) * 1000 + d)
-    nlist, n, nq = 8, 4096, 64
+    nlist, n, nq = 8, (4096 if d <= 1024 else 1024), 64
     x, q = blobs(rng, nlist, n, nq, d)
     if name == "one_huge_element":
         hit = rng.random(n) < 0.1

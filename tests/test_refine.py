@@ -61,8 +61,9 @@ def device_refine(rows, metric, q, cand, k):
 # ---------------------------------------------------------------------------------------- 1. parity table
 
 # the pad (3), no pad (4), the tail group (67: 17 pieces), exactly one batch of twelve pieces a lane (768), one batch plus a tail
-# (772), the four-at-a-time remainder (256: 4 pieces; 1000: 15 full + 10 of 16 lanes), two batches (1536), beyond (2052: 32 + 1 lane)
-DIMS = [3, 4, 67, 256, 768, 772, 1000, 1536, 2052]
+# (772), the four-at-a-time remainder (256: 4 pieces; 1000: 15 full + 10 of 16 lanes), two batches (1536), beyond (2052: 32 + 1 lane),
+# the limit of the row store (8192: 32 KiB of query in LDS, ten batches and a remainder of eight) and the last ld below it (8188)
+DIMS = [3, 4, 67, 256, 768, 772, 1000, 1536, 2052, 8188, 8192]
 NQS = [1, 3, 65]
 KCK = [(1, 1), (10, 10), (100, 10), (256, 256), (257, 100), (1024, 256), (5, 20)]  # one key a thread / four; k < = > kc; the limits
 

@@ -70,7 +70,7 @@ def search_both_forms(ix, q, k, nprobe, opt, oi, od, what="", cap=None):
 
 # d -> (rows, lists): jfull = d / 64 whole pieces per lane, jtail = (d / 4) % 16 lanes with one more
 SHAPES = {20: (20000, 32), 64: (20000, 32), 100: (20000, 32), 760: (6000, 16), 768: (6000, 16), 772: (6000, 16), 1100: (5000, 16),
-          1536: (4000, 16)}
+          1536: (4000, 16), 2432: (3000, 16)}  # 2432: the largest d the shadow list scan serves -- 38 pieces, three batches and two more
 KS = (1, 10, 12, 13, 40, 41, 100)  # kc = 32 / 64 / 256 (R = 4); 12 | 13: the edge of the first early-exit round
 ROW_CASES = [(d, capi.METRIC_L2, None) for d in SHAPES] + [(d, capi.METRIC_IP, None) for d in SHAPES] \
     + [(d, capi.METRIC_COSINE, None) for d in (64, 768)] + [(d, capi.METRIC_L2, f) for d in (64, 768) for f in ("2", "3")]
@@ -81,7 +81,9 @@ ROW_CASES = [(d, capi.METRIC_L2, None) for d in SHAPES] + [(d, capi.METRIC_IP, N
 def test_row_shapes_match_the_oracle_under_both_forms(d, metric, h16_form, opt):
     """Every split of a row into whole pieces and a tail (one batch of twelve at d = 768, two at 1536, a batch and a remainder
     four at a time at 772 and 1100, the four-at-a-time loop alone below 768), every candidate count, L2 / IP / cosine, and the fp16 (2) and int8 residual (3) shadows forced at build time.
-    Under default settings at most a tenth of the queries may reach the canonical fallback, in either form."""
+    Under default settings at most a tenth of the queries may reach the canonical fallback, in either form.  d = 2432, the largest
+    dimension the shadow list scan serves (three batches of twelve pieces and two more): measured on an MI355X, none of the 300
+    queries fell back at any k, L2 or IP, in either form -- the cap holds there as it stands."""
     n, nlist = SHAPES[d]
     x, q = clustered(8000 + d, n, d, nlist, NQ)
     if h16_form is not None:
