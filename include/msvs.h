@@ -53,9 +53,10 @@ enum msvs_metric { MSVS_METRIC_L2 = 0, MSVS_METRIC_IP = 1, MSVS_METRIC_COSINE = 
 enum msvs_index_type { MSVS_INDEX_FLAT = 0, MSVS_INDEX_IVFFLAT = 1 };
 enum msvs_mem { MSVS_MEM_HOST = 0, MSVS_MEM_DEVICE = 1 };
 
-/* largest k (and nprobe) one device top-k pass supports; the limit of the binary, sharded and routed searches */
+/* largest k (and nprobe) one device top-k pass supports; the limit of the sharded and routed searches and of every entry that has a
+ * *_rounds twin (the coded and the binary indexes, msvs_knn_bin) */
 #define MSVS_MAX_K 256
-/* largest k of msvs_index_search[_filter][_device], msvs_knn_f32, the BM25 entries and msvs_hybrid_fuse_device: beyond
+/* largest k of msvs_index_search[_filter][_device], msvs_knn_f32, the *_rounds entries, the BM25 entries and msvs_hybrid_fuse_device: beyond
  * MSVS_MAX_K they run exact rounds of MSVS_MAX_K ranks, each excluding the rows already returned (covers the reference's
  * k + deleted-rows over-fetch, LIMIT 1000 and the 3 x LIMIT candidates of a hybrid search).  The vector searches run their
  * rounds one query at a time; the BM25 entries over the whole batch at once.  Beyond it: MSVS_ERR_UNSUPPORTED_K. */
@@ -96,6 +97,11 @@ MSVS_API int msvs_normalize_f32(float * x, size_t n, size_t d);
  * with distance FLT_MAX.  k <= MSVS_MAX_K. */
 MSVS_API int msvs_knn_bin(const uint8_t * x, const uint8_t * y, size_t nbytes, size_t k, size_t nx, size_t ny,
                           int metric, const uint64_t * alive_bits, int64_t * ids, float * dis);
+/* The same search and the same definition of its result with k <= MSVS_MAX_K_ROUNDS (MSVS_ERR_UNSUPPORTED_K beyond); for
+ * k <= MSVS_MAX_K the same bits.  Beyond MSVS_MAX_K the scan runs once per MSVS_MAX_K ranks for the whole batch, each time behind
+ * the last (distance, row) the query has returned -- see msvs_bin_index_search_rounds.  msvs_knn_bin keeps refusing k > MSVS_MAX_K. */
+MSVS_API int msvs_knn_bin_rounds(const uint8_t * x, const uint8_t * y, size_t nbytes, size_t k, size_t nx, size_t ny,
+                                 int metric, const uint64_t * alive_bits, int64_t * ids, float * dis);
 
 /* Seam A1 for BinaryVector -- Search::VectorIndex<IS, OS, Bitmap, DataType::BinaryVector> (VICommon.h:142-143; the host creates
  * it at VIWithDataPart.cpp:431-446 and searches it at :928-935; index types BinaryFLAT / BinaryMSTG, goldens 00038): an
@@ -139,6 +145,29 @@ MSVS_API int msvs_bin_index_search_params(const msvs_bin_index_t * index, const 
                                           const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
 MSVS_API int msvs_bin_index_export(const msvs_bin_index_t * index, uint8_t * centroids, int64_t * list_off, uint8_t * rows,
                                    int64_t * labels);
+/* k beyond MSVS_MAX_K, and device pointers, for both forms of the binary index.  The result is defined exactly as above: the first k
+ * alive rows (of the probed lists) by (distance, label), unfilled slots -1 / FLT_MAX.
+ * search_rounds (host pointers): k <= MSVS_MAX_K_ROUNDS (MSVS_ERR_UNSUPPORTED_K beyond); params NULL, "" or "nprobe=P" as
+ *   search_params; for k <= MSVS_MAX_K the same bits as search / search_params.  Beyond MSVS_MAX_K the scan runs once per MSVS_MAX_K
+ *   ranks for the whole batch, each time behind the last (distance, label) the query has returned.  Hamming distances are small
+ *   integers, so such a boundary usually lies inside a run of equal distances: the label decides there, exactly.  Two rows that carry
+ *   the SAME label at the same distance are returned once when they straddle such a boundary (labels are expected to be distinct).
+ * search_device: d_x (nx dense rows of nbytes), d_alive_bits (nullable, ceil(nbits / 64) words), d_ids and d_dis ([nx][k]) are DEVICE
+ *   pointers; everything is enqueued on hip_stream and nothing waits for the host -- except at the first search (on this device)
+ *   after an add, train or set_centroids, which builds the index's device image and synchronises hip_stream while it does.  The index
+ *   must not be added to or freed before hip_stream has run the search.  k <= MSVS_MAX_K; nprobe as search_params' (a flat index
+ *   ignores it, a partitioned one wants nprobe >= 1: MSVS_ERR_INVALID_ARGUMENT); a null buffer with nx > 0 and k > 0 is
+ *   MSVS_ERR_INVALID_ARGUMENT; k = 0 or nx = 0 is a no-op; a partitioned index without centroids is MSVS_ERR_NOT_READY.  The same
+ *   bits as search_params.
+ * search_rounds_device: search_device with k <= MSVS_MAX_K_ROUNDS, the rounds run back to back on hip_stream.
+ * search, search_params and search_device keep refusing k > MSVS_MAX_K. */
+MSVS_API int msvs_bin_index_search_rounds(const msvs_bin_index_t * index, const uint8_t * x, size_t nx, size_t k, const char * params,
+                                          const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_bin_index_search_device(const msvs_bin_index_t * index, const uint8_t * d_x, size_t nx, size_t k, size_t nprobe,
+                                          const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream);
+MSVS_API int msvs_bin_index_search_rounds_device(const msvs_bin_index_t * index, const uint8_t * d_x, size_t nx, size_t k, size_t nprobe,
+                                                 const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                                 void * hip_stream);
 
 /* IVFSQ -- an inverted-file index of Float32 vectors that keeps 8-bit residual codes ONLY (no f32 row survives build): dim bytes
  * (padded to 16) + a u32 label per row.  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All arithmetic

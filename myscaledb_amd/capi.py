@@ -17,7 +17,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 MAX_K = 256
 REFINE_MAX_CAND = 1024  # MSVS_REFINE_MAX_CAND: candidates per query of refine()
 ROWS_DEVICE, ROWS_HOST_PINNED = 0, 1  # msvs_rows_placement
-MAX_K_ROUNDS = 4096  # MSVS_MAX_K_ROUNDS: the BM25, device-fusion and (non-sharded, non-binary) vector searches go this far in exact rounds
+MAX_K_ROUNDS = 4096  # MSVS_MAX_K_ROUNDS: the BM25, device-fusion and (non-sharded) vector searches go this far in exact rounds
 METRICS = {"L2": METRIC_L2, "IP": METRIC_IP, "Cosine": METRIC_COSINE, "COSINE": METRIC_COSINE, "cosine": METRIC_COSINE}
 
 OK, ERR_INVALID_ARGUMENT, ERR_NOT_IMPLEMENTED, ERR_DEVICE, ERR_OOM, ERR_NOT_READY, ERR_UNSUPPORTED_K, ERR_ID_RANGE, \
@@ -42,6 +42,7 @@ SYMBOLS = [
     "msvs_bin_index_add", "msvs_bin_index_num_data", "msvs_bin_index_search", "msvs_bin_index_serialize_io", "msvs_bin_index_load_io",
     "msvs_bin_index_create_ivf", "msvs_bin_index_train", "msvs_bin_index_set_centroids", "msvs_bin_index_num_lists",
     "msvs_bin_index_search_params", "msvs_bin_index_export",
+    "msvs_knn_bin_rounds", "msvs_bin_index_search_rounds", "msvs_bin_index_search_device", "msvs_bin_index_search_rounds_device",
     "msvs_sq_index_create", "msvs_sq_index_free", "msvs_sq_index_train", "msvs_sq_index_set_codebook", "msvs_sq_index_add",
     "msvs_sq_index_build", "msvs_sq_index_ready", "msvs_sq_index_num_data", "msvs_sq_index_num_lists", "msvs_sq_index_memory_usage",
     "msvs_sq_index_search", "msvs_sq_index_search_device", "msvs_sq_index_export", "msvs_sq_index_serialize_io", "msvs_sq_index_load_io",
@@ -192,7 +193,7 @@ def knn(x, y, k, metric, alive=None):
     return ids, dis
 
 
-def knn_bin(x, y, k, metric, alive=None):
+def knn_bin(x, y, k, metric, alive=None, _entry="msvs_knn_bin"):
     """msvs_knn_bin: x [nx, nbytes], y [ny, nbytes] uint8 host arrays -> (ids int64 [nx, k], dis f32 [nx, k])."""
     y = np.ascontiguousarray(y, np.uint8)
     nb = y.shape[1]
@@ -201,10 +202,15 @@ def knn_bin(x, y, k, metric, alive=None):
     ids = np.empty((nx, k), np.int64)
     dis = np.empty((nx, k), np.float32)
     bits = None if alive is None else pack_bits(alive)
-    _check(lib().msvs_knn_bin(_p(x, C.c_uint8), _p(y, C.c_uint8), C.c_size_t(nb), C.c_size_t(k), C.c_size_t(nx),
-                              C.c_size_t(y.shape[0]), int(metric), _p(bits, C.c_uint64), _p(ids, C.c_int64),
-                              _p(dis, C.c_float)))
+    _check(getattr(lib(), _entry)(_p(x, C.c_uint8), _p(y, C.c_uint8), C.c_size_t(nb), C.c_size_t(k), C.c_size_t(nx),
+                                  C.c_size_t(y.shape[0]), int(metric), _p(bits, C.c_uint64), _p(ids, C.c_int64),
+                                  _p(dis, C.c_float)))
     return ids, dis
+
+
+def knn_bin_rounds(x, y, k, metric, alive=None):
+    """msvs_knn_bin_rounds: knn_bin with k <= MAX_K_ROUNDS (beyond MAX_K the scan runs once per MAX_K ranks)."""
+    return knn_bin(x, y, k, metric, alive, _entry="msvs_knn_bin_rounds")
 
 
 class BinIndex:
@@ -263,6 +269,31 @@ class BinIndex:
             _check(lib().msvs_bin_index_search_params(self._h, _p(x, C.c_uint8), C.c_size_t(x.shape[0]), C.c_size_t(k), params.encode(),
                                                       _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
         return ids, dis
+
+    def search_rounds(self, x, k, alive=None, params=None, nbits=None):
+        """search with k <= MAX_K_ROUNDS (msvs_bin_index_search_rounds): beyond MAX_K the scan runs once per MAX_K ranks.
+        params: None, "" or "nprobe=P"."""
+        x = np.ascontiguousarray(x, np.uint8).reshape(-1, self.nbytes)
+        ids = np.empty((x.shape[0], k), np.int64)
+        dis = np.empty((x.shape[0], k), np.float32)
+        bits = None if alive is None else pack_bits(alive)
+        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
+        _check(lib().msvs_bin_index_search_rounds(self._h, _p(x, C.c_uint8), C.c_size_t(x.shape[0]), C.c_size_t(k),
+                                                  None if params is None else params.encode(), _p(bits, C.c_uint64), nb,
+                                                  _p(ids, C.c_int64), _p(dis, C.c_float)))
+        return ids, dis
+
+    def search_device(self, d_x, nx, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0, _entry="msvs_bin_index_search_device"):
+        """msvs_bin_index_search_device: all buffers are raw device addresses (ints; d_x: nx dense rows of nbytes); enqueues on
+        `stream` and returns (the first search after an add builds the device image and synchronises the stream)."""
+        _check(getattr(lib(), _entry)(self._h, C.c_void_p(int(d_x)) if d_x else None, C.c_size_t(nx), C.c_size_t(k), C.c_size_t(nprobe),
+                                      C.c_void_p(int(d_alive)) if d_alive else None, C.c_size_t(nbits),
+                                      C.c_void_p(int(d_ids)) if d_ids else None, C.c_void_p(int(d_dis)) if d_dis else None,
+                                      C.c_void_p(int(stream)) if stream else None))
+
+    def search_rounds_device(self, d_x, nx, k, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """search_device with k <= MAX_K_ROUNDS (msvs_bin_index_search_rounds_device)."""
+        self.search_device(d_x, nx, k, nprobe, d_ids, d_dis, stream, d_alive, nbits, _entry="msvs_bin_index_search_rounds_device")
 
     def export(self):
         """Partitioned index -> (centroids [nlist, nbytes], list offsets [nlist + 1], rows and labels in list-major order)."""

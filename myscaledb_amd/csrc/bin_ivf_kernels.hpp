@@ -180,11 +180,15 @@ struct BinIvfParams
     const int64_t * list_off; // [nlist + 1]
     const uint32_t * pair_off, * work_off, * pairs; // the plan (IvfPlanParams)
     uint64_t * partial;       // [pair][seg_max][k], prefilled with KEY_NONE: a (pair, segment) without rows is never written
+    const uint64_t * after;   // AFTER 1 only: [query of the round] continuation keys (search in rank rounds, binary.hip)
 };
 
 /// grid: any size; slot -> work item as in ivf_batched_scan_kernel (tiles of one list back to back on one XCD).
 /// dynamic LDS: T * ld16 * 16 + 5 * k * 8 bytes.  REG: ld16 == G, a lane's word of every query of the tile lives in registers.
-template <int METRIC, int G, int T, int R, bool REG>
+/// AFTER 1 (a later round of a search with k > MSVS_MAX_K): a row is offered to tile query t only if its key is strictly greater than
+/// a.after[query of t], the last key the query has returned; KEY_NONE there admits nothing.  The tile's floors are read once per work
+/// item and are uniform over the workgroup.  AFTER 0 never reads a.after.
+template <int METRIC, int G, int T, int R, bool REG, int AFTER = 0>
 __global__ __launch_bounds__(BLOCK) void bin_ivf_scan_kernel(const BinIvfParams a)
 {
     uint4 * qs = reinterpret_cast<uint4 *>(msvs_smem);
@@ -209,6 +213,13 @@ __global__ __launch_bounds__(BLOCK) void bin_ivf_scan_kernel(const BinIvfParams 
             qs[i] = a.Q[(size_t)(a.pairs[pb + t] / a.nprobe) * a.ld16 + c];
         }
         __syncthreads();
+        uint64_t floor_key[AFTER ? T : 1];
+        if (AFTER)
+        {
+#pragma unroll
+            for (int t = 0; t < T; t++) // (short tiles repeat their last query: its slot is never offered to)
+                floor_key[AFTER ? t : 0] = uniform_key(a.after[a.pairs[pb + min((uint32_t)t, nt - 1)] / a.nprobe]);
+        }
         uint4 xq[REG ? T : 1];
         if (REG)
         {
@@ -288,7 +299,10 @@ __global__ __launch_bounds__(BLOCK) void bin_ivf_scan_kernel(const BinIvfParams 
                             x1 += (uint32_t)__shfl_xor((int)x1, o);
                     }
                     const float v = METRIC == B_HAMMING ? (float)x0 : (x1 == 0 ? 1.0f : __fdiv_rn((float)(x1 - x0), (float)x1));
-                    top[t].offer(ok ? make_key<M_L2>(v, id) : KEY_NONE, k, lane);
+                    uint64_t key = ok ? make_key<M_L2>(v, id) : KEY_NONE;
+                    if (AFTER)
+                        key = key > floor_key[AFTER ? t : 0] ? key : KEY_NONE;
+                    top[t].offer(key, k, lane);
                 }
         }
         uint64_t * merged = lds_merge + 4 * k;

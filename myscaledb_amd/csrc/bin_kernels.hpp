@@ -32,15 +32,20 @@ struct BinParams
     uint32_t ld16;
     uint32_t n_rows, rows_per_block, n_blocks, k, nq;
     uint64_t * partial; // [nq][n_blocks][k]
+    const uint64_t * after; // AFTER 1 only: [nq] continuation keys (a later rank round of a search with k > MSVS_MAX_K, binary.hip)
 };
 
 /// grid (n_blocks, nq); dynamic LDS: ld16 * 16 + 5 * k * 8 bytes.
-template <int METRIC, int G, int R>
+/// AFTER 1 (a later round of a search with k > MSVS_MAX_K): a row is offered only if its key is strictly greater than a.after[q], the
+/// last key the query has returned (unsigned compare: distance word first, then label -- inside a run of equal distances the label
+/// carries the continuation); KEY_NONE there admits nothing.  The floor is uniform over the block.  AFTER 0 never reads a.after.
+template <int METRIC, int G, int R, int AFTER = 0>
 __global__ __launch_bounds__(BLOCK) void bin_scan_kernel(const BinParams a)
 {
     uint4 * qs = reinterpret_cast<uint4 *>(msvs_smem);
     uint64_t * lds_merge = reinterpret_cast<uint64_t *>(msvs_smem + (size_t)a.ld16 * 16);
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = blockIdx.y, k = a.k;
+    const uint64_t floor_key = AFTER ? uniform_key(a.after[q]) : 0;
     for (uint32_t c = tid; c < a.ld16; c += BLOCK)
         qs[c] = a.Q[(size_t)q * a.ld16 + c];
     __syncthreads();
@@ -81,7 +86,10 @@ __global__ __launch_bounds__(BLOCK) void bin_scan_kernel(const BinParams a)
         if (ok && a.alive)
             ok = id < a.nbits && ((a.alive[id >> 6] >> (id & 63)) & 1);
         const float v = METRIC == B_HAMMING ? (float)c0 : (c1 == 0 ? 1.0f : __fdiv_rn((float)(c1 - c0), (float)c1));
-        top.offer(ok ? make_key<M_L2>(v, id) : KEY_NONE, k, lane);
+        uint64_t key = ok ? make_key<M_L2>(v, id) : KEY_NONE;
+        if (AFTER)
+            key = key > floor_key ? key : KEY_NONE;
+        top.offer(key, k, lane);
     }
     top.store(lds_merge + wave * k, k, lane);
     __syncthreads();

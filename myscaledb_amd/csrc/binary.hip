@@ -1,4 +1,5 @@
-// binary.hip -- seam A2 for BinaryVector: msvs_knn_bin (include/msvs.h), see bin_kernels.hpp.
+// binary.hip -- seam A2 for BinaryVector: msvs_knn_bin[_rounds] (include/msvs.h), see bin_kernels.hpp; below it seam A1, the binary
+// index (flat and partitioned), with host-pointer, device-pointer and rank-round (k > MSVS_MAX_K) entries.
 #include <algorithm>
 
 #include <cstring>
@@ -53,7 +54,8 @@ static void launch_bin_assign(const unsigned char * dy, const unsigned char * dc
     MSVS_HIP(hipGetLastError());
 }
 
-/// g: lanes per row, a power of two up to 16 (bin_lanes)
+/// g: lanes per row, a power of two up to 16 (bin_lanes).  A later rank round (a.after) takes the AFTER form, which exists with four
+/// top-k registers per lane only: such a round follows one of MSVS_MAX_K ranks, and its own k is the search's remainder.
 static void launch_bin_scan(int metric, uint32_t g, const BinParams & a, hipStream_t stream)
 {
     ProfileScope prof("bin_scan", stream);
@@ -61,30 +63,44 @@ static void launch_bin_scan(int metric, uint32_t g, const BinParams & a, hipStre
     const size_t lds = (size_t)a.ld16 * 16 + (size_t)5 * a.k * 8;
     with_int<B_HAMMING, B_JACCARD>(metric == MSVS_METRIC_HAMMING ? B_HAMMING : B_JACCARD, [&](auto m) {
         with_int<1, 2, 4, 8, 16>(g, [&](auto lanes) {
-            with_int<1, 4>(a.k <= 64 ? 1 : 4, [&](auto r) {
-                constexpr int METRIC = decltype(m)::value, G = decltype(lanes)::value, R = decltype(r)::value;
-                hipLaunchKernelGGL((bin_scan_kernel<METRIC, G, R>), grid, dim3(BLOCK), lds, stream, a);
-            });
+            constexpr int METRIC = decltype(m)::value, G = decltype(lanes)::value;
+            if (a.after)
+                hipLaunchKernelGGL((bin_scan_kernel<METRIC, G, 4, 1>), grid, dim3(BLOCK), lds, stream, a);
+            else
+                with_int<1, 4>(a.k <= 64 ? 1 : 4, [&](auto r) {
+                    hipLaunchKernelGGL((bin_scan_kernel<METRIC, G, decltype(r)::value>), grid, dim3(BLOCK), lds, stream, a);
+                });
         });
     });
     MSVS_HIP(hipGetLastError());
 }
 
+/// queries per tile of the list scan for a plan whose (first) round returns k ranks
+static uint32_t bin_ivf_tile(size_t k) { return k <= 64 ? BIN_IVF_T : BIN_IVF_T / 2; }
+
 /// List scan over the plan's work items; tiles of BIN_IVF_T queries with one top-k register per lane up to k = 64, half the tile and
-/// four registers beyond; REG: the row fits the group's registers (ld16 == G).
+/// four registers beyond; REG: the row fits the group's registers (ld16 == G).  A later rank round (a.after) takes the AFTER form,
+/// which exists in the second shape only: the plan it walks was made for a first round of MSVS_MAX_K ranks, whatever its own k.
 static void launch_bin_ivf_scan(int metric, uint32_t g, uint32_t grid, const BinIvfParams & a, hipStream_t stream)
 {
     ProfileScope prof("bin_ivf_scan", stream);
     with_int<B_HAMMING, B_JACCARD>(metric == MSVS_METRIC_HAMMING ? B_HAMMING : B_JACCARD, [&](auto m) {
         with_int<1, 2, 4, 8, 16>(g, [&](auto lanes) {
-            with_bool(a.k <= 64, [&](auto small) {
-                with_bool(a.ld16 == (uint32_t)decltype(lanes)::value, [&](auto reg) {
-                    constexpr int METRIC = decltype(m)::value, G = decltype(lanes)::value;
-                    constexpr int T = decltype(small)::value ? BIN_IVF_T : BIN_IVF_T / 2, R = decltype(small)::value ? 1 : 4;
-                    constexpr bool REG = decltype(reg)::value;
+            with_bool(a.ld16 == (uint32_t)decltype(lanes)::value, [&](auto reg) {
+                constexpr int METRIC = decltype(m)::value, G = decltype(lanes)::value;
+                constexpr bool REG = decltype(reg)::value;
+                if (a.after)
+                {
+                    constexpr int T = BIN_IVF_T / 2;
                     const size_t lds = (size_t)T * a.ld16 * 16 + (size_t)5 * a.k * 8;
-                    hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, T, R, REG>), dim3(grid), dim3(BLOCK), lds, stream, a);
-                });
+                    hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, T, 4, REG, 1>), dim3(grid), dim3(BLOCK), lds, stream, a);
+                }
+                else
+                    with_bool(a.k <= 64, [&](auto small) {
+                        constexpr int T = decltype(small)::value ? BIN_IVF_T : BIN_IVF_T / 2, R = decltype(small)::value ? 1 : 4;
+                        const size_t lds = (size_t)T * a.ld16 * 16 + (size_t)5 * a.k * 8;
+                        hipLaunchKernelGGL((bin_ivf_scan_kernel<METRIC, G, T, R, REG>), dim3(grid), dim3(BLOCK), lds, stream, a);
+                    });
             });
         });
     });
@@ -95,93 +111,157 @@ static void launch_bin_ivf_scan(int metric, uint32_t g, uint32_t grid, const Bin
 
 using namespace msvs;
 
-/// The scan + merge over rows already on the device (dy: n rows of ldb bytes, zero padded to 16-byte words); x, alive_bits
-/// (over labels, nbits of them), ids, dis on the HOST.
-static void bin_search_rows(const unsigned char * dy, const uint32_t * d_labels, size_t ny, size_t nbytes, const uint8_t * x, size_t nx,
-                            size_t k, int metric, const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis, hipStream_t stream)
+// Both searches come as a device core (everything enqueued on `stream`: queries, filter and outputs are DEVICE pointers, nothing waits
+// for the host) and a host-pointer wrapper around it (bin_search_host).  k > MSVS_MAX_K runs in rank rounds like the coded indexes'
+// search_device (coded_ivf.hpp): everything up to the plan once per chunk of queries, then ceil(k / MSVS_MAX_K) times the scan with
+// k_round = min(MSVS_MAX_K, k - done) ranks (from the second round on its AFTER form: only rows whose key is strictly greater than the
+// query's continuation key), the merge to keys, and launch_round_scatter into columns [done, done + k_round) of the [nx][k] outputs,
+// which also writes the continuation key -- a full round's last key, KEY_NONE after a short one.  Hamming distances are small
+// integers: a round boundary nearly always falls inside a run of equal distances, and the label half of the key carries the
+// continuation there.  Segments, tile, LDS and partial lists are sized by min(k, MSVS_MAX_K).
+
+constexpr size_t BIN_FLAT_CHUNK = 65535; // queries of one flat scan launch (they sit on grid.y)
+
+/// d_x: n dense rows of nbytes on the device -> n rows of ldb bytes (zero padded) in dq
+static void bin_pad_device_rows(unsigned char * dq, const uint8_t * d_x, size_t n, size_t nbytes, size_t ldb, hipStream_t stream)
+{
+    if (ldb != nbytes)
+        MSVS_HIP(hipMemsetAsync(dq, 0, n * ldb, stream));
+    MSVS_HIP(hipMemcpy2DAsync(dq, ldb, d_x, nbytes, nbytes, n, hipMemcpyDeviceToDevice, stream));
+}
+
+/// The scan + merge over rows already on the device (dy: n rows of ldb bytes, zero padded to 16-byte words); d_x (nx dense rows of
+/// nbytes), d_alive (over labels, nbits of them), d_ids, d_dis ([nx][k]) on the DEVICE.
+static void bin_search_rows_device(const unsigned char * dy, const uint32_t * d_labels, size_t ny, size_t nbytes, const uint8_t * d_x, size_t nx,
+                                   size_t k, int metric, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis,
+                                   hipStream_t stream)
 {
     const uint32_t ld16 = (uint32_t)ceil_div(nbytes, (size_t)16);
     const size_t ldb = (size_t)ld16 * 16;
-    if (ldb + 5 * k * 8 > SCAN_LDS_BUDGET)
+    const bool rounds = k > MSVS_MAX_K;
+    const size_t kl = std::min<size_t>(k, MSVS_MAX_K); // ranks of one scan
+    if (ldb + 5 * kl * 8 > SCAN_LDS_BUDGET)
         fail(MSVS_ERR_INVALID_ARGUMENT, "binary vectors of %zu bytes are too long for the LDS query stage", nbytes);
-    uint32_t g = 1; // lanes per row: one 16-byte word each per step
-    while (g < 16 && g * 2 <= ld16)
-        g *= 2;
+    const uint32_t g = bin_lanes(ld16);
+    const size_t chunk = std::min(nx, BIN_FLAT_CHUNK);
     // row ranges: ~2048 blocks over the chip, at least one wavefront step each
     const size_t rows_step = 4 * (64 / g);
-    const size_t want = std::max<size_t>(1, 2048 / nx);
+    const size_t want = std::max<size_t>(1, 2048 / chunk);
     const size_t nb = std::max<size_t>(1, std::min(want, ceil_div(std::max<size_t>(ny, 1), rows_step)));
     const uint32_t rpb = (uint32_t)round_up(ceil_div(std::max<size_t>(ny, 1), nb), rows_step);
     const uint32_t n_blocks = (uint32_t)ceil_div(std::max<size_t>(ny, 1), (size_t)rpb);
-    const size_t words = alive_bits ? std::max<size_t>(1, ceil_div(nbits, (size_t)64)) : 0;
     Scratch & scr = scratch_for(stream);
-    scr.reserve(nx * ldb + nx * (size_t)n_blocks * k * 8 + nx * k * 12 + words * 8 + 8192, stream);
-    unsigned char * dq = scr.take<unsigned char>(nx * ldb);
-    uint64_t * partial = scr.take<uint64_t>(nx * (size_t)n_blocks * k);
-    int64_t * d_ids = scr.take<int64_t>(nx * k);
-    float * d_dis = scr.take<float>(nx * k);
-    uint64_t * d_alive = words ? scr.take<uint64_t>(words) : nullptr;
-    if (ldb != nbytes)
-        MSVS_HIP(hipMemsetAsync(dq, 0, nx * ldb, stream));
-    MSVS_HIP(hipMemcpy2DAsync(dq, ldb, x, nbytes, nbytes, nx, hipMemcpyHostToDevice, stream));
+    scr.reserve(chunk * ldb + chunk * (size_t)n_blocks * kl * 8 + (rounds ? chunk * (size_t)(MSVS_MAX_K + 1) * 8 : 0) + 8192, stream);
+    unsigned char * dq = scr.take<unsigned char>(chunk * ldb);
+    uint64_t * partial = scr.take<uint64_t>(chunk * (size_t)n_blocks * kl);
+    uint64_t * round_keys = rounds ? scr.take<uint64_t>(chunk * MSVS_MAX_K) : nullptr;
+    uint64_t * after = rounds ? scr.take<uint64_t>(chunk) : nullptr;
+    for (size_t q0 = 0; q0 < nx; q0 += chunk)
+    {
+        const size_t nq = std::min(chunk, nx - q0);
+        bin_pad_device_rows(dq, d_x + q0 * nbytes, nq, nbytes, ldb, stream);
+        BinParams a{};
+        a.Y = reinterpret_cast<const uint4 *>(dy);
+        a.Q = reinterpret_cast<const uint4 *>(dq);
+        a.alive = d_alive;
+        a.labels = d_labels;
+        a.nbits = (uint32_t)std::min<size_t>(nbits, 0xffffffffu);
+        a.ld16 = ld16;
+        a.n_rows = (uint32_t)ny;
+        a.rows_per_block = rpb;
+        a.n_blocks = n_blocks;
+        a.nq = (uint32_t)nq;
+        a.partial = partial;
+        for (size_t done = 0; done < k; done += MSVS_MAX_K) // (one pass unless `rounds`)
+        {
+            const size_t kr = std::min<size_t>(MSVS_MAX_K, k - done);
+            a.k = (uint32_t)kr;
+            a.after = done ? after : nullptr;
+            launch_bin_scan(metric, g, a, stream);
+            MergeParams m{};
+            m.partial = partial;
+            m.n_lists = n_blocks;
+            m.k = (uint32_t)kr;
+            m.out_ids = d_ids + q0 * k;
+            m.out_dis = d_dis + q0 * k;
+            if (rounds)
+            {
+                m.mode = 2;
+                m.out_keys = round_keys;
+            }
+            launch_merge(M_L2, m, (uint32_t)nq, stream);
+            if (rounds)
+                launch_round_scatter(M_L2, round_keys, nq, kr, k, done, false, d_ids + q0 * k, d_dis + q0 * k, after, stream);
+        }
+    }
+}
+
+/// The host-pointer form of a device core: the queries (nx dense rows of nbytes) and the filter staged to the device,
+/// dev(d_x, d_alive, d_ids, d_dis) enqueues the search on `stream`, the results are copied back; synchronises.
+template <class DeviceSearch>
+static void bin_search_host(const uint8_t * x, size_t nx, size_t nbytes, size_t k, const uint64_t * alive_bits, size_t nbits, int64_t * ids,
+                            float * dis, hipStream_t stream, DeviceSearch dev)
+{
+    const size_t words = alive_bits ? std::max<size_t>(1, ceil_div(nbits, (size_t)64)) : 0;
+    Scratch & stg = staging_for(stream);
+    stg.reserve(nx * nbytes + nx * k * 12 + words * 8 + 4 * 256, stream);
+    unsigned char * d_x = stg.take<unsigned char>(nx * nbytes);
+    int64_t * d_ids = stg.take<int64_t>(nx * k);
+    float * d_dis = stg.take<float>(nx * k);
+    uint64_t * d_alive = words ? stg.take<uint64_t>(words) : nullptr;
+    MSVS_HIP(hipMemcpyAsync(d_x, x, nx * nbytes, hipMemcpyHostToDevice, stream));
     if (words)
         MSVS_HIP(hipMemcpyAsync(d_alive, alive_bits, words * 8, hipMemcpyHostToDevice, stream));
-    BinParams a{};
-    a.Y = reinterpret_cast<const uint4 *>(dy);
-    a.Q = reinterpret_cast<const uint4 *>(dq);
-    a.alive = d_alive;
-    a.labels = d_labels;
-    a.nbits = (uint32_t)std::min<size_t>(nbits, 0xffffffffu);
-    a.ld16 = ld16;
-    a.n_rows = (uint32_t)ny;
-    a.rows_per_block = rpb;
-    a.n_blocks = n_blocks;
-    a.k = (uint32_t)k;
-    a.nq = (uint32_t)nx;
-    a.partial = partial;
-    launch_bin_scan(metric, g, a, stream);
-    MergeParams m{};
-    m.partial = partial;
-    m.n_lists = n_blocks;
-    m.k = (uint32_t)k;
-    m.out_ids = d_ids;
-    m.out_dis = d_dis;
-    launch_merge(M_L2, m, (uint32_t)nx, stream);
+    dev(d_x, d_alive, d_ids, d_dis);
     MSVS_HIP(hipMemcpyAsync(ids, d_ids, nx * k * 8, hipMemcpyDeviceToHost, stream));
     MSVS_HIP(hipMemcpyAsync(dis, d_dis, nx * k * 4, hipMemcpyDeviceToHost, stream));
     MSVS_HIP(hipStreamSynchronize(stream));
 }
 
-static void bin_check_args(size_t nbytes, size_t k, int metric)
+/// k_max: the entry's limit of k (MSVS_MAX_K, or MSVS_MAX_K_ROUNDS for the entries that search in rank rounds)
+static void bin_check_args(size_t nbytes, size_t k, int metric, size_t k_max = MSVS_MAX_K)
 {
     if (metric != MSVS_METRIC_HAMMING && metric != MSVS_METRIC_JACCARD)
         fail(MSVS_ERR_NOT_IMPLEMENTED, "Metric not implemented in brute force search for Binary Vector");
     if (nbytes == 0)
         fail(MSVS_ERR_INVALID_ARGUMENT, "zero dimension");
-    if (k > MSVS_MAX_K)
-        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the device top-k limit %d", k, MSVS_MAX_K);
+    if (k > k_max)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the device top-k limit %d", k, (int)k_max);
+}
+
+static void bin_knn(const uint8_t * x, const uint8_t * y, size_t nbytes, size_t k, size_t k_max, size_t nx, size_t ny, int metric,
+                    const uint64_t * alive_bits, int64_t * ids, float * dis)
+{
+    bin_check_args(std::max<size_t>(nbytes, 1), k, metric, k_max);
+    if (nx == 0 || k == 0)
+        return;
+    if (!x || !ids || !dis || (ny && !y) || nbytes == 0)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer or zero dimension");
+    if (ny > 0xfffffff0ull)
+        fail(MSVS_ERR_ID_RANGE, "ny exceeds the u32 id range");
+    hipStream_t stream = thread_stream();
+    const size_t ldb = round_up(nbytes, (size_t)16);
+    DevBuf<unsigned char> dy(std::max<size_t>(ny, 1) * ldb);
+    if (ldb != nbytes)
+        MSVS_HIP(hipMemsetAsync(dy.p, 0, std::max<size_t>(ny, 1) * ldb, stream));
+    if (ny)
+        MSVS_HIP(hipMemcpy2DAsync(dy.p, ldb, y, nbytes, nbytes, ny, hipMemcpyHostToDevice, stream));
+    bin_search_host(x, nx, nbytes, k, alive_bits, ny, ids, dis, stream,
+                    [&](const uint8_t * d_x, const uint64_t * d_alive, int64_t * d_ids, float * d_dis) {
+                        bin_search_rows_device(dy.p, nullptr, ny, nbytes, d_x, nx, k, metric, d_alive, ny, d_ids, d_dis, stream);
+                    });
 }
 
 extern "C" int msvs_knn_bin(const uint8_t * x, const uint8_t * y, size_t nbytes, size_t k, size_t nx, size_t ny, int metric,
                             const uint64_t * alive_bits, int64_t * ids, float * dis)
 {
-    return guarded([&] {
-        bin_check_args(std::max<size_t>(nbytes, 1), k, metric);
-        if (nx == 0 || k == 0)
-            return;
-        if (!x || !ids || !dis || (ny && !y) || nbytes == 0)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer or zero dimension");
-        if (ny > 0xfffffff0ull)
-            fail(MSVS_ERR_ID_RANGE, "ny exceeds the u32 id range");
-        hipStream_t stream = thread_stream();
-        const size_t ldb = round_up(nbytes, (size_t)16);
-        DevBuf<unsigned char> dy(std::max<size_t>(ny, 1) * ldb);
-        if (ldb != nbytes)
-            MSVS_HIP(hipMemsetAsync(dy.p, 0, std::max<size_t>(ny, 1) * ldb, stream));
-        if (ny)
-            MSVS_HIP(hipMemcpy2DAsync(dy.p, ldb, y, nbytes, nbytes, ny, hipMemcpyHostToDevice, stream));
-        bin_search_rows(dy.p, nullptr, ny, nbytes, x, nx, k, metric, alive_bits, ny, ids, dis, stream);
-    });
+    return guarded([&] { bin_knn(x, y, nbytes, k, MSVS_MAX_K, nx, ny, metric, alive_bits, ids, dis); });
+}
+
+extern "C" int msvs_knn_bin_rounds(const uint8_t * x, const uint8_t * y, size_t nbytes, size_t k, size_t nx, size_t ny, int metric,
+                                   const uint64_t * alive_bits, int64_t * ids, float * dis)
+{
+    return guarded([&] { bin_knn(x, y, nbytes, k, MSVS_MAX_K_ROUNDS, nx, ny, metric, alive_bits, ids, dis); });
 }
 
 // ------------------------------------------------------------------------------------------- seam A1 for BinaryVector
@@ -314,40 +394,40 @@ static std::shared_ptr<msvs_bin_index::Image> bin_image(const msvs_bin_index * i
     return slot;
 }
 
-/// Coarse probe, plan, list scan and merge over a partitioned image; x, alive_bits, ids, dis on the HOST.
-static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbytes, int metric, const uint8_t * x, size_t nx, size_t k,
-                                 size_t nprobe, const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis, hipStream_t stream)
+/// Coarse probe, plan, list scan and merge over a partitioned image; d_x, d_alive, d_ids, d_dis on the DEVICE (as bin_search_rows_device).
+static void bin_ivf_search_image_device(const msvs_bin_index::Image & img, size_t nbytes, int metric, const uint8_t * d_x, size_t nx, size_t k,
+                                        size_t nprobe, const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis,
+                                        hipStream_t stream)
 {
     const uint32_t ld16 = (uint32_t)ceil_div(nbytes, (size_t)16);
     const size_t ldb = (size_t)ld16 * 16;
     const uint32_t g = bin_lanes(ld16);
     const size_t nlist = img.nlist, P = std::min(nprobe, nlist);
-    // row segments of whole wavefront steps; per query of a round: its distances to the centroids, probes and pairs, padded row, results
-    const SegmentPlan sp = plan_segments(img.max_len, options().bin_ivf_rpb, 4 * (64 / g), P, k, nlist * 4 + P * 8 + ldb + k * 12, nx);
+    const bool rounds = k > MSVS_MAX_K;
+    const size_t kl = std::min<size_t>(k, MSVS_MAX_K); // ranks of one scan
+    // row segments of whole wavefront steps; per query of a round: its distances to the centroids, probes and pairs, padded row
+    // (rounds: a round's merged keys and the continuation key)
+    const SegmentPlan sp = plan_segments(img.max_len, options().bin_ivf_rpb, 4 * (64 / g), P, kl,
+                                         nlist * 4 + P * 8 + ldb + (rounds ? (size_t)(MSVS_MAX_K + 1) * 8 : 0), nx);
     const uint32_t rpb = sp.rpb;
     const size_t seg_max = sp.seg_max, per_q = sp.per_q, chunk = sp.chunk;
-    const size_t words = alive_bits ? std::max<size_t>(1, ceil_div(nbits, (size_t)64)) : 0;
     Scratch & scr = scratch_for(stream);
-    scr.reserve(chunk * per_q + (nlist + 1) * 16 + words * 8 + 16 * 256, stream);
+    scr.reserve(chunk * per_q + (nlist + 1) * 16 + 16 * 256, stream);
     unsigned char * dq = scr.take<unsigned char>(chunk * ldb);
     uint32_t * dist = scr.take<uint32_t>(chunk * nlist);
     int32_t * probes = scr.take<int32_t>(chunk * P);
     const GroupedPlan plan(scr, nlist, chunk * P);
-    uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * k);
-    int64_t * d_ids = scr.take<int64_t>(chunk * k);
-    float * d_dis = scr.take<float>(chunk * k);
-    uint64_t * d_alive = words ? scr.take<uint64_t>(words) : nullptr;
-    if (words)
-        MSVS_HIP(hipMemcpyAsync(d_alive, alive_bits, words * 8, hipMemcpyHostToDevice, stream));
+    uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * kl);
+    uint64_t * round_keys = rounds ? scr.take<uint64_t>(chunk * MSVS_MAX_K) : nullptr;
+    uint64_t * after = rounds ? scr.take<uint64_t>(chunk) : nullptr;
     for (size_t q0 = 0; q0 < nx; q0 += chunk)
     {
         const size_t nq = std::min(chunk, nx - q0);
-        bin_upload_padded(dq, x + q0 * nbytes, nq, nbytes, ldb, stream);
+        bin_pad_device_rows(dq, d_x + q0 * nbytes, nq, nbytes, ldb, stream);
         launch_bin_assign(dq, img.cent.p, nq, nlist, ld16, nullptr, dist, stream);
         hipLaunchKernelGGL(bin_probe_select_kernel, dim3((unsigned)nq), dim3(BLOCK), 0, stream, dist, (uint32_t)nlist, (uint32_t)P, ld16 * 128u, probes);
         MSVS_HIP(hipGetLastError());
-        MSVS_HIP(hipMemsetAsync(partial, 0xff, nq * P * seg_max * k * 8, stream)); // KEY_NONE: (pair, segment) slots without rows
-        plan.run(probes, img.list_off.p, nq * P, rpb, k <= 64 ? BIN_IVF_T : BIN_IVF_T / 2, stream);
+        plan.run(probes, img.list_off.p, nq * P, rpb, bin_ivf_tile(kl), stream);
         BinIvfParams a{};
         a.Y = reinterpret_cast<const uint4 *>(img.rows.p);
         a.Q = reinterpret_cast<const uint4 *>(dq);
@@ -355,7 +435,6 @@ static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbyte
         a.labels = img.labels.p;
         a.nbits = (uint32_t)std::min<size_t>(nbits, 0xffffffffu);
         a.ld16 = ld16;
-        a.k = (uint32_t)k;
         a.nprobe = (uint32_t)P;
         a.nlist = (uint32_t)nlist;
         a.rows_per_block = rpb;
@@ -365,18 +444,30 @@ static void bin_ivf_search_image(const msvs_bin_index::Image & img, size_t nbyte
         a.work_off = plan.work_off;
         a.pairs = plan.pairs;
         a.partial = partial;
-        launch_bin_ivf_scan(metric, g, (uint32_t)std::min<size_t>(2048, nq * P * seg_max), a, stream);
-        MergeParams m{};
-        m.partial = partial;
-        m.n_lists = (uint32_t)(P * seg_max);
-        m.k = (uint32_t)k;
-        m.out_ids = d_ids;
-        m.out_dis = d_dis;
-        launch_merge(M_L2, m, (uint32_t)nq, stream);
-        MSVS_HIP(hipMemcpyAsync(ids + q0 * k, d_ids, nq * k * 8, hipMemcpyDeviceToHost, stream));
-        MSVS_HIP(hipMemcpyAsync(dis + q0 * k, d_dis, nq * k * 4, hipMemcpyDeviceToHost, stream));
+        for (size_t done = 0; done < k; done += MSVS_MAX_K) // (one pass unless `rounds`)
+        {
+            const size_t kr = std::min<size_t>(MSVS_MAX_K, k - done);
+            a.k = (uint32_t)kr;
+            a.after = done ? after : nullptr;
+            // KEY_NONE: (pair, segment) slots without rows -- every round anew, the slots of a round are k_round keys apart
+            MSVS_HIP(hipMemsetAsync(partial, 0xff, nq * P * seg_max * kr * 8, stream));
+            launch_bin_ivf_scan(metric, g, (uint32_t)std::min<size_t>(2048, nq * P * seg_max), a, stream);
+            MergeParams m{};
+            m.partial = partial;
+            m.n_lists = (uint32_t)(P * seg_max);
+            m.k = (uint32_t)kr;
+            m.out_ids = d_ids + q0 * k;
+            m.out_dis = d_dis + q0 * k;
+            if (rounds)
+            {
+                m.mode = 2;
+                m.out_keys = round_keys;
+            }
+            launch_merge(M_L2, m, (uint32_t)nq, stream);
+            if (rounds)
+                launch_round_scatter(M_L2, round_keys, nq, kr, k, done, false, d_ids + q0 * k, d_dis + q0 * k, after, stream);
+        }
     }
-    MSVS_HIP(hipStreamSynchronize(stream));
 }
 
 extern "C" int msvs_bin_index_create(size_t nbytes, int metric, msvs_bin_index_t ** out)
@@ -532,45 +623,97 @@ extern "C" int msvs_bin_index_add(msvs_bin_index_t * ix, const uint8_t * rows, c
 
 extern "C" size_t msvs_bin_index_num_data(const msvs_bin_index_t * ix) { return ix ? ix->labels.size() : 0; }
 
-static void bin_index_search(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, size_t nprobe, const uint64_t * alive_bits,
-                             size_t nbits, int64_t * ids, float * dis)
+/// What every index search checks before it touches the device, in this order; false: nothing to do (nx or k is 0).
+/// x, ids, dis: the entry's own pointers, host or device.
+static bool bin_index_search_checks(const msvs_bin_index_t * ix, const void * x, size_t nx, size_t k, size_t k_max, size_t nprobe, const void * ids,
+                                    const void * dis)
 {
-    bin_check_args(ix->nbytes, k, ix->metric);
+    if (!ix)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
+    bin_check_args(ix->nbytes, k, ix->metric, k_max);
     {
         std::lock_guard<std::mutex> lk(ix->mu);
         if (!ix->ready())
             fail(MSVS_ERR_NOT_READY, "the partitioned binary index has no centroids yet (train / set_centroids)");
     }
+    if (ix->partitioned() && nprobe < 1)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "nprobe must be >= 1");
     if (nx == 0 || k == 0)
-        return;
+        return false;
     if (!x || !ids || !dis)
         fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
-    hipStream_t stream = thread_stream();
+    return true;
+}
+
+/// The device core of an index search (checked arguments, device pointers): the image of the calling thread's device -- built on
+/// `stream`, with host synchronisation, if an add dropped it -- and the family's scan, enqueued on `stream`.
+static void bin_index_search_device(const msvs_bin_index_t * ix, const uint8_t * d_x, size_t nx, size_t k, size_t nprobe, const uint64_t * d_alive,
+                                    size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+{
     const std::shared_ptr<msvs_bin_index::Image> img = bin_image(ix, stream);
     if (ix->partitioned())
-        bin_ivf_search_image(*img, ix->nbytes, ix->metric, x, nx, k, nprobe, alive_bits, nbits, ids, dis, stream);
+        bin_ivf_search_image_device(*img, ix->nbytes, ix->metric, d_x, nx, k, nprobe, d_alive, nbits, d_ids, d_dis, stream);
     else
-        bin_search_rows(img->rows.p, img->labels.p, img->n, ix->nbytes, x, nx, k, ix->metric, alive_bits, nbits, ids, dis, stream);
+        bin_search_rows_device(img->rows.p, img->labels.p, img->n, ix->nbytes, d_x, nx, k, ix->metric, d_alive, nbits, d_ids, d_dis, stream);
+}
+
+// The C entries come in two forms that differ in their limit of k alone: the one-round form (k <= MSVS_MAX_K) and the rounds form
+// (k <= MSVS_MAX_K_ROUNDS).
+
+static int bin_index_search_entry(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, size_t k_max, const char * params,
+                                  const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return guarded([&] {
+        const size_t nprobe = parse_nprobe(params);
+        if (!bin_index_search_checks(ix, x, nx, k, k_max, nprobe, ids, dis))
+            return;
+        hipStream_t stream = thread_stream();
+        bin_search_host(x, nx, ix->nbytes, k, alive_bits, nbits, ids, dis, stream,
+                        [&](const uint8_t * d_x, const uint64_t * d_alive, int64_t * d_ids, float * d_dis) {
+                            bin_index_search_device(ix, d_x, nx, k, nprobe, d_alive, nbits, d_ids, d_dis, stream);
+                        });
+    });
+}
+
+static int bin_index_search_device_entry(const msvs_bin_index_t * ix, const uint8_t * d_x, size_t nx, size_t k, size_t k_max, size_t nprobe,
+                                         const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return guarded([&] {
+        if (!bin_index_search_checks(ix, d_x, nx, k, k_max, nprobe, d_ids, d_dis))
+            return;
+        bin_index_search_device(ix, d_x, nx, k, nprobe, d_alive_bits, nbits, d_ids, d_dis, reinterpret_cast<hipStream_t>(hip_stream));
+    });
 }
 
 extern "C" int msvs_bin_index_search(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, const uint64_t * alive_bits,
                                      size_t nbits, int64_t * ids, float * dis)
 {
-    return guarded([&] {
-        if (!ix)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
-        bin_index_search(ix, x, nx, k, 1, alive_bits, nbits, ids, dis);
-    });
+    return bin_index_search_entry(ix, x, nx, k, MSVS_MAX_K, nullptr, alive_bits, nbits, ids, dis);
 }
 
 extern "C" int msvs_bin_index_search_params(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, const char * params,
                                             const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
 {
-    return guarded([&] {
-        if (!ix)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
-        bin_index_search(ix, x, nx, k, parse_nprobe(params), alive_bits, nbits, ids, dis);
-    });
+    return bin_index_search_entry(ix, x, nx, k, MSVS_MAX_K, params, alive_bits, nbits, ids, dis);
+}
+
+extern "C" int msvs_bin_index_search_rounds(const msvs_bin_index_t * ix, const uint8_t * x, size_t nx, size_t k, const char * params,
+                                            const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return bin_index_search_entry(ix, x, nx, k, MSVS_MAX_K_ROUNDS, params, alive_bits, nbits, ids, dis);
+}
+
+extern "C" int msvs_bin_index_search_device(const msvs_bin_index_t * ix, const uint8_t * d_x, size_t nx, size_t k, size_t nprobe,
+                                            const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return bin_index_search_device_entry(ix, d_x, nx, k, MSVS_MAX_K, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
+}
+
+extern "C" int msvs_bin_index_search_rounds_device(const msvs_bin_index_t * ix, const uint8_t * d_x, size_t nx, size_t k, size_t nprobe,
+                                                   const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
+                                                   void * hip_stream)
+{
+    return bin_index_search_device_entry(ix, d_x, nx, k, MSVS_MAX_K_ROUNDS, nprobe, d_alive_bits, nbits, d_ids, d_dis, hip_stream);
 }
 
 extern "C" int msvs_bin_index_export(const msvs_bin_index_t * ix, uint8_t * centroids, int64_t * list_off, uint8_t * rows, int64_t * labels)

@@ -93,6 +93,38 @@ void launch_flat_scan(int metric, const FlatPlan & plan, ScanParams a, hipStream
 /// partial[nq][n_lists][k] -> final results.
 void launch_merge(int metric, MergeParams a, uint32_t nq, hipStream_t stream);
 
+/// One rank round of a search with k > MSVS_MAX_K (the coded indexes, coded_ivf.hpp; the binary searches, binary.hip): the round's
+/// merged keys, [nq][kr] ascending and KEY_NONE-padded (a merge's out_keys), go to columns [col0, col0 + kr) of the [nq][k] outputs as
+/// the one-round merge writes them (label or -1; the key's value, fl(1 - v) for cosine in every slot), and a full round's LAST key
+/// becomes the query's continuation key -- KEY_NONE when the round came back short: the query is finished, later rounds offer nothing
+/// and its tail stays padded.  (kr < MSVS_MAX_K: the last round.)
+template <int METRIC>
+static __global__ __launch_bounds__(MSVS_MAX_K) void coded_round_scatter_kernel(const uint64_t * keys, uint32_t kr, uint32_t k, uint32_t col0,
+                                                                               int cosine, int64_t * out_ids, float * out_dis, uint64_t * after)
+{
+    const uint32_t q = blockIdx.x, i = threadIdx.x;
+    const uint64_t key = i < kr ? keys[(size_t)q * kr + i] : KEY_NONE;
+    if (i < kr)
+    {
+        const size_t o = (size_t)q * k + col0 + i;
+        out_ids[o] = key == KEY_NONE ? -1 : (int64_t)(uint32_t)key;
+        const float v = key_value<METRIC>(key);
+        out_dis[o] = cosine ? __fsub_rn(1.0f, v) : v;
+    }
+    if (i == MSVS_MAX_K - 1)
+        after[q] = key;
+}
+
+inline void launch_round_scatter(int metric, const uint64_t * keys, size_t nq, size_t kr, size_t k, size_t col0, bool cosine, int64_t * out_ids,
+                                 float * out_dis, uint64_t * after, hipStream_t stream)
+{
+    with_int<M_IP, M_L2>(metric, [&](auto m) {
+        hipLaunchKernelGGL((coded_round_scatter_kernel<decltype(m)::value>), dim3((unsigned)nq), dim3(MSVS_MAX_K), 0, stream, keys, (uint32_t)kr,
+                           (uint32_t)k, (uint32_t)col0, cosine ? 1 : 0, out_ids, out_dis, after);
+    });
+    MSVS_HIP(hipGetLastError());
+}
+
 /// IVF list scan, one query per block, grid (seg_max, nprobe, nq).
 void launch_ivf_scan(int metric, ScanParams a, hipStream_t stream);
 

@@ -357,8 +357,11 @@ public:
             words.assign((nbits + 63) / 64 + 1, 0);
             memcpy(words.data(), filter->get_bitmap(), filter->byte_size());
         }
-        check(msvs_bin_index_search(ix, reinterpret_cast<const uint8_t *>(queries->getData()), (size_t)queries->numData(), (size_t)k,
-                                    filter ? words.data() : nullptr, nbits, res->getResultIndices(), res->getResultDistances()));
+        // (the rounds entry: the host asks the binary index for the same k as the float one -- LIMIT 1000, k + deleted rows; up to
+        // MSVS_MAX_K the same bits as msvs_bin_index_search)
+        check(msvs_bin_index_search_rounds(ix, reinterpret_cast<const uint8_t *>(queries->getData()), (size_t)queries->numData(), (size_t)k,
+                                           nullptr, filter ? words.data() : nullptr, nbits, res->getResultIndices(),
+                                           res->getResultDistances()));
         return res;
     }
     std::shared_ptr<Search::SearchResult> computeTopDistanceSubset(std::shared_ptr<Search::DataSet<bool>>,

@@ -3,7 +3,10 @@ nprobe 64.  Times whole search calls (host clock around calls that end in a stre
 indexes alternating) and, in a pass of its own, the kernel families by HIP events (msvs_profile_*).  The flat search is the
 yardstick; the partitioned one touches ~1/16 of the rows.  Writes one JSON file (default profiles/bin_ivf.json).
 
-    python -m tools.bench_bin_ivf [--rows N] [--nlist L] [--queries Q] [--nprobe P] [--k K] [--reps R] [--out FILE]
+    python -m tools.bench_bin_ivf [--rows N] [--nlist L] [--queries Q] [--nprobe P] [--k K] [--reps R] [--rounds-k K1,K2] [--out FILE]
+
+Also (--rounds-k, default 256,1024): the same two searches through search_rounds with each of those k, whole calls and kernel
+families, to price a search in rank rounds against one round.
 """
 import argparse
 import json
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--nprobe", type=int, default=64)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rounds-k", default="256,1024", help="k values of the rank-round comparison through search_rounds ('' skips it)")
     ap.add_argument("--out", default=os.path.join("profiles", "bin_ivf.json"))
     a = ap.parse_args()
     capi.set_device(0)
@@ -85,6 +89,28 @@ def main():
         d = POP8[q[b:b + 64, None, :] ^ centres[None, :, :]].sum(axis=2, dtype=np.int64)
         order = np.argsort(d * a.nlist + np.arange(a.nlist)[None, :], axis=1)[:, :min(a.nprobe, a.nlist)]
         probed += int(lens[order].sum())
+    # k beyond 256 in rank rounds against one round on the same data: whole calls, alternating, and the scan / merge families of
+    # one call each by HIP events (the expectation: about k / 256 times the scan, one plan)
+    rounds = {}
+    if a.rounds_k:
+        ks = [int(v) for v in a.rounds_k.split(",")]
+        calls = {(name, k): [] for name in ("ivf", "flat") for k in ks}
+        for rep in range(1 + a.reps):  # (the first pass warms up every shape)
+            for k in ks:
+                for name, ix, p in (("ivf", ivf, params), ("flat", flat, None)):
+                    t0 = time.perf_counter()
+                    ix.search_rounds(q, k, params=p)
+                    if rep:
+                        calls[(name, k)].append(time.perf_counter() - t0)
+        capi.profile_enable(True)
+        for k in ks:
+            for name, ix, p in (("ivf", ivf, params), ("flat", flat, None)):
+                capi.profile_reset()
+                ix.search_rounds(q, k, params=p)
+                rounds["%s_k%d" % (name, k)] = {
+                    "call_ms_median": 1e3 * float(np.median(calls[(name, k)])), "call_ms_all": [1e3 * t for t in calls[(name, k)]],
+                    "kernel_ms_hip_events": {n: dict(zip(("calls", "ms"), capi.profile_get(n))) for n in names}}
+        capi.profile_enable(False)
     recall = float(np.mean([len(set(ii[i]) & set(fi[i])) / a.k for i in range(a.queries)]))
     ivf_ms, flat_ms = 1e3 * float(np.median(t_ivf)), 1e3 * float(np.median(t_flat))
     scan_ms = kern["bin_ivf_scan"]["ms"]
@@ -100,6 +126,7 @@ def main():
         "flat_scan_bytes_per_s": a.queries * a.rows * a.nbytes / (kern["bin_scan"]["ms"] * 1e-3) if kern["bin_scan"]["ms"] else None,
         "longest_list": int(lens.max()), "empty_lists": int((lens == 0).sum()),
         "recall_at_k_vs_flat": recall, "first_search_with_image_build_s": t_build, "version": capi.version(),
+        "rank_rounds": rounds,
     }
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
