@@ -704,8 +704,14 @@ MSVS_API int msvs_merge_topk_device_strided(const int64_t * d_ids, size_t ids_pa
  * kv, kt, topk <= MSVS_MAX_K_ROUNDS (lists of at most 256 rows: every entry compares itself with every other; longer ones: a hash
  * table of the text labels and a sort of the fused rows, one workgroup per query either way).  fusion_type: 0 = RRF (score = sum of 1 / (fusion_k + rank), fusion_k 0 = 60), 1 = RSF (fusion_weight *
  * normalised text score + (1 - fusion_weight) * normalised vector score, vector_scan_direction -1: larger is better).
- * Outputs [nq][topk]: fused scores descending, ties by ascending label; label -1 / score 0 past d_n_out[q] rows.  Same
- * arithmetic, same order, same bits as msvs_host_hybrid_search_batch (include/msvs_host.h).  Stream-ordered, no host sync. */
+ * Outputs [nq][topk]: fused scores descending, ties by ascending label; label -1 / score +0 past d_n_out[q] rows.  Same
+ * arithmetic, same order, same bits as msvs_host_hybrid_search_batch (include/msvs_host.h).  Stream-ordered, no host sync.
+ * NaN fused scores: RSF normalises with (s - min) / (max - min), so a +inf distance at the head of an otherwise finite list
+ * (an overflowing row under inner product) or a NaN handed in gives a NaN fused score.  A row whose fused score is NaN ranks
+ * behind every row whose score is not NaN; NaN rows among themselves are ordered by ascending label; they count in d_n_out
+ * like any other row.
+ * Precondition: each list holds distinct labels (the row ids of one search).  For a list with a repeated label the result is
+ * unspecified, but every access stays in bounds. */
 MSVS_API int msvs_hybrid_fuse_device(int fusion_type, const float * d_vec_dis, const int64_t * d_vec_ids, size_t kv,
                                      const float * d_txt_scores, const int64_t * d_txt_ids, size_t kt, size_t nq,
                                      uint64_t fusion_k, float fusion_weight, int vector_scan_direction, size_t topk,

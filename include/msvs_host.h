@@ -79,7 +79,11 @@ MSVS_HOST_API size_t msvs_host_hybrid_search(int fusion_type, const float * vec_
 
 /* The same fusion for a batch of queries straight from the device searches' output arrays (one part): query q's vector rows are
  * vec_dis / vec_ids[q * kv ...] (an id < 0 ends the list, like the host's `> -1` unpack, MergeTreeVSManager.cpp:1110-1140), its text
- * rows txt_scores / txt_ids[q * kt ...]; out_scores / out_labels[q * topk ...], n_out[q] rows each. */
+ * rows txt_scores / txt_ids[q * kt ...]; out_scores / out_labels[q * topk ...], n_out[q] rows each (the slots past them are left
+ * as they were).  Order: descending fused score, ties by ascending label.  A row whose fused score is NaN (RSF: inf / inf for a
+ * +inf distance at the head of a finite list) ranks behind every row whose score is not NaN, NaN rows among themselves by ascending
+ * label, and they count in n_out like any other row: the order of msvs_hybrid_fuse_device (include/msvs.h).  The map-based
+ * msvs_host_hybrid_search above keeps the reference's multimap, whose order is undefined once a score is NaN. */
 MSVS_HOST_API int msvs_host_hybrid_search_batch(int fusion_type, const float * vec_dis, const int64_t * vec_ids, size_t kv,
                                                 const float * txt_scores, const int64_t * txt_ids, size_t kt, size_t nq,
                                                 uint64_t fusion_k, float fusion_weight, int vector_scan_direction, size_t topk,

@@ -5,14 +5,16 @@
 // MergeTreeHybridSearchManager::hybridSearch applies them -- the arithmetic and order of msvs_host_hybrid_search_batch
 // (host/msvs_host.cpp), which tests hold against the map-based mirror: a label's contributions are applied in list order
 // (RRF: 0 + 1/(k + rank_vector), then + 1/(k + rank_text); RSF: the text list ASSIGNS weight * norm, the vector list adds),
-// output = descending fused score, ties by ascending label.  A hybrid batch of 64 queries spent 0.6 of its 2.7 ms in that
-// host loop behind a stream synchronisation and four device-to-host copies; here the lists never leave the device and only
-// the top-k rows are read back.
+// output = descending fused score, ties by ascending label; a NaN fused score (RSF: a +inf distance at the head of a finite list
+// normalises to inf / inf) ranks behind every other score, NaN scores among themselves by ascending label.
+// A hybrid batch of 64 queries spent 0.6 of its 2.7 ms in that host loop behind a stream synchronisation and four
+// device-to-host copies; here the lists never leave the device and only the top-k rows are read back.
 //
 // One workgroup per query, thread i = entry i of (vector list | text list), both <= 256 long.  Every entry looks its label
 // up in the other list (LDS, <= 256 compares); an entry is the OWNER of its label when it is the vector entry, or a text
 // entry without a vector partner; owners rank themselves against each other by (score desc, label asc) and write themselves
-// to their output slot.  The lists hold distinct labels each (row ids of one search).
+// to their output slot.  The lists hold distinct labels each (row ids of one search: the precondition of include/msvs.h; with a
+// repeated label two owners can share a rank or a hash chain a partner, and every access stays in bounds).
 //
 // Longer lists (up to FUSE_LONG_MAX = MSVS_MAX_K_ROUNDS rows each: a hybrid search asks both sides for 3 x LIMIT candidates) take
 // hybrid_fuse_long_kernel: the same arithmetic in the same order, but the all-pairs compares (4096 x 4096) give way to a hash table
@@ -64,12 +66,35 @@ __device__ __forceinline__ float fuse_norm(const float s, const float first, con
     return __fdiv_rn(__fsub_rn(s, mn), __fsub_rn(mx, mn));
 }
 
+/// The rank order of the output -- descending fused score, ties by ascending label, NaN scores behind every other score and by
+/// ascending label among themselves -- compares integer keys, so that a NaN costs the ranking loops nothing.  fuse_key: a score as
+/// an unsigned key that ascends with the score; 0 is left to the entries that do not rank (empty slots, non-owners), NaN is 1, every
+/// other score the sign-flipped bit pattern (-inf, the least: 0x007FFFFF), which fuse_key_score turns back into the score (a NaN
+/// comes back as the canonical one).  fuse_order_key: the key as the order compares it: -0.0 (0x7FFFFFFF) ties with +0.0.
+constexpr uint32_t FUSE_KEY_NAN = 1u, FUSE_KEY_NEG_ZERO = 0x7FFFFFFFu;
+
+__device__ __forceinline__ uint32_t fuse_key(const float s)
+{
+    if (s != s)
+        return FUSE_KEY_NAN;
+    const uint32_t b = __float_as_uint(s);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ float fuse_key_score(const uint32_t k)
+{
+    if (k == FUSE_KEY_NAN)
+        return __uint_as_float(0x7FC00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+__device__ __forceinline__ uint32_t fuse_order_key(const uint32_t k) { return k + (k == FUSE_KEY_NEG_ZERO ? 1u : 0u); }
+
 static __global__ __launch_bounds__(2 * FUSE_MAX) void hybrid_fuse_kernel(const FuseParams p)
 {
     __shared__ uint64_t s_label[2 * FUSE_MAX];
     __shared__ float s_value[2 * FUSE_MAX];
-    __shared__ float s_score[2 * FUSE_MAX]; // fused score of the owners, NaN-free; non-owners: marked by s_owner = 0
-    __shared__ uint8_t s_owner[2 * FUSE_MAX];
+    __shared__ uint32_t s_key[2 * FUSE_MAX]; // fuse_order_key of the owners' fused scores (>= 1); non-owners: 0
     __shared__ uint32_t s_n[3]; // nv, nt, owners
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
     const int64_t * vi = p.vec_ids + (size_t)q * p.kv, * ti = p.txt_ids + (size_t)q * p.kt;
@@ -139,18 +164,18 @@ static __global__ __launch_bounds__(2 * FUSE_MAX) void hybrid_fuse_kernel(const 
             score = p.rsf ? value : __fadd_rn(0.0f, value);
         }
     }
-    s_owner[tid] = owner ? 1 : 0;
-    s_score[tid] = score;
+    const uint32_t key = owner ? fuse_order_key(fuse_key(score)) : 0u;
+    s_key[tid] = key;
     __syncthreads();
     if (owner)
     {
+        // the owners before this one: a greater key (a better score; NaN has the least key of the owners), or an equal one with a
+        // smaller label; a non-owner's key 0 is neither
         uint32_t rank = 0;
         for (uint32_t j = 0; j < 2 * FUSE_MAX; j++)
         {
-            if (!s_owner[j])
-                continue;
-            const float sj = s_score[j];
-            rank += (sj > score || (sj == score && s_label[j] < label)) ? 1u : 0u;
+            const uint32_t kj = s_key[j];
+            rank += (kj > key || (kj == key && s_label[j] < label)) ? 1u : 0u;
         }
         atomicAdd(&s_n[2], 1u);
         if (rank < p.topk)
@@ -170,12 +195,12 @@ static __global__ __launch_bounds__(2 * FUSE_MAX) void hybrid_fuse_kernel(const 
     }
 }
 
-/// The rank order of the output: descending fused score, ties by ascending label; an empty slot sorts behind every entry.
-__device__ __forceinline__ bool fuse_before(const uint64_t la, const float sa, const uint64_t lb, const float sb)
+/// The rank order over (label, fuse_key) entries: an empty slot (key 0, FUSE_NO_LABEL) sorts behind every entry, two of them are
+/// equal.  A strict total order over distinct labels, NaN included (the bitonic network needs one).
+__device__ __forceinline__ bool fuse_before(const uint64_t la, const uint32_t ka, const uint64_t lb, const uint32_t kb)
 {
-    if (la == FUSE_NO_LABEL || lb == FUSE_NO_LABEL)
-        return lb == FUSE_NO_LABEL && la != FUSE_NO_LABEL;
-    return sa > sb || (sa == sb && la < lb);
+    const uint32_t a = fuse_order_key(ka), b = fuse_order_key(kb);
+    return a > b || (a == b && la < lb);
 }
 
 /// Lists of up to FUSE_LONG_MAX rows: one workgroup per query, both lists in LDS (entry i of the vector list at i, of the text list at
@@ -183,7 +208,7 @@ __device__ __forceinline__ bool fuse_before(const uint64_t la, const float sa, c
 ///   1. list lengths (the first id < 0 ends a list) by an LDS minimum; labels and per-list values as in hybrid_fuse_kernel;
 ///   2. the text labels go into an open-addressing hash table (2 P slots: at most half full); every vector entry looks its label up,
 ///      adds its partner's value in the prescribed order and takes the partner out of the ranking;
-///   3. the owners (label, fused score) are sorted in place by fuse_before (bitonic, 2 P entries); the first topk leave.
+///   3. the owners (label, fuse_key of the fused score) are sorted in place by fuse_before (bitonic, 2 P entries); the first topk leave.
 /// Dynamic LDS sized by P (fuse_long_lds_bytes: 33 P bytes -- 16.5 KB for the 300-row lists of a LIMIT 100 hybrid search, 132 of the
 /// 160 KB at 4096 rows) and min(P, 1024) threads, so that short lists share a CU.
 inline size_t fuse_long_lds_bytes(uint32_t P) { return (size_t)P * (2 * 8 + 2 * 4 + 2 * 4 + 1); }
@@ -192,8 +217,8 @@ static __global__ __launch_bounds__(FUSE_LONG_THREADS) void hybrid_fuse_long_ker
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char fuse_smem[];
     uint64_t * const s_label = reinterpret_cast<uint64_t *>(fuse_smem);       // [2 P]
-    float * const s_value = reinterpret_cast<float *>(s_label + 2 * P);       // [2 P]
-    uint32_t * const s_tab = reinterpret_cast<uint32_t *>(s_value + 2 * P);   // [2 P] text entry + 1 (0: empty)
+    uint32_t * const s_bits = reinterpret_cast<uint32_t *>(s_label + 2 * P);  // [2 P] a value's float bits; from the fused scores on: fuse_key
+    uint32_t * const s_tab = s_bits + 2 * P;                                    // [2 P] text entry + 1 (0: empty)
     uint8_t * const s_taken = reinterpret_cast<uint8_t *>(s_tab + 2 * P);     // [P] text entry has a vector partner
     __shared__ uint32_t s_n[3];                                               // nv, nt, owners
     const uint32_t q = blockIdx.x, tid = threadIdx.x, nthreads = blockDim.x;
@@ -247,9 +272,9 @@ static __global__ __launch_bounds__(FUSE_LONG_THREADS) void hybrid_fuse_long_ker
                 h = (h + 1) & tmask;
         }
         s_label[i] = lv;
-        s_value[i] = xv;
+        s_bits[i] = __float_as_uint(xv); // (no entry: 0, the key of an empty slot)
         s_label[P + i] = lt;
-        s_value[P + i] = xt;
+        s_bits[P + i] = __float_as_uint(xt);
     }
     __syncthreads();
     // the vector entries: RRF (0 + vector) + text; RSF: text assigns, vector adds
@@ -257,7 +282,7 @@ static __global__ __launch_bounds__(FUSE_LONG_THREADS) void hybrid_fuse_long_ker
     for (uint32_t i = tid; i < nv; i += nthreads)
     {
         const uint64_t label = s_label[i];
-        const float value = s_value[i];
+        const float value = __uint_as_float(s_bits[i]);
         int partner = -1;
         uint32_t h = (uint32_t)((label * 0x9E3779B97F4A7C15ull) >> 40) & tmask;
         for (uint32_t e = s_tab[h]; e != 0u; h = (h + 1) & tmask, e = s_tab[h])
@@ -268,29 +293,33 @@ static __global__ __launch_bounds__(FUSE_LONG_THREADS) void hybrid_fuse_long_ker
             }
         float score;
         if (p.rsf)
-            score = partner >= 0 ? __fadd_rn(s_value[P + partner], value) : __fadd_rn(0.0f, value);
+            score = partner >= 0 ? __fadd_rn(__uint_as_float(s_bits[P + partner]), value) : __fadd_rn(0.0f, value);
         else
-            score = partner >= 0 ? __fadd_rn(__fadd_rn(0.0f, value), s_value[P + partner]) : __fadd_rn(0.0f, value);
+            score = partner >= 0 ? __fadd_rn(__fadd_rn(0.0f, value), __uint_as_float(s_bits[P + partner])) : __fadd_rn(0.0f, value);
         if (partner >= 0)
             s_taken[partner] = 1;
-        s_value[i] = score; // (the vector half: nobody reads it in this phase)
+        s_bits[i] = fuse_key(score); // (the vector half: nobody reads it in this phase)
         owners++;
     }
     __syncthreads();
     for (uint32_t i = tid; i < nt; i += nthreads)
     {
         if (s_taken[i])
+        {
             s_label[P + i] = FUSE_NO_LABEL;
+            s_bits[P + i] = 0;
+        }
         else
         {
-            s_value[P + i] = p.rsf ? s_value[P + i] : __fadd_rn(0.0f, s_value[P + i]);
+            const float value = __uint_as_float(s_bits[P + i]);
+            s_bits[P + i] = fuse_key(p.rsf ? value : __fadd_rn(0.0f, value));
             owners++;
         }
     }
     if (owners)
         atomicAdd(&s_n[2], owners);
     __syncthreads();
-    // bitonic sort of the 2 P (label, score) entries, best first
+    // bitonic sort of the 2 P (label, key) entries, best first
     for (uint32_t k2 = 2; k2 <= N; k2 <<= 1)
         for (uint32_t j = k2 >> 1; j > 0; j >>= 1)
         {
@@ -299,13 +328,13 @@ static __global__ __launch_bounds__(FUSE_LONG_THREADS) void hybrid_fuse_long_ker
                 const uint32_t a = 2 * j * (t / j) + (t & (j - 1)), b = a + j;
                 const bool up = (a & k2) == 0;
                 const uint64_t la = s_label[a], lb = s_label[b];
-                const float sa = s_value[a], sb = s_value[b];
-                if (up ? fuse_before(lb, sb, la, sa) : fuse_before(la, sa, lb, sb))
+                const uint32_t ka = s_bits[a], kb = s_bits[b];
+                if (up ? fuse_before(lb, kb, la, ka) : fuse_before(la, ka, lb, kb))
                 {
                     s_label[a] = lb;
                     s_label[b] = la;
-                    s_value[a] = sb;
-                    s_value[b] = sa;
+                    s_bits[a] = kb;
+                    s_bits[b] = ka;
                 }
             }
             __syncthreads();
@@ -315,7 +344,7 @@ static __global__ __launch_bounds__(FUSE_LONG_THREADS) void hybrid_fuse_long_ker
         p.n_out[q] = n;
     for (uint32_t r = tid; r < p.topk; r += nthreads)
     {
-        p.out_scores[(size_t)q * p.topk + r] = r < n ? s_value[r] : 0.f;
+        p.out_scores[(size_t)q * p.topk + r] = r < n ? fuse_key_score(s_bits[r]) : 0.f;
         p.out_labels[(size_t)q * p.topk + r] = r < n ? (int64_t)s_label[r] : -1;
     }
 }

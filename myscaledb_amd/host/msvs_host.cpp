@@ -805,7 +805,11 @@ extern "C" int msvs_host_hybrid_search_batch(int fusion_type, const float * vec_
             f.push_back(Fused{c[i].label, sc});
             i = j;
         }
-        std::stable_sort(f.begin(), f.end(), [](const Fused & a, const Fused & b) { return a.score > b.score; });
+        // (a NaN score -- RSF: inf / inf -- ranks behind every other score, NaN scores among themselves by ascending label)
+        std::stable_sort(f.begin(), f.end(), [](const Fused & a, const Fused & b) {
+            const bool na = a.score != a.score, nb = b.score != b.score;
+            return na || nb ? !na && nb : a.score > b.score;
+        });
         const size_t n = std::min(f.size(), topk);
         for (size_t i = 0; i < n; i++)
         {

@@ -712,6 +712,10 @@ static void normalized(const float *s, size_t n, float *out)
 static int fuse_score_cmp(const void *a, const void *b)
 {
     const fuse_t *x = (const fuse_t *)a, *y = (const fuse_t *)b;
+    /* a NaN score (RSF: inf / inf) ranks behind every other score; NaN scores among themselves by key.  (The reference's
+     * multimap<float, greater> is undefined there; this is the order every implementation of the project keeps.) */
+    const int nx = x->score != x->score, ny = y->score != y->score;
+    if (nx != ny) return nx ? 1 : -1;
     if (x->score > y->score) return -1;
     if (x->score < y->score) return 1;
     return fuse_key_cmp(a, b);
