@@ -6,7 +6,6 @@
 #include <mutex>
 
 #include "bm25_kernels.hpp"
-#include "bm25p_kernels.hpp"
 #include "bm25r_kernels.hpp"
 #include "bm25l_kernels.hpp"
 #include "device_ops.hpp"
@@ -137,7 +136,7 @@ PinnedRing & pinned_ring(hipStream_t stream)
     return rings[{dev, stream}];
 }
 
-/// Resident workgroups of the wave scorer per CU: 8 B of LDS per document (+ 1 per text column) and wavefront.
+/// Resident workgroups of bm25w_kernel per CU: 8 B of LDS per document (+ 1 per text column) and wavefront.
 uint32_t bw_blocks_per_cu(bool one_field)
 {
     const size_t per_block = (size_t)BW_WAVES * BW_DOCS * (8 + (one_field ? 1 : 4)) + 4096;
@@ -338,6 +337,61 @@ static uint32_t bm25_sub_docs_for(double rho)
 /// Resident workgroups of bm25r_kernel per CU by its LDS (8192 hash slots: 38 KB per workgroup; 16384: 46 KB).
 uint32_t br_blocks_per_cu(bool big_slots) { return big_slots ? 3u : 4u; }
 
+/// What scores a chunk of queries, decided once per chunk (bm25_chunk_device).
+struct Bm25Scorer
+{
+    enum Kind
+    {
+        DENSE,  // bm25w_kernel: the dense accumulator, batches of frequent terms
+        RECORD, // bm25r_kernel: windows of score-ready records
+        LEAN    // bm25l_kernel: its lean form, no query of the chunk has more than BL_NT terms
+    } kind;
+    bool big_slots;      // RECORD: 16384 hash slots instead of 8192 (option bm25_slots)
+    bool one_field;      // DENSE: one text column
+    const uint2 * rec;   // RECORD / LEAN: the posting set's records
+    uint32_t max_blocks; // resident workgroups of the kernel on the device: no launch is wider
+};
+
+/// One scorer launch over the items of `w`: its item table, else (chunk, query) items for every query.  Rs: the top-k registers
+/// per lane the site needs -- MODE and Rs are the kernel instantiations.  `after`: the continuation keys of BM25_TOPK_AFTER.
+template <int MODE, int... Rs>
+void bm25_launch_scorer(const Bm25Scorer & sc, const Bm25WParams & w, const uint64_t * after, hipStream_t stream)
+{
+    const size_t n_items = w.items ? w.n_items_tab : (size_t)w.n_items_c * w.p.nq;
+    const int r = r_for_k(w.p.kk);
+    if (sc.kind == Bm25Scorer::DENSE)
+    {
+        if constexpr (MODE == BM25_TOPK_AFTER)
+            fail(MSVS_ERR_UNSUPPORTED_K, "the rank-window rounds need the record scorers");
+        else
+        {
+            const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div(n_items, (size_t)BW_WAVES), sc.max_blocks)));
+            with_int<1, 4>(sc.one_field ? 1 : 4, [&](auto nf) {
+                with_int<Rs...>(r, [&](auto rr) {
+                    constexpr int R = decltype(rr)::value, NF = decltype(nf)::value;
+                    hipLaunchKernelGGL((bm25w_kernel<MODE, R, NF>), grid, dim3(64 * BW_WAVES), 0, stream, w);
+                });
+            });
+        }
+    }
+    else
+    {
+        const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div(n_items, (size_t)BP_WAVES), sc.max_blocks)));
+        Bm25RParams rp{w, sc.rec};
+        rp.after = after;
+        with_int<Rs...>(r, [&](auto rr) {
+            constexpr int R = decltype(rr)::value;
+            if (sc.kind == Bm25Scorer::LEAN)
+                hipLaunchKernelGGL((bm25l_kernel<MODE, R, 8192>), grid, dim3(64 * BP_WAVES), 0, stream, rp);
+            else if (sc.big_slots)
+                hipLaunchKernelGGL((bm25r_kernel<MODE, R, 16384>), grid, dim3(64 * BP_WAVES), 0, stream, rp);
+            else
+                hipLaunchKernelGGL((bm25r_kernel<MODE, R, 8192>), grid, dim3(64 * BP_WAVES), 0, stream, rp);
+        });
+    }
+    MSVS_HIP(hipGetLastError());
+}
+
 /// One pass over a chunk of the batch.  Host inputs (term ids, df, statistics: a few numbers per query -- the weights
 /// need libm's logf to match tantivy), device work on `stream`, results left in d_ids / d_scores ([nq][k], id -1 = no
 /// hit).  d_alive: the effective filter, already on the device.
@@ -352,17 +406,15 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     // per-chunk lists are kl wide either way
     const bool rounds = k > MSVS_MAX_K;
     const size_t kl = rounds ? (size_t)MSVS_MAX_K : k;
-    // two kernels share this flow: the wave-private streaming scorer (default) and the block scorer it replaced (knob)
-    const bool wave = options().bm25_wave != 0;
-    // ... and, for batches of sparse terms, the posting-as-unit scorer (bm25p_kernels.hpp).  Its sub-range size follows the
-    // densest query of the batch (postings of all its terms per document): that query's windows (<= BP_CAP postings) are
-    // single sub-ranges, sparser queries take several per window.  Frequent terms (over 1/8 posting per document) keep the dense accumulator,
-    // which they fill.
-    bool posting = wave && options().bm25_posting != 0;
+    // The scorer of the chunk.  Batches of sparse terms take the record scorers (bm25r_kernels.hpp); their sub-range size follows
+    // the densest query of the batch (postings of all its terms per document): that query's windows (<= BP_CAP postings) are
+    // single sub-ranges, sparser queries take several per window.  Frequent terms (over 1/8 posting per document) keep the dense
+    // accumulator (bm25w_kernel), which they fill.  (d_rec is null with option bm25_posting = 0: always the dense accumulator.)
+    bool records = d_rec != nullptr;
     static thread_local std::vector<uint64_t> q_postings;
     uint64_t all_postings = 0;
-    uint32_t sub_docs = BW_DOCS;
-    if (posting)
+    uint32_t sub_docs = BW_DOCS; // documents per sub-range
+    if (records)
     {
         double rho = 0;
         q_postings.assign(nq, 0);
@@ -381,7 +433,7 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
         }
         // 2: always (tests: every sub-range of a frequent term is split); the rounds run on the record scorers whatever the density
         if (rho > 0.125 && options().bm25_posting != 2 && !rounds)
-            posting = false;
+            records = false;
         else
         {
             // the densest query's windows are single sub-ranges filled to ~3/4 of the cap; sparser queries take several
@@ -390,33 +442,36 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
                 sub_docs = (uint32_t)options().bm25_sub_docs;
         }
     }
-    const uint32_t docs_per_block = posting ? sub_docs : (wave ? BW_DOCS : BM25_DOCS);
-    const uint32_t n_blocks = (uint32_t)std::max<size_t>(1, ceil_div(ps.num_docs, (size_t)docs_per_block));
-    // wave scorer: an item = spi consecutive sub-ranges of one query; enough items for ~4 per resident wavefront
-    // (posting scorer: at least 32 chunks whenever there are 32 sub-ranges -- the sample / cut / emit flow below needs them, and a batch
-    // whose densest query is sparse (8192-document sub-ranges, 1221 of them over 10M documents) must not fall off it: measured 2.2 ms
-    // of per-chunk lists for a 1024-query batch against 0.95 ms)
-    const uint32_t spi = (uint32_t)std::min<size_t>(std::min<size_t>(64, posting ? std::max<size_t>(1, n_blocks / 32) : 64),
-                                                    std::max<size_t>(1, (size_t)n_blocks * nq / 8192));
-    const uint32_t n_chunks = wave ? (uint32_t)ceil_div((size_t)n_blocks, (size_t)spi) : n_blocks;
-    // long corpora: sample -> cut -> emit -> select (+ exact fallback); short ones: per-chunk top-k lists, one merge
-    // (the rounds are exact by construction: the cut and the candidate buffer of the emit flow were sized for k <= 256)
-    const bool emit = n_chunks >= (wave ? 32u : 64u) && ps.num_docs >= 500000 && options().bm25_emit != 0 && !rounds;
-    const uint32_t cand_cap = options().bm25_cand_cap > 0 ? (uint32_t)std::min<double>(options().bm25_cand_cap, BM25_CAND_CAP) : BM25_CAND_CAP;
-    unsigned long long * stat_fail = bm25_fail_counter();
-    // posting scorer, EMIT pass: items of about equal postings (a uniform spread of a term over the documents assumed), twice
-    // as many as resident wavefronts -- the launch walks them with a static stride
-    const uint32_t cus = bm25_cu_count();
-    // the record scorer (bm25r_kernel) when the posting set has its score-ready records for this call's statistics
-    const bool recs = posting && d_rec != nullptr;
-    if (rounds && !recs)
-        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds %d: the rank-window rounds need the record scorers", k, MSVS_MAX_K);
-    const bool big_slots = options().bm25_slots >= 16384;
-    // ... and its lean form (bm25l_kernels.hpp) when no query of the chunk has more than four terms
-    bool lean = recs && options().bm25_lean != 0;
+    // ... and the lean form of the record scorer (bm25l_kernels.hpp) when no query of the chunk has more than four terms
+    bool lean = records && options().bm25_lean != 0;
     for (size_t q = 0; q < nq && lean; q++)
         lean = qoff[q + 1] < qoff[q] || qoff[q + 1] - qoff[q] <= BL_NT;
-    const uint32_t bpc = lean ? BL_WAVES_PER_SIMD : recs ? br_blocks_per_cu(big_slots) : BP_BLOCKS_PER_CU; // resident workgroups per CU of the posting scorer
+    const uint32_t cus = bm25_cu_count();
+    Bm25Scorer sc{};
+    sc.kind = !records ? Bm25Scorer::DENSE : lean ? Bm25Scorer::LEAN : Bm25Scorer::RECORD;
+    sc.big_slots = options().bm25_slots >= 16384;
+    sc.one_field = ps.num_fields == 1;
+    sc.rec = d_rec;
+    if (rounds && !records)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds %d: the rank-window rounds need the record scorers", k, MSVS_MAX_K);
+    // resident workgroups per CU of the record scorers: their launches and their item tables are sized by it
+    const uint32_t bpc = sc.kind == Bm25Scorer::LEAN ? BL_WAVES_PER_SIMD : br_blocks_per_cu(sc.big_slots);
+    sc.max_blocks = cus * (records ? bpc : bw_blocks_per_cu(sc.one_field));
+    const uint32_t n_blocks = (uint32_t)std::max<size_t>(1, ceil_div(ps.num_docs, (size_t)sub_docs));
+    // an item = spi consecutive sub-ranges of one query; enough items for ~4 per resident wavefront
+    // (record scorers: at least 32 chunks whenever there are 32 sub-ranges -- the sample / cut / emit flow below needs them, and a batch
+    // whose densest query is sparse (8192-document sub-ranges, 1221 of them over 10M documents) must not fall off it: measured 2.2 ms
+    // of per-chunk lists for a 1024-query batch against 0.95 ms)
+    const uint32_t spi = (uint32_t)std::min<size_t>(std::min<size_t>(64, records ? std::max<size_t>(1, n_blocks / 32) : 64),
+                                                    std::max<size_t>(1, (size_t)n_blocks * nq / 8192));
+    const uint32_t n_chunks = (uint32_t)ceil_div((size_t)n_blocks, (size_t)spi);
+    // long corpora: sample -> cut -> emit -> select (+ exact fallback); short ones: per-chunk top-k lists, one merge
+    // (the rounds are exact by construction: the cut and the candidate buffer of the emit flow were sized for k <= 256)
+    const bool emit = n_chunks >= 32u && ps.num_docs >= 500000 && options().bm25_emit != 0 && !rounds;
+    const uint32_t cand_cap = options().bm25_cand_cap > 0 ? (uint32_t)std::min<double>(options().bm25_cand_cap, BM25_CAND_CAP) : BM25_CAND_CAP;
+    unsigned long long * stat_fail = bm25_fail_counter();
+    // record scorers, EMIT pass: items of about equal postings (a uniform spread of a term over the documents assumed), twice
+    // as many as resident wavefronts -- the launch walks them with a static stride
     // items per resident wavefront of the EMIT pass: an item costs ~7 us of dependent loads before its first window, a wavefront with
     // one long item cannot even out the others' tails -- measured: 1 item at 64 queries (0.163 -> 0.146 ms), 2 at 256, 4 at 1024
     // (0.749 -> 0.698 ms): ~4600 postings per item, between 1 and 4 items
@@ -430,20 +485,18 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
         return (uint32_t)std::min<double>(n_blocks, std::max(1.0, std::floor(per_item * n_blocks / (double)q_postings[q])));
     };
     size_t n_items_e = 0;
-    if (posting && emit)
+    if (records && emit)
         for (size_t q = 0; q < nq; q++)
             n_items_e += ceil_div((size_t)n_blocks, (size_t)spi_of(q));
-    // the sample (every 16th chunk) walks a FINER partition in the wave scorer: with the emit pass's chunks (38 sub-ranges at
-    // 64 queries over 10M documents) it was 576 items of 112 us each on 2048 resident wavefronts = one item's duration
-    // (posting scorer: no finer than one item per resident wavefront -- a sample item costs ~30 us whatever it holds, and 5248
+    // the sample (every 16th chunk) walks a FINER partition: with the emit pass's chunks (38 sub-ranges at 64 queries over 10M
+    // documents) it was 576 items of 112 us each on 2048 resident wavefronts = one item's duration
+    // (record scorers: no finer than one item per resident wavefront -- a sample item costs ~30 us whatever it holds, and 5248
     // items on 4096 wavefront slots were two rounds of them)
-    const uint32_t spi_s = wave && options().bm25_fine_sample != 0
-        ? std::max<uint32_t>(std::max<uint32_t>(1, spi / 8),
-                             posting ? (uint32_t)ceil_div((size_t)n_blocks * nq, (size_t)BM25_SAMPLE_STEP * cus * (bpc * BP_WAVES)) : 1u)
-        : spi;
-    const uint32_t n_chunks_s = wave ? (uint32_t)ceil_div((size_t)n_blocks, (size_t)spi_s) : n_blocks;
+    const uint32_t spi_s = std::max<uint32_t>(std::max<uint32_t>(1, spi / 8),
+                                              records ? (uint32_t)ceil_div((size_t)n_blocks * nq, (size_t)BM25_SAMPLE_STEP * cus * (bpc * BP_WAVES)) : 1u);
+    const uint32_t n_chunks_s = (uint32_t)ceil_div((size_t)n_blocks, (size_t)spi_s);
     uint32_t n_sb = (uint32_t)ceil_div((size_t)n_chunks_s, (size_t)BM25_SAMPLE_STEP);
-    // posting scorer: the sample's items hold equal postings too (every 16th chunk of a PER-QUERY chunking: one window each,
+    // record scorers: the sample's items hold equal postings too (every 16th chunk of a PER-QUERY chunking: one window each,
     // one item per resident wavefront at most) -- with the same chunks for every query the launch lasted as long as the densest
     // query's items, 50 us
     const double per_item_s = std::max(384.0, (double)all_postings / BM25_SAMPLE_STEP / (cus * (double)(bpc * BP_WAVES)));
@@ -456,7 +509,7 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
         return (uint32_t)std::min<double>(spi_s_cap, std::max(1.0, std::floor(per_item_s * n_blocks / (double)q_postings[q])));
     };
     size_t n_items_s = 0;
-    if (posting && emit)
+    if (records && emit)
     {
         uint32_t lists_s = 1;
         for (size_t q = 0; q < nq; q++)
@@ -557,13 +610,10 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     uint64_t * partial = scr.take<uint64_t>(nq * (size_t)n_chunks * kl);
     uint64_t * round_keys = rounds ? scr.take<uint64_t>(nq * kl) : nullptr; // a round's merged keys ...
     uint64_t * d_after = rounds ? scr.take<uint64_t>(nq) : nullptr;         // ... and the continuation key of every query
-    bool after_mode = false; // launch_topk: the BM25_TOPK_AFTER form of the record scorers
     memcpy(blob_pinned, blob, blob_bytes);
-    // the tables go to the device with the bounds launch (bm25_bounds8_kernel) when there is one, else with a copy kernel of their own;
-    // the first scorer launch behind them tells the host that the pinned slot is free again (Bm25Params::slot_done)
-    const bool tables_ride = n_flat != 0 && options().bm25_bounds8 != 0 && options().bm25_tables_ride != 0;
-    if (!tables_ride)
-        fetch_from_pinned(d_blob, blob_pinned, blob_bytes, stream);
+    // the tables go to the device with a copy kernel; the first scorer launch behind them tells the host that the pinned slot is
+    // free again (Bm25Params::slot_done)
+    fetch_from_pinned(d_blob, blob_pinned, blob_bytes, stream);
     a.slot_done = ring.done + slot;
     a.slot_seq = ring.arm(slot);
     a.post_off = ps.post_off.p;
@@ -589,81 +639,26 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     a.qfield = d_blob + o_field;
     a.bounds = d_bounds;
     a.bounds_hi = d_bounds_hi;
+    // the items of a scorer launch: `lists` chunks of `item_spi` sub-ranges, every `step`-th one, for every query -- or the item table
+    auto items_of = [&](const Bm25Params & p, uint32_t lists, uint32_t step, uint32_t item_spi, uint32_t item_chunks,
+                        const uint32_t * items = nullptr, size_t n_items_tab = 0) {
+        Bm25WParams w{};
+        w.p = p;
+        w.spi = item_spi;
+        w.n_chunks = item_chunks;
+        w.cstep = step;
+        w.n_items_c = lists;
+        w.lists = lists;
+        w.sub_docs = sub_docs;
+        w.dbg = (uint32_t)options().bm25_dbg;
+        w.items = items;
+        w.n_items_tab = (uint32_t)n_items_tab;
+        return w;
+    };
     // TOPK over (a sample of) the chunks: lists of p.kk keys into p.partial, `lists` per slot
-    auto launch_topk = [&](Bm25Params p, uint32_t lists, uint32_t step, size_t slots_bound, uint32_t item_spi, uint32_t item_chunks,
+    auto launch_topk = [&](const Bm25Params & p, uint32_t lists, uint32_t step, uint32_t item_spi, uint32_t item_chunks,
                            const uint32_t * items = nullptr, size_t n_items_tab = 0) {
-        if (wave)
-        {
-            Bm25WParams w{};
-            w.p = p;
-            w.spi = item_spi;
-            w.n_chunks = item_chunks;
-            w.cstep = step;
-            w.n_items_c = lists;
-            w.lists = lists;
-            w.sub_docs = docs_per_block;
-            w.dbg = (uint32_t)options().bm25_dbg;
-            const bool nf1k = ps.num_fields == 1;
-            const int r = r_for_k(p.kk);
-            if (posting)
-            {
-                w.items = items;
-                w.n_items_tab = (uint32_t)n_items_tab;
-                const size_t n_it = items ? n_items_tab : (size_t)lists * slots_bound;
-                const unsigned pgrid = (unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div(n_it, (size_t)BP_WAVES), (size_t)cus * bpc));
-                if (recs)
-                {
-                    Bm25RParams rp{w, d_rec};
-                    if (after_mode)
-                    {
-                        // instantiations of their own: the ones that serve k <= 256 (below) are untouched
-                        rp.after = d_after;
-                        if (lean)
-                            hipLaunchKernelGGL((bm25l_kernel<BM25_TOPK_AFTER, 4, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
-                        else if (big_slots)
-                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK_AFTER, 4, 16384>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
-                        else
-                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK_AFTER, 4, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
-                        MSVS_HIP(hipGetLastError());
-                        return;
-                    }
-                    with_int<1, 2, 4>(r, [&](auto rr) {
-                        constexpr int R = decltype(rr)::value;
-                        if (lean)
-                            hipLaunchKernelGGL((bm25l_kernel<BM25_TOPK, R, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
-                        else if (big_slots)
-                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK, R, 16384>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
-                        else
-                            hipLaunchKernelGGL((bm25r_kernel<BM25_TOPK, R, 8192>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, rp);
-                    });
-                    MSVS_HIP(hipGetLastError());
-                    return;
-                }
-                with_int<1, 2, 4>(r, [&](auto rr) {
-                    hipLaunchKernelGGL((bm25p_kernel<BM25_TOPK, decltype(rr)::value>), dim3(pgrid), dim3(64 * BP_WAVES), 0, stream, w);
-                });
-                MSVS_HIP(hipGetLastError());
-                return;
-            }
-            const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div((size_t)lists * slots_bound, (size_t)BW_WAVES), (size_t)cus * bw_blocks_per_cu(nf1k)));
-            with_int<1, 4>(nf1k ? 1 : 4, [&](auto nf) {
-                with_int<1, 2, 4>(r, [&](auto rr) {
-                    constexpr int R = decltype(rr)::value, NF = decltype(nf)::value;
-                    hipLaunchKernelGGL((bm25w_kernel<BM25_TOPK, R, NF>), dim3(grid), dim3(64 * BW_WAVES), 0, stream, w);
-                });
-            });
-        }
-        else
-        {
-            p.n_pad = lists;
-            p.bstep = step;
-            const size_t lds = (size_t)5 * p.kk * 8;
-            const dim3 grid(lists, (uint32_t)std::min<size_t>(slots_bound, std::max<size_t>(1, 2048 / lists)));
-            with_int<1, 2, 4>(r_for_k(p.kk), [&](auto rr) {
-                hipLaunchKernelGGL((bm25_score_kernel<BM25_TOPK, decltype(rr)::value>), grid, dim3(BLOCK), lds, stream, p);
-            });
-        }
-        MSVS_HIP(hipGetLastError());
+        bm25_launch_scorer<BM25_TOPK, 1, 2, 4>(sc, items_of(p, lists, step, item_spi, item_chunks, items, n_items_tab), nullptr, stream);
     };
     ProfileScope prof("bm25_score", stream);
     // the buffers of the sample / emit path, taken here so that the bounds launch can fill them on its way
@@ -676,21 +671,11 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     {
         if ((uint32_t)options().bm25_dbg & 32u) // experiment: does the first launch of a batch wait for the blob copy?
             hipLaunchKernelGGL(bm25_nop_kernel, dim3(1), dim3(64), 0, stream);
-        const dim3 bgrid((unsigned)ceil_div(n_flat * (size_t)(n_blocks + 1), (size_t)256));
-        Bm25Params ab = a;
-        if (tables_ride) // (the launch that copies the tables reads its own input, the flat terms, from the pinned slot)
-            ab.qterms = reinterpret_cast<const uint32_t *>(blob_pinned + o_terms);
-        if (options().bm25_bounds8 != 0)
-            hipLaunchKernelGGL(bm25_bounds8_kernel,
-                               dim3((unsigned)ceil_div((size_t)n_blocks + 1, (size_t)256), (unsigned)std::min<size_t>(n_flat, 65535)), dim3(256), 0, stream, ab, d_bounds,
-                               recs ? (int64_t *)nullptr : d_bounds_hi /* only bm25p_kernel reads the shifted copy */, (uint32_t)n_flat, docs_per_block,
-                               counters, fills_ride ? nq + 1 : (size_t)0, sample, fills_ride && n_items_s ? nq * (size_t)n_sb * cut_m : (size_t)0,
-                               ps.skip_n ? ps.skip_row.p : (const int32_t *)nullptr, ps.skip_tab.p, ps.skip_n,
-                               tables_ride ? reinterpret_cast<bm25_u32x4 *>(d_blob) : (bm25_u32x4 *)nullptr,
-                               reinterpret_cast<const bm25_u32x4 *>(blob_pinned), tables_ride ? blob_bytes / 16 : (size_t)0);
-        else
-            hipLaunchKernelGGL(bm25_bounds_kernel, bgrid, dim3(256), 0, stream, a, d_bounds, d_bounds_hi, (uint32_t)n_flat, docs_per_block,
-                               counters, fills_ride ? nq + 1 : (size_t)0, sample, fills_ride && n_items_s ? nq * (size_t)n_sb * cut_m : (size_t)0);
+        hipLaunchKernelGGL(bm25_bounds8_kernel, dim3((unsigned)ceil_div((size_t)n_blocks + 1, (size_t)256), (unsigned)std::min<size_t>(n_flat, 65535)),
+                           dim3(256), 0, stream, a, d_bounds, records ? (int64_t *)nullptr : d_bounds_hi /* only bm25w_kernel reads the shifted copy */,
+                           (uint32_t)n_flat, sub_docs, counters, fills_ride ? nq + 1 : (size_t)0, sample,
+                           fills_ride && n_items_s ? nq * (size_t)n_sb * cut_m : (size_t)0, ps.skip_n ? ps.skip_row.p : (const int32_t *)nullptr,
+                           ps.skip_tab.p, ps.skip_n);
     }
     if (!emit)
     {
@@ -702,7 +687,7 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
         m.k = (uint32_t)kl;
         if (!rounds)
         {
-            launch_topk(a, n_chunks, 1, nq, spi, n_chunks);
+            launch_topk(a, n_chunks, 1, spi, n_chunks);
             m.out_ids = d_ids;
             m.out_dis = d_scores;
             launch_merge(M_IP, m, (uint32_t)nq, stream);
@@ -713,13 +698,13 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
         // lists, one merge -- over the documents behind the query's continuation key, for the whole chunk of queries at once.  The
         // bounds and tables above are shared by all rounds.  Round 0 starts from key 0, which admits every key (no score makes it:
         // make_key turns NaN into KEY_NONE); a query whose round came back short continues from KEY_NONE, which admits none.
-        after_mode = true;
         m.mode = 2;
         m.out_keys = round_keys;
         MSVS_HIP(hipMemsetAsync(d_after, 0, nq * 8, stream));
         for (size_t done = 0; done < k; done += kl)
         {
-            launch_topk(a, n_chunks, 1, nq, spi, n_chunks);
+            // (instantiations of their own: the ones that serve k <= 256 are untouched)
+            bm25_launch_scorer<BM25_TOPK_AFTER, 4>(sc, items_of(a, n_chunks, 1, spi, n_chunks), d_after, stream);
             launch_merge(M_IP, m, (uint32_t)nq, stream);
             hipLaunchKernelGGL(bm25_round_scatter_kernel, dim3((unsigned)nq), dim3(MSVS_MAX_K), 0, stream, round_keys, (uint32_t)k, (uint32_t)done,
                                (uint32_t)std::min(kl, k - done), d_ids, d_scores, d_after);
@@ -734,14 +719,9 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     Bm25Params sp = a;
     sp.partial = sample;
     sp.kk = cut_m;
-    if (n_items_s)
-    {
-        if (!fills_ride)
-            MSVS_HIP(hipMemsetAsync(sample, 0xFF, nq * (size_t)n_sb * cut_m * 8, stream)); // a query with fewer items leaves lists unused
-        launch_topk(sp, n_sb, BM25_SAMPLE_STEP, nq, spi_s, n_chunks_s, reinterpret_cast<const uint32_t *>(d_blob + o_items_s), n_items_s);
-    }
-    else
-        launch_topk(sp, n_sb, BM25_SAMPLE_STEP, nq, spi_s, n_chunks_s);
+    if (n_items_s && !fills_ride)
+        MSVS_HIP(hipMemsetAsync(sample, 0xFF, nq * (size_t)n_sb * cut_m * 8, stream)); // a query with fewer items leaves lists unused
+    launch_topk(sp, n_sb, BM25_SAMPLE_STEP, spi_s, n_chunks_s, n_items_s ? reinterpret_cast<const uint32_t *>(d_blob + o_items_s) : nullptr, n_items_s);
     const size_t n_sample_keys = (size_t)n_sb * cut_m;
     if (options().bm25_cutk != 0 && (n_sample_keys <= 4096 || (nq <= 512 && n_sample_keys <= 8192 && cut_m <= 64)))
     {
@@ -782,63 +762,20 @@ void bm25_chunk_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     ep.cand = cand;
     ep.ccnt = ccnt;
     ep.cand_cap = cand_cap;
-    if (wave)
-    {
-        Bm25WParams w{};
-        w.p = ep;
-        w.spi = spi;
-        w.n_chunks = n_chunks;
-        w.cstep = 1;
-        w.n_items_c = n_chunks;
-        w.lists = n_chunks;
-        w.sub_docs = docs_per_block;
-        w.dbg = (uint32_t)options().bm25_dbg;
-        w.items = posting ? reinterpret_cast<const uint32_t *>(d_blob + o_items) : nullptr;
-        w.n_items_tab = (uint32_t)n_items_e;
-        const bool nf1k = ps.num_fields == 1;
-        const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div((size_t)n_chunks * nq, (size_t)BW_WAVES), (size_t)cus * bw_blocks_per_cu(nf1k)));
-        if (recs)
-        {
-            const dim3 egrid((unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div(std::max<size_t>(n_items_e, 1), (size_t)BP_WAVES), (size_t)cus * bpc)));
-            Bm25RParams rp{w, d_rec};
-            if (lean)
-                hipLaunchKernelGGL((bm25l_kernel<BM25_EMIT, 1, 8192>), egrid, dim3(64 * BP_WAVES), 0, stream, rp);
-            else if (big_slots)
-                hipLaunchKernelGGL((bm25r_kernel<BM25_EMIT, 1, 16384>), egrid, dim3(64 * BP_WAVES), 0, stream, rp);
-            else
-                hipLaunchKernelGGL((bm25r_kernel<BM25_EMIT, 1, 8192>), egrid, dim3(64 * BP_WAVES), 0, stream, rp);
-        }
-        else if (posting)
-            hipLaunchKernelGGL((bm25p_kernel<BM25_EMIT, 1>), dim3((unsigned)std::max<size_t>(1, std::min<size_t>(ceil_div((size_t)n_chunks * nq, (size_t)BP_WAVES), (size_t)cus * BP_BLOCKS_PER_CU))),
-                               dim3(64 * BP_WAVES), 0, stream, w);
-        else if (nf1k)
-            hipLaunchKernelGGL((bm25w_kernel<BM25_EMIT, 1, 1>), dim3(grid), dim3(64 * BW_WAVES), 0, stream, w);
-        else
-            hipLaunchKernelGGL((bm25w_kernel<BM25_EMIT, 1, 4>), dim3(grid), dim3(64 * BW_WAVES), 0, stream, w);
-    }
-    else
-    {
-        ep.bstep = 1;
-        hipLaunchKernelGGL((bm25_score_kernel<BM25_EMIT, 1>), dim3(n_blocks, (uint32_t)std::min<size_t>(nq, ceil_div((size_t)4096, (size_t)n_blocks))),
-                           dim3(BLOCK), 0, stream, ep);
-    }
-    // 3. select, or queue for the fallback
-    const size_t lds_k = (size_t)5 * k * 8;
-    if (options().bm25_select2 != 0 && k <= 256)
-        hipLaunchKernelGGL(bm25_select2_kernel, dim3((unsigned)nq), dim3(BLOCK), 0, stream, cand, ccnt, cand_cap, cut_keys, cut_m, (uint32_t)k, d_ids,
-                           d_scores, failq, nfail, stat_fail);
-    else
-        hipLaunchKernelGGL(bm25_select_kernel, dim3((unsigned)nq), dim3(BM25_SELECT_THREADS), 0, stream, cand, ccnt, cand_cap, cut_keys, cut_m,
-                           (uint32_t)k, d_ids, d_scores, failq, nfail, stat_fail);
+    bm25_launch_scorer<BM25_EMIT, 1>(sc, items_of(ep, n_chunks, 1, spi, n_chunks, records ? reinterpret_cast<const uint32_t *>(d_blob + o_items) : nullptr, n_items_e),
+                                     nullptr, stream);
+    // 3. select, or queue for the fallback (the emit flow serves k <= MSVS_MAX_K only)
+    hipLaunchKernelGGL(bm25_select2_kernel, dim3((unsigned)nq), dim3(BLOCK), 0, stream, cand, ccnt, cand_cap, cut_keys, cut_m, (uint32_t)k, d_ids, d_scores,
+                       failq, nfail, stat_fail);
     // 4. the exact fallback over the queue (empty launches when nobody queued)
     Bm25Params fp = a;
     fp.partial = partial;
     fp.kk = (uint32_t)k;
     fp.qsel = failq;
     fp.nsel = nfail;
-    launch_topk(fp, n_chunks, 1, std::min<size_t>(nq, wave ? nq : 4), spi, n_chunks);
+    launch_topk(fp, n_chunks, 1, spi, n_chunks);
     with_int<1, 2, 4>(r_for_k((uint32_t)k), [&](auto rr) {
-        hipLaunchKernelGGL((bm25_fb_merge_kernel<decltype(rr)::value>), dim3((unsigned)nq), dim3(BLOCK), lds_k, stream, partial, n_chunks,
+        hipLaunchKernelGGL((bm25_fb_merge_kernel<decltype(rr)::value>), dim3((unsigned)nq), dim3(BLOCK), (size_t)5 * k * 8, stream, partial, n_chunks,
                            n_chunks, (uint32_t)k, failq, nfail, d_ids, d_scores);
     });
     MSVS_HIP(hipGetLastError());
@@ -854,12 +791,11 @@ void bm25_batch_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
 {
     if (k > MSVS_MAX_K_ROUNDS)
         fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds the limit %d", k, MSVS_MAX_K_ROUNDS);
-    // beyond one top-k list: exact rank-window rounds on the record scorers (bm25_chunk_device).  The knobs that select another scorer
-    // keep the old limit.
+    // beyond one top-k list: exact rank-window rounds on the record scorers (bm25_chunk_device).  The knob that forces the dense
+    // accumulator keeps the old limit.
     const bool rounds = k > MSVS_MAX_K;
-    if (rounds && (options().bm25_wave == 0 || options().bm25_posting == 0 || options().bm25_rec == 0))
-        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds %d, which only the record scorers serve: not with option %s = 0", k, MSVS_MAX_K,
-             options().bm25_wave == 0 ? "bm25_wave" : options().bm25_posting == 0 ? "bm25_posting" : "bm25_rec");
+    if (rounds && options().bm25_posting == 0)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds %d, which only the record scorers serve: not with option bm25_posting = 0", k, MSVS_MAX_K);
     if (total_docs == 0)
         fail(MSVS_ERR_INVALID_ARGUMENT, "total_docs is zero");
     // tantivy Bm25Weight (bm25.rs): K1 = 1.2, B = 0.75, all f32
@@ -904,14 +840,14 @@ void bm25_batch_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
             eff_bits = res_bits;
         }
     }
-    // score-ready records of the posting scorer (bm25r_kernels.hpp): derived per fieldnorm cache, built on first use
+    // score-ready records of the record scorers (bm25r_kernels.hpp): derived per fieldnorm cache, built on first use
     std::shared_ptr<msvs_postings::RecSet> recset;
-    if (options().bm25_wave != 0 && options().bm25_posting != 0 && options().bm25_rec != 0)
+    if (options().bm25_posting != 0)
         recset = records_for(ps, cache, stream);
-    // an upper bound of the sub-ranges per query term: the posting scorer's sub-range size follows the densest query (a chunk's
+    // an upper bound of the sub-ranges per query term: the record scorers' sub-range size follows the densest query (a chunk's
     // densest query is no denser than the batch's, so its sub-ranges are no shorter than this one)
     size_t sub_ub = BW_DOCS;
-    if (options().bm25_wave != 0 && options().bm25_posting != 0)
+    if (options().bm25_posting != 0)
     {
         double rho = 0;
         for (size_t q = 0; q < nq; q++)
@@ -924,7 +860,7 @@ void bm25_batch_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
         }
         const size_t formula = bm25_sub_docs_for(rho);
         const size_t sub_p = options().bm25_sub_docs >= 16 ? (size_t)options().bm25_sub_docs : formula;
-        // no chunk can be denser than the batch: all of them take the posting scorer, or some may keep the dense accumulator
+        // no chunk can be denser than the batch: all of them take the record scorers, or some may keep the dense accumulator
         // (the rounds of k > MSVS_MAX_K always do)
         sub_ub = rho <= 0.125 || options().bm25_posting == 2 || rounds ? sub_p : std::min<size_t>(BW_DOCS, sub_p);
     }
@@ -934,8 +870,7 @@ void bm25_batch_device(const msvs_postings & ps, size_t nq, const uint32_t * qof
     // seven launches each)
     // (k > MSVS_MAX_K: the lists of a round are MSVS_MAX_K wide, plus the round's merged keys and the continuation key)
     const size_t kl = std::min<size_t>(k, MSVS_MAX_K);
-    const size_t per_q = (size_t)BM25_CAND_CAP * 8 + 4 * 16 * (n_blocks + 1) + 64 * kl * 8 + (rounds ? (kl + 1) * 8 : 0) + 64
-        + (options().bm25_wave != 0 ? 0 : ceil_div(ps.num_docs, (size_t)BM25_DOCS) * k * 8); // the block scorer: a list per block
+    const size_t per_q = (size_t)BM25_CAND_CAP * 8 + 4 * 16 * (n_blocks + 1) + 64 * kl * 8 + (rounds ? (kl + 1) * 8 : 0) + 64;
     const size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)1024 << 20) / per_q));
     for (size_t q0 = 0; q0 < nq; q0 += chunk)
     {

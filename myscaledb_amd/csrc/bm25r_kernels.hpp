@@ -1,11 +1,23 @@
-// bm25r_kernels.hpp -- BM25 posting scorer over SCORE-READY RECORDS (seam B, TantivyIndexStore.cpp:900-954), round 5.
+// bm25r_kernels.hpp -- BM25 scorer with the POSTING as the unit of work, over SCORE-READY RECORDS (seam B,
+// TantivyIndexStore.cpp:900-954).
 //
-// bm25p_kernel (bm25p_kernels.hpp) made the posting the unit of work; what it still paid per posting was (a) a third
-// dependent memory round trip -- the fieldnorm byte of the posting's document, gathered -- followed by a table lookup and an
-// f32 division, (b) every record written to LDS so that the few shared documents could be binary-searched in the other terms'
-// slices, and (c) 128 VGPRs with spills.  ~1300 wavefront instructions per 512-posting window, 0.043 of HBM.
-//
-// Here:
+// bm25w_kernel (bm25_kernels.hpp) keeps a dense per-document accumulator for 2048 documents per wavefront and walks the
+// query's terms one after the other over it: ~550 wavefront instructions per 2048 documents whatever the lane use, and a
+// mid-frequency term has ~10 postings there (profiles/r02_bm25.txt: 9.5 us per query at batch 64 where the bytes cost 0.15).
+// Here nothing is indexed by document:
+//   * a work item = (run of consecutive sub-ranges, query), one wavefront.  The EMIT and the SAMPLE launch walk a host-built
+//     item table (Bm25WParams::items: query, first sub-range, end, list index) whose items hold about the same number of
+//     postings whatever the query -- long document ranges for rare terms, short ones for frequent terms; the other TOPK
+//     launches take (chunk of `spi` sub-ranges, query) items and rotate the query with the chunk (with a wavefront count that
+//     is a multiple of the batch size every wavefront would otherwise see the SAME query for the whole launch, and a query of
+//     frequent terms holds six times the postings of a query of rare ones);
+//   * inside an item the wavefront cuts WINDOWS: as many whole sub-ranges as hold <= BP_CAP postings of all the query's terms
+//     together (bounds at sub-range granularity from bm25_bounds8_kernel, lane t = term t).  The sub-range size is chosen per
+//     batch from the posting density so that a window is a few sub-ranges; a single sub-range over the cap (a local density
+//     spike) is cut by document id with a per-lane binary search -- slow and rare, batches of frequent terms go to
+//     bm25w_kernel instead;
+//   * the window's postings are ONE flat sequence (term 0's slice, term 1's, ...): lane l takes records l, l + 64, ...,
+//     every lane busy but the last few;
 //   * the postings are read as RECORDS (doc, tfn): tfn = tf / (tf + cache[field][fieldnorm[doc]]) with the scorer's own f32
 //     operations, precomputed once per (posting set, fieldnorm cache) by bm25_rec_build_kernel -- derived data like the fp16
 //     shadow of the vector side, 8 B per posting, rebuilt when the corpus statistics (average field length) change.  A record is
@@ -18,15 +30,44 @@
 //     term order) and resolved among themselves: a flagged record with an earlier flagged record of the same document is not
 //     the owner; the owner adds its later partners in list order -- the dense accumulator's additions in query-term order,
 //     starting from its own partial (0 + s = s);
-//   * everything else -- items, windows, staged EMIT appends, the TOPK floor -- is bm25p_kernel's.
+//   * owners that qualify (operator, cut, filter) are offered to the item's WaveTopK (TOPK: sample, short corpora, exact
+//     fallback, rank-window rounds) or appended to the query's candidates (EMIT).  EMIT: passing keys wait in an LDS stage
+//     (with their query) and leave in rounds of 64, one returning atomic per distinct query of a round -- a query's counter
+//     is ONE address for the whole chip, and ~500 windows per query each taking their turn at it was a quarter of the kernel;
+//   * TOPK, the item's list not full yet: offering a window's ~400 records one by one costs ~100 list insertions.  The kk-th
+//     largest of the 64 lanes' BEST scores is a floor -- kk records at or above it exist -- and what lies below it cannot be
+//     among the window's kk best: ~30 insertions instead.
 #pragma once
-#include "bm25p_kernels.hpp"
+#include "bm25_kernels.hpp"
 #include "mfma_scan_kernels.hpp" // wave_kth_word_radix
 
 #pragma clang fp contract(off)
 
 namespace msvs
 {
+
+constexpr uint32_t BP_WAVES = 4;             // wavefronts per workgroup
+constexpr uint32_t BP_RMAX = 8;              // records per lane and window
+constexpr uint32_t BP_CAP = 64 * BP_RMAX;    // postings per window
+constexpr uint32_t BP_STAGE = 128;           // EMIT: staged keys per wavefront (>= 64 free slots after a flush)
+constexpr uint32_t BP_MIN_DOCS = 512;        // sub-range sizes the host picks from
+constexpr uint32_t BP_MAX_DOCS = 8192;
+
+/// LDS traffic of ONE wavefront: its ds operations execute in order, so a wait + a compiler barrier is all a
+/// write -> read-by-another-lane hand-over needs.
+__device__ __forceinline__ void bp_wave_lds_fence()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ uint64_t bp_wave_sum(uint64_t v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        v += (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)v, o) | ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o) << 32);
+    return v;
+}
 
 struct Bm25RParams
 {
@@ -242,7 +283,7 @@ __global__ __launch_bounds__(64 * BP_WAVES, 4) void bm25r_kernel(const Bm25RPara
                 W = 0; // the query is finished: an empty list
             W = (uint32_t)__builtin_amdgcn_readfirstlane((int)W);
         }
-        // ---- the window generator (bm25p_kernel's loop head as a function: it runs one window AHEAD of the scoring)
+        // ---- the window generator (a function: it runs one window AHEAD of the scoring)
         uint32_t s = W ? s_begin : s_end;
         bool splitting = false;
         uint32_t d_lo = 0, d_end = 0;
@@ -648,11 +689,14 @@ __global__ __launch_bounds__(BLOCK) void bm25_cut_block_kernel(const uint64_t * 
         cut_keys[(size_t)q * m + m - 1] = G == 0xFFFFFFFFu ? KEY_NONE : (uint64_t)G << 32;
 }
 
-/// bm25_select_kernel by SELECTION instead of ranking every candidate against every other (~500 candidates per query: 14 us per launch,
-/// as long as the sample pass of a 64-query batch): the four wavefronts of a workgroup each select the k smallest score words of a
-/// quarter of the keys (register radix select), the first one the k-th smallest of those 4 k -- the k-th smallest word G of all; the keys
-/// with a word <= G (k of them plus the ties of the last score) are ranked among themselves.  More than 1024 such keys (a score
-/// shared by a thousand documents at the cut): the full ranking.  Same outputs, same failure rule.
+/// One workgroup per query (k <= MSVS_MAX_K): top-k of its candidates -> results; a query whose candidates cannot prove its top-k
+/// (list overflowed, or a real cut let fewer than k through) joins the fallback queue instead.
+/// By SELECTION, not by ranking every candidate against every other (~500 candidates per query: 14 us per launch, as long as the
+/// sample pass of a 64-query batch): the four wavefronts of a workgroup each select the k smallest score words of a quarter of
+/// the keys (register radix select), the first one the k-th smallest of those 4 k -- the k-th smallest word G of all; the keys
+/// with a word <= G (k of them plus the ties of the last score) are ranked among themselves (a key holds the document id: no
+/// two are equal; rank < k is the output position).  More than 1024 such keys (a score shared by a thousand documents at the
+/// cut): the full ranking.
 static __global__ __launch_bounds__(BLOCK) void bm25_select2_kernel(const uint64_t * cand, const uint32_t * ccnt, uint32_t cand_cap,
                                                                      const uint64_t * cut_keys, uint32_t cut_m, uint32_t k, int64_t * out_ids,
                                                                      float * out_scores, uint32_t * failq, uint32_t * nfail,
@@ -809,22 +853,15 @@ static __global__ void bm25_skip_build_kernel(const int64_t * post_off, const ui
     tab[i] = (uint32_t)(lo - base);
 }
 
-/// bm25_bounds_kernel with an 8-ary search: the chain of dependent loads is what the launch costs (21 steps for a list of 2M
-/// postings); seven independent probes per step cut it to 7.
-typedef uint32_t bm25_u32x4 __attribute__((ext_vector_type(4)));
+/// The sub-range bounds of a batch: bounds[j][b] = first posting of flat term j with a document id >= b * docs_per_block
+/// (bounds_hi, nullable: the same array shifted by one sub-range, for bm25w_kernel).  An 8-ary search: the chain of dependent
+/// loads is what the launch costs (21 binary steps for a list of 2M postings); seven independent probes per step cut it to 7.
+/// The fills of the batch ride along (nullable): `zero` = the candidate counters + fail counter, `ones` = the sample's
+/// per-query lists (KEY_NONE = all bits set) -- two launches less in front of the sample pass.
 static __global__ void bm25_bounds8_kernel(const Bm25Params a, int64_t * bounds, int64_t * bounds_hi, uint32_t n_flat,
                                            uint32_t docs_per_block, uint32_t * zero, size_t n_zero, uint64_t * ones, size_t n_ones,
-                                           const int32_t * skip_row, const uint32_t * skip_tab, uint32_t skip_n,
-                                           bm25_u32x4 * tables_dst = nullptr, const bm25_u32x4 * tables_pinned = nullptr, size_t tables_n16 = 0)
+                                           const int32_t * skip_row, const uint32_t * skip_tab, uint32_t skip_n)
 {
-    // Round 6: the batch's tables ride along too -- this launch copies them from their pinned slot to the device (every thread a
-    // grid-stride share; the scorers behind it read the device copy) and reads the ONE table it needs itself, the flat terms, straight
-    // from pinned memory (a.qterms points there for this launch).  A copy of its own in front cost a launch and the gap behind it.
-    {
-        const size_t gsz = (size_t)gridDim.x * gridDim.y * blockDim.x;
-        for (size_t i = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < tables_n16; i += gsz)
-            tables_dst[i] = __builtin_nontemporal_load(&tables_pinned[i]);
-    }
     // grid: x over the boundaries of a term, y over the flat terms (the term and its list ends are uniform: scalar loads, and no
     // 64-bit division per thread -- the flat index form spent more on `i / nb1` than on its search)
     {

@@ -165,7 +165,6 @@ struct Options
     double coarse_h16 = 1;    // coarse quantiser of batches through the centroid shadow (0: the split-bf16 table pass)
     double wave_select = 1;   // candidate selection by the bitwise wave search (0: WaveTopK insertion kernels)
     double plan_lds = 1;      // plan histogram / scatter aggregated in LDS per 2048 pairs (0: one global atomic per pair)
-    double bm25_fine_sample = 1; // BM25 wave scorer: the sample pass walks items of spi / 8 sub-ranges (0: the emit pass's items)
     double lat_select = 1;    // few-query path: probe list by register selection in the last block of stage 1 (0: list merge)
     double rerank_early = 1;  // re-rank of result passes: sorted candidates, skip those beyond the exact k-th of the first rounds +- eps
     double rerank_groups = 16; // candidate rows in flight per re-rank block (32: 512-thread blocks, measured slower: 70 vs 47 us)
@@ -241,14 +240,12 @@ struct Options
     double coarse_band = 1;   // coarse quantiser of batches: only the candidates near the top-nprobe boundary are evaluated canonically (0: all 64)
     double rerank_chain = 1;  // re-rank blocks: one prologue round trip, eps formed once, a lane's whole row in flight (0: loads where each step needs them)
     double rerank_hint = 1;   // second-chance re-rank: skip rows that cannot beat the first stage's k-th exact distance (0: evaluate the whole buffer)
-    double bm25_wave = 1;     // BM25: wave-private streaming scorer (1) or the barrier-synchronised block scorer (0)
-    double bm25_posting = 1;  // BM25: posting-as-unit scorer (bm25p_kernel) for batches of sparse terms; 0: always the dense accumulator, 2: always the posting scorer
+    double bm25_posting = 1;  // BM25: the record scorers (bm25r_kernel / bm25l_kernel) for batches of sparse terms; 0: always the dense accumulator (bm25w_kernel), 2: always the record scorers
     double bm25_dbg = 0;      // BM25 posting scorer: experiment masks (1 no owner search, 2 no fieldnorm gather, 4 no output, 8 windows only)
     double bm25_sub_docs = 0; // BM25 posting scorer: documents per sub-range (0: from the batch's posting density)
     double bm25_emit = 1;     // BM25 over long corpora: sample / cut / emit (1) or per-block top-k lists only (0)
     double bm25_cand_cap = 0; // BM25 candidate slots per query (0 = 2048; small values force the fallback)
     double flat_few = 1;      // FLAT index, fewer than 16 queries over a large table: through the fp16 shadow pass (0: the canonical f32 scan; 2: whatever the table size)
-    double bm25_rec = 1;      // BM25 posting scorer over score-ready records (bm25r_kernel; 0: bm25p_kernel over doc ids / tfs / gathered fieldnorms)
     double bm25_slots = 0;    // bm25r_kernel: hash slots of the shared-document filter (0 = 8192, 4 workgroups per CU; 16384: 3 per CU, fewer false alarms)
     double bm25_cutk = 1;     // BM25 cut by a register radix select per query (0: the list merge kernel)
     double bm25_lean = 1;     // BM25 record scorer: the four-term form (bm25l_kernel) when every query of the chunk has <= 4 terms (0: bm25r_kernel)
@@ -260,11 +257,7 @@ struct Options
     double flat_sample_few = 1;  // FLAT shadow pass, <= 32 queries: sample + cut in one launch (flat_sample_few_kernel; 0: coarse_h16_kernel + flat_cut_kernel)
     double flat_host_signal = 1; // FLAT, a few queries, host pointers: pinned in / out + a completion word (0: copies + stream synchronisation)
     double bm25_items_per_wave = 0; // BM25 emit pass: equal-postings items per resident wavefront (0 = 2)
-    double bm25_select2 = 1;  // BM25 top-k of the candidates by selection (bm25_select2_kernel; 0: rank every candidate against every other)
     double bm25_skip = 1;     // BM25 posting sets carry a skip table of their frequent terms (read at msvs_postings_create)
-    double bm25_tables_ride = 0; // BM25: the batch's tables are copied to the device by the bounds launch instead of a copy kernel of their own in front
-                                 // of it (measured: 1.97 -> 1.96-1.99 us/query at 64, 0.66 -> 0.68 at 1024 -- the bounds launch reads its terms over the link: off)
-    double bm25_bounds8 = 1;  // BM25 sub-range bounds by an 8-ary search (0: binary)
     double pinned_fetch = 1;     // small host -> device hand-overs out of pinned memory by a copy kernel instead of hipMemcpyAsync (device_ops.hpp: fetch_from_pinned)
     double pinned_fetch_max = 1048576; // ... up to this many bytes
     double bin_ivf_rpb = 0;     // partitioned binary index: rows per work item of the list scan (0 = planned: <= ~8 segments per list, >= 2048 rows; tests: small segments)

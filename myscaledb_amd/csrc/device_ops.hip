@@ -531,7 +531,7 @@ const OptionField g_option_fields[] = {
     {"coarse_h16", &Options::coarse_h16},   {"wave_select", &Options::wave_select},
     {"plan_lds", &Options::plan_lds},       {"fb_segs", &Options::fb_segs},
     {"h16_kc", &Options::h16_kc},           {"coarse_kc", &Options::coarse_kc},
-    {"bm25_fine_sample", &Options::bm25_fine_sample}, {"lat_select", &Options::lat_select},
+    {"lat_select", &Options::lat_select},
     {"rerank_stats", &Options::rerank_stats},   {"rerank_early", &Options::rerank_early},
     {"rerank_groups", &Options::rerank_groups}, {"combine", &Options::combine},           {"h16_k128", &Options::h16_k128},
     {"h16_target", &Options::h16_target},       
@@ -545,13 +545,13 @@ const OptionField g_option_fields[] = {
     {"h16_min_pairs", &Options::h16_min_pairs}, {"h16_ncb", &Options::h16_ncb},
     {"h16_nocut", &Options::h16_nocut},     {"fb_cap", &Options::fb_cap},           {"rerank_second", &Options::rerank_second}, {"rerank_fused", &Options::rerank_fused},
     {"lat_path", &Options::lat_path},         {"filter_compact_below", &Options::filter_compact_below},
-    {"bm25_wave", &Options::bm25_wave},     {"rerank_hint", &Options::rerank_hint}, {"rerank_chain", &Options::rerank_chain}, {"coarse_band", &Options::coarse_band}, {"coarse_tail", &Options::coarse_tail}, {"merge_small", &Options::merge_small}, {"route_streams", &Options::route_streams}, {"coarse_slow_inline", &Options::coarse_slow_inline}, {"coarse_slow_window", &Options::coarse_slow_window}, {"h16_prune", &Options::h16_prune}, {"h16_feedback", &Options::h16_feedback}, {"h16_group_appends", &Options::h16_group_appends}, {"h16_preprune", &Options::h16_preprune}, {"lat_prune", &Options::lat_prune}, {"lat_items", &Options::lat_items}, {"lat_hint", &Options::lat_hint},     {"bm25_posting", &Options::bm25_posting}, {"bm25_sub_docs", &Options::bm25_sub_docs}, {"bm25_dbg", &Options::bm25_dbg},
+    {"rerank_hint", &Options::rerank_hint}, {"rerank_chain", &Options::rerank_chain}, {"coarse_band", &Options::coarse_band}, {"coarse_tail", &Options::coarse_tail}, {"merge_small", &Options::merge_small}, {"route_streams", &Options::route_streams}, {"coarse_slow_inline", &Options::coarse_slow_inline}, {"coarse_slow_window", &Options::coarse_slow_window}, {"h16_prune", &Options::h16_prune}, {"h16_feedback", &Options::h16_feedback}, {"h16_group_appends", &Options::h16_group_appends}, {"h16_preprune", &Options::h16_preprune}, {"lat_prune", &Options::lat_prune}, {"lat_items", &Options::lat_items}, {"lat_hint", &Options::lat_hint},     {"bm25_posting", &Options::bm25_posting}, {"bm25_sub_docs", &Options::bm25_sub_docs}, {"bm25_dbg", &Options::bm25_dbg},
     {"h8_pairs", &Options::h8_pairs}, {"h8_pairs_grid", &Options::h8_pairs_grid}, {"h8_pairs_plan", &Options::h8_pairs_plan}, {"h8_pairs_split", &Options::h8_pairs_split},
     {"h16_rho", &Options::h16_rho}, {"h16_form", &Options::h16_form}, {"h16_segs", &Options::h16_segs}, {"h16_stamps", &Options::h16_stamps}, {"h16_items", &Options::h16_items},   {"flat_h16", &Options::flat_h16},     {"flat_segb", &Options::flat_segb}, {"flat_rot", &Options::flat_rot}, {"flat_lazy_flush", &Options::flat_lazy_flush},   {"flat_ncb", &Options::flat_ncb},
     {"bm25_emit", &Options::bm25_emit},     {"bm25_cand_cap", &Options::bm25_cand_cap},
     {"flat_few", &Options::flat_few},
-    {"bm25_rec", &Options::bm25_rec},       {"bm25_slots", &Options::bm25_slots},
-    {"bm25_cutk", &Options::bm25_cutk},     {"bm25_bounds8", &Options::bm25_bounds8}, {"bm25_tables_ride", &Options::bm25_tables_ride}, {"bm25_lean", &Options::bm25_lean}, {"bm25_skip", &Options::bm25_skip}, {"bm25_select2", &Options::bm25_select2}, {"bm25_items_per_wave", &Options::bm25_items_per_wave}, {"flat_host_signal", &Options::flat_host_signal}, {"flat_sample_few", &Options::flat_sample_few}, {"plan_fused", &Options::plan_fused}, {"coarse_dense", &Options::coarse_dense}, {"host_signal_batch", &Options::host_signal_batch}, {"combine_spin", &Options::combine_spin}, {"host_pinned", &Options::host_pinned}, {"coarse_few", &Options::coarse_few}, {"pinned_fetch", &Options::pinned_fetch}, {"pinned_fetch_max", &Options::pinned_fetch_max},
+    {"bm25_slots", &Options::bm25_slots},
+    {"bm25_cutk", &Options::bm25_cutk},     {"bm25_lean", &Options::bm25_lean}, {"bm25_skip", &Options::bm25_skip}, {"bm25_items_per_wave", &Options::bm25_items_per_wave}, {"flat_host_signal", &Options::flat_host_signal}, {"flat_sample_few", &Options::flat_sample_few}, {"plan_fused", &Options::plan_fused}, {"coarse_dense", &Options::coarse_dense}, {"host_signal_batch", &Options::host_signal_batch}, {"combine_spin", &Options::combine_spin}, {"host_pinned", &Options::host_pinned}, {"coarse_few", &Options::coarse_few}, {"pinned_fetch", &Options::pinned_fetch}, {"pinned_fetch_max", &Options::pinned_fetch_max},
     {"route_self_rccl", &Options::route_self_rccl},
     {"coarse_prune_first", &Options::coarse_prune_first}, {"coarse_prune_debug", &Options::coarse_prune_debug},
     {"bin_ivf_rpb", &Options::bin_ivf_rpb},

@@ -49,7 +49,7 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 constexpr int H_ROWS = 32;  // rows per shadow block (one wavefront's B operand)
 
 /// LDS traffic of ONE wavefront: its ds operations execute in order, a wait + a compiler barrier is all a write -> read-by-another-lane
-/// hand-over needs (bm25p_kernels.hpp has the same helper).
+/// hand-over needs (bm25r_kernels.hpp has the same helper).
 __device__ __forceinline__ void bp_wave_lds_fence_h16()
 {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

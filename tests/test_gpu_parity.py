@@ -1748,20 +1748,20 @@ def test_bm25_synthetic_corpus_matches_oracle():
 
 
 def bm25_scorer(opt, which):
-    """"r": the posting scorer over score-ready records forced (bm25r_kernel; frequent terms take its split path), "p": the
-    same over doc ids / tfs / gathered fieldnorms (bm25p_kernel, round 3), "w": the wave-private dense accumulator, "0": the
-    block scorer it replaced.  (The default routes a batch to "r" or "w" by its posting density.)"""
-    opt("bm25_wave", "0" if which == "0" else "1")
-    opt("bm25_posting", "2" if which in ("p", "r") else "0")
-    opt("bm25_rec", "1" if which == "r" else "0")
+    """"r": the record scorers forced (bm25r_kernel / bm25l_kernel; frequent terms take their split path), "w": the wave-private
+    dense accumulator (bm25w_kernel).  (The default routes a batch to "r" or "w" by its posting density.)"""
+    opt("bm25_posting", "2" if which == "r" else "0")
 
 
-@pytest.mark.parametrize("wave", ["r", "p", "w", "0"])
-@pytest.mark.parametrize("mode", ["emit", "lists", "forced_fallback"])
+@pytest.mark.parametrize("wave", ["r", "w"])
+@pytest.mark.parametrize("mode", ["emit", "lists", "forced_fallback", "emit_list_cut"])
 def test_bm25_many_doc_blocks(mode, wave, opt):
     """>= 64 document blocks (here 700k documents = 86 blocks): sample -> cut -> emit -> select; the same with the
-    candidate list too small for any query (every query takes the exact fallback); and per-block lists only."""
+    candidate list too small for any query (every query takes the exact fallback); per-block lists only; and the emit flow
+    with the cut taken by the list merge (bm25_cutk = 0: what sample sets above 4096 / 8192 keys get)."""
     bm25_scorer(opt, wave)
+    if mode == "emit_list_cut":
+        opt("bm25_cutk", "0")
     if mode == "lists":
         opt("bm25_emit", "0")
     if mode == "forced_fallback":
@@ -1792,7 +1792,7 @@ def test_bm25_many_doc_blocks(mode, wave, opt):
             assert (got[1].view(np.uint32) == exp[1].view(np.uint32)).all()
             n_q += 1
     q1, f1 = capi.bm25_stats()
-    if mode == "emit":
+    if mode in ("emit", "emit_list_cut"):
         assert q1 - q0 == n_q and f1 - f0 <= 1
     if mode == "forced_fallback":
         assert q1 - q0 == n_q and f1 - f0 == n_q
@@ -1823,7 +1823,7 @@ def synthetic_postings(rng, n_docs, vocab, mean_len, num_fields=1):
     return post_off, np.concatenate(docs), np.concatenate(tfs), np.stack(fns), term_field, np.asarray(tokens, np.uint64)
 
 
-@pytest.mark.parametrize("wave", ["r", "p", "w", "0"])
+@pytest.mark.parametrize("wave", ["r", "w"])
 def test_bm25_batch_equals_single_queries_and_oracle(wave, opt):
     """msvs_bm25_search_batch: every query of a batch == the one-query entry point == the oracle, bit for bit; the
     resident alive bitmap (msvs_postings_set_alive) ANDs with the per-call one."""
@@ -1874,7 +1874,7 @@ def test_bm25_batch_equals_single_queries_and_oracle(wave, opt):
         assert (od[qi].cpu().numpy()[:len(gr)].view(np.uint32) == gs.view(np.uint32)).all()
 
 
-@pytest.mark.parametrize("wave", ["r", "p", "w", "0"])
+@pytest.mark.parametrize("wave", ["r", "w"])
 @pytest.mark.parametrize("num_fields", [1, 3])
 def test_bm25_and_operator_and_text_columns(num_fields, wave, opt):
     """operator_or = false (every token must match, in any column) and an index over several text columns: one term
@@ -1905,14 +1905,13 @@ def test_bm25_and_operator_and_text_columns(num_fields, wave, opt):
             assert n_hits > 0
 
 
-@pytest.mark.parametrize("rec", ["1", "0", "16384"])
+@pytest.mark.parametrize("rec", ["1", "16384"])
 @pytest.mark.parametrize("sub_docs", ["0", "8192", "512"])
 def test_bm25_posting_scorer_windows_duplicates_and_density_routing(sub_docs, rec, opt):
-    """The default routing: a batch of sparse terms goes to the posting-as-unit scorer (bm25p_kernel), whatever sub-range
-    size it cuts its windows from; terms repeated inside a query, terms sharing most of their documents, 40-term queries
+    """The default routing: a batch of sparse terms goes to the record scorer (bm25r_kernel, 8192 / 16384 hash slots), whatever
+    sub-range size it cuts its windows from; terms repeated inside a query, terms sharing most of their documents, 40-term queries
     and empty posting lists -- every hit and score bit == the oracle's dense term-order accumulation."""
     opt("bm25_sub_docs", sub_docs)
-    opt("bm25_rec", "0" if rec == "0" else "1")  # 0: bm25p_kernel; else bm25r_kernel with 8192 / 16384 hash slots
     if rec == "16384":
         opt("bm25_slots", rec)
     rng = np.random.default_rng(123)

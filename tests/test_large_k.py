@@ -247,15 +247,24 @@ def test_bm25_first_256_of_300_are_the_256_result(corpus):
 
 
 @gpu
-@pytest.mark.parametrize("knob", ["bm25_wave", "bm25_posting", "bm25_rec"])
+@pytest.mark.parametrize("knob", ["bm25_posting"])
 def test_bm25_other_scorers_keep_the_old_limit(knob, corpus, opt):
-    """The rounds run on the record scorers only: a knob that selects another scorer answers k > 256 as before, and says which."""
+    """The rounds run on the record scorers only: the knob that selects the dense accumulator answers k > 256 as before, and says
+    which."""
     c = corpus
     opt(knob, "0")
     with pytest.raises(capi.MsvsError) as e:
         c.ps.bm25_search_batch([[T_BIG]], c.dfs([[T_BIG]]), N_DOCS, c.total, 300)
     assert e.value.code == capi.ERR_UNSUPPORTED_K and knob in str(e.value)
     same_hits(c.ps.bm25_search_batch([[T_BIG]], c.dfs([[T_BIG]]), N_DOCS, c.total, 256)[0], c.oracle([T_BIG], 256), knob)
+
+
+@pytest.mark.parametrize("name", ["bm25_wave", "bm25_rec", "bm25_select2", "bm25_bounds8", "bm25_tables_ride", "bm25_fine_sample"])
+def test_bm25_retired_options_are_unknown(name):
+    """The knobs of the scorers, selection and bounds kernels that are gone: setting one is an error, not a silent no-op."""
+    with pytest.raises(capi.MsvsError) as e:
+        capi.set_option(name, "0")
+    assert e.value.code == capi.ERR_INVALID_ARGUMENT and name in str(e.value)
 
 
 # ---------------------------------------------------------------------------------------- fusion

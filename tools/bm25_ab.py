@@ -14,12 +14,9 @@ import myscaledb_amd.capi as capi  # noqa: E402
 from bench import build_postings  # noqa: E402
 
 VARIANTS = [
-    ("r5 default (records, 8192 slots, radix cut, 8-ary bounds)", {}),
-    ("round-4 scorer (bm25_rec=0, cutk=0, bounds8=0)", {"bm25_rec": "0", "bm25_cutk": "0", "bm25_bounds8": "0"}),
+    ("default (records, 8192 slots, radix cut)", {}),
     ("records, 16384 slots", {"bm25_slots": "16384"}),
     ("records, list-merge cut", {"bm25_cutk": "0"}),
-    ("records, binary bounds", {"bm25_bounds8": "0"}),
-    ("bm25p + radix cut + 8-ary bounds (bm25_rec=0)", {"bm25_rec": "0"}),
     # ablations of the record scorer (results are WRONG by construction: timing only)
     ("ablation: windows generated, nothing loaded or scored (dbg=8)", {"bm25_dbg": "8"}),
     ("ablation: no shared-document filter (dbg=1)", {"bm25_dbg": "1"}),
@@ -29,7 +26,6 @@ VARIANTS = [
     ("general record scorer (bm25_lean=0)", {"bm25_lean": "0"}),
     ("ablation: filter runs, its flags are ignored (dbg=16)", {"bm25_dbg": "16"}),
     ("experiment: an empty launch in front of the bounds launch (dbg=32; exact)", {"bm25_dbg": "32"}),
-    ("ranking select kernel (bm25_select2=0)", {"bm25_select2": "0"}),
     ("1.5 emit items per resident wavefront", {"bm25_items_per_wave": "1.5"}),
     ("four emit items per resident wavefront", {"bm25_items_per_wave": "4"}),
 ]
