@@ -170,7 +170,7 @@ MSVS_API int msvs_bin_index_search_rounds_device(const msvs_bin_index_t * index,
                                                  void * hip_stream);
 
 /* IVFSQ -- an inverted-file index of Float32 vectors that keeps 8-bit residual codes ONLY (no f32 row survives build): dim bytes
- * (padded to 16) + a u32 label per row.  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All arithmetic
+ * (padded to 16) + a u32 label per row; 4-bit codes or binary16 residuals with bit_size=4 / 16 (below).  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All arithmetic
  * is f32 with separately rounded operations (fl), no fma, IEEE division:
  *   - contents: nlist centroids c_l; ONE quantiser vmin[j], vmax[j] per dimension, step[j] = fl(fl(vmax[j] - vmin[j]) / 255);
  *     per row its list, label and dim codes; rows inside a list in ascending label order;
@@ -183,8 +183,21 @@ MSVS_API int msvs_bin_index_search_rounds_device(const msvs_bin_index_t * index,
  *     unfilled slots -1 and the metric's neutral value; cosine normalises the query, searches with IP and reports fl(1 - ip) in
  *     every slot; the filter is indexed by label.  The search over what the index stores is exact; the quantiser is lossy.
  *   - a row is assigned to its nearest centroid by L2 (L2 indexes) or by inner product (IP and cosine), as msvs_index_add does.
- * create: params as msvs_index_create's for IVFFLAT (ncentroids, kmeans_iters, train_sample, seed, ...).  dim is bounded by the
- *   scan's LDS stage (round_up(dim, 16) <= 2240), checked here and at load.
+ *   - bit_size=4 (create): the same index with 4-bit codes, two a stored byte: step[j] = fl(fl(vmax[j] - vmin[j]) / 15),
+ *     code = min(15, max(0, rint(t))) (ties to even), 0 where step[j] == 0; t, decode, training, the trained range, set_codebook's
+ *     checks and the clamping of rows outside the range as above.
+ *   - bit_size=16 (create): the code is the IEEE binary16 value nearest to r = fl(x_j - c_lj), round to nearest even, binary16
+ *     subnormals kept in both directions, overflow to +-inf, a NaN stays a NaN; decode: x^_j = fl(c_lj + float(h)), the conversion
+ *     to f32 being exact.  vmin / vmax keep their place in train, set_codebook, export and the file -- computed, validated, stored
+ *     and returned exactly as at 8 bits, so that there is one file layout and one binding -- but NEITHER enters encode or decode:
+ *     no row is clamped.  They remain the exact range of the training residuals, from which a host can see that nothing
+ *     approaches 65504.
+ *   Everything else -- the definition of search, assignment, labels, the filter, cosine, the limits of k and nprobe, search_rounds,
+ *   search_refine[_rounds] and their device forms -- is shared by the three widths.
+ * create: params as msvs_index_create's for IVFFLAT (ncentroids, kmeans_iters, train_sample, seed, ...) and bit_size, the bits of a
+ *   code: 8 (the default), 4 or 16, anything else MSVS_ERR_INVALID_ARGUMENT; without bit_size, or with bit_size=8, every result,
+ *   every file byte and every error code is what it was.  dim is bounded by the scan's LDS stage (round_up(dim, 16) <= 2240) at
+ *   every width, checked here and at load.
  * train: the IVFFLAT k-means over the rows, then vmin / vmax = exact minimum / maximum of the residuals of ALL n training rows
  *   against their assigned centroids; the same input gives the same bits.  set_codebook: centroids and quantiser from the caller.
  *   (vmin / vmax must be finite with vmax >= vmin: MSVS_ERR_INVALID_ARGUMENT otherwise).  Both must precede add
@@ -206,10 +219,16 @@ MSVS_API int msvs_bin_index_search_rounds_device(const msvs_bin_index_t * index,
  *   query has returned: two rows that carry the SAME label at the same distance are returned once when they straddle such a
  *   boundary (labels are expected to be distinct).  search / search_device keep refusing k > MSVS_MAX_K.
  * export: centroids nlist * dim, vmin / vmax dim each, nlist + 1 offsets, codes n * dim in NATURAL column order, labels n; any
- *   output may be NULL.
- * memory_usage after build <= n * (round_up(dim, 16) + 8) + the centroids, quantiser and offsets + 4096 bytes.
+ *   output may be NULL.  bit_size=4: one code a byte (values < 16), n * dim bytes.  bit_size=16: `codes` receives n * dim
+ *   little-endian uint16 bit patterns, 2 * n * dim bytes.  bit_size: 4, 8 or 16 (0 for NULL): what a host that loaded an index
+ *   sizes export's buffer by.
+ * memory_usage after build <= n * (round_up(dim, 16) + 8) + the centroids, quantiser and offsets + 4096 bytes; the row term is
+ *   round_up(ceil(dim / 2), 16) + 8 at bit_size=4 and 2 * round_up(dim, 16) + 8 at bit_size=16.
  * Files "sq_data" / "sq_ids" through the caller's stream openers (a built index only); load validates sizes, offsets, labels and
- * a checksum of each header: a corrupt or truncated file is MSVS_ERR_IO. */
+ * a checksum of each header: a corrupt or truncated file is MSVS_ERR_IO.  The data file's 56-byte header carries the code width
+ * in its `reserved` word: 0 for 8 bits (the files of before bit_size, byte for byte), 4 or 16; any other value is MSVS_ERR_IO.
+ * Its codes section is n * dim bytes (8), n * ceil(dim / 2) bytes with code j in the low (even j) or high nibble of byte j / 2 and a
+ * zero pad nibble at odd dim (4; a non-zero one is MSVS_ERR_IO), or 2 * n * dim bytes, little endian (16), in natural order. */
 typedef struct msvs_sq_index msvs_sq_index_t;
 MSVS_API int msvs_sq_index_create(int metric, size_t dim, const char * params, msvs_sq_index_t ** out);
 MSVS_API void msvs_sq_index_free(msvs_sq_index_t * index);
@@ -222,6 +241,7 @@ MSVS_API int msvs_sq_index_ready(const msvs_sq_index_t * index);
 MSVS_API size_t msvs_sq_index_num_data(const msvs_sq_index_t * index);
 MSVS_API size_t msvs_sq_index_num_lists(const msvs_sq_index_t * index);
 MSVS_API size_t msvs_sq_index_memory_usage(const msvs_sq_index_t * index);
+MSVS_API size_t msvs_sq_index_bit_size(const msvs_sq_index_t * index);
 MSVS_API int msvs_sq_index_search(const msvs_sq_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
                                   const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
 MSVS_API int msvs_sq_index_search_device(const msvs_sq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t nprobe,

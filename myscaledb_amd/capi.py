@@ -46,6 +46,7 @@ SYMBOLS = [
     "msvs_sq_index_create", "msvs_sq_index_free", "msvs_sq_index_train", "msvs_sq_index_set_codebook", "msvs_sq_index_add",
     "msvs_sq_index_build", "msvs_sq_index_ready", "msvs_sq_index_num_data", "msvs_sq_index_num_lists", "msvs_sq_index_memory_usage",
     "msvs_sq_index_search", "msvs_sq_index_search_device", "msvs_sq_index_export", "msvs_sq_index_serialize_io", "msvs_sq_index_load_io",
+    "msvs_sq_index_bit_size",
     "msvs_pq_index_create", "msvs_pq_index_free", "msvs_pq_index_train", "msvs_pq_index_set_codebook", "msvs_pq_index_add",
     "msvs_pq_index_build", "msvs_pq_index_ready", "msvs_pq_index_num_data", "msvs_pq_index_num_lists", "msvs_pq_index_memory_usage",
     "msvs_pq_index_bit_size", "msvs_pq_index_query_tables", "msvs_pq_index_export_row_terms",
@@ -470,7 +471,9 @@ class _CodedIndex:
 
 class SqIndex(_CodedIndex):
     """msvs_sq_index_t: the IVFSQ index -- coarse centroids, one per-dimension 8-bit quantiser of the residuals, and per row its
-    list, label and dim code bytes (no f32 row is kept).  params as Index's for IVFFLAT ("ncentroids=N,kmeans_iters=I,...")."""
+    list, label and dim code bytes (no f32 row is kept).  params as Index's for IVFFLAT ("ncentroids=N,kmeans_iters=I,...") and,
+    optionally, bit_size: 4 (4-bit codes) or 16 (binary16 residuals).  .bits is the index's own answer (msvs_sq_index_bit_size): 4,
+    8 or 16."""
     _c = "msvs_sq_index"
 
     def __init__(self, metric, dim, params="", _handle=None):
@@ -480,6 +483,7 @@ class SqIndex(_CodedIndex):
             self._h = _handle
         else:
             _check(lib().msvs_sq_index_create(int(metric), C.c_size_t(dim), params.encode(), C.byref(self._h)))
+        self.bits = self._size("bit_size")
 
     def set_codebook(self, centroids, vmin, vmax, nlist=None, mem=MEM_HOST):
         """mem=MEM_DEVICE: centroids, vmin and vmax are raw device addresses (ints); nlist is the number of centroid rows."""
@@ -492,25 +496,26 @@ class SqIndex(_CodedIndex):
                                                 MEM_HOST))
 
     def export(self, with_lists=True):
-        """-> (centroids [nlist, dim], vmin [dim], vmax [dim], list offsets [nlist + 1], codes [n, dim] u8 in natural column order,
-        labels [n]) in list-major order; with_lists=False (an index not built yet): the codebook only, None for the rest."""
+        """-> (centroids [nlist, dim], vmin [dim], vmax [dim], list offsets [nlist + 1], codes [n, dim] u8 in natural column order
+        (bits 4: one code a byte; bits 16: uint16, the binary16 bit patterns), labels [n]) in list-major order; with_lists=False (an
+        index not built yet): the codebook only, None for the rest."""
         nl, d = self.num_lists, self.dim
         cent = np.empty((nl, d), np.float32)
         lo, hi = np.empty(d, np.float32), np.empty(d, np.float32)
         off = codes = labels = None
         if with_lists:
             n = self.num_data
-            off, codes, labels = np.empty(nl + 1, np.int64), np.empty((n, d), np.uint8), np.empty(n, np.int64)
+            off, codes, labels = np.empty(nl + 1, np.int64), np.empty((n, d), np.uint16 if self.bits == 16 else np.uint8), np.empty(n, np.int64)
         _check(lib().msvs_sq_index_export(self._h, _p(cent, C.c_float), _p(lo, C.c_float), _p(hi, C.c_float), _p(off, C.c_int64),
-                                          _p(codes, C.c_uint8), _p(labels, C.c_int64)))
+                                          None if codes is None else codes.ctypes.data_as(C.POINTER(C.c_uint8)), _p(labels, C.c_int64)))
         return cent, lo, hi, off, codes, labels
 
     @classmethod
-    def load_io(cls, store, metric=None, dim=None):
-        """metric / dim come from the file (SqHeader: magic[8], u32 version, i32 metric, u64 dim, ...); where given, they must
-        agree with it (ValueError otherwise)."""
+    def load_io(cls, store, metric=None, dim=None, bits=None):
+        """metric / dim come from the file (SqHeader: magic[8], u32 version, i32 metric, u64 dim, ...), bits from the loaded index;
+        where given, they must agree with it (ValueError otherwise)."""
         h, (f_metric, f_dim) = cls._load(store, "sq_data", "<iQ")
-        return cls(f_metric, f_dim, _handle=h)._agree("IVFSQ", metric=metric, dim=dim)
+        return cls(f_metric, f_dim, _handle=h)._agree("IVFSQ", metric=metric, dim=dim, bits=bits)
 
 
 class PqIndex(_CodedIndex):

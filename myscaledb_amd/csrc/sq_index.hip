@@ -1,5 +1,6 @@
 // sq_index.hip -- the IVFSQ index (include/msvs.h: msvs_sq_index_*): coarse centroids + ONE per-dimension 8-bit quantiser of the
-// residuals; codes, lists and labels are all the index keeps.  Semantics and layout: sq_ivf_kernels.hpp, DESIGN.md 4.11.
+// residuals (bit_size=4: 4-bit; bit_size=16: binary16 residuals, no quantiser in the arithmetic); codes, lists and labels are all
+// the index keeps.  Semantics and layout: sq_ivf_kernels.hpp, sq_layout.hpp, DESIGN.md 4.11.
 // Here: the geometry, the quantiser (bounds, range pass), the scan's shapes and dispatch, the data file and the stored order of a
 // row.  Everything the index has in common with IVFPQ -- staging, add, build, the search skeleton, labels, the id file -- is
 // coded_ivf.hpp, which also lists what is reused as it is.
@@ -14,9 +15,9 @@ namespace
 {
 constexpr const char * SQ = "IVFSQ";
 
-/// ldc: bytes of a stored row = floats of a padded query / centroid row
+/// floats of a padded query / centroid row (= bytes of a stored row at 8 bits)
 inline uint32_t sq_ld(size_t dim) { return (uint32_t)round_up(dim, (size_t)16); }
-/// the smallest tile with the largest k must fit the scan's LDS budget
+/// the smallest tile with the largest k must fit the scan's LDS budget (the 8-bit image: no width has a larger one)
 inline bool sq_fits(size_t dim) { return dim >= 1 && dim <= 8192 && sq_lds_bytes(2, sq_ld(dim) / 4, MSVS_MAX_K) <= SCAN_LDS_BUDGET; }
 
 inline float sq_ord2f(uint32_t o)
@@ -28,17 +29,53 @@ inline float sq_ord2f(uint32_t o)
 }
 }
 
-struct msvs_sq_index : CodedIvf // ld = row_bytes = round_up(dim, 16); codes: max(n, 1) rows, not zeroed
+struct msvs_sq_index : CodedIvf // ld = round_up(dim, 16), row_bytes = 16 sq_row_words(bits, ld); codes: max(n, 1) rows, not zeroed
 {
+    uint32_t bits = 8;                 // 4, 8 or 16
     std::vector<float> h_vmin, h_vmax; // dim
-    DevBuf<float> d_vmin, d_step;      // ld each, zero padded
+    DevBuf<float> d_vmin, d_step;      // ld each, zero padded (bits 16: none, the range enters no arithmetic)
 };
 
-static void sq_set_geometry(msvs_sq_index & ix, int metric, size_t dim)
+static void sq_set_geometry(msvs_sq_index & ix, int metric, size_t dim, uint32_t bits)
 {
     ix.metric = metric;
     ix.dim = dim;
-    ix.ld = ix.row_bytes = sq_ld(dim);
+    ix.bits = bits;
+    ix.ld = sq_ld(dim);
+    ix.row_bytes = 16 * sq_row_words(bits, ix.ld);
+}
+
+/// bytes of a code in export's buffer (one code a byte at 4 and 8 bits, a little-endian uint16 at 16)
+inline size_t sq_export_size(uint32_t bits) { return bits == 16 ? 2 : 1; }
+/// bytes of a row in the data file: two codes a byte at 4 bits
+inline size_t sq_file_row(uint32_t bits, size_t dim) { return bits == 4 ? (dim + 1) / 2 : dim * sq_export_size(bits); }
+
+/// code of natural column j out of / into a stored row (sq_layout.hpp)
+inline uint16_t sq_get(const uint8_t * row, uint32_t j, uint32_t ld, uint32_t bits)
+{
+    if (bits == 8)
+        return row[sq_stored_pos(j, ld)];
+    if (bits == 4)
+    {
+        const uint32_t p = sq4_stored_pos(j, ld);
+        return (row[p >> 1] >> (4 * (p & 1))) & 15;
+    }
+    uint16_t h;
+    memcpy(&h, row + 2 * (size_t)sq16_stored_pos(j, ld), 2);
+    return h;
+}
+
+inline void sq_put(uint8_t * row, uint32_t j, uint32_t ld, uint32_t bits, uint16_t code) // (row: zeroed)
+{
+    if (bits == 8)
+        row[sq_stored_pos(j, ld)] = (uint8_t)code;
+    else if (bits == 4)
+    {
+        const uint32_t p = sq4_stored_pos(j, ld);
+        row[p >> 1] |= (uint8_t)(code << (4 * (p & 1)));
+    }
+    else
+        memcpy(row + 2 * (size_t)sq16_stored_pos(j, ld), &code, 2);
 }
 
 /// centroids (nlist x ld on the device already) + quantiser bounds -> the index's codebook
@@ -47,12 +84,18 @@ static void sq_set_quantiser(msvs_sq_index & ix, const float * vmin, const float
     const size_t d = ix.dim;
     ix.h_vmin.assign(vmin, vmin + d);
     ix.h_vmax.assign(vmax, vmax + d);
+    if (ix.bits == 16)
+    {
+        finish_codebook(ix, stream);
+        return;
+    }
     std::vector<float> pm(ix.ld, 0.f), ps(ix.ld, 0.f);
+    const float top = ix.bits == 4 ? 15.0f : 255.0f;
     for (size_t j = 0; j < d; j++)
     {
         const float range = vmax[j] - vmin[j];
         pm[j] = vmin[j];
-        ps[j] = range / 255.0f;
+        ps[j] = range / top;
     }
     ix.d_vmin.alloc(ix.ld);
     ix.d_step.alloc(ix.ld);
@@ -68,9 +111,13 @@ extern "C" int msvs_sq_index_create(int metric, size_t dim, const char * params,
         check_metric(metric, SQ);
         if (!sq_fits(dim))
             fail(MSVS_ERR_INVALID_ARGUMENT, "dimension %zu out of range for the IVFSQ index (the list scan's LDS stage holds up to 2240)", dim);
-        check_ncentroids(parse_params(params));
+        const auto p = parse_params(params);
+        check_ncentroids(p);
+        const long bits = param_int(p, "bit_size", 8);
+        if (bits != 4 && bits != 8 && bits != 16)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the IVFSQ index has 4, 8 or 16 bits per dimension (bit_size %ld)", bits);
         std::unique_ptr<msvs_sq_index> ix(new msvs_sq_index);
-        sq_set_geometry(*ix, metric, dim);
+        sq_set_geometry(*ix, metric, dim, (uint32_t)bits);
         ix->params = params ? params : "";
         MSVS_HIP(hipGetDevice(&ix->device));
         *out = ix.release();
@@ -158,8 +205,11 @@ extern "C" int msvs_sq_index_add(msvs_sq_index_t * ix, const float * x, const in
 {
     return guarded([&] {
         add_rows(ix, x, ids, n, mem, SQ, false, [&](const float * d_x, const int32_t * d_assign, size_t m, uint8_t * dst, hipStream_t stream) {
-            hipLaunchKernelGGL(sq_encode_kernel, dim3((unsigned)ceil_div(m * ix->ld, (size_t)BLOCK)), dim3(BLOCK), 0, stream, d_x, d_assign,
-                               ix->centroids.p, ix->d_vmin.p, ix->d_step.p, m, (uint32_t)ix->dim, ix->ld, ix->ld, dst);
+            const uint32_t ldc = ix->bits == 4 ? ix->row_bytes : ix->ld; // elements of a row, one thread each
+            with_int<8, 4, 16>((int)ix->bits, [&](auto b) {
+                hipLaunchKernelGGL(sq_encode_kernel<decltype(b)::value>, dim3((unsigned)ceil_div(m * ldc, (size_t)BLOCK)), dim3(BLOCK), 0, stream,
+                                   d_x, d_assign, ix->centroids.p, ix->d_vmin.p, ix->d_step.p, m, (uint32_t)ix->dim, ix->ld, ldc, dst);
+            });
         });
     });
 }
@@ -168,7 +218,7 @@ extern "C" int msvs_sq_index_build(msvs_sq_index_t * ix)
 {
     return guarded([&] {
         build_lists(ix, SQ, 1, false, [&](const uint8_t * src, uint8_t * dst, const uint32_t * d_pos, size_t m, hipStream_t stream) {
-            const uint32_t ld16 = ix->ld / 16;
+            const uint32_t ld16 = ix->row_bytes / 16;
             hipLaunchKernelGGL(sq_scatter_rows_kernel, dim3((unsigned)ceil_div(m * ld16, (size_t)256)), dim3(256), 0, stream,
                                reinterpret_cast<const uint4 *>(src), reinterpret_cast<uint4 *>(dst), d_pos, m, ld16);
         });
@@ -178,6 +228,7 @@ extern "C" int msvs_sq_index_build(msvs_sq_index_t * ix)
 extern "C" int msvs_sq_index_ready(const msvs_sq_index_t * ix) { return ix && ix->ready ? 1 : 0; }
 extern "C" size_t msvs_sq_index_num_data(const msvs_sq_index_t * ix) { return ix ? (ix->ready ? ix->n : ix->staged) : 0; }
 extern "C" size_t msvs_sq_index_num_lists(const msvs_sq_index_t * ix) { return ix ? ix->nlist : 0; }
+extern "C" size_t msvs_sq_index_bit_size(const msvs_sq_index_t * ix) { return ix ? ix->bits : 0; }
 extern "C" size_t msvs_sq_index_memory_usage(const msvs_sq_index_t * ix)
 {
     return ix ? coded_bytes(*ix) + ix->d_vmin.bytes() + ix->d_step.bytes() : 0;
@@ -187,17 +238,19 @@ extern "C" size_t msvs_sq_index_memory_usage(const msvs_sq_index_t * ix)
 
 /// tiles of 2, 4 or 8 queries (no T = 1).  A later rank round (a.after) takes the AFTER form, which exists with four top-k
 /// registers per lane only: such a round follows one of MSVS_MAX_K ranks, and its own k is the search's remainder
+template <int BITS>
 static void launch_sq_ivf_scan(int metric, uint32_t T, uint32_t grid, const SqIvfParams & a, hipStream_t stream)
 {
     with_int<M_IP, M_L2>(metric, [&](auto m) {
         with_int<2, 4, 8>(T, [&](auto t) {
             constexpr int METRIC = decltype(m)::value, TQ = decltype(t)::value;
+            const size_t lds = sq_lds_bytes(TQ, a.ld4, a.k, BITS);
             if (a.after)
-                hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, TQ, 4, 1>), dim3(grid), dim3(BLOCK), sq_lds_bytes(TQ, a.ld4, a.k), stream, a);
+                hipLaunchKernelGGL((sq_ivf_scan_kernel<BITS, METRIC, TQ, 4, 1>), dim3(grid), dim3(BLOCK), lds, stream, a);
             else
                 with_int<1, 2, 4>(r_for_k(a.k), [&](auto r) {
                     constexpr int R = decltype(r)::value;
-                    hipLaunchKernelGGL((sq_ivf_scan_kernel<METRIC, TQ, R>), dim3(grid), dim3(BLOCK), sq_lds_bytes(TQ, a.ld4, a.k), stream, a);
+                    hipLaunchKernelGGL((sq_ivf_scan_kernel<BITS, METRIC, TQ, R>), dim3(grid), dim3(BLOCK), lds, stream, a);
                 });
         });
     });
@@ -212,7 +265,7 @@ static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, 
         ix, SQ, "sq_ivf_scan", d_queries, nq, k, k_max, nprobe, d_alive, nbits, d_ids, d_dis, stream, 16, options().sq_ivf_rpb,
         [&](size_t n_pairs, size_t k_) {
             uint32_t T = n_pairs >= 16 * ix.nlist ? 8 : (n_pairs >= 2 * ix.nlist ? 4 : 2);
-            while (T > 2 && sq_lds_bytes(T, ld4, (uint32_t)k_) > SCAN_LDS_BUDGET)
+            while (T > 2 && sq_lds_bytes(T, ld4, (uint32_t)k_, ix.bits) > SCAN_LDS_BUDGET)
                 T /= 2;
             return T;
         },
@@ -225,7 +278,7 @@ static void sq_search_device(const msvs_sq_index & ix, const float * d_queries, 
             a.vmin = reinterpret_cast<const float4 *>(ix.d_vmin.p);
             a.step = reinterpret_cast<const float4 *>(ix.d_step.p);
             a.ld4 = ld4;
-            launch_sq_ivf_scan(r.metric, T, grid, a, stream);
+            with_int<8, 4, 16>((int)ix.bits, [&](auto b) { launch_sq_ivf_scan<decltype(b)::value>(r.metric, T, grid, a, stream); });
         });
 }
 
@@ -334,20 +387,25 @@ extern "C" int msvs_sq_index_search_refine_rounds(const msvs_sq_index_t * ix, co
 
 // ------------------------------------------------------------------------------------------- export and files
 
-/// the built index's codes in NATURAL column order (n x dim) and its labels, on the host
+/// the built index's codes in NATURAL column order (n x dim; export's form: a byte a code, a little-endian uint16 at 16 bits) and
+/// its labels, on the host
 static void sq_fetch(const msvs_sq_index & ix, uint8_t * codes, int64_t * ids, hipStream_t stream)
 {
-    const size_t piece = std::max<size_t>(1, ((size_t)64 << 20) / ix.ld);
+    const size_t rb = ix.row_bytes, es = sq_export_size(ix.bits);
+    const size_t piece = std::max<size_t>(1, ((size_t)64 << 20) / rb);
     std::vector<uint8_t> buf;
     for (size_t r0 = 0; codes && r0 < ix.n; r0 += piece)
     {
         const size_t m = std::min(piece, ix.n - r0);
-        buf.resize(m * ix.ld);
-        MSVS_HIP(hipMemcpyAsync(buf.data(), ix.codes.p + r0 * ix.ld, m * ix.ld, hipMemcpyDeviceToHost, stream));
+        buf.resize(m * rb);
+        MSVS_HIP(hipMemcpyAsync(buf.data(), ix.codes.p + r0 * rb, m * rb, hipMemcpyDeviceToHost, stream));
         MSVS_HIP(hipStreamSynchronize(stream));
         for (size_t r = 0; r < m; r++)
             for (size_t j = 0; j < ix.dim; j++)
-                codes[(r0 + r) * ix.dim + j] = buf[r * ix.ld + sq_stored_pos((uint32_t)j, ix.ld)];
+            {
+                const uint16_t c = sq_get(&buf[r * rb], (uint32_t)j, ix.ld, ix.bits);
+                memcpy(codes + ((r0 + r) * ix.dim + j) * es, &c, es); // (little endian: the low byte is the code at 4 and 8 bits)
+            }
     }
     fetch_labels(ix, ids, stream);
 }
@@ -375,7 +433,7 @@ struct SqHeader // 56 bytes, little endian
     uint32_t version; // 1
     int32_t metric;
     uint64_t dim, nlist, n;
-    uint64_t reserved;
+    uint64_t reserved; // the code width: 0 for 8 bits (the files of before bit_size), 4 or 16
     uint64_t check; // FNV-1a of the bytes before it
 };
 }
@@ -386,9 +444,18 @@ extern "C" int msvs_sq_index_serialize_io(const msvs_sq_index_t * ix, const msvs
         DeviceGuard on_device(ix ? ix->device : -1);
         check_index(ix);
         check_built(*ix, SQ);
-        std::vector<uint8_t> codes(ix->n * ix->dim);
+        std::vector<uint8_t> codes(ix->n * ix->dim * sq_export_size(ix->bits));
         std::vector<int64_t> ids(ix->n);
         sq_fetch(*ix, codes.data(), ids.data(), thread_stream());
+        if (ix->bits == 4) // the file keeps two codes a byte in natural order: code j in the low (even j) or high nibble of byte j / 2
+        {
+            const size_t fr = sq_file_row(4, ix->dim);
+            std::vector<uint8_t> packed(ix->n * fr, 0);
+            for (size_t r = 0; r < ix->n; r++)
+                for (size_t j = 0; j < ix->dim; j++)
+                    packed[r * fr + j / 2] |= (uint8_t)(codes[r * ix->dim + j] << (4 * (j & 1)));
+            codes.swap(packed);
+        }
         {
             IoStream f(io, "sq_data", 1);
             SqHeader h{};
@@ -398,6 +465,7 @@ extern "C" int msvs_sq_index_serialize_io(const msvs_sq_index_t * ix, const msvs
             h.dim = ix->dim;
             h.nlist = ix->nlist;
             h.n = ix->n;
+            h.reserved = ix->bits == 8 ? 0 : ix->bits;
             h.check = fnv1a(&h, offsetof(SqHeader, check));
             f.write(&h, sizeof(h));
             f.write(ix->h_cent.data(), ix->h_cent.size() * 4);
@@ -426,33 +494,48 @@ extern "C" int msvs_sq_index_load_io(const msvs_io_t * io, msvs_sq_index_t ** ou
             SqHeader h{};
             f.read(&h, sizeof(h));
             if (memcmp(h.magic, "MSVSSQ01", 8) != 0 || h.version != 1 || h.check != fnv1a(&h, offsetof(SqHeader, check))
-                || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || !sq_fits(h.dim))
+                || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || !sq_fits(h.dim) || (h.reserved != 0 && h.reserved != 4 && h.reserved != 16))
                 fail(MSVS_ERR_IO, "corrupt msvs IVFSQ index header");
-            sq_set_geometry(*ix, h.metric, (size_t)h.dim);
+            sq_set_geometry(*ix, h.metric, (size_t)h.dim, h.reserved ? (uint32_t)h.reserved : 8);
             ix->nlist = (size_t)h.nlist;
             ix->n = (size_t)h.n;
             read_grow(f, cent, ix->nlist * ix->dim);
             read_grow(f, lo, ix->dim);
             read_grow(f, hi, ix->dim);
             read_list_offsets(f, *ix, SQ);
-            read_grow(f, codes, ix->n * ix->dim);
+            read_grow(f, codes, ix->n * sq_file_row(ix->bits, ix->dim));
             expect_end(f);
+            if (ix->bits == 4 && (ix->dim & 1))
+                for (size_t r = 0, fr = sq_file_row(4, ix->dim); r < ix->n; r++)
+                    if (codes[r * fr + fr - 1] >> 4)
+                        fail(MSVS_ERR_IO, "corrupt msvs IVFSQ index: a pad nibble of row %zu is not 0", r);
         }
         const std::vector<int64_t> ids = read_id_file(io, "sq_ids", "MSVSSQID", ix->n, SQ);
         // the stored form: columns permuted per row, labels as u32
         upload_centroids(*ix, cent.data(), ix->nlist, MSVS_MEM_HOST, stream);
         sq_set_quantiser(*ix, lo.data(), hi.data(), stream);
         alloc_lists(*ix, ix->n, 1, false, stream);
-        const size_t piece = std::max<size_t>(1, ((size_t)64 << 20) / ix->ld);
+        const size_t rb = ix->row_bytes, fr = sq_file_row(ix->bits, ix->dim);
+        const size_t piece = std::max<size_t>(1, ((size_t)64 << 20) / rb);
         std::vector<uint8_t> buf;
         for (size_t r0 = 0; r0 < ix->n; r0 += piece)
         {
             const size_t m = std::min(piece, ix->n - r0);
-            buf.assign(m * ix->ld, 0);
+            buf.assign(m * rb, 0);
             for (size_t r = 0; r < m; r++)
+            {
+                const uint8_t * src = &codes[(r0 + r) * fr];
                 for (size_t j = 0; j < ix->dim; j++)
-                    buf[r * ix->ld + sq_stored_pos((uint32_t)j, ix->ld)] = codes[(r0 + r) * ix->dim + j];
-            MSVS_HIP(hipMemcpyAsync(ix->codes.p + r0 * ix->ld, buf.data(), m * ix->ld, hipMemcpyHostToDevice, stream));
+                {
+                    uint16_t c = 0;
+                    if (ix->bits == 4)
+                        c = (src[j / 2] >> (4 * (j & 1))) & 15;
+                    else
+                        memcpy(&c, src + j * sq_export_size(ix->bits), sq_export_size(ix->bits));
+                    sq_put(&buf[r * rb], (uint32_t)j, ix->ld, ix->bits, c);
+                }
+            }
+            MSVS_HIP(hipMemcpyAsync(ix->codes.p + r0 * rb, buf.data(), m * rb, hipMemcpyHostToDevice, stream));
             MSVS_HIP(hipStreamSynchronize(stream));
         }
         finish_load(*ix, ids, stream);
