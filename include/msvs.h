@@ -177,12 +177,16 @@ MSVS_API int msvs_bin_index_search_rounds_device(const msvs_bin_index_t * index,
  *   - stored row x: the row as fed (L2, IP) or the normalised row (cosine; msvs_normalize_f32's arithmetic);
  *   - encode in list l: r = fl(x_j - c_lj), t = fl(fl(r - vmin[j]) / step[j]), code = min(255, max(0, rint(t))) (ties to even),
  *     0 where step[j] == 0; rows outside the trained range are clamped;
+ *     a NaN residual (a NaN in the row, or inf - inf) has code 0, +inf the top code and -inf code 0, at 8 and at 4 bits;
  *   - decode: x^_j = fl(c_lj + fl(vmin[j] + fl(float(code) * step[j])));
  *   - search = the IVFFLAT search of the decoded rows: the canonical exact top-min(nprobe, nlist) lists by (distance to the
  *     centroid, list id), every alive row of them scored with the canonical scan arithmetic over x^, top-k by (distance, label),
  *     unfilled slots -1 and the metric's neutral value; cosine normalises the query, searches with IP and reports fl(1 - ip) in
  *     every slot; the filter is indexed by label.  The search over what the index stores is exact; the quantiser is lossy.
  *   - a row is assigned to its nearest centroid by L2 (L2 indexes) or by inner product (IP and cosine), as msvs_index_add does.
+ *     Its rule for a row without a finite score: the score of centroid l is |c_l|^2 - 2 <c_l, x> (L2) or -<c_l, x>; the smallest
+ *     score that is not NaN and not above FLT_MAX wins, -inf included, the lowest l among equals; a row all of whose scores are NaN
+ *     or +inf goes to list 0.
  *   - bit_size=4 (create): the same index with 4-bit codes, two a stored byte: step[j] = fl(fl(vmax[j] - vmin[j]) / 15),
  *     code = min(15, max(0, rint(t))) (ties to even), 0 where step[j] == 0; t, decode, training, the trained range, set_codebook's
  *     checks and the clamping of rows outside the range as above.
@@ -200,7 +204,10 @@ MSVS_API int msvs_bin_index_search_rounds_device(const msvs_bin_index_t * index,
  *   every width, checked here and at load.
  * train: the IVFFLAT k-means over the rows, then vmin / vmax = exact minimum / maximum of the residuals of ALL n training rows
  *   against their assigned centroids; the same input gives the same bits.  set_codebook: centroids and quantiser from the caller.
- *   (vmin / vmax must be finite with vmax >= vmin: MSVS_ERR_INVALID_ARGUMENT otherwise).  Both must precede add
+ *   (vmin / vmax must be finite with vmax >= vmin: MSVS_ERR_INVALID_ARGUMENT otherwise).  At 8 and 4 bits fl(vmax[j] - vmin[j]) must
+ *   be finite too, or the step is infinite and every row decodes to NaN: set_codebook refuses such bounds and train refuses rows whose
+ *   residuals span such a range (one infinite element is enough), both with MSVS_ERR_INVALID_ARGUMENT and without leaving a codebook;
+ *   load refuses such a file with MSVS_ERR_IO.  At bit_size=16 train accepts them: the range enters no arithmetic.  Both must precede add
  *   (MSVS_ERR_NOT_READY from add before either).
  * add: any number of chunks before build; rows are encoded as they arrive, only codes, lists and labels are staged.  ids: labels
  *   in [0, 2^32 - 1) (MSVS_ERR_ID_RANGE otherwise), NULL = staging order; labels are expected to be distinct, as for
@@ -275,6 +282,9 @@ MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t **
  *     (+-FLT_MAX), unfilled slots -1 and that value; cosine normalises the query, searches with IP and reports fl(1 - ip) in every
  *     slot; the filter is indexed by label.  The search over what the index stores is exact; the quantiser is lossy.
  *   - a row is assigned to its nearest centroid by L2 (L2 indexes) or by inner product (IP and cosine), as msvs_index_add does.
+ *     Its rule for a row without a finite score: the score of centroid l is |c_l|^2 - 2 <c_l, x> (L2) or -<c_l, x>; the smallest
+ *     score that is not NaN and not above FLT_MAX wins, -inf included, the lowest l among equals; a row all of whose scores are NaN
+ *     or +inf goes to list 0.
  * create: params as msvs_index_create's for IVFFLAT (ncentroids, kmeans_iters, train_sample, seed, ...) plus m, the number of
  *   sub-quantisers (required), and bit_size, the bits of a code: 8 (the default) or 4, anything else MSVS_ERR_INVALID_ARGUMENT.
  *   bit_size=8: 1 <= m <= 128, m divides dim, dim <= 8192, and the list scan's smallest LDS image, m KiB of tables +
@@ -285,7 +295,9 @@ MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t **
  * train: the coarse centroids by the IVFFLAT k-means over the rows; then the residuals fl(x - c_l) of at most 262144 training rows
  *   (row floor(i * n / cap), i < cap = min(n, 262144)); for every s the dsub columns of sub-space s go through the same k-means
  *   (L2, ksub centroids, the same iterations and seed): its centroids are cb[s].  n < ksub: MSVS_ERR_INVALID_ARGUMENT.  The same input
- *   gives the same bits.  set_codebook: centroids (nlist * dim) and codebooks (m * ksub * dsub, [s][j][t]) from the caller; a
+ *   gives the same bits.  Training rows with NaN or infinite elements: a coarse centroid or a codebook entry that comes out non-finite
+ *   is MSVS_ERR_INVALID_ARGUMENT and leaves the index without a codebook, as set_codebook does (such a row that no trainer's sample
+ *   holds changes nothing): train never leaves a non-finite codebook.  set_codebook: centroids (nlist * dim) and codebooks (m * ksub * dsub, [s][j][t]) from the caller; a
  *   non-finite codebook entry is MSVS_ERR_INVALID_ARGUMENT and leaves the index without a codebook.  Both must precede add
  *   (MSVS_ERR_NOT_READY from add before either; MSVS_ERR_INVALID_ARGUMENT from either after add).
  * add: any number of chunks before build; rows are encoded as they arrive, only codes, lists and labels are staged.  ids: labels

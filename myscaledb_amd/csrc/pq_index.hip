@@ -182,6 +182,18 @@ extern "C" int msvs_pq_index_train(msvs_pq_index_t * ix, const float * x, size_t
         const size_t d = ix->dim, m = ix->m, dsub = ix->dsub;
         pq_drop_codebook(*ix);
         train_centroids(*ix, x, n, mem, stream);
+        {
+            // a NaN or infinite training row in the coarse trainer's sample ends in the mean of its list; the sub-codebooks trained on the
+            // residuals could still come out finite (the residual sample is another one), so the coarse centroids are checked here
+            std::vector<float> hc(ix->nlist * d);
+            MSVS_HIP(hipMemcpy2D(hc.data(), d * 4, ix->centroids.p, (size_t)ix->ld * 4, d * 4, ix->nlist, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < hc.size(); i++)
+                if (!std::isfinite(hc[i]))
+                {
+                    pq_drop_codebook(*ix);
+                    fail(MSVS_ERR_INVALID_ARGUMENT, "coarse centroid %zu is not finite: a training row is NaN, infinite or overflows", i / d);
+                }
+        }
         // the residuals fl(x - c_l) of the evenly spaced training rows floor(i * n / cap), dense on the device
         const size_t cap = std::min(n, PQ_TRAIN_ROWS);
         DevBuf<float> d_res(cap * d);

@@ -78,7 +78,25 @@ inline void sq_put(uint8_t * row, uint32_t j, uint32_t ld, uint32_t bits, uint16
         memcpy(row + 2 * (size_t)sq16_stored_pos(j, ld), &code, 2);
 }
 
-/// centroids (nlist x ld on the device already) + quantiser bounds -> the index's codebook
+/// the first dimension whose bounds sq_set_quantiser cannot turn into a finite step (vmin, vmax or fl(vmax - vmin) is not finite), or
+/// dim if there is none.  With an infinite step every code of the column is 0 and decodes to vmin + 0 * inf = NaN: the index would
+/// build and never return a row.  At 16 bits the range enters no arithmetic and any range passes.
+static size_t sq_unusable_dimension(uint32_t bits, const float * vmin, const float * vmax, size_t dim)
+{
+    for (size_t j = 0; bits != 16 && j < dim; j++)
+        if (!std::isfinite(vmin[j]) || !std::isfinite(vmax[j]) || !std::isfinite(vmax[j] - vmin[j]))
+            return j;
+    return dim;
+}
+
+static void sq_drop_codebook(msvs_sq_index & ix)
+{
+    ix.trained = false;
+    ix.nlist = 0;
+    ix.centroids.release();
+}
+
+/// centroids (nlist x ld on the device already) + quantiser bounds (sq_unusable_dimension: none) -> the index's codebook
 static void sq_set_quantiser(msvs_sq_index & ix, const float * vmin, const float * vmax, hipStream_t stream)
 {
     const size_t d = ix.dim;
@@ -149,13 +167,15 @@ extern "C" int msvs_sq_index_set_codebook(msvs_sq_index_t * ix, const float * ce
         ix->trained = false;
         ix->nlist = nlist;
         upload_centroids(*ix, centroids, nlist, mem, stream);
-        for (size_t j = 0; j < ix->dim; j++)
+        size_t bad = sq_unusable_dimension(ix->bits, lo.data(), hi.data(), ix->dim);
+        for (size_t j = 0; j < bad; j++)
             if (!std::isfinite(lo[j]) || !std::isfinite(hi[j]) || hi[j] < lo[j])
-            {
-                ix->nlist = 0;
-                ix->centroids.release();
-                fail(MSVS_ERR_INVALID_ARGUMENT, "quantiser bounds of dimension %zu are not finite or vmax < vmin", j);
-            }
+                bad = j;
+        if (bad < ix->dim)
+        {
+            sq_drop_codebook(*ix);
+            fail(MSVS_ERR_INVALID_ARGUMENT, "quantiser bounds of dimension %zu are not finite, vmax < vmin or vmax - vmin overflows", bad);
+        }
         sq_set_quantiser(*ix, lo.data(), hi.data(), stream);
     });
 }
@@ -196,6 +216,14 @@ extern "C" int msvs_sq_index_train(msvs_sq_index_t * ix, const float * x, size_t
             const bool seen = range[j] <= range[ix->dim + j]; // (a column of NaNs: the empty range 0 .. 0)
             lo[j] = seen ? sq_ord2f(range[j]) : 0.f;
             hi[j] = seen ? sq_ord2f(range[ix->dim + j]) : 0.f;
+        }
+        const size_t bad = sq_unusable_dimension(ix->bits, lo.data(), hi.data(), ix->dim);
+        if (bad < ix->dim)
+        {
+            sq_drop_codebook(*ix);
+            fail(MSVS_ERR_INVALID_ARGUMENT,
+                 "the training residuals of dimension %zu span %g .. %g: no finite quantiser step (an infinite or overflowing training row?)", bad,
+                 (double)lo[bad], (double)hi[bad]);
         }
         sq_set_quantiser(*ix, lo.data(), hi.data(), stream);
     });
@@ -505,6 +533,9 @@ extern "C" int msvs_sq_index_load_io(const msvs_io_t * io, msvs_sq_index_t ** ou
             read_list_offsets(f, *ix, SQ);
             read_grow(f, codes, ix->n * sq_file_row(ix->bits, ix->dim));
             expect_end(f);
+            const size_t bad = sq_unusable_dimension(ix->bits, lo.data(), hi.data(), ix->dim);
+            if (bad < ix->dim)
+                fail(MSVS_ERR_IO, "corrupt msvs IVFSQ index: the quantiser bounds of dimension %zu give no finite step", bad);
             if (ix->bits == 4 && (ix->dim & 1))
                 for (size_t r = 0, fr = sq_file_row(4, ix->dim); r < ix->n; r++)
                     if (codes[r * fr + fr - 1] >> 4)

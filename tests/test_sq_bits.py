@@ -507,6 +507,92 @@ def test_lifecycle_and_errors(bits):
     assert code_of(lambda: bad.add(x)) == capi.ERR_NOT_READY  # a refused codebook leaves none
 
 
+def small_index(bits, dim=16):
+    rng = np.random.default_rng(70 + bits)
+    _, x = blobs(rng, 500, dim, 4)
+    x[:, 5] = np.abs(x[:, 5]) + F(1)  # (every centroid is positive there: a row with +inf in that column has a nearest one)
+    return x, "ncentroids=4,kmeans_iters=3,bit_size=%d" % bits
+
+
+@pytest.mark.parametrize("bits", [8, 4, 16])
+def test_a_quantiser_without_a_finite_step_is_refused(bits):
+    """vmin = -3e38, vmax = 3e38 are finite and ordered, but fl(vmax - vmin) = inf: the step is infinite, every code of the column is
+    0 and decodes to vmin + 0 * inf = NaN, and the index would build, save, load and never return a row.  At 8 and 4 bits set_codebook
+    and train refuse it (MSVS_ERR_INVALID_ARGUMENT, no codebook left) and load does (MSVS_ERR_IO); one infinite element among the
+    training rows is enough for train.  At 16 bits the range enters no arithmetic and all three accept it, as they did."""
+    dim, j = 16, 5
+    x, params_ = small_index(bits, dim)
+    cent = np.ascontiguousarray(x[:4])
+    lo, hi = np.full(dim, -1, F), np.full(dim, 1, F)
+    lo[j], hi[j] = -3e38, 3e38
+    q = x[:20] + F(0.05)
+    # set_codebook
+    ix = capi.SqIndex(L2, dim, "bit_size=%d" % bits)
+    if bits == 16:
+        ix.set_codebook(cent, lo, hi)
+        ix.add(x)
+        ix.build()
+        assert (ix.search(q, 5, "nprobe=4")[0] >= 0).all()
+    else:
+        with pytest.raises(capi.MsvsError) as e:
+            ix.set_codebook(cent, lo, hi)
+        assert e.value.code == capi.ERR_INVALID_ARGUMENT and "dimension %d" % j in str(e.value)
+        assert code_of(lambda: ix.add(x)) == capi.ERR_NOT_READY  # a refused codebook leaves none
+        lo[j], hi[j] = -1.7e38, 1.7e38  # the widest kind of range that has a finite step: accepted
+        ix.set_codebook(cent, lo, hi)
+        ix.add(x)
+        ix.build()
+        exp = ix.export()
+        same(ix.search(q, 5, "nprobe=4"), ref_search(exp, decoded(exp, bits), q, 4, 5, L2))
+    ix.close()
+    # train: one +inf element among the training rows
+    xi = x.copy()
+    xi[123, j] = np.inf
+    ix = capi.SqIndex(L2, dim, params_)
+    if bits == 16:
+        ix.train(xi)
+        assert ix.export(with_lists=False)[2][j] == np.inf  # the exact range of the training residuals, as the header promises
+    else:
+        with pytest.raises(capi.MsvsError) as e:
+            ix.train(xi)
+        assert e.value.code == capi.ERR_INVALID_ARGUMENT and "dimension %d" % j in str(e.value)
+        assert code_of(lambda: ix.add(x)) == capi.ERR_NOT_READY and ix.num_lists == 0  # untrained
+        ix.train(x)  # ... and trainable
+        ix.add(x)
+        ix.build()
+        assert (ix.search(q, 5, "nprobe=4")[0] >= 0).all()
+    ix.close()
+    # load: a file whose range has been patched, under a correct header check word
+    ix = capi.SqIndex(L2, dim, params_)
+    ix.train(x)
+    ix.add(x)
+    ix.build()
+    want = ix.search(q, 5, "nprobe=4")
+    store = {}
+    ix.serialize_io(store)
+    ix.close()
+    full = bytes(store["sq_data"])
+    at_lo = 56 + 4 * dim * 4 + 4 * j
+    at_hi = at_lo + 4 * dim
+    for a, b in ((-3e38, 3e38), (-1.0, np.inf), (np.nan, 1.0)):
+        body = bytearray(full[56:])
+        body[at_lo - 56:at_lo - 52] = struct.pack("<f", a)
+        body[at_hi - 56:at_hi - 52] = struct.pack("<f", b)
+        bad = dict(store)
+        bad["sq_data"] = bytearray(cf.with_check(full[:48]) + bytes(body))
+        if bits == 16:
+            ld = capi.SqIndex.load_io(bad)
+            same(ld.search(q, 5, "nprobe=4"), want)
+            ld.close()
+        else:
+            assert code_of(lambda: capi.SqIndex.load_io(bad)) == capi.ERR_IO, (a, b)
+    good = dict(store)
+    good["sq_data"] = bytearray(cf.with_check(full[:48]) + full[56:])
+    ld = capi.SqIndex.load_io(good)
+    same(ld.search(q, 5, "nprobe=4"), want)
+    ld.close()
+
+
 # ---------------------------------------------------------------------------------------- 10. quality of the specification
 
 @pytest.mark.parametrize("metric", [L2, IP])
