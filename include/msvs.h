@@ -454,6 +454,75 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
                                                        const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis,
                                                        void * hip_stream);
 
+/* Graph index -- a seeded beam search over a fixed-degree neighbour graph (the host's HNSWFLAT / MSTG territory; the shim's mapping
+ * of index types onto it is not part of this interface yet).  Every returned id and distance is a function of the inputs alone.
+ *
+ * Contents: a BORROWED row store (the caller keeps it alive and stops appending; n = msvs_rows_num at build / set_graph / load;
+ * `normalized` must be set exactly when the metric is cosine: MSVS_ERR_INVALID_ARGUMENT otherwise), nlist coarse centroids
+ * (nlist x dim f32), seed[l] (one label per centroid, or -1) and nbr[n][R] u32, R = degree in {16, 32, 64} (default 32), 0xFFFFFFFF =
+ * no edge.  Self loops, repeated labels in a row and empty slots anywhere are legal; the search copes with all of them.  Metrics:
+ * L2, IP, cosine (normalises the query, searches with IP, reports fl(1 - ip) in every slot); others MSVS_ERR_NOT_IMPLEMENTED.
+ *
+ * Search parameters (search: "ef=..,nprobe=..,width=..,max_iters=.."; search_device: arguments, 0 = the default of ef / max_iters):
+ *   ef 1 .. MSVS_MAX_K, default max(k, 64) capped at MSVS_MAX_K; nprobe >= 1, default 8; width 1 .. 4, default 1; max_iters >= 1,
+ *   default ceil(2 ef / width) + 8.  Out of range: MSVS_ERR_INVALID_ARGUMENT.  k <= ef, and min(nprobe, nlist) <= MSVS_MAX_K
+ *   (MSVS_ERR_UNSUPPORTED_K otherwise).  A parameter set whose LDS image (the query, 6 KiB of beam, the visited table) cannot fit
+ *   160 KiB is MSVS_ERR_INVALID_ARGUMENT.
+ * For each query q (normalised first for cosine):
+ *   1. Seeds: the canonical exact top-min(nprobe, nlist) centroids by (distance to the centroid, list id) -- the coded indexes'
+ *      coarse step; their seed[l] >= 0, in that order, are the seeds.
+ *   2. State: V, the exact set of labels scored so far; B, the beam: at most ef entries (key, expanded?) in ascending key order,
+ *      key = (score, label): distance ascending (descending for IP), then label ascending.  A label enters B only if strictly
+ *      better than the neutral +-FLT_MAX; NaN never enters.
+ *   3. Scoring: a label not in V is added to V and scored against its stored row with the canonical scan arithmetic (msvs_refine's,
+ *      bit for bit: 64 partial sums, separately rounded multiply and add, no fma, adjacent pairwise tree); a label in V is skipped.
+ *   4. Init: score the seeds; B = the ef best admitted of them.
+ *   5. Iteration i = 0, 1, ...: stop before it if i == max_iters, or B has no unexpanded entry, or |V| + width * R >
+ *      MSVS_GRAPH_VISITED_MAX.  Otherwise the parents are the `width` lowest-key unexpanded entries of B (fewer if fewer exist); mark
+ *      them expanded; score every label of the parents' nbr rows that is not 0xFFFFFFFF, is below n and is not in V; B becomes the
+ *      ef lowest keys of B plus the newly admitted (old entries keep their flags).  Keys are unique because labels are: a set
+ *      operation, so no scoring order inside an iteration can change it.
+ *   6. Result: the first k entries of the final B whose label is alive under the filter (indexed by label; NULL = all alive), in
+ *      key order; unfilled slots -1 and the neutral value.  Dead rows are traversed and occupy B; a selective filter wants a larger ef.
+ *   k = 0 or nq = 0 is a no-op; before build / set_graph: MSVS_ERR_NOT_READY.
+ *
+ * build: deterministic (the same input gives the same bits) and O(n^2) -- every row is searched exactly over all rows.  K0 = 2R.
+ *   1. centroids: the IVFFLAT trainer over the store's rows (create's params: ncentroids, kmeans_iters, train_sample, seed).
+ *   2. seed[l] = the label of the exact top-1 of centroid l, searched as a query of the index's metric over all rows; -1 if none.
+ *   3. L_i[0 .. K0) = the exact top-(K0 + 1) of row i as such a query, by (distance, label), label i removed if present, else the
+ *      last entry dropped; -1 padded.  (Cosine: the query is normalised again, as every query is.)
+ *   4. detour(i, b) = the number of a < b with L_i[a] >= 0 for which L_i[b] occurs in L_{L_i[a]} at a position r < b;
+ *      F_i = the valid entries of L_i by (detour ascending, b ascending), cut to R.
+ *   5. The incoming edges of j are (r, i) with F_i[r] = j; G_j = the i of the R/2 smallest (r, i), in that order.  N_j = the valid
+ *      entries of F_j[0 .. R/2), then the G_j not yet present, then the F_j[R/2 .. R) not yet present, cut to R; the rest 0xFFFFFFFF.
+ *   An empty row store: MSVS_ERR_INVALID_ARGUMENT.
+ * set_graph installs the caller's structure instead (host or device: mem); a non-finite centroid, a seed outside [-1, n) or an edge
+ *   that is neither below n nor 0xFFFFFFFF is MSVS_ERR_INVALID_ARGUMENT.
+ * memory_usage: device bytes of the graph, the centroids and the seeds.  export: any output may be NULL.
+ * File: `graph_data` through the caller's stream openers: a 64-byte header (magic, version, metric, dim, nlist, n, degree, FNV-1a of
+ *   the body, FNV-1a of the header), the centroids, the seeds, nbr.  load checks sizes, ranges and n == msvs_rows_num(rows); anything
+ *   corrupt is MSVS_ERR_IO. */
+#define MSVS_GRAPH_VISITED_MAX 12288
+typedef struct msvs_graph_index msvs_graph_index_t;
+MSVS_API int msvs_graph_index_create(int metric, const msvs_rows_t * rows, const char * params, msvs_graph_index_t ** out);
+MSVS_API void msvs_graph_index_free(msvs_graph_index_t * index);
+MSVS_API int msvs_graph_index_build(msvs_graph_index_t * index);
+MSVS_API int msvs_graph_index_set_graph(msvs_graph_index_t * index, const float * centroids, size_t nlist, const int32_t * seeds,
+                                        const uint32_t * nbr, int mem);
+MSVS_API int msvs_graph_index_ready(const msvs_graph_index_t * index);
+MSVS_API size_t msvs_graph_index_num_data(const msvs_graph_index_t * index);
+MSVS_API size_t msvs_graph_index_num_lists(const msvs_graph_index_t * index);
+MSVS_API size_t msvs_graph_index_degree(const msvs_graph_index_t * index);
+MSVS_API size_t msvs_graph_index_memory_usage(const msvs_graph_index_t * index);
+MSVS_API int msvs_graph_index_export(const msvs_graph_index_t * index, float * centroids, int32_t * seeds, uint32_t * nbr);
+MSVS_API int msvs_graph_index_search(const msvs_graph_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
+                                     const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_graph_index_search_device(const msvs_graph_index_t * index, const float * d_queries, size_t nq, size_t k, size_t ef,
+                                            size_t nprobe, size_t width, size_t max_iters, const uint64_t * d_alive_bits, size_t nbits,
+                                            int64_t * d_ids, float * d_dis, void * hip_stream);
+MSVS_API int msvs_graph_index_serialize_io(const msvs_graph_index_t * index, const struct msvs_io * io);
+MSVS_API int msvs_graph_index_load_io(const struct msvs_io * io, const msvs_rows_t * rows, msvs_graph_index_t ** out);
+
 /* Resident blocks for the brute-force path: the GPU analogue of VICacheManager / VIWithMeta
  * (src/VectorIndex/Cache/VICacheObject.h:40-162) for the dense block a mark of a part turns into
  * (MergeTreeVSManager.cpp:1380-1392).  msvs_knn_f32 moves that block over PCIe on every query; here it is uploaded

@@ -62,6 +62,10 @@ SYMBOLS = [
     "msvs_comm_free", "msvs_comm_all_reduce_u64", "msvs_comm_rank", "msvs_comm_size", "msvs_shard_search_device", "msvs_shard_search_device_async", "msvs_shard_search_drain", "msvs_shard_search_routed_device",
     "msvs_shard_search_routed_filtered_device", "msvs_shard_search_routed_device_async",
     "msvs_hybrid_fuse_device",
+    "msvs_graph_index_create", "msvs_graph_index_free", "msvs_graph_index_build", "msvs_graph_index_set_graph", "msvs_graph_index_ready",
+    "msvs_graph_index_num_data", "msvs_graph_index_num_lists", "msvs_graph_index_degree", "msvs_graph_index_memory_usage",
+    "msvs_graph_index_export", "msvs_graph_index_search", "msvs_graph_index_search_device", "msvs_graph_index_serialize_io",
+    "msvs_graph_index_load_io",
 ]
 
 
@@ -621,6 +625,64 @@ class Rows:
             self._h = None
 
     __del__ = close
+
+
+GRAPH_VISITED_MAX = 12288  # MSVS_GRAPH_VISITED_MAX: labels one graph search scores at most
+GRAPH_NO_EDGE = 0xFFFFFFFF
+
+
+class GraphIndex(_CodedIndex):
+    """msvs_graph_index_t: coarse centroids, a seed label per centroid and a fixed-degree neighbour graph over the rows of `rows` (a
+    Rows the caller keeps alive and no longer appends to), searched by the seeded beam search include/msvs.h defines.  params:
+    "degree=16|32|64" and the IVFFLAT trainer's keys ("ncentroids=N,kmeans_iters=I,...")."""
+    _c = "msvs_graph_index"
+
+    def __init__(self, metric, rows, params="", _handle=None):
+        self.metric, self.rows, self.dim = int(metric), rows, rows.dim
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            _check(lib().msvs_graph_index_create(int(metric), rows._h, params.encode(), C.byref(self._h)))
+        self.degree = self._size("degree")
+
+    train = add = search_refine = search_refine_device = None  # (the coded indexes' alone)
+
+    def set_graph(self, centroids, seeds, nbr, nlist=None, mem=MEM_HOST):
+        """centroids [nlist, dim] f32, seeds [nlist] i32 (-1: none), nbr [n, degree] u32 (GRAPH_NO_EDGE: no edge); mem=MEM_DEVICE: raw
+        device addresses (ints) and nlist."""
+        if mem == MEM_DEVICE:
+            _check(lib().msvs_graph_index_set_graph(self._h, self._dev(centroids), C.c_size_t(nlist), self._dev(seeds), self._dev(nbr), mem))
+            return
+        c = _f32(centroids).reshape(-1, self.dim)
+        s = np.ascontiguousarray(seeds, np.int32)
+        e = np.ascontiguousarray(nbr, np.uint32)
+        _check(lib().msvs_graph_index_set_graph(self._h, _p(c, C.c_float), C.c_size_t(c.shape[0]), _p(s, C.c_int32), _p(e, C.c_uint32), MEM_HOST))
+
+    def search(self, queries, k, params="", alive=None, nbits=None):
+        """params: "ef=E,nprobe=P,width=W,max_iters=I" (any subset); alive: bool over labels."""
+        return _CodedIndex.search(self, queries, k, params, alive, nbits)
+
+    def search_device(self, d_queries, nq, k, d_ids, d_dis, ef=0, nprobe=8, width=1, max_iters=0, stream=0, d_alive=0, nbits=0):
+        """All buffers are raw device addresses (ints); ef / max_iters 0: the defaults; enqueues on `stream` and returns immediately."""
+        _check(lib().msvs_graph_index_search_device(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(ef),
+                                                    C.c_size_t(nprobe), C.c_size_t(width), C.c_size_t(max_iters), self._dev(d_alive),
+                                                    C.c_size_t(nbits), C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)), self._dev(stream)))
+
+    def export(self):
+        """-> (centroids [nlist, dim], seeds [nlist] i32, nbr [n, degree] u32)"""
+        cent = np.empty((self.num_lists, self.dim), np.float32)
+        seeds = np.empty(self.num_lists, np.int32)
+        nbr = np.empty((self.num_data, self.degree), np.uint32)
+        _check(lib().msvs_graph_index_export(self._h, _p(cent, C.c_float), _p(seeds, C.c_int32), _p(nbr, C.c_uint32)))
+        return cent, seeds, nbr
+
+    @classmethod
+    def load_io(cls, store, rows):
+        """the file's metric (GraphHeader: magic[8], u32 version, i32 metric, ...) over the caller's row store"""
+        h = C.c_void_p()
+        _check(lib().msvs_graph_index_load_io(C.byref(_DictIO(store).io), rows._h, C.byref(h)))
+        return cls(struct.unpack_from("<i", bytes(store["graph_data"][:16]), 12)[0], rows, _handle=h)
 
 
 def refine(rows, metric, queries, cand, k):

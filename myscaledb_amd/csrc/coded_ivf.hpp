@@ -531,6 +531,17 @@ inline void search_host(const CodedIvf * ix, const char * name, const float * qu
 void refine_device(const msvs_rows * rows, int metric, const float * d_queries, size_t nq, const int64_t * d_cand, size_t kc, size_t k,
                    int64_t * d_ids, float * d_dis, hipStream_t stream);
 
+/// what another translation unit may know of a row store (refine.hip): the address a kernel reads the table at, the host address of
+/// a pinned store's table (null for a device store), the row stride in floats, the rows in it
+struct RowsView
+{
+    const float * table, * host;
+    uint32_t ld;
+    size_t n, dim;
+    int device, normalize;
+};
+RowsView rows_view(const msvs_rows * rows);
+
 /// The composed entries: first(d_cand_ids, d_cand_dis) is the index's own device search with kc results (the filter applies
 /// there), its labels stay in an arena of their own on the same stream, then the refine step with the index's metric: no host round trip between.
 /// kc_max: MSVS_MAX_K, or MSVS_REFINE_MAX_CAND for the entries whose first stage searches in rank rounds.

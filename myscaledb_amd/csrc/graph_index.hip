@@ -1,0 +1,527 @@
+// graph_index.hip -- the graph index (include/msvs.h: msvs_graph_index_*): coarse centroids, one seed label per centroid and a
+// fixed-degree neighbour graph over the rows of a borrowed row store; searched by a seeded beam search whose every id and distance
+// is a function of the inputs alone.  The kernels and their layout: graph_kernels.hpp.  DESIGN.md 4.14.
+// Reused as they are: the row store (refine.hip), the canonical scoring of refine_kernels.hpp's chain, the k-means trainer and the
+// canonical coarse top-P (coded_ivf.hpp: kmeans, flat_search_device), the exact FLAT search for the build's neighbour lists.
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <mutex>
+
+#include "coded_ivf.hpp"
+#include "graph_kernels.hpp"
+
+using namespace msvs;
+
+static_assert(MSVS_MAX_K <= GRAPH_ROUND, "a beam entry, a seed and a staged key per thread of a block");
+
+struct msvs_graph_index
+{
+    int metric = MSVS_METRIC_L2;
+    size_t dim = 0, n = 0, nlist = 0;
+    uint32_t ld = 0, R = 32;
+    int device = 0;
+    std::string params;
+    const msvs_rows * rows = nullptr; // borrowed
+    DevBuf<float> centroids;          // nlist x ld
+    DevBuf<int32_t> seeds;            // nlist
+    DevBuf<uint32_t> nbr;             // n x R
+    bool ready = false;
+};
+
+namespace
+{
+const char * const GRAPH = "graph";
+constexpr size_t GRAPH_LDS_MAX = 160 * 1024;
+constexpr size_t GRAPH_QUERY_CHUNK = 16384; // queries of one coarse step + launch
+constexpr size_t GRAPH_LIST_CHUNK = 4096;   // rows whose exact lists one FLAT search of the build returns
+
+uint32_t log2_of(uint32_t v)
+{
+    uint32_t l = 0;
+    while ((1u << l) < v)
+        l++;
+    return l;
+}
+
+void check_graph(const msvs_graph_index * ix)
+{
+    if (!ix)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "null index");
+}
+
+void check_graph_ready(const msvs_graph_index & ix)
+{
+    if (!ix.ready)
+        fail(MSVS_ERR_NOT_READY, "the graph index has no graph yet (build / set_graph)");
+}
+
+struct GraphSearch // the search parameters, defaults filled in
+{
+    size_t ef = 0, nprobe = 8, width = 1, max_iters = 0;
+};
+
+/// ef 0: max(k, 64) capped at MSVS_MAX_K; max_iters 0: ceil(2 ef / width) + 8
+GraphSearch graph_defaults(size_t k, size_t ef, size_t nprobe, size_t width, size_t max_iters)
+{
+    GraphSearch s;
+    s.ef = ef ? ef : std::min<size_t>(std::max<size_t>(k, 64), MSVS_MAX_K);
+    s.nprobe = nprobe;
+    s.width = width;
+    if (s.ef > MSVS_MAX_K || width < 1 || width > 4 || nprobe < 1)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "graph search needs 1 <= ef <= %d, 1 <= width <= 4 and nprobe >= 1 (ef %zu, width %zu, nprobe %zu)", MSVS_MAX_K,
+             s.ef, width, nprobe);
+    s.max_iters = max_iters ? max_iters : ceil_div(2 * s.ef, width) + 8;
+    return s;
+}
+
+GraphSearch parse_graph_search(const char * params, size_t k)
+{
+    const auto p = parse_params(params);
+    for (const auto & kv : p)
+        if (kv.first != "ef" && kv.first != "nprobe" && kv.first != "width" && kv.first != "max_iters")
+            fail(MSVS_ERR_INVALID_ARGUMENT, "unknown search parameter `%s`", kv.first.c_str());
+    const long ef = param_int(p, "ef", 0), nprobe = param_int(p, "nprobe", 8), width = param_int(p, "width", 1), it = param_int(p, "max_iters", 0);
+    if ((p.count("ef") && ef < 1) || nprobe < 1 || width < 1 || (p.count("max_iters") && it < 1))
+        fail(MSVS_ERR_INVALID_ARGUMENT, "ef, nprobe, width and max_iters must be >= 1");
+    return graph_defaults(k, (size_t)ef, (size_t)nprobe, (size_t)width, (size_t)it);
+}
+
+template <int METRIC>
+void launch_graph_search(const GraphSearchParams & a, size_t nq, size_t lds, hipStream_t stream)
+{
+    constexpr auto kernel = &graph_search_kernel<METRIC>;
+    static std::once_flag once; // more than 64 KiB of dynamic LDS needs the attribute raised once per kernel
+    std::call_once(once, [] {
+        MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRAPH_LDS_MAX));
+    });
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(BLOCK), lds, stream, a);
+}
+
+/// Everything on the device, enqueued on `stream`: queries padded (normalised for cosine), the canonical coarse top-P, one launch.
+void graph_search_device(const msvs_graph_index & ix, const float * d_queries, size_t nq, size_t k, const GraphSearch & s, const uint64_t * d_alive,
+                         size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+{
+    check_k(k);
+    check_graph_ready(ix);
+    if (k > s.ef)
+        fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds ef = %zu, the beam of the graph search", k, s.ef);
+    const size_t P = std::min(s.nprobe, ix.nlist), fan = s.width * ix.R;
+    if (P > MSVS_MAX_K)
+        fail(MSVS_ERR_UNSUPPORTED_K, "min(nprobe, nlist) = %zu exceeds the coarse quantiser's top-k limit %d", P, MSVS_MAX_K);
+    // the visited table: what the search can score at most, at load factor <= 0.5
+    const size_t iters = std::min<size_t>(s.max_iters, MSVS_GRAPH_VISITED_MAX), reach = std::min<size_t>(MSVS_GRAPH_VISITED_MAX, P + iters * fan);
+    const uint32_t tab = (uint32_t)(2 * std::max<size_t>(reach, 32)), ld4 = ix.ld / 4;
+    const size_t lds = graph_lds_bytes(ld4, tab);
+    if (lds > GRAPH_LDS_MAX)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the graph search's LDS image (%zu bytes) exceeds %zu", lds, GRAPH_LDS_MAX);
+    if (nq == 0 || k == 0)
+        return;
+    if (!d_queries || !d_ids || !d_dis)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
+    const RowsView rv = rows_view(ix.rows);
+    if (rv.n < ix.n)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the row store holds %zu rows, the graph was made over %zu", rv.n, ix.n);
+    const int m = scan_metric(ix.metric);
+    const size_t chunk = std::min(nq, GRAPH_QUERY_CHUNK);
+    Scratch & scr = scratch_for(stream);
+    scr.reserve(chunk * ((size_t)ix.ld * 4 + P * 4) + flat_scratch_bytes(ix.nlist, chunk, (uint32_t)P, ix.ld) + 8 * 256, stream);
+    float * dq = scr.take<float>(chunk * ix.ld);
+    int32_t * probes = scr.take<int32_t>(chunk * P);
+    const size_t mark = scr.used;
+    for (size_t q0 = 0; q0 < nq; q0 += chunk)
+    {
+        const size_t nqc = std::min(chunk, nq - q0);
+        upload_rows(dq, d_queries + q0 * ix.dim, nqc, (uint32_t)ix.dim, ix.ld, MSVS_MEM_DEVICE, stream);
+        if (ix.metric == MSVS_METRIC_COSINE)
+            normalize_device_rows(dq, nqc, (uint32_t)ix.dim, ix.ld, stream);
+        scr.used = mark;
+        MergeParams co{};
+        co.mode = 1;
+        co.out_probes = probes;
+        flat_search_device(scr, m, ix.centroids.p, nullptr, ix.nlist, ix.ld, dq, nqc, (uint32_t)P, nullptr, 0, co, stream);
+        GraphSearchParams a{};
+        a.rows = reinterpret_cast<const float4 *>(rv.table);
+        a.Q = reinterpret_cast<const float4 *>(dq);
+        a.nbr = ix.nbr.p;
+        a.seed = ix.seeds.p;
+        a.probes = probes;
+        a.alive = d_alive;
+        a.out_ids = d_ids + q0 * k;
+        a.out_dis = d_dis + q0 * k;
+        a.nbits = (uint32_t)std::min<size_t>(nbits, 0xffffffffu);
+        a.n = (uint32_t)ix.n;
+        a.ld4 = ld4;
+        a.R = ix.R;
+        a.lgR = log2_of(ix.R);
+        a.ef = (uint32_t)s.ef;
+        a.k = (uint32_t)k;
+        a.width = (uint32_t)s.width;
+        a.max_iters = (uint32_t)std::min<size_t>(s.max_iters, 0xffffffffu);
+        a.P = (uint32_t)P;
+        a.tab = tab;
+        a.cosine = ix.metric == MSVS_METRIC_COSINE;
+        ProfileScope prof("graph_search", stream);
+        with_int<M_IP, M_L2>(m, [&](auto mm) { launch_graph_search<decltype(mm)::value>(a, nqc, lds, stream); });
+        MSVS_HIP(hipGetLastError());
+    }
+}
+
+/// centroids (nlist x dim, host), seeds and edges (host) -> the index's device buffers; the caller has validated them
+void install_graph(msvs_graph_index & ix, const float * centroids, size_t nlist, const int32_t * seeds, const uint32_t * nbr, hipStream_t stream)
+{
+    ix.nlist = nlist;
+    ix.centroids.alloc(nlist * ix.ld);
+    upload_rows(ix.centroids.p, centroids, nlist, (uint32_t)ix.dim, ix.ld, MSVS_MEM_HOST, stream);
+    ix.seeds.alloc(nlist);
+    MSVS_HIP(hipMemcpyAsync(ix.seeds.p, seeds, nlist * 4, hipMemcpyHostToDevice, stream));
+    ix.nbr.alloc(std::max<size_t>(ix.n * ix.R, 1));
+    if (ix.n)
+        MSVS_HIP(hipMemcpyAsync(ix.nbr.p, nbr, ix.n * ix.R * 4, hipMemcpyHostToDevice, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
+    ix.ready = true;
+}
+
+/// what a caller's or a file's structure must satisfy -> nullptr, or what is wrong with it
+const char * graph_structure_error(const float * centroids, size_t nlist, size_t dim, const int32_t * seeds, const uint32_t * nbr, size_t n, uint32_t R)
+{
+    for (size_t i = 0; i < nlist * dim; i++)
+        if (!std::isfinite(centroids[i]))
+            return "a centroid is not finite";
+    for (size_t l = 0; l < nlist; l++)
+        if (seeds[l] < -1 || (seeds[l] >= 0 && (size_t)seeds[l] >= n))
+            return "a seed is outside [-1, n)";
+    for (size_t e = 0; e < n * R; e++)
+        if (nbr[e] != GRAPH_EMPTY && nbr[e] >= n)
+            return "an edge is neither below n nor 0xFFFFFFFF";
+    return nullptr;
+}
+
+std::vector<float> host_centroids(const msvs_graph_index & ix, hipStream_t stream)
+{
+    std::vector<float> c(ix.nlist * ix.dim);
+    MSVS_HIP(hipMemcpy2DAsync(c.data(), ix.dim * 4, ix.centroids.p, (size_t)ix.ld * 4, ix.dim * 4, ix.nlist, hipMemcpyDeviceToHost, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    return c;
+}
+
+struct GraphHeader // 64 bytes, little endian
+{
+    char magic[8]; // "MSVSGR01"
+    uint32_t version; // 1
+    int32_t metric;
+    uint64_t dim, nlist, n, degree;
+    uint64_t body; // FNV-1a of the centroids, the seeds and the edges
+    uint64_t check; // FNV-1a of the bytes before it
+};
+
+uint64_t graph_body_check(const std::vector<float> & c, const std::vector<int32_t> & s, const std::vector<uint32_t> & e)
+{
+    const uint64_t h[3] = {fnv1a(c.data(), c.size() * 4), fnv1a(s.data(), s.size() * 4), fnv1a(e.data(), e.size() * 4)};
+    return fnv1a(h, sizeof(h));
+}
+}
+
+extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, const char * params, msvs_graph_index_t ** out)
+{
+    return guarded([&] {
+        clear_out(out);
+        check_metric(metric, GRAPH);
+        if (!rows)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store");
+        const RowsView rv = rows_view(rows);
+        if ((metric == MSVS_METRIC_COSINE) != (rv.normalize != 0))
+            fail(MSVS_ERR_INVALID_ARGUMENT, "a cosine graph index needs a row store created with normalize=1, L2 and IP one with normalize=0");
+        const auto p = parse_params(params);
+        check_ncentroids(p);
+        const long degree = param_int(p, "degree", 32);
+        if (degree != 16 && degree != 32 && degree != 64)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index has degree 16, 32 or 64 (degree %ld)", degree);
+        std::unique_ptr<msvs_graph_index> ix(new msvs_graph_index);
+        ix->metric = metric;
+        ix->dim = rv.dim;
+        ix->ld = rv.ld;
+        ix->R = (uint32_t)degree;
+        ix->rows = rows;
+        ix->device = rv.device;
+        ix->params = params ? params : "";
+        *out = ix.release();
+    });
+}
+
+extern "C" void msvs_graph_index_free(msvs_graph_index_t * ix) { delete ix; }
+extern "C" int msvs_graph_index_ready(const msvs_graph_index_t * ix) { return ix && ix->ready ? 1 : 0; }
+extern "C" size_t msvs_graph_index_num_data(const msvs_graph_index_t * ix) { return ix && ix->ready ? ix->n : 0; }
+extern "C" size_t msvs_graph_index_num_lists(const msvs_graph_index_t * ix) { return ix ? ix->nlist : 0; }
+extern "C" size_t msvs_graph_index_degree(const msvs_graph_index_t * ix) { return ix ? ix->R : 0; }
+extern "C" size_t msvs_graph_index_memory_usage(const msvs_graph_index_t * ix)
+{
+    return ix ? ix->nbr.bytes() + ix->centroids.bytes() + ix->seeds.bytes() : 0;
+}
+
+extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float * centroids, size_t nlist, const int32_t * seeds, const uint32_t * nbr,
+                                          int mem)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        const size_t n = msvs_rows_num(ix->rows);
+        if (!centroids || !seeds || (n && !nbr) || nlist == 0 || nlist > 0x7fffffffull)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null graph / no centroids");
+        std::vector<float> c(nlist * ix->dim);
+        std::vector<int32_t> s(nlist);
+        std::vector<uint32_t> e(n * ix->R);
+        auto take = [&](void * dst, const void * src, size_t bytes) {
+            if (mem == MSVS_MEM_DEVICE)
+                MSVS_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+            else
+                memcpy(dst, src, bytes);
+        };
+        take(c.data(), centroids, c.size() * 4);
+        take(s.data(), seeds, s.size() * 4);
+        if (!e.empty())
+            take(e.data(), nbr, e.size() * 4);
+        if (const char * bad = graph_structure_error(c.data(), nlist, ix->dim, s.data(), e.data(), n, ix->R))
+            fail(MSVS_ERR_INVALID_ARGUMENT, "set_graph: %s", bad);
+        ix->ready = false;
+        ix->n = n;
+        install_graph(*ix, c.data(), nlist, s.data(), e.data(), thread_stream());
+    });
+}
+
+/// Deterministic, from exact lists (include/msvs.h); O(n^2): every row is searched over all rows.
+extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        const RowsView rv = rows_view(ix->rows);
+        const size_t n = rv.n, dim = ix->dim;
+        const uint32_t R = ix->R, K0 = 2 * R;
+        if (n == 0)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the row store is empty: nothing to build a graph over");
+        hipStream_t stream = thread_stream();
+        ix->ready = false;
+        // the store's rows, dense, on the device: the trainer's and the FLAT index's feed, and the lists' queries
+        DevBuf<float> dense(n * dim);
+        MSVS_HIP(hipMemcpy2DAsync(dense.p, dim * 4, rv.host ? rv.host : rv.table, (size_t)rv.ld * 4, dim * 4, n, hipMemcpyDefault, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+        // 1. centroids: the IVFFLAT trainer as it is
+        {
+            const TmpIndex tmp = kmeans(ix->metric, dim, ix->params, dense.p, n, MSVS_MEM_DEVICE);
+            ix->nlist = tmp->nlist;
+            ix->centroids.alloc(ix->nlist * ix->ld);
+            MSVS_HIP(hipMemsetAsync(ix->centroids.p, 0, ix->nlist * ix->ld * 4, stream));
+            MSVS_HIP(hipMemcpy2DAsync(ix->centroids.p, (size_t)ix->ld * 4, tmp->centroids.p, (size_t)tmp->ld * 4, dim * 4, ix->nlist,
+                                      hipMemcpyDeviceToDevice, stream));
+            MSVS_HIP(hipStreamSynchronize(stream));
+        }
+        const size_t nlist = ix->nlist;
+        // the exact search: a temporary FLAT index over the same rows (cosine: inner product over the stored unit rows, the queries normalised here)
+        msvs_index_t * raw = nullptr;
+        int rc = msvs_index_create(MSVS_INDEX_FLAT, ix->metric == MSVS_METRIC_L2 ? MSVS_METRIC_L2 : MSVS_METRIC_IP, dim, "", &raw);
+        const TmpIndex flat(raw, msvs_index_free);
+        if (rc == MSVS_OK)
+            rc = msvs_index_add(raw, dense.p, nullptr, n, MSVS_MEM_DEVICE);
+        if (rc == MSVS_OK)
+            rc = msvs_index_build(raw);
+        if (rc != MSVS_OK)
+            fail(rc, "%s", std::string(msvs_last_error()).c_str());
+        const size_t chunk = std::max(GRAPH_LIST_CHUNK, nlist);
+        DevBuf<float> dq(chunk * dim), ddis(chunk * (K0 + 1));
+        DevBuf<int64_t> dids(chunk * (K0 + 1));
+        auto exact = [&](const float * src, size_t src_ld, size_t cnt, uint32_t k) {
+            MSVS_HIP(hipMemcpy2DAsync(dq.p, dim * 4, src, src_ld * 4, dim * 4, cnt, hipMemcpyDeviceToDevice, stream));
+            if (ix->metric == MSVS_METRIC_COSINE)
+                normalize_device_rows(dq.p, cnt, (uint32_t)dim, (uint32_t)dim, stream);
+            rc = msvs_index_search_device(raw, dq.p, cnt, (int)k, 1, nullptr, 0, dids.p, ddis.p, stream);
+            if (rc != MSVS_OK)
+                fail(rc, "%s", std::string(msvs_last_error()).c_str());
+        };
+        // 2. seeds: the exact top-1 of every centroid
+        exact(ix->centroids.p, ix->ld, nlist, 1);
+        std::vector<int64_t> top(nlist);
+        MSVS_HIP(hipMemcpyAsync(top.data(), dids.p, nlist * 8, hipMemcpyDeviceToHost, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+        std::vector<int32_t> seeds(nlist);
+        for (size_t l = 0; l < nlist; l++)
+            seeds[l] = top[l] >= 0 && (size_t)top[l] < n ? (int32_t)top[l] : -1;
+        // 3. lists: the exact top-(K0 + 1) of every row, the row itself taken out
+        DevBuf<int32_t> lists(n * K0);
+        for (size_t i0 = 0; i0 < n; i0 += chunk)
+        {
+            const size_t cnt = std::min(chunk, n - i0);
+            exact(dense.p + i0 * dim, dim, cnt, K0 + 1);
+            hipLaunchKernelGGL(graph_lists_kernel, dim3((unsigned)ceil_div(cnt, (size_t)256)), dim3(256), 0, stream, dids.p, (uint32_t)cnt, (uint32_t)i0,
+                               K0, lists.p);
+            MSVS_HIP(hipGetLastError());
+        }
+        // 4. prune by detours; 5. reverse edges: count, prefix sum, scatter, per-node selection and merge
+        const size_t words = n * R;
+        DevBuf<uint32_t> F(words), cnt(n);
+        DevBuf<uint64_t> off(n + 1), seg(words);
+        ix->nbr.alloc(words);
+        static std::once_flag once;
+        std::call_once(once, [] {
+            MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&graph_prune_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)graph_prune_lds_bytes(128)));
+        });
+        hipLaunchKernelGGL(graph_prune_kernel, dim3((unsigned)n), dim3(BLOCK), graph_prune_lds_bytes(K0), stream, lists.p, (uint32_t)n, K0, R, F.p);
+        MSVS_HIP(hipMemsetAsync(cnt.p, 0, n * 4, stream));
+        const unsigned egrid = (unsigned)ceil_div(words, (size_t)256);
+        hipLaunchKernelGGL(graph_count_kernel, dim3(egrid), dim3(256), 0, stream, F.p, words, cnt.p);
+        hipLaunchKernelGGL(graph_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, cnt.p, (uint32_t)n, off.p);
+        hipLaunchKernelGGL(graph_scatter_kernel, dim3(egrid), dim3(256), 0, stream, F.p, words, log2_of(R), off.p, cnt.p, seg.p);
+        hipLaunchKernelGGL(graph_reverse_kernel, dim3((unsigned)ceil_div(n, (size_t)4)), dim3(BLOCK), 0, stream, F.p, off.p, seg.p, (uint32_t)n, R,
+                           ix->nbr.p);
+        MSVS_HIP(hipGetLastError());
+        ix->seeds.alloc(nlist);
+        MSVS_HIP(hipMemcpyAsync(ix->seeds.p, seeds.data(), nlist * 4, hipMemcpyHostToDevice, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+        MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
+        ix->n = n;
+        ix->ready = true;
+    });
+}
+
+extern "C" int msvs_graph_index_search_device(const msvs_graph_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t ef, size_t nprobe,
+                                              size_t width, size_t max_iters, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
+                                              float * d_dis, void * hip_stream)
+{
+    return guarded([&] {
+        check_graph(ix);
+        check_k(k);
+        graph_search_device(*ix, d_queries, nq, k, graph_defaults(k, ef, nprobe, width, max_iters), d_alive_bits, nbits, d_ids, d_dis,
+                            as_stream(hip_stream));
+    });
+}
+
+extern "C" int msvs_graph_index_search(const msvs_graph_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
+                                       const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        check_k(k);
+        const GraphSearch s = parse_graph_search(params, k);
+        check_graph_ready(*ix);
+        if (k > s.ef)
+            fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds ef = %zu, the beam of the graph search", k, s.ef);
+        if (nq == 0 || k == 0)
+            return;
+        if (!queries || !ids || !dis)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
+        hipStream_t stream = thread_stream();
+        const size_t words = alive_bits ? std::max<size_t>(1, ceil_div(nbits, (size_t)64)) : 0;
+        Scratch & stg = staging_for(stream);
+        stg.reserve(nq * ix->dim * 4 + nq * k * 12 + words * 8 + 4 * 256, stream);
+        float * dq = stg.take<float>(nq * ix->dim);
+        int64_t * d_ids = stg.take<int64_t>(nq * k);
+        float * d_dis = stg.take<float>(nq * k);
+        uint64_t * d_alive = words ? stg.take<uint64_t>(words) : nullptr;
+        MSVS_HIP(hipMemcpyAsync(dq, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, stream));
+        if (words)
+            MSVS_HIP(hipMemcpyAsync(d_alive, alive_bits, words * 8, hipMemcpyHostToDevice, stream));
+        graph_search_device(*ix, dq, nq, k, s, d_alive, nbits, d_ids, d_dis, stream);
+        MSVS_HIP(hipMemcpyAsync(ids, d_ids, nq * k * 8, hipMemcpyDeviceToHost, stream));
+        MSVS_HIP(hipMemcpyAsync(dis, d_dis, nq * k * 4, hipMemcpyDeviceToHost, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+    });
+}
+
+// ------------------------------------------------------------------------------------------- export and files
+
+extern "C" int msvs_graph_index_export(const msvs_graph_index_t * ix, float * centroids, int32_t * seeds, uint32_t * nbr)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        check_graph_ready(*ix);
+        hipStream_t stream = thread_stream();
+        if (centroids)
+        {
+            const std::vector<float> c = host_centroids(*ix, stream);
+            memcpy(centroids, c.data(), c.size() * 4);
+        }
+        if (seeds)
+            MSVS_HIP(hipMemcpyAsync(seeds, ix->seeds.p, ix->nlist * 4, hipMemcpyDeviceToHost, stream));
+        if (nbr && ix->n)
+            MSVS_HIP(hipMemcpyAsync(nbr, ix->nbr.p, ix->n * ix->R * 4, hipMemcpyDeviceToHost, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+    });
+}
+
+extern "C" int msvs_graph_index_serialize_io(const msvs_graph_index_t * ix, const msvs_io_t * io)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        check_graph_ready(*ix);
+        hipStream_t stream = thread_stream();
+        const std::vector<float> c = host_centroids(*ix, stream);
+        std::vector<int32_t> s(ix->nlist);
+        std::vector<uint32_t> e(ix->n * ix->R);
+        MSVS_HIP(hipMemcpy(s.data(), ix->seeds.p, s.size() * 4, hipMemcpyDeviceToHost));
+        if (!e.empty())
+            MSVS_HIP(hipMemcpy(e.data(), ix->nbr.p, e.size() * 4, hipMemcpyDeviceToHost));
+        IoStream f(io, "graph_data", 1);
+        GraphHeader h{};
+        memcpy(h.magic, "MSVSGR01", 8);
+        h.version = 1;
+        h.metric = ix->metric;
+        h.dim = ix->dim;
+        h.nlist = ix->nlist;
+        h.n = ix->n;
+        h.degree = ix->R;
+        h.body = graph_body_check(c, s, e);
+        h.check = fnv1a(&h, offsetof(GraphHeader, check));
+        f.write(&h, sizeof(h));
+        f.write(c.data(), c.size() * 4);
+        f.write(s.data(), s.size() * 4);
+        if (!e.empty())
+            f.write(e.data(), e.size() * 4);
+        f.finish();
+    });
+}
+
+extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t * rows, msvs_graph_index_t ** out)
+{
+    return guarded([&] {
+        clear_out(out);
+        if (!rows)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store");
+        const RowsView rv = rows_view(rows);
+        DeviceGuard on_device(rv.device);
+        std::unique_ptr<msvs_graph_index> ix(new msvs_graph_index);
+        std::vector<float> c;
+        std::vector<int32_t> s;
+        std::vector<uint32_t> e;
+        IoStream f(io, "graph_data", 0);
+        GraphHeader h{};
+        f.read(&h, sizeof(h));
+        if (memcmp(h.magic, "MSVSGR01", 8) != 0 || h.version != 1 || h.check != fnv1a(&h, offsetof(GraphHeader, check))
+            || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || (h.degree != 16 && h.degree != 32 && h.degree != 64))
+            fail(MSVS_ERR_IO, "corrupt msvs graph index header");
+        if (h.n != rv.n || h.dim != rv.dim || (h.metric == MSVS_METRIC_COSINE) != (rv.normalize != 0))
+            fail(MSVS_ERR_IO, "the msvs graph index file (n %llu, dim %llu) does not belong to this row store (n %zu, dim %zu)",
+                 (unsigned long long)h.n, (unsigned long long)h.dim, rv.n, rv.dim);
+        read_grow(f, c, (size_t)(h.nlist * h.dim));
+        read_grow(f, s, (size_t)h.nlist);
+        read_grow(f, e, (size_t)(h.n * h.degree));
+        expect_end(f);
+        if (h.body != graph_body_check(c, s, e))
+            fail(MSVS_ERR_IO, "corrupt msvs graph index: the body's checksum does not match");
+        if (const char * bad = graph_structure_error(c.data(), (size_t)h.nlist, (size_t)h.dim, s.data(), e.data(), (size_t)h.n, (uint32_t)h.degree))
+            fail(MSVS_ERR_IO, "corrupt msvs graph index: %s", bad);
+        ix->metric = h.metric;
+        ix->dim = rv.dim;
+        ix->ld = rv.ld;
+        ix->R = (uint32_t)h.degree;
+        ix->rows = rows;
+        ix->device = rv.device;
+        ix->n = (size_t)h.n;
+        install_graph(*ix, c.data(), (size_t)h.nlist, s.data(), e.data(), thread_stream());
+        *out = ix.release();
+    });
+}

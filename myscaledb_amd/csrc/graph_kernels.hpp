@@ -1,0 +1,441 @@
+// graph_kernels.hpp -- device code of the graph index (graph_index.hip): the seeded beam search over a fixed-degree
+// neighbour graph whose rows live in a row store (row i is label i), and the integer kernels that build such a graph from exact
+// neighbour lists.
+//
+// graph_search_kernel: one block of 256 threads per query, the whole search of include/msvs.h's definition in one launch.
+//   LDS image (graph_lds): the query (ld4 x 16 bytes, staged once) | beam keys (256 x 8) | staged new keys (256 x 8) | expanded
+//   flags (256 x 4) | labels to score (256 x 4) | control words (16 x 4) | the visited table (tab x 4).
+//   A round takes at most 256 candidate labels, one per thread (the seeds; later the width x R neighbour words of the parents):
+//     1. visit: atomicCAS into the open-addressing table; the thread whose CAS wins owns the label, a duplicate loses and is dropped.
+//        Winners are compacted into the score list by one LDS atomic per wavefront (their order there reaches no result).
+//     2. score: sixteen 16-lane groups take the list's labels grp, grp + 16, ...: canonical_row_chain + row16_tree_sum, as refine_kernel,
+//        so sixteen 256-byte-contiguous row requests are in flight; make_key (strict admission, NaN never) -> staged key.
+//     3. merge by ranking: thread t holds beam[t] and staged[t] in registers.  An old key's rank is t + the staged keys below it, a new
+//        key's the beam keys below it (binary search: the beam is sorted) + the staged keys below it (one pass of broadcast reads both
+//        ranks share).  After a barrier every key with rank < ef writes itself and its flag to that rank.  No sort, no serial insertion.
+//   Between rounds the parents are the first `width` clear flags of the sorted beam: a ballot per wavefront, four words in LDS, and
+//   every thread of a parent's R-lane slice finds its parent from them and loads its neighbour word.
+//   The table holds at most tab / 2 labels (the launcher sizes it from the search's own bound), so a probe sequence always ends.
+//
+// graph_prune_kernel, graph_count_kernel, graph_scan_kernel, graph_scatter_kernel, graph_reverse_kernel: the build, integers only.
+#pragma once
+
+#include "mfma_scan_kernels.hpp"
+#include "scan_kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace msvs
+{
+
+constexpr uint32_t GRAPH_EMPTY = 0xFFFFFFFFu; // no edge / a free slot of the visited table
+constexpr uint32_t GRAPH_ROUND = 256;         // candidates of a round at most: min(nprobe, nlist) seeds, width x R neighbour words
+constexpr uint32_t GRAPH_CTL = 16;            // control words
+
+struct GraphSearchParams
+{
+    const float4 * rows;    // n x ld4 at least, zero padded; HBM or mapped pinned host memory
+    const float4 * Q;       // nq x ld4, zero padded (normalised for cosine)
+    const uint32_t * nbr;   // n x R
+    const int32_t * seed;   // nlist
+    const int32_t * probes; // nq x P list ids, canonical order, -1 padded
+    const uint64_t * alive; // nullable filter bitmap over labels
+    int64_t * out_ids;      // nq x k
+    float * out_dis;        // nq x k
+    uint32_t nbits, n, ld4, R, lgR, ef, k, width, max_iters, P, tab;
+    int cosine;
+};
+
+inline size_t graph_lds_bytes(uint32_t ld4, uint32_t tab)
+{
+    return (size_t)ld4 * 16 + GRAPH_ROUND * (8 + 8 + 4 + 4) + GRAPH_CTL * 4 + (size_t)tab * 4;
+}
+
+struct GraphLds
+{
+    float4 * qs;
+    uint64_t * beam, * stage;
+    uint32_t * flag, * slab, * ctl, * table;
+    // ctl: 0 labels to score this round, 1 |V|, 2 beam entries, 3 newly admitted keys, 4 alive results; 8 .. 15 four 64-bit ballots
+};
+
+/// label -> true if this thread is the one that put it into the visited table
+__device__ __forceinline__ bool graph_visit(uint32_t * table, const uint32_t tab, const uint32_t label)
+{
+    uint32_t h = __umulhi(label * 0x9E3779B1u, tab);
+    for (;;)
+    {
+        const uint32_t prev = atomicCAS(&table[h], GRAPH_EMPTY, label);
+        if (prev == GRAPH_EMPTY)
+            return true;
+        if (prev == label)
+            return false;
+        h = h + 1 == tab ? 0 : h + 1;
+    }
+}
+
+/// the wavefront's lanes with `pred` get consecutive places behind *counter (one atomic per wavefront) -> this lane's place
+__device__ __forceinline__ uint32_t graph_wave_place(uint32_t * counter, const bool pred, const uint32_t lane)
+{
+    const uint64_t b = __ballot(pred);
+    uint32_t base = 0;
+    if (lane == 0 && b)
+        base = atomicAdd(counter, (uint32_t)__popcll(b));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    return base + (uint32_t)__popcll(b & ((1ull << lane) - 1));
+}
+
+/// One round: this thread's candidate label (GRAPH_EMPTY: none) is visited, the winners are scored and merged into the beam.
+/// Entered and left with every thread past a barrier and ctl[0] = ctl[3] = 0.
+template <int METRIC>
+__device__ __forceinline__ void graph_round(const GraphSearchParams & a, const GraphLds & L, const uint32_t lab, const uint32_t tid)
+{
+    const uint32_t lane = tid & 63, grp = tid >> 4, g = tid & 15;
+    const bool won = lab != GRAPH_EMPTY && graph_visit(L.table, a.tab, lab);
+    const uint32_t place = graph_wave_place(&L.ctl[0], won, lane);
+    if (won)
+        L.slab[place] = lab;
+    __syncthreads();
+    const uint32_t m = L.ctl[0], cnt = L.ctl[2];
+    const uint32_t jfull = a.ld4 >> 4, jtail = a.ld4 & 15;
+    for (uint32_t c = grp; c < m; c += 16)
+    {
+        uint32_t id = L.slab[c]; // uniform over the 16 lanes that own slot c
+        const float4 acc = canonical_row_chain<METRIC>(a.rows + (size_t)id * a.ld4 + g, L.qs + g, jfull, jtail, g, nullptr, id);
+        float s = __fadd_rn(__fadd_rn(acc.x, acc.y), __fadd_rn(acc.z, acc.w));
+        s = row16_tree_sum(s);
+        if (g == 0)
+            L.stage[c] = make_key<METRIC>(s, id);
+    }
+    __syncthreads();
+    const uint64_t old = tid < cnt ? L.beam[tid] : KEY_NONE, neu = tid < m ? L.stage[tid] : KEY_NONE;
+    const uint32_t old_flag = tid < cnt ? L.flag[tid] : 0;
+    uint32_t rank_old = tid, rank_new = 0;
+    for (uint32_t j = 0; j < m; j++)
+    {
+        const uint64_t kj = L.stage[j]; // one address for the whole block: a broadcast read
+        rank_old += kj < old ? 1u : 0u;
+        rank_new += kj < neu ? 1u : 0u;
+    }
+    if (neu != KEY_NONE)
+    {
+        uint32_t lo = 0, hi = cnt; // beam keys below neu
+        while (lo < hi)
+        {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (L.beam[mid] < neu)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        rank_new += lo;
+    }
+    (void)graph_wave_place(&L.ctl[3], neu != KEY_NONE, lane);
+    __syncthreads(); // everybody has read the beam, the flags and the staged keys
+    if (old != KEY_NONE && rank_old < a.ef)
+    {
+        L.beam[rank_old] = old;
+        L.flag[rank_old] = old_flag;
+    }
+    if (neu != KEY_NONE && rank_new < a.ef)
+    {
+        L.beam[rank_new] = neu;
+        L.flag[rank_new] = 0;
+    }
+    const uint32_t admitted = L.ctl[3];
+    __syncthreads();
+    if (tid == 0)
+    {
+        L.ctl[2] = min(a.ef, cnt + admitted);
+        L.ctl[1] += m;
+        L.ctl[0] = 0;
+        L.ctl[3] = 0;
+    }
+    __syncthreads();
+}
+
+template <int METRIC>
+static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphSearchParams a)
+{
+    extern __shared__ __align__(16) unsigned char graph_lds[];
+    GraphLds L;
+    L.qs = reinterpret_cast<float4 *>(graph_lds);
+    L.beam = reinterpret_cast<uint64_t *>(graph_lds + (size_t)a.ld4 * 16);
+    L.stage = L.beam + GRAPH_ROUND;
+    L.flag = reinterpret_cast<uint32_t *>(L.stage + GRAPH_ROUND);
+    L.slab = L.flag + GRAPH_ROUND;
+    L.ctl = L.slab + GRAPH_ROUND;
+    L.table = L.ctl + GRAPH_CTL;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t i = tid; i < a.ld4; i += BLOCK)
+        L.qs[i] = a.Q[(size_t)q * a.ld4 + i];
+    for (uint32_t i = tid; i < a.tab; i += BLOCK)
+        L.table[i] = GRAPH_EMPTY;
+    if (tid < GRAPH_CTL)
+        L.ctl[tid] = 0;
+    __syncthreads();
+    // the seeds of the probed lists
+    uint32_t lab = GRAPH_EMPTY;
+    if (tid < a.P)
+    {
+        const int32_t l = a.probes[(size_t)q * a.P + tid];
+        const int32_t s = l >= 0 ? a.seed[l] : -1;
+        if (s >= 0 && (uint32_t)s < a.n)
+            lab = (uint32_t)s;
+    }
+    graph_round<METRIC>(a, L, lab, tid);
+    uint64_t * ballots = reinterpret_cast<uint64_t *>(L.ctl + 8);
+    const uint32_t fan = a.width << a.lgR;
+    for (uint32_t it = 0; it < a.max_iters; it++)
+    {
+        const uint32_t cnt = L.ctl[2];
+        if (L.ctl[1] + fan > MSVS_GRAPH_VISITED_MAX)
+            break;
+        const uint64_t b = __ballot(tid < cnt && L.flag[tid] == 0);
+        if (lane == 0)
+            ballots[wave] = b;
+        __syncthreads();
+        const uint64_t b0 = ballots[0], b1 = ballots[1], b2 = ballots[2], b3 = ballots[3];
+        __syncthreads(); // (the next iteration's ballots must not overtake a reader)
+        const uint32_t open = (uint32_t)(__popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3));
+        if (open == 0)
+            break;
+        lab = GRAPH_EMPTY;
+        const uint32_t p = tid >> a.lgR; // this thread's parent: the p-th clear flag
+        if (tid < fan && p < open)
+        {
+            uint32_t skip = p, base = 0;
+            uint64_t w = b0;
+            if (skip >= (uint32_t)__popcll(w))
+                skip -= (uint32_t)__popcll(w), w = b1, base = 64;
+            if (skip >= (uint32_t)__popcll(w))
+                skip -= (uint32_t)__popcll(w), w = b2, base = 128;
+            if (skip >= (uint32_t)__popcll(w))
+                skip -= (uint32_t)__popcll(w), w = b3, base = 192;
+            for (; skip; skip--)
+                w &= w - 1;
+            const uint32_t slot = base + (uint32_t)__builtin_ctzll(w);
+            const uint32_t parent = (uint32_t)L.beam[slot], r = tid & (a.R - 1);
+            const uint32_t e = a.nbr[(size_t)parent * a.R + r];
+            lab = e < a.n ? e : GRAPH_EMPTY;
+            if (r == 0)
+                L.flag[slot] = 1;
+        }
+        graph_round<METRIC>(a, L, lab, tid);
+    }
+    // the first k alive entries of the beam
+    const uint32_t cnt = L.ctl[2];
+    const uint64_t key = tid < cnt ? L.beam[tid] : KEY_NONE;
+    bool ok = key != KEY_NONE;
+    if (ok && a.alive)
+    {
+        const uint32_t id = (uint32_t)key;
+        ok = id < a.nbits && ((a.alive[id >> 6] >> (id & 63)) & 1);
+    }
+    const uint64_t bo = __ballot(ok);
+    if (lane == 0)
+        ballots[wave] = bo;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t w = 0; w < 4; w++)
+    {
+        const uint32_t c = (uint32_t)__popcll(ballots[w]);
+        before += w < wave ? c : 0;
+        total += c;
+    }
+    const uint32_t rank = before + (uint32_t)__popcll(bo & ((1ull << lane) - 1));
+    if (ok && rank < a.k)
+    {
+        const size_t o = (size_t)q * a.k + rank;
+        a.out_ids[o] = (int64_t)(uint32_t)key;
+        const float v = key_value<METRIC>(key);
+        a.out_dis[o] = a.cosine ? __fsub_rn(1.0f, v) : v;
+    }
+    for (uint32_t i = total + tid; i < a.k; i += BLOCK)
+    {
+        const size_t o = (size_t)q * a.k + i;
+        a.out_ids[o] = -1;
+        const float v = key_value<METRIC>(KEY_NONE);
+        a.out_dis[o] = a.cosine ? __fsub_rn(1.0f, v) : v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------- build
+
+/// ids [n][kk] of an exact search of row i0 + i (labels or -1) -> L[i0 + i][0 .. K0): label i0 + i removed if present, else the last
+/// entry dropped; kk = K0 + 1
+static __global__ void graph_lists_kernel(const int64_t * ids, uint32_t cnt, uint32_t i0, uint32_t K0, int32_t * L)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt)
+        return;
+    const int64_t * src = ids + (size_t)i * (K0 + 1);
+    int32_t * dst = L + (size_t)(i0 + i) * K0;
+    uint32_t o = 0;
+    for (uint32_t j = 0; j <= K0 && o < K0; j++)
+        if (src[j] != (int64_t)(i0 + i))
+            dst[o++] = (int32_t)src[j];
+}
+
+inline size_t graph_prune_lds_bytes(uint32_t K0) { return ((size_t)K0 * K0 + 2 * K0) * 4; }
+
+/// One block per node i: its list and the lists of its K0 neighbours sit in LDS (K0 x K0 x 4 bytes); detour(b) counts the a < b
+/// whose list holds L_i[b] at a position r < b; F_i = the valid entries by (detour, b), cut to R.  Integer work only.
+static __global__ __launch_bounds__(BLOCK) void graph_prune_kernel(const int32_t * L, uint32_t n, uint32_t K0, uint32_t R, uint32_t * F)
+{
+    extern __shared__ __align__(16) unsigned char graph_lds[];
+    int32_t * mine = reinterpret_cast<int32_t *>(graph_lds);
+    uint32_t * detour = reinterpret_cast<uint32_t *>(mine + K0);
+    int32_t * lists = mine + 2 * K0; // [a][r]
+    const uint32_t i = blockIdx.x, tid = threadIdx.x;
+    if (tid < K0)
+    {
+        const int32_t v = L[(size_t)i * K0 + tid];
+        mine[tid] = v >= 0 && (uint32_t)v < n ? v : -1;
+        detour[tid] = 0;
+    }
+    if (tid < R)
+        F[(size_t)i * R + tid] = GRAPH_EMPTY;
+    __syncthreads();
+    for (uint32_t e = tid; e < K0 * K0; e += BLOCK)
+    {
+        const int32_t a = mine[e / K0];
+        lists[e] = a >= 0 ? L[(size_t)a * K0 + e % K0] : -1;
+    }
+    __syncthreads();
+    // thread (b, slice): the a of its slice below b
+    const uint32_t b = tid % K0, slices = BLOCK / K0, slice = tid / K0; // K0 <= 128: at least two slices
+    const int32_t target = mine[b];
+    if (slice < slices && target >= 0)
+    {
+        uint32_t d = 0;
+        for (uint32_t a = slice; a < b; a += slices)
+        {
+            if (mine[a] < 0)
+                continue;
+            bool hit = false;
+            for (uint32_t r = 0; r < b; r++)
+                hit |= lists[a * K0 + r] == target;
+            d += hit ? 1u : 0u;
+        }
+        if (d)
+            atomicAdd(&detour[b], d);
+    }
+    __syncthreads();
+    if (tid < K0 && mine[tid] >= 0)
+    {
+        const uint32_t d = detour[tid];
+        uint32_t rank = 0;
+        for (uint32_t c = 0; c < K0; c++)
+            rank += mine[c] >= 0 && (detour[c] < d || (detour[c] == d && c < tid)) ? 1u : 0u;
+        if (rank < R)
+            F[(size_t)i * R + rank] = (uint32_t)mine[tid];
+    }
+}
+
+/// incoming edges of every node: cnt[F[i][r]]++
+static __global__ void graph_count_kernel(const uint32_t * F, size_t words, uint32_t * cnt)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < words && F[e] != GRAPH_EMPTY)
+        atomicAdd(&cnt[F[e]], 1u);
+}
+
+/// off[0 .. n] = exclusive prefix sums of cnt[0 .. n) (one block; 64-bit: n x R edges); cnt is cleared for the scatter's fill counters
+static __global__ __launch_bounds__(BLOCK) void graph_scan_kernel(uint32_t * cnt, uint32_t n, uint64_t * off)
+{
+    __shared__ uint64_t part[BLOCK];
+    __shared__ uint64_t carry;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0)
+        carry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < n; base += BLOCK)
+    {
+        const uint32_t i = base + tid;
+        const uint64_t v = i < n ? cnt[i] : 0;
+        part[tid] = v;
+        __syncthreads();
+        for (uint32_t s = 1; s < BLOCK; s <<= 1)
+        {
+            const uint64_t add = tid >= s ? part[tid - s] : 0;
+            __syncthreads();
+            part[tid] += add;
+            __syncthreads();
+        }
+        if (i < n)
+        {
+            off[i] = carry + part[tid] - v;
+            cnt[i] = 0;
+        }
+        __syncthreads();
+        if (tid == BLOCK - 1)
+            carry += part[tid];
+        __syncthreads();
+    }
+    if (tid == 0)
+        off[n] = carry;
+}
+
+/// edge (r, i) with F[i][r] = j goes somewhere into j's segment: the place is the atomics' business, the selection ranks the keys
+static __global__ void graph_scatter_kernel(const uint32_t * F, size_t words, uint32_t lgR, const uint64_t * off, uint32_t * fill, uint64_t * seg)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= words || F[e] == GRAPH_EMPTY)
+        return;
+    const uint32_t j = F[e], i = (uint32_t)(e >> lgR), r = (uint32_t)e & ((1u << lgR) - 1);
+    seg[off[j] + atomicAdd(&fill[j], 1u)] = (uint64_t)r << 32 | i;
+}
+
+/// One wavefront per node j: G_j = the sources of the R / 2 smallest (r, i) of its segment (R / 2 passes of "the smallest key above
+/// the last one"), then N_j = F_j[0 .. R/2), the G_j not yet there, the F_j[R/2 .. R) not yet there, compacted and cut to R.
+static __global__ __launch_bounds__(BLOCK) void graph_reverse_kernel(const uint32_t * F, const uint64_t * off, const uint64_t * seg, uint32_t n,
+                                                                     uint32_t R, uint32_t * nbr)
+{
+    __shared__ uint32_t cand_all[4][96]; // R / 2 + R / 2 + R / 2 <= 96 candidates of a node, in order
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, H = R / 2;
+    const bool live = blockIdx.x * 4 + wave < n; // (the last block's spare wavefronts keep the barriers company on node 0, and write nothing)
+    const uint32_t j = live ? blockIdx.x * 4 + wave : 0;
+    uint32_t * cand = cand_all[wave];
+    for (uint32_t s = lane; s < 3 * H; s += 64)
+        cand[s] = s < H ? F[(size_t)j * R + s] : (s < 2 * H ? GRAPH_EMPTY : F[(size_t)j * R + s - H]);
+    __syncthreads();
+    const uint64_t s0 = off[j], s1 = off[j + 1];
+    uint64_t last = 0;
+    for (uint32_t t = 0; t < H && s0 + t < s1; t++)
+    {
+        uint64_t best = KEY_NONE;
+        for (uint64_t e = s0 + lane; e < s1; e += 64)
+        {
+            const uint64_t key = seg[e];
+            if ((t == 0 || key > last) && key < best)
+                best = key;
+        }
+        for (int d = 32; d; d >>= 1)
+        {
+            const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)best, d);
+            best = o < best ? o : best;
+        }
+        last = best;
+        if (lane == 0)
+            cand[H + t] = (uint32_t)best;
+    }
+    __syncthreads();
+    uint32_t placed = 0;
+    for (uint32_t s = lane; s < ((3 * H + 63) & ~63u); s += 64) // whole wavefronts: every lane votes
+    {
+        const uint32_t v = s < 3 * H ? cand[s] : GRAPH_EMPTY;
+        bool keep = v != GRAPH_EMPTY;
+        for (uint32_t e = 0; keep && e < s; e++)
+            keep = cand[e] != v;
+        const uint64_t b = __ballot(keep);
+        const uint32_t at = placed + (uint32_t)__popcll(b & ((1ull << lane) - 1));
+        if (live && keep && at < R)
+            nbr[(size_t)j * R + at] = v;
+        placed += (uint32_t)__popcll(b);
+    }
+    for (uint32_t s = placed + lane; live && s < R; s += 64)
+        nbr[(size_t)j * R + s] = GRAPH_EMPTY;
+}
+
+}

@@ -152,6 +152,11 @@ static bool refine_checks(const msvs_rows * rows, int metric, const float * quer
 
 namespace msvs
 {
+RowsView rows_view(const msvs_rows * rows)
+{
+    return RowsView{rows->table(), rows->placement == MSVS_ROWS_DEVICE ? nullptr : rows->host, rows->ld, rows->n, rows->dim, rows->device, rows->normalize};
+}
+
 void refine_device(const msvs_rows * rows, int metric, const float * d_queries, size_t nq, const int64_t * d_cand, size_t kc, size_t k,
                    int64_t * d_ids, float * d_dis, hipStream_t stream)
 {

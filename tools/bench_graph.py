@@ -1,0 +1,111 @@
+"""The graph index on one GPU: --rows x --dim rows of one of bench.py's data models (--data mid | iid | blobs03) in a device row
+store, a built index of degree --degree, searched through the device entry on one stream.  Reports, gates nothing.
+
+  - the build's wall time (msvs_graph_index_build as a whole: trainer, exact lists, prune, reverse edges);
+  - for nq in --batches and ef in --efs: recall@10 against an exact scan of the rows (torch, on the first 256 queries), the median
+    time of --reps calls between HIP events after a warm-up call, queries/s;
+  - beside them the IVFFLAT index of the same rows (nlist --nlist) at --nprobes, the same way, to read the nprobe of equal recall off.
+
+Writes one JSON file (default profiles/graph.json) and prints it.
+
+    python -m tools.bench_graph [--rows N] [--dim D] [--data mid] [--degree 32] [--nlist 1024] [--batches 1,64,4096] [--efs 32,64,128,256]
+                                [--nprobes 8,16,32,64] [--reps R] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+import myscaledb_amd.capi as capi  # noqa: E402
+
+
+def main():
+    import torch
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1 << 20)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--data", default="mid", choices=("mid", "iid", "blobs03"))
+    ap.add_argument("--degree", type=int, default=32)
+    ap.add_argument("--nlist", type=int, default=1024)
+    ap.add_argument("--batches", default="1,64,4096")
+    ap.add_argument("--efs", default="32,64,128,256")
+    ap.add_argument("--nprobes", default="8,16,32,64")
+    ap.add_argument("--reps", type=int, default=11)
+    ap.add_argument("--out", default=os.path.join("profiles", "graph.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_graph needs a GPU: there is nothing to measure without one")
+    capi.set_device(0)
+    dev = torch.device("cuda", 0)
+    batches = [int(v) for v in a.batches.split(",")]
+    nq, k = max(batches), 10
+    x, q, what = bench.data_model(a.data, a.rows, nq, a.dim, dev)
+    x, q = x.contiguous(), q.contiguous()
+    torch.cuda.synchronize()
+    stream = torch.cuda.current_stream().cuda_stream
+    nt = min(256, nq)  # the exact answer, by chunks of rows
+    best = torch.full((nt, k), float("inf"), device=dev)
+    best_i = torch.zeros((nt, k), device=dev, dtype=torch.int64)
+    for r0 in range(0, a.rows, 1 << 16):
+        d2 = torch.cdist(q[:nt].double(), x[r0:r0 + (1 << 16)].double()) ** 2
+        cat_d = torch.cat([best, d2.float()], 1)
+        cat_i = torch.cat([best_i, torch.arange(r0, r0 + d2.shape[1], device=dev).expand(nt, -1)], 1)
+        best, sel = torch.topk(cat_d, k, dim=1, largest=False)
+        best_i = torch.gather(cat_i, 1, sel)
+    truth = best_i.cpu().numpy()
+
+    def recall(ids):
+        return float(np.mean([len(set(t.tolist()) & set(g.tolist())) / k for t, g in zip(truth, ids[:nt])]))
+
+    di = torch.empty((nq, k), device=dev, dtype=torch.int64)
+    dd = torch.empty((nq, k), device=dev, dtype=torch.float32)
+
+    def timed(call):
+        call()  # warm-up: arenas, the kernel's attribute
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms))
+
+    out = {"data": what, "rows": a.rows, "dim": a.dim, "degree": a.degree, "nlist": a.nlist, "graph": [], "ivfflat": []}
+    rows = capi.Rows(a.dim, a.rows)
+    rows.append(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
+    gx = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,ncentroids=%d,kmeans_iters=10" % (a.degree, a.nlist))
+    t0 = time.perf_counter()
+    gx.build()
+    out["build_s"] = time.perf_counter() - t0
+    out["graph_bytes"] = gx.memory_usage
+    for b in batches:
+        for ef in (int(v) for v in a.efs.split(",")):
+            ms = timed(lambda: gx.search_device(q.data_ptr(), b, k, di.data_ptr(), dd.data_ptr(), ef=ef, stream=stream))
+            out["graph"].append({"nq": b, "ef": ef, "ms": ms, "qps": b / ms * 1e3, "recall@10": recall(di.cpu().numpy()) if b >= nt else None})
+    gx.close()
+    ivf = capi.Index(capi.INDEX_IVFFLAT, capi.METRIC_L2, a.dim, "ncentroids=%d,kmeans_iters=10" % a.nlist)
+    ivf.train(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
+    ivf.add(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
+    ivf.build()
+    for b in batches:
+        for p in (int(v) for v in a.nprobes.split(",")):
+            ms = timed(lambda: ivf.search_device(q.data_ptr(), b, k, p, di.data_ptr(), dd.data_ptr(), stream))
+            out["ivfflat"].append({"nq": b, "nprobe": p, "ms": ms, "qps": b / ms * 1e3, "recall@10": recall(di.cpu().numpy()) if b >= nt else None})
+    text = json.dumps(out, indent=1)
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
