@@ -264,6 +264,41 @@ MSVS_API int msvs_sq_index_export(const msvs_sq_index_t * index, float * centroi
 MSVS_API int msvs_sq_index_serialize_io(const msvs_sq_index_t * index, const struct msvs_io * io);
 MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t ** out);
 
+/* IVFSQ candidate search (8-bit indexes only; bit_size=4 and 16: MSVS_ERR_NOT_IMPLEMENTED): an exact integer pass over the stored
+ * codes picks kc candidates per query, a canonical re-rank of those codes gives the k results.  All float arithmetic is f32 with
+ * separately rounded operations (fl) and no fma; cip(a, b) is the canonical inner product of the scans (msvs_refine's arithmetic).
+ * Index constants (prepare_candidates): o_j = fl(vmin_j + fl(128 * step_j)); for an L2 index every row of list l gets
+ *   E_row = fl(cip(e, e) + fl(2 * cip(c_l, e))), e_j = fl(vmin_j + fl(float(code_j) * step_j)) (the decode's inner term); padding
+ *   columns contribute +0.
+ * Per query q (normalised first for cosine): u_j = fl(q_j * step_j), M = max_j |u_j|, D = fl(M / 16256); if D is not a finite
+ *   positive number, D = 0 and every w_j = 0, otherwise w_j = clamp(rint(fl(u_j / D)), -16256, 16256) (ties to even); the planes
+ *   h_j = floor(w_j / 128) in [-127, 127] and l_j = w_j - 128 * h_j in [0, 127]; Qo = cip(q, o).
+ * Per row of a probed list: s_j = code_j - 128; S = 128 * sum_j h_j s_j + sum_j l_j s_j, an exact integer (each sum fits int32 at
+ *   every accepted dim, the combination is formed in 64 bits); float(S) is rounded to nearest even.
+ * Candidate score, with P_ql / D_ql the coarse step's canonical inner product / L2 distance of the query to centroid l:
+ *   IP, cosine: a = fl(fl(P_ql + Qo) + fl(D * float(S))), larger is better;
+ *   L2:         a = fl(fl(D_ql + E_row) - fl(2 * fl(Qo + fl(D * float(S))))), smaller is better.
+ * search_candidates(k, kc, nprobe): the probed lists are search's.  C_q = the first kc alive rows of those lists by (a better first,
+ *   global list-major row position ascending); a is compared as a number and a NaN a is never a candidate; the filter is indexed by
+ *   label as everywhere.  The result is the top k of C_q by (canonical distance over the decoded row, label): exactly the numbers
+ *   search returns for those rows; padding -1 / the neutral value, cosine reports fl(1 - ip).  Consequence: with kc >= the number of
+ *   alive rows in the probed lists the result is search's, bit for bit.  For queries or quantisers with non-finite values the result
+ *   is still a correctly scored and ordered subset of the probed rows; which subset is unspecified.
+ * Known limit: the L2 form cancels terms of the size of |x^|^2 in f32, so on data far from the origin the candidate order coarsens
+ *   and wants a larger kc (a residual form of the query image would not; it is not built).
+ * prepare_candidates: after build or load, idempotent; computes, for L2, the E_row table (4 bytes a row, device only, never in
+ *   a file, counted by memory_usage from then on); o is formed from vmin and step where it is used and takes no memory, so
+ *   memory_usage of an IP or cosine index does not change.  Before build: MSVS_ERR_NOT_READY.  An index that never calls it is unchanged.
+ * search_candidates (host pointers, params "nprobe=P") / search_candidates_device (device pointers, no host synchronisation):
+ *   1 <= k <= kc <= MSVS_MAX_K (beyond MSVS_MAX_K: MSVS_ERR_UNSUPPORTED_K; k > kc: MSVS_ERR_INVALID_ARGUMENT); an index that is not
+ *   built or not prepared: MSVS_ERR_NOT_READY; nq = 0 or k = 0 is a no-op; min(nprobe, nlist) <= MSVS_MAX_K as for search. */
+MSVS_API int msvs_sq_index_prepare_candidates(msvs_sq_index_t * index);
+MSVS_API int msvs_sq_index_search_candidates(const msvs_sq_index_t * index, const float * queries, size_t nq, size_t k, size_t kc,
+                                             const char * params, const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_sq_index_search_candidates_device(const msvs_sq_index_t * index, const float * d_queries, size_t nq, size_t k, size_t kc,
+                                                    size_t nprobe, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
+                                                    float * d_dis, void * hip_stream);
+
 /* IVFPQ -- an inverted-file index of Float32 vectors that keeps product-quantised residual codes ONLY (no f32 row survives build):
  * m code bytes, or ceil(m / 2) at bit_size=4, (padded to 4) + a u32 label per row.  metric: L2 / IP / COSINE (anything else -> MSVS_ERR_NOT_IMPLEMENTED).  All
  * arithmetic is f32 with separately rounded operations (fl), no fma:

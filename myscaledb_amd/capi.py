@@ -57,6 +57,7 @@ SYMBOLS = [
     "msvs_sq_index_search_rounds", "msvs_sq_index_search_rounds_device", "msvs_sq_index_search_refine_rounds",
     "msvs_sq_index_search_refine_rounds_device", "msvs_pq_index_search_rounds", "msvs_pq_index_search_rounds_device",
     "msvs_pq_index_search_refine_rounds", "msvs_pq_index_search_refine_rounds_device",
+    "msvs_sq_index_prepare_candidates", "msvs_sq_index_search_candidates", "msvs_sq_index_search_candidates_device",
     "msvs_cache_evict", "msvs_cache_stats", "msvs_knn_resident", "msvs_index_set_delete_bitmap",
     "msvs_index_set_merged_maps", "msvs_comm_unique_id", "msvs_comm_init", "msvs_comm_init_custom",
     "msvs_comm_free", "msvs_comm_all_reduce_u64", "msvs_comm_rank", "msvs_comm_size", "msvs_shard_search_device", "msvs_shard_search_device_async", "msvs_shard_search_drain", "msvs_shard_search_routed_device",
@@ -513,6 +514,28 @@ class SqIndex(_CodedIndex):
         _check(lib().msvs_sq_index_export(self._h, _p(cent, C.c_float), _p(lo, C.c_float), _p(hi, C.c_float), _p(off, C.c_int64),
                                           None if codes is None else codes.ctypes.data_as(C.POINTER(C.c_uint8)), _p(labels, C.c_int64)))
         return cent, lo, hi, off, codes, labels
+
+    def prepare_candidates(self):
+        """msvs_sq_index_prepare_candidates: the constants of search_candidates (after build or load; 8-bit indexes)."""
+        _check(lib().msvs_sq_index_prepare_candidates(self._h))
+
+    def search_candidates(self, queries, k, kc, params="", alive=None, nbits=None):
+        """The candidate search: the int8 matrix-core pass keeps kc rows per query, their canonical re-rank gives the k results
+        (include/msvs.h).  params, alive and nbits as search's."""
+        q = _f32(queries).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), np.int64)
+        dis = np.empty((q.shape[0], k), np.float32)
+        bits = None if alive is None else pack_bits(alive)
+        nb = C.c_size_t(0 if alive is None else (len(alive) if nbits is None else int(nbits)))
+        _check(lib().msvs_sq_index_search_candidates(self._h, _p(q, C.c_float), C.c_size_t(q.shape[0]), C.c_size_t(k), C.c_size_t(kc),
+                                                     params.encode(), _p(bits, C.c_uint64), nb, _p(ids, C.c_int64), _p(dis, C.c_float)))
+        return ids, dis
+
+    def search_candidates_device(self, d_queries, nq, k, kc, nprobe, d_ids, d_dis, stream=0, d_alive=0, nbits=0):
+        """search_candidates with raw device addresses (ints); enqueues on `stream` and returns immediately."""
+        _check(lib().msvs_sq_index_search_candidates_device(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(kc),
+                                                            C.c_size_t(nprobe), self._dev(d_alive), C.c_size_t(nbits),
+                                                            C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)), self._dev(stream)))
 
     @classmethod
     def load_io(cls, store, metric=None, dim=None, bits=None):

@@ -8,6 +8,7 @@
 #pragma once
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -355,11 +356,15 @@ struct ScanRound
     const uint64_t * after = nullptr;
 };
 
-/// What an index wants of a round beside the common buffers: scratch bytes per query of its own, the coarse step's distances.
+/// What an index wants of a round beside the common buffers: scratch bytes per query of its own, the coarse step's distances, and
+/// (finish) the merged KEYS of the round's queries, [query][k] ascending and KEY_NONE-padded, instead of ids and distances: the
+/// merge writes them into the arena and finish(round, keys, q0) enqueues what turns them into results (q0: the round's first query
+/// in the batch; d_ids / d_dis of the search are not written by the skeleton then).  One-round searches only.
 struct RoundExtra
 {
     size_t bytes_per_q = 0;
     bool probe_dis = false;
+    std::function<void(const ScanRound &, const uint64_t *, size_t)> finish;
 };
 
 /// the fields every grouped scan's parameter block has
@@ -415,21 +420,21 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
     // per query of a round: its padded row, its probes and pairs (rounds: a round's merged keys and the continuation key)
     const SegmentPlan sp = plan_segments(ix.max_list_len, rpb_knob, row_step, P, kl,
                                          (size_t)ld * 4 + P * 8 + 64 + extra.bytes_per_q + (extra.probe_dis ? P * 4 : 0)
-                                             + (rounds ? (size_t)(MSVS_MAX_K + 1) * 8 : 0),
+                                             + (rounds ? (size_t)(MSVS_MAX_K + 1) * 8 : 0) + (extra.finish ? kl * 8 : 0),
                                          nq);
     const uint32_t rpb = sp.rpb;
     const size_t seg_max = sp.seg_max, per_q = sp.per_q, chunk = sp.chunk;
     const size_t last = nq % chunk;
     const size_t coarse = std::max(flat_scratch_bytes(nlist, chunk, (uint32_t)P, ld), last ? flat_scratch_bytes(nlist, last, (uint32_t)P, ld) : 0);
     Scratch & scr = scratch_for(stream);
-    scr.reserve(chunk * per_q + coarse + (nlist + 1) * 16 + 20 * 256, stream);
+    scr.reserve(chunk * per_q + coarse + (nlist + 1) * 16 + 21 * 256, stream);
     float * dq = scr.take<float>(chunk * ld);
     int32_t * probes = scr.take<int32_t>(chunk * P);
     float * probe_dis = extra.probe_dis ? scr.take<float>(chunk * P) : nullptr;
     void * extra_buf = extra.bytes_per_q ? scr.take<unsigned char>(chunk * extra.bytes_per_q) : nullptr;
     const GroupedPlan plan(scr, nlist, chunk * P);
     uint64_t * partial = scr.take<uint64_t>(chunk * P * seg_max * kl);
-    uint64_t * round_keys = rounds ? scr.take<uint64_t>(chunk * MSVS_MAX_K) : nullptr;
+    uint64_t * round_keys = rounds ? scr.take<uint64_t>(chunk * MSVS_MAX_K) : (extra.finish ? scr.take<uint64_t>(chunk * kl) : nullptr);
     uint64_t * after = rounds ? scr.take<uint64_t>(chunk) : nullptr;
     const size_t mark = scr.used;
     for (size_t q0 = 0; q0 < nq; q0 += chunk)
@@ -479,6 +484,11 @@ inline void search_device(const CodedIvf & ix, const char * name, const char * p
             launch_ivf_merge(m, im, (uint32_t)nqc, stream);
             if (rounds)
                 launch_round_scatter(m, round_keys, nqc, kr, k, done, ix.metric == MSVS_METRIC_COSINE, d_ids + q0 * k, d_dis + q0 * k, after, stream);
+            else if (extra.finish)
+            {
+                extra.finish(round, round_keys, q0);
+                MSVS_HIP(hipGetLastError());
+            }
         }
     }
 }

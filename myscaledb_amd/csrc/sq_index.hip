@@ -6,15 +6,13 @@
 // coded_ivf.hpp, which also lists what is reused as it is.
 #include <cmath>
 
-#include "coded_ivf.hpp"
+#include "sq_index.hpp"
 #include "sq_ivf_kernels.hpp"
 
 using namespace msvs;
 
 namespace
 {
-constexpr const char * SQ = "IVFSQ";
-
 /// floats of a padded query / centroid row (= bytes of a stored row at 8 bits)
 inline uint32_t sq_ld(size_t dim) { return (uint32_t)round_up(dim, (size_t)16); }
 /// the smallest tile with the largest k must fit the scan's LDS budget (the 8-bit image: no width has a larger one)
@@ -28,13 +26,6 @@ inline float sq_ord2f(uint32_t o)
     return f;
 }
 }
-
-struct msvs_sq_index : CodedIvf // ld = round_up(dim, 16), row_bytes = 16 sq_row_words(bits, ld); codes: max(n, 1) rows, not zeroed
-{
-    uint32_t bits = 8;                 // 4, 8 or 16
-    std::vector<float> h_vmin, h_vmax; // dim
-    DevBuf<float> d_vmin, d_step;      // ld each, zero padded (bits 16: none, the range enters no arithmetic)
-};
 
 static void sq_set_geometry(msvs_sq_index & ix, int metric, size_t dim, uint32_t bits)
 {
@@ -259,7 +250,7 @@ extern "C" size_t msvs_sq_index_num_lists(const msvs_sq_index_t * ix) { return i
 extern "C" size_t msvs_sq_index_bit_size(const msvs_sq_index_t * ix) { return ix ? ix->bits : 0; }
 extern "C" size_t msvs_sq_index_memory_usage(const msvs_sq_index_t * ix)
 {
-    return ix ? coded_bytes(*ix) + ix->d_vmin.bytes() + ix->d_step.bytes() : 0;
+    return ix ? coded_bytes(*ix) + ix->d_vmin.bytes() + ix->d_step.bytes() + ix->d_erow.bytes() : 0;
 }
 
 // ------------------------------------------------------------------------------------------- search

@@ -10,8 +10,15 @@ limit, and the run stops at the first child that fails.  Writes one JSON file (d
 every one is timed, alternating with the others, and a 4-bit index is also searched through search_refine at kc = 50 and 100 over
 a row store of the original rows (recall only).  --competitors 0 leaves the IVFFLAT indexes out.
 
+--candidates takes a list of kc (32,100): the 8-bit index is prepared and search_candidates(k, kc) joins the alternating whole-call
+timings beside search on the same index in the same process (sq_cand_kc32, ...); the candidate scan and the re-rank are timed by
+HIP events in the pass of their own (families sq_cand_scan, sq_cand_rerank), the scan's rate is stated over the code bytes it
+streams (rows x round_up(dim, 16) bytes, a 32-query tile), recall@10 stands beside search's.  A difference to search counts only
+beyond the min -- max spread of search's own repeated calls, which the output carries (call_ms_all).  Default output then:
+profiles/sq_ivf_candidates.json.
+
     python -m tools.bench_sq_ivf [--rows N] [--dim D] [--nlist L] [--batches 64,1024,4096] [--nprobe P] [--k K] [--reps R] [--out FILE]
-                                 [--bit-size 8,4,16] [--competitors 0]
+                                 [--bit-size 8,4,16] [--competitors 0] [--candidates 32,100]
 """
 import argparse
 import json
@@ -36,14 +43,14 @@ def blobs(rng, centres, n):
     return out
 
 
-def streamed_rows(q, cent, lens, nprobe, nlist):
+def streamed_rows(q, cent, lens, nprobe, nlist, tile=0):
     """rows the list scan of the SQ index streams: sum over lists of ceil(pairs / T) * len, with sq_index.hip's choice of T (k = 10
     fits every tile) and the probe lists recomputed here in float64 (the boundary probes may differ from the canonical ones)."""
     d = (q.astype(np.float64) ** 2).sum(1)[:, None] - 2.0 * q.astype(np.float64) @ cent.T.astype(np.float64) + (cent.astype(np.float64) ** 2).sum(1)[None, :]
     probes = np.argsort(d, axis=1)[:, :nprobe]
     pairs = np.bincount(probes.ravel(), minlength=nlist)
     n_pairs = probes.size
-    T = 8 if n_pairs >= 16 * nlist else (4 if n_pairs >= 2 * nlist else 2)
+    T = tile if tile else (8 if n_pairs >= 16 * nlist else (4 if n_pairs >= 2 * nlist else 2))
     return int((-(-pairs // T) * lens).sum()), int((pairs * lens).sum()), T
 
 
@@ -86,6 +93,13 @@ def child(a, nq):
     runs = {name: (lambda ix: lambda: ix.search(q, a.k, sp))(ix) for name, ix in sqs.items()}
     for name, ix in flats.items():
         runs[name] = (lambda ix: lambda: ix.search(q, a.k, sp))(ix)
+    kcs = [int(v) for v in a.candidates.split(",")] if a.candidates else []
+    if kcs:
+        if "sq" not in sqs:
+            raise SystemExit("--candidates needs the 8-bit index (--bit-size 8,...)")
+        sqs["sq"].prepare_candidates()
+        for kc in kcs:
+            runs["sq_cand_kc%d" % kc] = (lambda kc: lambda: sqs["sq"].search_candidates(q, a.k, kc, sp))(kc)
 
     def canonical():
         """the shadow=0 index through the canonical batched list scan alone: no candidate pass, no probe pruning"""
@@ -114,7 +128,7 @@ def child(a, nq):
         capi.profile_enable(True)
         capi.profile_reset()
         fn()
-        fams = ("sq_ivf_scan", "ivf_scan", "ivf_plan", "flat_scan", "merge", "coarse_pass")
+        fams = ("sq_ivf_scan", "sq_cand_scan", "sq_cand_rerank", "ivf_scan", "ivf_plan", "flat_scan", "merge", "coarse_pass")
         kern[name] = {f: dict(zip(("calls", "ms"), capi.profile_get(f))) for f in fams}
         capi.profile_enable(False)
     nt = min(nq, 256)
@@ -138,7 +152,23 @@ def child(a, nq):
     scan_ms = scan[sq_name(widths[0])]
     f32_ms = kern["ivfflat_canonical"]["ivf_scan"]["ms"] if a.competitors else None
     ldc = row_bytes[sq_name(widths[0])] - 4
+    cand = {}
+    if kcs:  # the candidate scan: the rows it streams at its 32-query tile (16 where the LDS image of 32 does not fit), code bytes only
+        tile = 32 if 32 * (2 * ld + 16 + 8 * ((max(kcs) + 128 + 63) // 64 * 64) + 24) <= 160 * 1024 else 16
+        rows_c = streamed_rows(q, cent, lens, min(a.nprobe, a.nlist), a.nlist, tile)[0]
+        lo, hi = min(times["sq"]), max(times["sq"])
+        for kc in kcs:
+            name = "sq_cand_kc%d" % kc
+            ms = kern[name]["sq_cand_scan"]["ms"]
+            med = float(np.median(times[name]))
+            cand[name] = {"tile": tile, "rows_streamed": rows_c, "code_bytes": rows_c * ld, "scan_ms": ms,
+                          "rerank_ms": kern[name]["sq_cand_rerank"]["ms"],
+                          "scan_code_bytes_per_s": rows_c * ld / (ms * 1e-3) if ms else None,
+                          "call_ms_median": 1e3 * med, "search_call_ms_min_max": [1e3 * lo, 1e3 * hi],
+                          "verdict_vs_search": "faster" if med < lo else ("slower" if med > hi else "inside search's own spread"),
+                          "recall_at_k_vs_exact": recall[name], "search_recall_at_k_vs_exact": recall["sq"]}
     return {
+        "candidates": cand,
         "queries": nq, "T": T, "build_s": t_build,
         "sq_scan_ms": scan,
         "sq_scan_bytes_per_s_by_width": {name: rows_s * row_bytes[name] / (ms * 1e-3) if ms else None for name, ms in scan.items()},
@@ -168,19 +198,21 @@ def main():
                          "the exact scan); 0: 300 + 300 per 2^20 rows")
     ap.add_argument("--bit-size", default="8", help="code widths of the SQ indexes, a list of 8, 4 and 16; the first one's figures fill the sq_scan_* fields")
     ap.add_argument("--competitors", type=int, default=1, help="0: no IVFFLAT indexes beside the SQ ones")
-    ap.add_argument("--out", default=os.path.join("profiles", "sq_ivf.json"))
+    ap.add_argument("--candidates", default="", help="a list of kc: search_candidates(k, kc) on the 8-bit index beside search, e.g. 32,100")
+    ap.add_argument("--out", default="", help="default profiles/sq_ivf.json, with --candidates profiles/sq_ivf_candidates.json")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    a.out = a.out or os.path.join("profiles", "sq_ivf_candidates.json" if a.candidates else "sq_ivf.json")
     limit = a.limit if a.limit > 0 else 300 + 300 * max(1, a.rows >> 20)
     if a.child:
         print("RESULT " + json.dumps(child(a, a.child)))
         return
-    res = {"rows": a.rows, "dim": a.dim, "nlist": a.nlist, "k": a.k, "nprobe": a.nprobe, "metric": "L2", "version": capi.version(), "bit_size": a.bit_size, "batches": []}
+    res = {"rows": a.rows, "dim": a.dim, "nlist": a.nlist, "k": a.k, "nprobe": a.nprobe, "metric": "L2", "version": capi.version(), "bit_size": a.bit_size, "candidates": a.candidates, "batches": []}
     for nq in [int(v) for v in a.batches.split(",")]:
         cmd = [sys.executable, "-m", "tools.bench_sq_ivf", "--child", str(nq)]
         for key in ("rows", "dim", "nlist", "nprobe", "k", "reps", "competitors"):
             cmd += ["--" + key, str(getattr(a, key))]
-        cmd += ["--bit-size", a.bit_size]
+        cmd += ["--bit-size", a.bit_size, "--candidates", a.candidates]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=limit, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not line:
