@@ -282,8 +282,11 @@ MSVS_API int msvs_sq_index_load_io(const struct msvs_io * io, msvs_sq_index_t **
  *   global list-major row position ascending); a is compared as a number and a NaN a is never a candidate; the filter is indexed by
  *   label as everywhere.  The result is the top k of C_q by (canonical distance over the decoded row, label): exactly the numbers
  *   search returns for those rows; padding -1 / the neutral value, cosine reports fl(1 - ip).  Consequence: with kc >= the number of
- *   alive rows in the probed lists the result is search's, bit for bit.  For queries or quantisers with non-finite values the result
- *   is still a correctly scored and ordered subset of the probed rows; which subset is unspecified.
+ *   alive rows in the probed lists the result is search's, bit for bit.  Query values that are not ordinary numbers follow the same
+ *   rules and nothing else: a list whose coarse score search's coarse step does not admit (a NaN, an L2 distance of FLT_MAX or more,
+ *   an inner product of -FLT_MAX or less) is not probed; an M that is NaN, infinite, zero or so small that D rounds to zero gives
+ *   D = 0 and w = 0; a subnormal D is used as it is; an a of +-inf is a candidate like any number.  For a quantiser with non-finite
+ *   values the result is still a correctly scored and ordered subset of the probed rows; which subset is unspecified.
  * Known limit: the L2 form cancels terms of the size of |x^|^2 in f32, so on data far from the origin the candidate order coarsens
  *   and wants a larger kc (a residual form of the query image would not; it is not built).
  * prepare_candidates: after build or load, idempotent; computes, for L2, the E_row table (4 bytes a row, device only, never in

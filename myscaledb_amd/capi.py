@@ -1273,6 +1273,14 @@ def debug_prune_first(nq, nprobe):
     return bool(have.value), probes, upre, flags
 
 
+def debug_sq_cand_tiles():
+    """msvs_debug_sq_cand_tiles -> (launches of the IVFSQ candidate scan with tiles of 32 queries, with tiles of 16) this thread has
+    enqueued since the last read; the read resets both."""
+    out = (C.c_uint32 * 2)()
+    _check(lib().msvs_debug_sq_cand_tiles(out))
+    return int(out[0]), int(out[1])
+
+
 def debug_prune_first_served():
     """Queries the coarse tail's prune-first path has served, cumulative -- counted only under coarse_prune_debug = 1."""
     out = C.c_uint64(0)

@@ -35,6 +35,10 @@ void launch_sq_cand_scan(uint32_t grid, size_t lds, const SqCandParams & a, hipS
 /// 32 queries a tile, 16 where the records and buffers of 32 exceed the LDS (every d the index accepts fits 16 at kc = MSVS_MAX_K)
 uint32_t sq_cand_tile(uint32_t ld, size_t kc) { return sqc_lds_bytes(32, ld, (uint32_t)kc) <= SQC_LDS_MAX ? 32 : 16; }
 
+/// Tests only (msvs_debug_sq_cand_tiles): the launches of sq_cand_scan_kernel this host thread has enqueued since the last read, by
+/// the tile of the instantiation that was launched: [0] 32 queries, [1] 16
+thread_local uint32_t g_cand_scans[2] = {0, 0};
+
 void sq_candidates_device(const msvs_sq_index & ix, const float * d_queries, size_t nq, size_t k, size_t kc, size_t nprobe,
                           const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
 {
@@ -89,7 +93,10 @@ void sq_candidates_device(const msvs_sq_index & ix, const float * d_queries, siz
             a.ld = ld;
             const size_t lds = sqc_lds_bytes(T, ld, a.k);
             with_int<M_IP, M_L2>(r.metric, [&](auto m) {
-                with_int<32, 16>((int)T, [&](auto t) { launch_sq_cand_scan<decltype(m)::value, decltype(t)::value>(grid, lds, a, stream); });
+                with_int<32, 16>((int)T, [&](auto t) {
+                    g_cand_scans[decltype(t)::value == 32 ? 0 : 1]++;
+                    launch_sq_cand_scan<decltype(m)::value, decltype(t)::value>(grid, lds, a, stream);
+                });
             });
         });
 }
@@ -117,6 +124,17 @@ extern "C" int msvs_sq_index_prepare_candidates(msvs_sq_index_t * ix)
         }
         MSVS_HIP(hipStreamSynchronize(stream)); // (the table is complete before any search, on whatever stream, can see cand_ready)
         ix->cand_ready = true;
+    });
+}
+
+/// Tests only (not in msvs.h): out2[0] = this thread's launches of the candidate scan with tiles of 32 queries since the last read,
+/// out2[1] = those with tiles of 16.  A read resets both.
+extern "C" __attribute__((visibility("default"))) int msvs_debug_sq_cand_tiles(uint32_t * out2)
+{
+    return guarded([&] {
+        out2[0] = g_cand_scans[0];
+        out2[1] = g_cand_scans[1];
+        g_cand_scans[0] = g_cand_scans[1] = 0;
     });
 }
 

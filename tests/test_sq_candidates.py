@@ -22,7 +22,10 @@ def cip(p):
     return o.np_dot_canonical(np.asarray(p, F))
 
 
-def ref_candidates(exp, q, k, kc, nprobe, metric, alive=None):
+def ref_scores(exp, q, nprobe, metric):
+    """The candidate pass of the definition before the filter and the cut to kc -> (xh, per query (x, pos, worse, planes)): the decoded
+    rows; the query as scored (normalised for cosine), the probed positions in probe order, their score a as `worse` (ascending =
+    better, NaN = never a candidate) and the two integer sums the int8 planes accumulate, sum h s and sum l s"""
     cent, lo, hi, off, codes, labels = exp
     l2 = metric == L2
     nlist, lists = len(cent), sq.lists_of(off)
@@ -33,13 +36,16 @@ def ref_candidates(exp, q, k, kc, nprobe, metric, alive=None):
     erow = (cip(e * e) + (F(2) * cip(cent[lists] * e)).astype(F)).astype(F)
     s = codes.astype(np.int64) - 128
     qn = o.normalize_rows(q) if metric == COS else np.ascontiguousarray(q, F)
-    ids = np.full((len(q), k), -1, np.int64)
-    dis = np.full((len(q), k), FLT_MAX if l2 else -FLT_MAX, F)
-    for qi, x in enumerate(qn):
+    # "the probed lists are search's": the first nprobe by (coarse score, list id) among those the coarse step admits -- never a NaN
+    # score, never an L2 distance of FLT_MAX or more, never an inner product of -FLT_MAX or less
+    searched = o.ivf_search(cent, off, xh, labels, qn, nprobe, 1, o.METRIC_L2 if l2 else o.METRIC_IP)[2]
+    per_query = []
+    for x, probes in zip(qn, searched):
         coarse = o.np_l2sqr(x, cent) if l2 else o.np_ip(x, cent)
-        probes = np.lexsort((np.arange(nlist), coarse if l2 else -coarse))[:min(nprobe, nlist)]
-        pos = np.concatenate([np.arange(off[l], off[l + 1]) for l in probes])
-        cd = np.concatenate([np.full(off[l + 1] - off[l], coarse[l], F) for l in probes])
+        probes = probes[probes >= 0]
+        assert len(probes) == min(nprobe, nlist) or not np.isfinite(coarse).all()
+        pos = np.concatenate([np.arange(0)] + [np.arange(off[l], off[l + 1]) for l in probes])
+        cd = np.concatenate([np.zeros(0, F)] + [np.full(off[l + 1] - off[l], coarse[l], F) for l in probes])
         u = (x * step).astype(F)
         delta = F(np.abs(u).max()) / F(16256)
         w = np.zeros(len(u), np.int64)
@@ -55,6 +61,17 @@ def ref_candidates(exp, q, k, kc, nprobe, metric, alive=None):
             worse = ((cd + erow[pos]).astype(F) - (F(2) * (qo + x2).astype(F)).astype(F)).astype(F)
         else:
             worse = -((cd + qo).astype(F) + x2).astype(F)
+        per_query.append((x, pos, worse, (s[pos] @ h, s[pos] @ lp)))
+    return xh, per_query
+
+
+def ref_candidates(exp, q, k, kc, nprobe, metric, alive=None):
+    labels = exp[5]
+    l2 = metric == L2
+    xh, per_query = ref_scores(exp, q, nprobe, metric)
+    ids = np.full((len(q), k), -1, np.int64)
+    dis = np.full((len(q), k), FLT_MAX if l2 else -FLT_MAX, F)
+    for qi, (x, pos, worse, _) in enumerate(per_query):
         keep = ~np.isnan(worse)
         if alive is not None:
             keep &= alive[labels[pos]]
