@@ -539,7 +539,33 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
  * memory_usage: device bytes of the graph, the centroids and the seeds.  export: any output may be NULL.
  * File: `graph_data` through the caller's stream openers: a 64-byte header (magic, version, metric, dim, nlist, n, degree, FNV-1a of
  *   the body, FNV-1a of the header), the centroids, the seeds, nbr.  load checks sizes, ranges and n == msvs_rows_num(rows); anything
- *   corrupt is MSVS_ERR_IO. */
+ *   corrupt is MSVS_ERR_IO.
+ *
+ * Coded rows: create's parameter bit_size.  32 (the default) is the index above.  8: the index also keeps ONE quantiser and n rows
+ * of 8-bit codes, and the search scores decoded rows; anything else is MSVS_ERR_INVALID_ARGUMENT.  All arithmetic is f32 with
+ * separately rounded operations and no fma.
+ *   Quantiser: vmin[j] / vmax[j] = the exact minimum / maximum of column j over all n stored rows (the normalised rows for cosine),
+ *     NaN ignored, a column with no non-NaN value 0 .. 0 (as msvs_sq_index_train); step[j] = fl(fl(vmax[j] - vmin[j]) / 255).
+ *     A range whose span is not finite (any +-inf element in the store) is refused by build / set_graph with
+ *     MSVS_ERR_INVALID_ARGUMENT and the index is left not ready.
+ *   Encode: t = fl(fl(x_j - vmin[j]) / step[j]), code = min(255, max(0, rint(t))) with ties to even; 0 where step[j] == 0; a NaN
+ *     element has code 0.  There is no centroid residual: a graph row belongs to no list.
+ *   Decode: x^_j = fl(vmin[j] + fl(float(code_j) * step[j])).
+ *   Search: steps 1 - 6 above word for word, with "scored against its stored row" read as "scored against its decoded row x^":
+ *     seeds, V, keys, admission, iteration, stopping rules, the filter, cosine's fl(1 - ip) and every limit are unchanged, so the
+ *     result equals the 32-bit search over a row store holding x^, bit for bit.  The LDS image holds vmin and step beside the
+ *     query (three rows of round_up(dim, 16) floats); the same 160 KiB limit applies, and dim = 8192 fits at the default ef.
+ *   build: steps 1 - 5 over the f32 rows (the graph is made from exact neighbours), then the quantiser and the codes.  set_graph:
+ *     the caller's structure as above, then the quantiser and the codes from the store.
+ *   The row store is read by build and set_graph only: search, export, serialize and memory_usage never touch it, and once the last
+ *     build / set_graph has returned the caller may free it.
+ *   bit_size: 32 or 8 (0 for NULL).  export_codes: vmin[dim], vmax[dim] and n x dim codes in natural column order, any output may
+ *     be NULL; MSVS_ERR_INVALID_ARGUMENT on a 32-bit index.  memory_usage grows by n x round_up(dim, 16) plus the device bytes of
+ *     vmin and step (2 x round_up(dim, 16) x 4).
+ *   File: header version 2, otherwise the same 64 bytes; the body is the centroids, the seeds, nbr, vmin, vmax and the codes as
+ *     n x dim bytes in natural order, all under the body's checksum.  A 32-bit index writes and reads version 1 exactly as before.
+ *     load_io takes a version-2 file with rows == NULL; a non-NULL store is checked for n alone.  Bounds that are not finite,
+ *     vmax < vmin, an infinite span or a wrong size are MSVS_ERR_IO like any corruption.  A version-1 file keeps its rules. */
 #define MSVS_GRAPH_VISITED_MAX 12288
 typedef struct msvs_graph_index msvs_graph_index_t;
 MSVS_API int msvs_graph_index_create(int metric, const msvs_rows_t * rows, const char * params, msvs_graph_index_t ** out);
@@ -553,6 +579,8 @@ MSVS_API size_t msvs_graph_index_num_lists(const msvs_graph_index_t * index);
 MSVS_API size_t msvs_graph_index_degree(const msvs_graph_index_t * index);
 MSVS_API size_t msvs_graph_index_memory_usage(const msvs_graph_index_t * index);
 MSVS_API int msvs_graph_index_export(const msvs_graph_index_t * index, float * centroids, int32_t * seeds, uint32_t * nbr);
+MSVS_API size_t msvs_graph_index_bit_size(const msvs_graph_index_t * index);
+MSVS_API int msvs_graph_index_export_codes(const msvs_graph_index_t * index, float * vmin, float * vmax, uint8_t * codes);
 MSVS_API int msvs_graph_index_search(const msvs_graph_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
                                      const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
 MSVS_API int msvs_graph_index_search_device(const msvs_graph_index_t * index, const float * d_queries, size_t nq, size_t k, size_t ef,

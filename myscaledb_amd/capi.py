@@ -66,7 +66,7 @@ SYMBOLS = [
     "msvs_graph_index_create", "msvs_graph_index_free", "msvs_graph_index_build", "msvs_graph_index_set_graph", "msvs_graph_index_ready",
     "msvs_graph_index_num_data", "msvs_graph_index_num_lists", "msvs_graph_index_degree", "msvs_graph_index_memory_usage",
     "msvs_graph_index_export", "msvs_graph_index_search", "msvs_graph_index_search_device", "msvs_graph_index_serialize_io",
-    "msvs_graph_index_load_io",
+    "msvs_graph_index_load_io", "msvs_graph_index_bit_size", "msvs_graph_index_export_codes",
 ]
 
 
@@ -657,11 +657,14 @@ GRAPH_NO_EDGE = 0xFFFFFFFF
 class GraphIndex(_CodedIndex):
     """msvs_graph_index_t: coarse centroids, a seed label per centroid and a fixed-degree neighbour graph over the rows of `rows` (a
     Rows the caller keeps alive and no longer appends to), searched by the seeded beam search include/msvs.h defines.  params:
-    "degree=16|32|64" and the IVFFLAT trainer's keys ("ncentroids=N,kmeans_iters=I,...")."""
+    "degree=16|32|64", "bit_size=32|8" and the IVFFLAT trainer's keys ("ncentroids=N,kmeans_iters=I,...").
+    bit_size=8: build / set_graph also make one 8-bit quantiser and a code row per label from the store; the search scores the decoded
+    rows, so its results are those of a 32-bit index over a store holding them, and after the last build / set_graph nothing reads
+    `rows` any more: it may be closed, and load_io needs none."""
     _c = "msvs_graph_index"
 
-    def __init__(self, metric, rows, params="", _handle=None):
-        self.metric, self.rows, self.dim = int(metric), rows, rows.dim
+    def __init__(self, metric, rows, params="", _handle=None, _dim=None):
+        self.metric, self.rows, self.dim = int(metric), rows, rows.dim if rows is not None else int(_dim)
         self._h = C.c_void_p()
         if _handle is not None:
             self._h = _handle
@@ -700,12 +703,26 @@ class GraphIndex(_CodedIndex):
         _check(lib().msvs_graph_index_export(self._h, _p(cent, C.c_float), _p(seeds, C.c_int32), _p(nbr, C.c_uint32)))
         return cent, seeds, nbr
 
+    @property
+    def bit_size(self):
+        """32: the search scores the store's f32 rows; 8: the index's own codes"""
+        return self._size("bit_size")
+
+    def export_codes(self):
+        """bit_size=8 -> (vmin [dim], vmax [dim], codes [n, dim] u8 in natural column order)"""
+        vmin, vmax = np.empty(self.dim, np.float32), np.empty(self.dim, np.float32)
+        codes = np.empty((self.num_data, self.dim), np.uint8)
+        _check(lib().msvs_graph_index_export_codes(self._h, _p(vmin, C.c_float), _p(vmax, C.c_float), _p(codes, C.c_uint8)))
+        return vmin, vmax, codes
+
     @classmethod
-    def load_io(cls, store, rows):
-        """the file's metric (GraphHeader: magic[8], u32 version, i32 metric, ...) over the caller's row store"""
+    def load_io(cls, store, rows=None):
+        """the file's metric and dim (GraphHeader: magic[8], u32 version, i32 metric, u64 dim, ...) over the caller's row store; the
+        file of a bit_size=8 index (version 2) needs no store: rows=None"""
         h = C.c_void_p()
-        _check(lib().msvs_graph_index_load_io(C.byref(_DictIO(store).io), rows._h, C.byref(h)))
-        return cls(struct.unpack_from("<i", bytes(store["graph_data"][:16]), 12)[0], rows, _handle=h)
+        _check(lib().msvs_graph_index_load_io(C.byref(_DictIO(store).io), rows._h if rows is not None else None, C.byref(h)))
+        metric, dim = struct.unpack_from("<iQ", bytes(store["graph_data"][:24]), 12)
+        return cls(metric, rows, _handle=h, _dim=dim)
 
 
 def refine(rows, metric, queries, cand, k):

@@ -1,6 +1,8 @@
 // graph_index.hip -- the graph index (include/msvs.h: msvs_graph_index_*): coarse centroids, one seed label per centroid and a
 // fixed-degree neighbour graph over the rows of a borrowed row store; searched by a seeded beam search whose every id and distance
 // is a function of the inputs alone.  The kernels and their layout: graph_kernels.hpp.  DESIGN.md 4.14.
+// bit_size=8: the index keeps one 8-bit quantiser and a code row per label, made from the store by build / set_graph; the search
+// scores decoded rows and nothing but build / set_graph reads the store.
 // Reused as they are: the row store (refine.hip), the canonical scoring of refine_kernels.hpp's chain, the k-means trainer and the
 // canonical coarse top-P (coded_ivf.hpp: kmeans, flat_search_device), the exact FLAT search for the build's neighbour lists.
 #include <algorithm>
@@ -26,6 +28,11 @@ struct msvs_graph_index
     DevBuf<float> centroids;          // nlist x ld
     DevBuf<int32_t> seeds;            // nlist
     DevBuf<uint32_t> nbr;             // n x R
+    // bit_size=8 (ldc = round_up(dim, 16) bytes a stored row, sq_layout.hpp's 8-bit order; ldc floats of padded vmin / step)
+    uint32_t bits = 32, ldc = 0;
+    std::vector<float> h_vmin, h_vmax; // dim
+    DevBuf<float> d_vmin, d_step;      // ldc, zero padded
+    DevBuf<uint8_t> codes;             // n x ldc
     bool ready = false;
 };
 
@@ -35,6 +42,7 @@ const char * const GRAPH = "graph";
 constexpr size_t GRAPH_LDS_MAX = 160 * 1024;
 constexpr size_t GRAPH_QUERY_CHUNK = 16384; // queries of one coarse step + launch
 constexpr size_t GRAPH_LIST_CHUNK = 4096;   // rows whose exact lists one FLAT search of the build returns
+constexpr size_t GRAPH_CODE_CHUNK = (size_t)1 << 27; // codes one launch of the encoder writes
 
 uint32_t log2_of(uint32_t v)
 {
@@ -87,10 +95,10 @@ GraphSearch parse_graph_search(const char * params, size_t k)
     return graph_defaults(k, (size_t)ef, (size_t)nprobe, (size_t)width, (size_t)it);
 }
 
-template <int METRIC>
+template <int METRIC, int BITS>
 void launch_graph_search(const GraphSearchParams & a, size_t nq, size_t lds, hipStream_t stream)
 {
-    constexpr auto kernel = &graph_search_kernel<METRIC>;
+    constexpr auto kernel = &graph_search_kernel<METRIC, BITS>;
     static std::once_flag once; // more than 64 KiB of dynamic LDS needs the attribute raised once per kernel
     std::call_once(once, [] {
         MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRAPH_LDS_MAX));
@@ -111,17 +119,23 @@ void graph_search_device(const msvs_graph_index & ix, const float * d_queries, s
         fail(MSVS_ERR_UNSUPPORTED_K, "min(nprobe, nlist) = %zu exceeds the coarse quantiser's top-k limit %d", P, MSVS_MAX_K);
     // the visited table: what the search can score at most, at load factor <= 0.5
     const size_t iters = std::min<size_t>(s.max_iters, MSVS_GRAPH_VISITED_MAX), reach = std::min<size_t>(MSVS_GRAPH_VISITED_MAX, P + iters * fan);
-    const uint32_t tab = (uint32_t)(2 * std::max<size_t>(reach, 32)), ld4 = ix.ld / 4;
-    const size_t lds = graph_lds_bytes(ld4, tab);
+    const uint32_t tab = (uint32_t)(2 * std::max<size_t>(reach, 32)), ld4 = ix.ld / 4, lc4 = ix.ldc / 4;
+    const bool coded = ix.bits == 8;
+    const size_t lds = coded ? graph_sq_lds_bytes(lc4, tab) : graph_lds_bytes(ld4, tab);
     if (lds > GRAPH_LDS_MAX)
         fail(MSVS_ERR_INVALID_ARGUMENT, "the graph search's LDS image (%zu bytes) exceeds %zu", lds, GRAPH_LDS_MAX);
     if (nq == 0 || k == 0)
         return;
     if (!d_queries || !d_ids || !d_dis)
         fail(MSVS_ERR_INVALID_ARGUMENT, "null buffer");
-    const RowsView rv = rows_view(ix.rows);
-    if (rv.n < ix.n)
-        fail(MSVS_ERR_INVALID_ARGUMENT, "the row store holds %zu rows, the graph was made over %zu", rv.n, ix.n);
+    const float * table = nullptr; // (a coded index never looks at the store)
+    if (!coded)
+    {
+        const RowsView rv = rows_view(ix.rows);
+        if (rv.n < ix.n)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the row store holds %zu rows, the graph was made over %zu", rv.n, ix.n);
+        table = rv.table;
+    }
     const int m = scan_metric(ix.metric);
     const size_t chunk = std::min(nq, GRAPH_QUERY_CHUNK);
     Scratch & scr = scratch_for(stream);
@@ -141,7 +155,11 @@ void graph_search_device(const msvs_graph_index & ix, const float * d_queries, s
         co.out_probes = probes;
         flat_search_device(scr, m, ix.centroids.p, nullptr, ix.nlist, ix.ld, dq, nqc, (uint32_t)P, nullptr, 0, co, stream);
         GraphSearchParams a{};
-        a.rows = reinterpret_cast<const float4 *>(rv.table);
+        a.rows = reinterpret_cast<const float4 *>(table);
+        a.codes = reinterpret_cast<const uint4 *>(ix.codes.p);
+        a.vmin = reinterpret_cast<const float4 *>(ix.d_vmin.p);
+        a.step = reinterpret_cast<const float4 *>(ix.d_step.p);
+        a.lc4 = lc4;
         a.Q = reinterpret_cast<const float4 *>(dq);
         a.nbr = ix.nbr.p;
         a.seed = ix.seeds.p;
@@ -162,7 +180,12 @@ void graph_search_device(const msvs_graph_index & ix, const float * d_queries, s
         a.tab = tab;
         a.cosine = ix.metric == MSVS_METRIC_COSINE;
         ProfileScope prof("graph_search", stream);
-        with_int<M_IP, M_L2>(m, [&](auto mm) { launch_graph_search<decltype(mm)::value>(a, nqc, lds, stream); });
+        with_int<M_IP, M_L2>(m, [&](auto mm) {
+            if (coded)
+                launch_graph_search<decltype(mm)::value, 8>(a, nqc, lds, stream);
+            else
+                launch_graph_search<decltype(mm)::value, 32>(a, nqc, lds, stream);
+        });
         MSVS_HIP(hipGetLastError());
     }
 }
@@ -180,7 +203,111 @@ void install_graph(msvs_graph_index & ix, const float * centroids, size_t nlist,
         MSVS_HIP(hipMemcpyAsync(ix.nbr.p, nbr, ix.n * ix.R * 4, hipMemcpyHostToDevice, stream));
     MSVS_HIP(hipStreamSynchronize(stream));
     MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
-    ix.ready = true;
+}
+
+/// bounds (usable: finite, vmax >= vmin, a finite span) -> the index's quantiser: step = fl(fl(vmax - vmin) / 255), both padded with 0
+void set_graph_quantiser(msvs_graph_index & ix, const float * vmin, const float * vmax, hipStream_t stream)
+{
+    ix.h_vmin.assign(vmin, vmin + ix.dim);
+    ix.h_vmax.assign(vmax, vmax + ix.dim);
+    std::vector<float> pm(ix.ldc, 0.f), ps(ix.ldc, 0.f);
+    for (size_t j = 0; j < ix.dim; j++)
+    {
+        const float range = vmax[j] - vmin[j];
+        pm[j] = vmin[j];
+        ps[j] = range / 255.0f;
+    }
+    ix.d_vmin.alloc(ix.ldc);
+    ix.d_step.alloc(ix.ldc);
+    MSVS_HIP(hipMemcpyAsync(ix.d_vmin.p, pm.data(), ix.ldc * 4, hipMemcpyHostToDevice, stream));
+    MSVS_HIP(hipMemcpyAsync(ix.d_step.p, ps.data(), ix.ldc * 4, hipMemcpyHostToDevice, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+}
+
+/// the first dimension whose bounds give no finite step (the rule of the IVFSQ index's sq_unusable_dimension), or dim
+size_t graph_unusable_dimension(const float * vmin, const float * vmax, size_t dim)
+{
+    for (size_t j = 0; j < dim; j++)
+        if (!std::isfinite(vmin[j]) || !std::isfinite(vmax[j]) || !std::isfinite(vmax[j] - vmin[j]))
+            return j;
+    return dim;
+}
+
+/// bit_size=8, after build / set_graph (ix.n is set): the quantiser over the store's n rows, then their codes.  The rows are read
+/// where they are (HBM or mapped pinned host memory), in chunks, by the IVFSQ index's range and encode kernels against ONE all-zero
+/// centroid: fl(x - 0) = x for every x, so the residual is the row and the codes are include/msvs.h's.
+void encode_store(msvs_graph_index & ix, hipStream_t stream)
+{
+    const RowsView rv = rows_view(ix.rows);
+    const size_t n = ix.n, dim = ix.dim;
+    if (rv.n < n)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the row store holds %zu rows, the graph was made over %zu", rv.n, n);
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::max<size_t>(n, 1), GRAPH_CODE_CHUNK / ix.ldc));
+    DevBuf<float> zero(rv.ld);
+    DevBuf<int32_t> list(chunk);
+    DevBuf<uint32_t> range(2 * dim);
+    MSVS_HIP(hipMemsetAsync(zero.p, 0, (size_t)rv.ld * 4, stream));
+    MSVS_HIP(hipMemsetAsync(list.p, 0, chunk * 4, stream));
+    MSVS_HIP(hipMemsetAsync(range.p, 0xff, dim * 4, stream));
+    MSVS_HIP(hipMemsetAsync(range.p + dim, 0, dim * 4, stream));
+    const uint32_t rpb = 64;
+    for (size_t r0 = 0; r0 < n; r0 += chunk)
+    {
+        const size_t m = std::min(chunk, n - r0);
+        hipLaunchKernelGGL(sq_range_kernel, dim3((unsigned)ceil_div(m, (size_t)rpb)), dim3(BLOCK), 0, stream, rv.table + r0 * rv.ld, list.p, zero.p, m,
+                           (uint32_t)dim, rv.ld, rpb, range.p, range.p + dim);
+        MSVS_HIP(hipGetLastError());
+    }
+    std::vector<uint32_t> ord(2 * dim);
+    MSVS_HIP(hipMemcpyAsync(ord.data(), range.p, ord.size() * 4, hipMemcpyDeviceToHost, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    std::vector<float> lo(dim), hi(dim);
+    auto value = [](uint32_t o) { // the ordered word of scan_kernels.hpp's f2ord, undone
+        const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    };
+    for (size_t j = 0; j < dim; j++)
+    {
+        const bool seen = ord[j] <= ord[dim + j]; // (a column of NaNs, or no row at all: the empty range 0 .. 0)
+        lo[j] = seen ? value(ord[j]) : 0.f;
+        hi[j] = seen ? value(ord[dim + j]) : 0.f;
+    }
+    const size_t bad = graph_unusable_dimension(lo.data(), hi.data(), dim);
+    if (bad < dim)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the stored rows of dimension %zu span %g .. %g: no finite quantiser step (an infinite row?)", bad,
+             (double)lo[bad], (double)hi[bad]);
+    set_graph_quantiser(ix, lo.data(), hi.data(), stream);
+    ix.codes.alloc(std::max<size_t>(n * ix.ldc, 1));
+    for (size_t r0 = 0; r0 < n; r0 += chunk)
+    {
+        const size_t m = std::min(chunk, n - r0);
+        hipLaunchKernelGGL(sq_encode_kernel<8>, dim3((unsigned)ceil_div(m * ix.ldc, (size_t)BLOCK)), dim3(BLOCK), 0, stream, rv.table + r0 * rv.ld, list.p,
+                           zero.p, ix.d_vmin.p, ix.d_step.p, m, (uint32_t)dim, rv.ld, ix.ldc, ix.codes.p + r0 * ix.ldc);
+        MSVS_HIP(hipGetLastError());
+    }
+    MSVS_HIP(hipStreamSynchronize(stream));
+    MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
+}
+
+/// the codes of the index, n x dim in natural column order (export, the file)
+std::vector<uint8_t> host_codes(const msvs_graph_index & ix, hipStream_t stream)
+{
+    std::vector<uint8_t> stored(ix.n * ix.ldc), out(ix.n * ix.dim);
+    if (!stored.empty())
+        MSVS_HIP(hipMemcpyAsync(stored.data(), ix.codes.p, stored.size(), hipMemcpyDeviceToHost, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    for (size_t r = 0; r < ix.n; r++)
+        for (size_t j = 0; j < ix.dim; j++)
+            out[r * ix.dim + j] = stored[r * ix.ldc + sq_stored_pos((uint32_t)j, ix.ldc)];
+    return out;
+}
+
+void check_graph_coded(const msvs_graph_index & ix)
+{
+    if (ix.bits != 8)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index keeps f32 rows of its row store (bit_size=32): it has no codes");
 }
 
 /// what a caller's or a file's structure must satisfy -> nullptr, or what is wrong with it
@@ -209,16 +336,24 @@ std::vector<float> host_centroids(const msvs_graph_index & ix, hipStream_t strea
 struct GraphHeader // 64 bytes, little endian
 {
     char magic[8]; // "MSVSGR01"
-    uint32_t version; // 1
+    uint32_t version; // 1: f32 rows of the store; 2: bit_size=8, the body continues with vmin, vmax and n x dim codes
     int32_t metric;
     uint64_t dim, nlist, n, degree;
-    uint64_t body; // FNV-1a of the centroids, the seeds and the edges
+    uint64_t body; // FNV-1a of the centroids, the seeds and the edges (version 2: and vmin, vmax, the codes)
     uint64_t check; // FNV-1a of the bytes before it
 };
 
 uint64_t graph_body_check(const std::vector<float> & c, const std::vector<int32_t> & s, const std::vector<uint32_t> & e)
 {
     const uint64_t h[3] = {fnv1a(c.data(), c.size() * 4), fnv1a(s.data(), s.size() * 4), fnv1a(e.data(), e.size() * 4)};
+    return fnv1a(h, sizeof(h));
+}
+
+uint64_t graph_body_check2(const std::vector<float> & c, const std::vector<int32_t> & s, const std::vector<uint32_t> & e, const std::vector<float> & lo,
+                           const std::vector<float> & hi, const std::vector<uint8_t> & codes)
+{
+    const uint64_t h[6] = {fnv1a(c.data(), c.size() * 4), fnv1a(s.data(), s.size() * 4), fnv1a(e.data(), e.size() * 4),
+                           fnv1a(lo.data(), lo.size() * 4), fnv1a(hi.data(), hi.size() * 4), fnv1a(codes.data(), codes.size())};
     return fnv1a(h, sizeof(h));
 }
 }
@@ -238,10 +373,15 @@ extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, con
         const long degree = param_int(p, "degree", 32);
         if (degree != 16 && degree != 32 && degree != 64)
             fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index has degree 16, 32 or 64 (degree %ld)", degree);
+        const long bits = param_int(p, "bit_size", 32);
+        if (bits != 32 && bits != 8)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index scores f32 rows (bit_size=32) or 8-bit codes (bit_size=8) (bit_size %ld)", bits);
         std::unique_ptr<msvs_graph_index> ix(new msvs_graph_index);
         ix->metric = metric;
         ix->dim = rv.dim;
         ix->ld = rv.ld;
+        ix->bits = (uint32_t)bits;
+        ix->ldc = (uint32_t)round_up(rv.dim, (size_t)16);
         ix->R = (uint32_t)degree;
         ix->rows = rows;
         ix->device = rv.device;
@@ -255,9 +395,13 @@ extern "C" int msvs_graph_index_ready(const msvs_graph_index_t * ix) { return ix
 extern "C" size_t msvs_graph_index_num_data(const msvs_graph_index_t * ix) { return ix && ix->ready ? ix->n : 0; }
 extern "C" size_t msvs_graph_index_num_lists(const msvs_graph_index_t * ix) { return ix ? ix->nlist : 0; }
 extern "C" size_t msvs_graph_index_degree(const msvs_graph_index_t * ix) { return ix ? ix->R : 0; }
+extern "C" size_t msvs_graph_index_bit_size(const msvs_graph_index_t * ix) { return ix ? ix->bits : 0; }
 extern "C" size_t msvs_graph_index_memory_usage(const msvs_graph_index_t * ix)
 {
-    return ix ? ix->nbr.bytes() + ix->centroids.bytes() + ix->seeds.bytes() : 0;
+    if (!ix)
+        return 0;
+    const size_t coded = ix->bits == 8 && ix->ready ? ix->n * ix->ldc + ix->d_vmin.bytes() + ix->d_step.bytes() : 0;
+    return ix->nbr.bytes() + ix->centroids.bytes() + ix->seeds.bytes() + coded;
 }
 
 extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float * centroids, size_t nlist, const int32_t * seeds, const uint32_t * nbr,
@@ -266,6 +410,8 @@ extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float *
     return guarded([&] {
         DeviceGuard on_device(ix ? ix->device : -1);
         check_graph(ix);
+        if (!ix->rows)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index was loaded without a row store: nothing to make a graph over");
         const size_t n = msvs_rows_num(ix->rows);
         if (!centroids || !seeds || (n && !nbr) || nlist == 0 || nlist > 0x7fffffffull)
             fail(MSVS_ERR_INVALID_ARGUMENT, "null graph / no centroids");
@@ -287,6 +433,9 @@ extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float *
         ix->ready = false;
         ix->n = n;
         install_graph(*ix, c.data(), nlist, s.data(), e.data(), thread_stream());
+        if (ix->bits == 8)
+            encode_store(*ix, thread_stream());
+        ix->ready = true;
     });
 }
 
@@ -296,6 +445,8 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
     return guarded([&] {
         DeviceGuard on_device(ix ? ix->device : -1);
         check_graph(ix);
+        if (!ix->rows)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index was loaded without a row store: nothing to build a graph over");
         const RowsView rv = rows_view(ix->rows);
         const size_t n = rv.n, dim = ix->dim;
         const uint32_t R = ix->R, K0 = 2 * R;
@@ -381,6 +532,8 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
         MSVS_HIP(hipStreamSynchronize(stream));
         MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
         ix->n = n;
+        if (ix->bits == 8)
+            encode_store(*ix, stream);
         ix->ready = true;
     });
 }
@@ -452,6 +605,25 @@ extern "C" int msvs_graph_index_export(const msvs_graph_index_t * ix, float * ce
     });
 }
 
+extern "C" int msvs_graph_index_export_codes(const msvs_graph_index_t * ix, float * vmin, float * vmax, uint8_t * codes)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        check_graph_coded(*ix);
+        check_graph_ready(*ix);
+        if (vmin)
+            memcpy(vmin, ix->h_vmin.data(), ix->dim * 4);
+        if (vmax)
+            memcpy(vmax, ix->h_vmax.data(), ix->dim * 4);
+        if (codes)
+        {
+            const std::vector<uint8_t> c = host_codes(*ix, thread_stream());
+            memcpy(codes, c.data(), c.size());
+        }
+    });
+}
+
 extern "C" int msvs_graph_index_serialize_io(const msvs_graph_index_t * ix, const msvs_io_t * io)
 {
     return guarded([&] {
@@ -465,22 +637,31 @@ extern "C" int msvs_graph_index_serialize_io(const msvs_graph_index_t * ix, cons
         MSVS_HIP(hipMemcpy(s.data(), ix->seeds.p, s.size() * 4, hipMemcpyDeviceToHost));
         if (!e.empty())
             MSVS_HIP(hipMemcpy(e.data(), ix->nbr.p, e.size() * 4, hipMemcpyDeviceToHost));
+        const bool coded = ix->bits == 8;
+        const std::vector<uint8_t> codes = coded ? host_codes(*ix, stream) : std::vector<uint8_t>();
         IoStream f(io, "graph_data", 1);
         GraphHeader h{};
         memcpy(h.magic, "MSVSGR01", 8);
-        h.version = 1;
+        h.version = coded ? 2 : 1;
         h.metric = ix->metric;
         h.dim = ix->dim;
         h.nlist = ix->nlist;
         h.n = ix->n;
         h.degree = ix->R;
-        h.body = graph_body_check(c, s, e);
+        h.body = coded ? graph_body_check2(c, s, e, ix->h_vmin, ix->h_vmax, codes) : graph_body_check(c, s, e);
         h.check = fnv1a(&h, offsetof(GraphHeader, check));
         f.write(&h, sizeof(h));
         f.write(c.data(), c.size() * 4);
         f.write(s.data(), s.size() * 4);
         if (!e.empty())
             f.write(e.data(), e.size() * 4);
+        if (coded)
+        {
+            f.write(ix->h_vmin.data(), ix->dim * 4);
+            f.write(ix->h_vmax.data(), ix->dim * 4);
+            if (!codes.empty())
+                f.write(codes.data(), codes.size());
+        }
         f.finish();
     });
 }
@@ -489,39 +670,72 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
 {
     return guarded([&] {
         clear_out(out);
-        if (!rows)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store");
-        const RowsView rv = rows_view(rows);
-        DeviceGuard on_device(rv.device);
+        int device = 0;
+        MSVS_HIP(hipGetDevice(&device));
+        RowsView rv{};
+        if (rows)
+            rv = rows_view(rows);
+        DeviceGuard on_device(rows ? rv.device : device);
         std::unique_ptr<msvs_graph_index> ix(new msvs_graph_index);
-        std::vector<float> c;
+        std::vector<float> c, lo, hi;
         std::vector<int32_t> s;
         std::vector<uint32_t> e;
+        std::vector<uint8_t> codes;
         IoStream f(io, "graph_data", 0);
         GraphHeader h{};
         f.read(&h, sizeof(h));
-        if (memcmp(h.magic, "MSVSGR01", 8) != 0 || h.version != 1 || h.check != fnv1a(&h, offsetof(GraphHeader, check))
+        if (memcmp(h.magic, "MSVSGR01", 8) != 0 || (h.version != 1 && h.version != 2) || h.check != fnv1a(&h, offsetof(GraphHeader, check))
             || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || (h.degree != 16 && h.degree != 32 && h.degree != 64))
             fail(MSVS_ERR_IO, "corrupt msvs graph index header");
-        if (h.n != rv.n || h.dim != rv.dim || (h.metric == MSVS_METRIC_COSINE) != (rv.normalize != 0))
+        const bool coded = h.version == 2;
+        if (!coded && !rows)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store: only a file of a bit_size=8 index carries what its search reads");
+        if (coded && h.dim == 0)
+            fail(MSVS_ERR_IO, "corrupt msvs graph index header");
+        if (coded ? (rows && h.n != rv.n) : (h.n != rv.n || h.dim != rv.dim || (h.metric == MSVS_METRIC_COSINE) != (rv.normalize != 0)))
             fail(MSVS_ERR_IO, "the msvs graph index file (n %llu, dim %llu) does not belong to this row store (n %zu, dim %zu)",
                  (unsigned long long)h.n, (unsigned long long)h.dim, rv.n, rv.dim);
         read_grow(f, c, (size_t)(h.nlist * h.dim));
         read_grow(f, s, (size_t)h.nlist);
         read_grow(f, e, (size_t)(h.n * h.degree));
+        if (coded)
+        {
+            read_grow(f, lo, (size_t)h.dim);
+            read_grow(f, hi, (size_t)h.dim);
+            read_grow(f, codes, (size_t)(h.n * h.dim));
+        }
         expect_end(f);
-        if (h.body != graph_body_check(c, s, e))
+        if (h.body != (coded ? graph_body_check2(c, s, e, lo, hi, codes) : graph_body_check(c, s, e)))
             fail(MSVS_ERR_IO, "corrupt msvs graph index: the body's checksum does not match");
         if (const char * bad = graph_structure_error(c.data(), (size_t)h.nlist, (size_t)h.dim, s.data(), e.data(), (size_t)h.n, (uint32_t)h.degree))
             fail(MSVS_ERR_IO, "corrupt msvs graph index: %s", bad);
+        if (coded)
+            for (size_t j = 0; j < h.dim; j++)
+                if (graph_unusable_dimension(&lo[j], &hi[j], 1) == 0 || hi[j] < lo[j])
+                    fail(MSVS_ERR_IO, "corrupt msvs graph index: the quantiser bounds of dimension %zu are not finite, vmax < vmin or their span is infinite", j);
         ix->metric = h.metric;
-        ix->dim = rv.dim;
-        ix->ld = rv.ld;
+        ix->dim = (size_t)h.dim;
+        ix->ld = padded_dim((size_t)h.dim);
+        ix->bits = coded ? 8 : 32;
+        ix->ldc = (uint32_t)round_up((size_t)h.dim, (size_t)16);
         ix->R = (uint32_t)h.degree;
-        ix->rows = rows;
-        ix->device = rv.device;
+        // (a version-2 file is checked against a store for n alone; build / set_graph need one of the index's own shape)
+        ix->rows = rows && rv.dim == h.dim && (h.metric == MSVS_METRIC_COSINE) == (rv.normalize != 0) ? rows : nullptr;
+        ix->device = rows ? rv.device : device;
         ix->n = (size_t)h.n;
-        install_graph(*ix, c.data(), (size_t)h.nlist, s.data(), e.data(), thread_stream());
+        hipStream_t stream = thread_stream();
+        install_graph(*ix, c.data(), (size_t)h.nlist, s.data(), e.data(), stream);
+        if (coded)
+        {
+            set_graph_quantiser(*ix, lo.data(), hi.data(), stream);
+            std::vector<uint8_t> stored(std::max<size_t>(ix->n * ix->ldc, 1), 0); // natural order -> the stored order, pad bytes 0
+            for (size_t r = 0; r < ix->n; r++)
+                for (size_t j = 0; j < ix->dim; j++)
+                    stored[r * ix->ldc + sq_stored_pos((uint32_t)j, ix->ldc)] = codes[r * ix->dim + j];
+            ix->codes.alloc(stored.size());
+            MSVS_HIP(hipMemcpy(ix->codes.p, stored.data(), stored.size(), hipMemcpyHostToDevice));
+        }
+        ix->ready = true;
         *out = ix.release();
     });
 }

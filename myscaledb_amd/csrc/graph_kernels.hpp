@@ -17,11 +17,27 @@
 //   every thread of a parent's R-lane slice finds its parent from them and loads its neighbour word.
 //   The table holds at most tab / 2 labels (the launcher sizes it from the search's own bound), so a probe sequence always ends.
 //
+//
+// graph_search_kernel<METRIC, 8>: the same search over 8-bit codes (create's bit_size=8) -- a label is scored against its DECODED row
+//   x^_j = fl(vmin[j] + fl(float(code_j) * step[j])), the IVFSQ quantiser (sq_ivf_kernels.hpp) without a centroid.  Visit, merge, parent
+//   pick and epilogue are the code above; the score step and the LDS image are its own:
+//   LDS image (graph_sq_lds_bytes): the query | vmin | step (lc4 = round_up(dim, 16) / 4 float4 each, zero padded, staged once) | the
+//   6 KiB of beam / stage / flags / labels | control words | the visited table.
+//   Stored row: lc4 x 4 bytes in sq_layout.hpp's 8-bit order: one 16-byte load inside a whole 256-byte block is the lane's float4
+//   columns 64 b + g, + 16, + 32, + 48 (a "unit"); the natural-order tail is one more unit of 32-bit words.  The lane's columns come
+//   out in ascending order, so the four component sums, their sum and the 16-lane tree are canonical_row_chain + row16_tree_sum's.
+//   score, rows of at most GRAPH_SQ_MULTI_UNITS units (dim <= 1024): a group takes its labels c, c + 16, c + 32, c + 48 of the round
+//   at once and requests every unit of all four rows before the first decode -- up to 64 rows and 16 requests a lane in flight per
+//   block, a whole width = 1 round in one go.  Longer rows: one row a group, chunks of GRAPH_SQ_LONG_UNITS units double buffered
+//   (the next chunk, or the next label's first, is on its way while this one is decoded), as sq_ivf_scan_kernel's wnext.
+//
 // graph_prune_kernel, graph_count_kernel, graph_scan_kernel, graph_scatter_kernel, graph_reverse_kernel: the build, integers only.
+// The coded form's quantiser and codes are made by sq_ivf_kernels.hpp's sq_range_kernel / sq_encode_kernel<8> fed a zero centroid.
 #pragma once
 
 #include "mfma_scan_kernels.hpp"
 #include "scan_kernels.hpp"
+#include "sq_ivf_kernels.hpp"
 
 #pragma clang fp contract(off)
 
@@ -31,6 +47,11 @@ namespace msvs
 constexpr uint32_t GRAPH_EMPTY = 0xFFFFFFFFu; // no edge / a free slot of the visited table
 constexpr uint32_t GRAPH_ROUND = 256;         // candidates of a round at most: min(nprobe, nlist) seeds, width x R neighbour words
 constexpr uint32_t GRAPH_CTL = 16;            // control words
+// The coded score step's switch point, from the compiler's resource report (gfx950): with four rows of 4 units held
+// (64 VGPRs of codes) the kernel takes 119 VGPRs, the f32 kernel's 4 waves per SIMD, no scratch; 6 units a row take 151 VGPRs
+// (3 waves), 8 take 184 (2 waves).
+constexpr uint32_t GRAPH_SQ_MULTI_UNITS = 4; // rows of up to 4 units (dim <= 1024): four labels a group at once
+constexpr uint32_t GRAPH_SQ_LONG_UNITS = 4;  // longer rows: units of a double-buffered chunk
 
 struct GraphSearchParams
 {
@@ -44,6 +65,10 @@ struct GraphSearchParams
     float * out_dis;        // nq x k
     uint32_t nbits, n, ld4, R, lgR, ef, k, width, max_iters, P, tab;
     int cosine;
+    // BITS 8 (rows is not read):
+    const uint4 * codes;         // n x lc4 / 4 16-byte words, stored order (sq_layout.hpp)
+    const float4 * vmin, * step; // lc4, zero padded
+    uint32_t lc4;                // round_up(dim, 16) / 4 >= ld4
 };
 
 inline size_t graph_lds_bytes(uint32_t ld4, uint32_t tab)
@@ -51,9 +76,12 @@ inline size_t graph_lds_bytes(uint32_t ld4, uint32_t tab)
     return (size_t)ld4 * 16 + GRAPH_ROUND * (8 + 8 + 4 + 4) + GRAPH_CTL * 4 + (size_t)tab * 4;
 }
 
+/// the coded image: vmin and step beside the query, all three of lc4 float4
+inline size_t graph_sq_lds_bytes(uint32_t lc4, uint32_t tab) { return graph_lds_bytes(lc4, tab) + (size_t)lc4 * 32; }
+
 struct GraphLds
 {
-    float4 * qs;
+    float4 * qs, * vm, * st; // (vm, st: BITS 8)
     uint64_t * beam, * stage;
     uint32_t * flag, * slab, * ctl, * table;
     // ctl: 0 labels to score this round, 1 |V|, 2 beam entries, 3 newly admitted keys, 4 alive results; 8 .. 15 four 64-bit ballots
@@ -85,18 +113,10 @@ __device__ __forceinline__ uint32_t graph_wave_place(uint32_t * counter, const b
     return base + (uint32_t)__popcll(b & ((1ull << lane) - 1));
 }
 
-/// One round: this thread's candidate label (GRAPH_EMPTY: none) is visited, the winners are scored and merged into the beam.
-/// Entered and left with every thread past a barrier and ctl[0] = ctl[3] = 0.
+/// score, f32 rows: group grp takes the list's labels grp, grp + 16, ... against the row store
 template <int METRIC>
-__device__ __forceinline__ void graph_round(const GraphSearchParams & a, const GraphLds & L, const uint32_t lab, const uint32_t tid)
+__device__ __forceinline__ void graph_score_rows(const GraphSearchParams & a, const GraphLds & L, const uint32_t m, const uint32_t grp, const uint32_t g)
 {
-    const uint32_t lane = tid & 63, grp = tid >> 4, g = tid & 15;
-    const bool won = lab != GRAPH_EMPTY && graph_visit(L.table, a.tab, lab);
-    const uint32_t place = graph_wave_place(&L.ctl[0], won, lane);
-    if (won)
-        L.slab[place] = lab;
-    __syncthreads();
-    const uint32_t m = L.ctl[0], cnt = L.ctl[2];
     const uint32_t jfull = a.ld4 >> 4, jtail = a.ld4 & 15;
     for (uint32_t c = grp; c < m; c += 16)
     {
@@ -107,6 +127,152 @@ __device__ __forceinline__ void graph_round(const GraphSearchParams & a, const G
         if (g == 0)
             L.stage[c] = make_key<METRIC>(s, id);
     }
+}
+
+/// unit u of a stored row of nb whole blocks and tc tail columns: a block -> the lane's 16 bytes of it; the tail -> one 32-bit word
+/// per float4 column the lane owns there (0 beyond the row), in the block's order of columns
+__device__ __forceinline__ uint4 graph_sq_load_unit(const uint4 * row, const uint32_t u, const uint32_t nb, const uint32_t tc, const uint32_t g)
+{
+    if (u < nb)
+        return row[u * 16 + g];
+    const uint32_t * tail = reinterpret_cast<const uint32_t *>(row) + nb * 64;
+    uint4 v;
+    v.x = g < tc ? tail[g] : 0u;
+    v.y = g + 16 < tc ? tail[g + 16] : 0u;
+    v.z = g + 32 < tc ? tail[g + 32] : 0u;
+    v.w = g + 48 < tc ? tail[g + 48] : 0u;
+    return v;
+}
+
+/// four codes (one float4 column) -> the decoded column: fl(vmin + fl(float(code) * step))
+__device__ __forceinline__ float4 graph_sq_decode(const uint32_t w, const float4 m, const float4 s)
+{
+    float4 y;
+    y.x = __fadd_rn(m.x, __fmul_rn((float)(w & 255u), s.x));
+    y.y = __fadd_rn(m.y, __fmul_rn((float)((w >> 8) & 255u), s.y));
+    y.z = __fadd_rn(m.z, __fmul_rn((float)((w >> 16) & 255u), s.z));
+    y.w = __fadd_rn(m.w, __fmul_rn((float)(w >> 24), s.w));
+    return y;
+}
+
+/// the lane's four columns of unit u, decoded and accumulated in ascending order (padding columns decode to 0 against a 0 query)
+template <int METRIC>
+__device__ __forceinline__ void graph_sq_score_unit(float4 & acc, const GraphLds & L, const uint4 cw, const uint32_t u, const uint32_t lc4, const uint32_t g)
+{
+    const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+    {
+        const uint32_t col = u * 64 + g + 16 * e;
+        if (col < lc4)
+            canonical_update<METRIC>(acc, L.qs[col], graph_sq_decode(words[e], L.vm[col], L.st[col]));
+    }
+}
+
+template <int METRIC>
+__device__ __forceinline__ uint64_t graph_sq_key(const float4 acc, const uint32_t id)
+{
+    const float s = __fadd_rn(__fadd_rn(acc.x, acc.y), __fadd_rn(acc.z, acc.w));
+    return make_key<METRIC>(row16_tree_sum(s), id);
+}
+
+/// score, 8-bit codes: the list's labels against their decoded rows (the header's two forms; nu is uniform over the block)
+template <int METRIC>
+__device__ __forceinline__ void graph_score_codes(const GraphSearchParams & a, const GraphLds & L, const uint32_t m, const uint32_t grp, const uint32_t g)
+{
+    const uint32_t lc4 = a.lc4, ld16 = lc4 >> 2, nb = lc4 >> 6, tc = lc4 & 63, nu = nb + (tc ? 1 : 0);
+    if (nu <= GRAPH_SQ_MULTI_UNITS)
+    {
+        for (uint32_t c0 = grp; c0 < m; c0 += 64)
+        {
+            uint4 w[4][GRAPH_SQ_MULTI_UNITS];
+            uint32_t id[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) // every request of the group's four rows leaves before the first decode
+            {
+                const uint32_t c = c0 + 16 * r;
+                id[r] = c < m ? L.slab[c] : GRAPH_EMPTY;
+                const uint4 * row = a.codes + (size_t)id[r] * ld16;
+#pragma unroll
+                for (uint32_t u = 0; u < GRAPH_SQ_MULTI_UNITS; u++)
+                {
+                    w[r][u] = make_uint4(0, 0, 0, 0);
+                    if (id[r] != GRAPH_EMPTY && u < nu)
+                        w[r][u] = graph_sq_load_unit(row, u, nb, tc, g);
+                }
+            }
+            // row after row (the four rows side by side, one LDS read of query, vmin and step serving all of them, measured slower:
+            // 129 VGPRs, 3 waves, and 3 - 5 % more time at every shape of DESIGN.md 4.14's table)
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (id[r] != GRAPH_EMPTY)
+                {
+                    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (uint32_t u = 0; u < GRAPH_SQ_MULTI_UNITS; u++)
+                        if (u < nu)
+                            graph_sq_score_unit<METRIC>(acc, L, w[r][u], u, lc4, g);
+                    const uint64_t key = graph_sq_key<METRIC>(acc, id[r]);
+                    if (g == 0)
+                        L.stage[c0 + 16 * r] = key;
+                }
+        }
+        return;
+    }
+    uint4 next[GRAPH_SQ_LONG_UNITS];
+    auto load_chunk = [&](const uint32_t id, const uint32_t u0) {
+        const uint4 * row = a.codes + (size_t)id * ld16;
+#pragma unroll
+        for (uint32_t e = 0; e < GRAPH_SQ_LONG_UNITS; e++)
+        {
+            next[e] = make_uint4(0, 0, 0, 0);
+            if (u0 + e < nu)
+                next[e] = graph_sq_load_unit(row, u0 + e, nb, tc, g);
+        }
+    };
+    if (grp < m)
+        load_chunk(L.slab[grp], 0);
+    for (uint32_t c = grp; c < m; c += 16)
+    {
+        const uint32_t id = L.slab[c];
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (uint32_t u0 = 0; u0 < nu; u0 += GRAPH_SQ_LONG_UNITS)
+        {
+            uint4 cur[GRAPH_SQ_LONG_UNITS];
+#pragma unroll
+            for (uint32_t e = 0; e < GRAPH_SQ_LONG_UNITS; e++)
+                cur[e] = next[e];
+            if (u0 + GRAPH_SQ_LONG_UNITS < nu)
+                load_chunk(id, u0 + GRAPH_SQ_LONG_UNITS);
+            else if (c + 16 < m)
+                load_chunk(L.slab[c + 16], 0);
+#pragma unroll
+            for (uint32_t e = 0; e < GRAPH_SQ_LONG_UNITS; e++)
+                if (u0 + e < nu)
+                    graph_sq_score_unit<METRIC>(acc, L, cur[e], u0 + e, lc4, g);
+        }
+        const uint64_t key = graph_sq_key<METRIC>(acc, id);
+        if (g == 0)
+            L.stage[c] = key;
+    }
+}
+
+/// One round: this thread's candidate label (GRAPH_EMPTY: none) is visited, the winners are scored and merged into the beam.
+/// Entered and left with every thread past a barrier and ctl[0] = ctl[3] = 0.
+template <int METRIC, int BITS>
+__device__ __forceinline__ void graph_round(const GraphSearchParams & a, const GraphLds & L, const uint32_t lab, const uint32_t tid)
+{
+    const uint32_t lane = tid & 63, grp = tid >> 4, g = tid & 15;
+    const bool won = lab != GRAPH_EMPTY && graph_visit(L.table, a.tab, lab);
+    const uint32_t place = graph_wave_place(&L.ctl[0], won, lane);
+    if (won)
+        L.slab[place] = lab;
+    __syncthreads();
+    const uint32_t m = L.ctl[0], cnt = L.ctl[2];
+    if constexpr (BITS == 8)
+        graph_score_codes<METRIC>(a, L, m, grp, g);
+    else
+        graph_score_rows<METRIC>(a, L, m, grp, g);
     __syncthreads();
     const uint64_t old = tid < cnt ? L.beam[tid] : KEY_NONE, neu = tid < m ? L.stage[tid] : KEY_NONE;
     const uint32_t old_flag = tid < cnt ? L.flag[tid] : 0;
@@ -154,21 +320,32 @@ __device__ __forceinline__ void graph_round(const GraphSearchParams & a, const G
     __syncthreads();
 }
 
-template <int METRIC>
+template <int METRIC, int BITS = 32>
 static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphSearchParams a)
 {
+    static_assert(BITS == 32 || BITS == 8, "f32 rows of a row store, or 8-bit codes");
     extern __shared__ __align__(16) unsigned char graph_lds[];
     GraphLds L;
     L.qs = reinterpret_cast<float4 *>(graph_lds);
-    L.beam = reinterpret_cast<uint64_t *>(graph_lds + (size_t)a.ld4 * 16);
+    L.vm = L.qs + a.lc4;
+    L.st = L.vm + a.lc4;
+    L.beam = reinterpret_cast<uint64_t *>(graph_lds + (BITS == 8 ? (size_t)a.lc4 * 48 : (size_t)a.ld4 * 16));
     L.stage = L.beam + GRAPH_ROUND;
     L.flag = reinterpret_cast<uint32_t *>(L.stage + GRAPH_ROUND);
     L.slab = L.flag + GRAPH_ROUND;
     L.ctl = L.slab + GRAPH_ROUND;
     L.table = L.ctl + GRAPH_CTL;
     const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t i = tid; i < a.ld4; i += BLOCK)
-        L.qs[i] = a.Q[(size_t)q * a.ld4 + i];
+    if constexpr (BITS == 8)
+        for (uint32_t i = tid; i < a.lc4; i += BLOCK)
+        {
+            L.qs[i] = i < a.ld4 ? a.Q[(size_t)q * a.ld4 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            L.vm[i] = a.vmin[i];
+            L.st[i] = a.step[i];
+        }
+    else
+        for (uint32_t i = tid; i < a.ld4; i += BLOCK)
+            L.qs[i] = a.Q[(size_t)q * a.ld4 + i];
     for (uint32_t i = tid; i < a.tab; i += BLOCK)
         L.table[i] = GRAPH_EMPTY;
     if (tid < GRAPH_CTL)
@@ -183,7 +360,7 @@ static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphS
         if (s >= 0 && (uint32_t)s < a.n)
             lab = (uint32_t)s;
     }
-    graph_round<METRIC>(a, L, lab, tid);
+    graph_round<METRIC, BITS>(a, L, lab, tid);
     uint64_t * ballots = reinterpret_cast<uint64_t *>(L.ctl + 8);
     const uint32_t fan = a.width << a.lgR;
     for (uint32_t it = 0; it < a.max_iters; it++)
@@ -221,7 +398,7 @@ static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphS
             if (r == 0)
                 L.flag[slot] = 1;
         }
-        graph_round<METRIC>(a, L, lab, tid);
+        graph_round<METRIC, BITS>(a, L, lab, tid);
     }
     // the first k alive entries of the beam
     const uint32_t cnt = L.ctl[2];

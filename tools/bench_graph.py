@@ -3,13 +3,15 @@ store, a built index of degree --degree, searched through the device entry on on
 
   - the build's wall time (msvs_graph_index_build as a whole: trainer, exact lists, prune, reverse edges);
   - for nq in --batches and ef in --efs: recall@10 against an exact scan of the rows (torch, on the first 256 queries), the median
-    time of --reps calls between HIP events after a warm-up call, queries/s;
+    time of --reps calls between HIP events after a warm-up call (and their spread, min .. max), queries/s;
+  - --bits 32,8: the index is built once at 32 bits, exported, and the same structure is handed (set_graph) to a bit_size=8 index
+    over the same store, so both forms search one graph; their repetitions alternate inside one process, shape by shape;
   - beside them the IVFFLAT index of the same rows (nlist --nlist) at --nprobes, the same way, to read the nprobe of equal recall off.
 
 Writes one JSON file (default profiles/graph.json) and prints it.
 
     python -m tools.bench_graph [--rows N] [--dim D] [--data mid] [--degree 32] [--nlist 1024] [--batches 1,64,4096] [--efs 32,64,128,256]
-                                [--nprobes 8,16,32,64] [--reps R] [--out FILE]
+                                [--bits 32,8] [--nprobes 8,16,32,64] [--reps R] [--out FILE]
 """
 import argparse
 import json
@@ -35,7 +37,8 @@ def main():
     ap.add_argument("--nlist", type=int, default=1024)
     ap.add_argument("--batches", default="1,64,4096")
     ap.add_argument("--efs", default="32,64,128,256")
-    ap.add_argument("--nprobes", default="8,16,32,64")
+    ap.add_argument("--bits", default="32", help="forms of the graph index to search: 32, 8 or 32,8")
+    ap.add_argument("--nprobes", default="8,16,32,64", help="of the IVFFLAT index beside it; empty: leave it out")
     ap.add_argument("--reps", type=int, default=11)
     ap.add_argument("--out", default=os.path.join("profiles", "graph.json"))
     a = ap.parse_args()
@@ -66,18 +69,24 @@ def main():
     di = torch.empty((nq, k), device=dev, dtype=torch.int64)
     dd = torch.empty((nq, k), device=dev, dtype=torch.float32)
 
-    def timed(call):
-        call()  # warm-up: arenas, the kernel's attribute
+    def timed_all(calls):
+        """the calls take turns, repetition by repetition -> [ms of every repetition] per call"""
+        for call in calls:
+            call()  # warm-up: arenas, the kernel's attribute
         torch.cuda.synchronize()
-        ms = []
+        ms = [[] for _ in calls]
         for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call()
-            e1.record()
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return float(np.median(ms))
+            for i, call in enumerate(calls):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                call()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[i].append(e0.elapsed_time(e1))
+        return ms
+
+    def timed(call):
+        return float(np.median(timed_all([call])[0]))
 
     out = {"data": what, "rows": a.rows, "dim": a.dim, "degree": a.degree, "nlist": a.nlist, "graph": [], "ivfflat": []}
     rows = capi.Rows(a.dim, a.rows)
@@ -86,17 +95,35 @@ def main():
     t0 = time.perf_counter()
     gx.build()
     out["build_s"] = time.perf_counter() - t0
-    out["graph_bytes"] = gx.memory_usage
+    forms = {32: gx}
+    bits = [int(v) for v in a.bits.split(",")]
+    if 8 in bits:
+        t0 = time.perf_counter()
+        forms[8] = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,bit_size=8" % a.degree)
+        forms[8].set_graph(*gx.export())
+        out["encode_s"] = time.perf_counter() - t0  # (with the structure's round trip through the host)
+    forms = {b: forms[b] for b in bits}
+    out["graph_bytes"] = {str(b): ix.memory_usage for b, ix in forms.items()}
+    out["row_bytes"] = {str(b): rows.memory_usage if b == 32 else 0 for b in forms}  # what the search needs resident besides
     for b in batches:
         for ef in (int(v) for v in a.efs.split(",")):
-            ms = timed(lambda: gx.search_device(q.data_ptr(), b, k, di.data_ptr(), dd.data_ptr(), ef=ef, stream=stream))
-            out["graph"].append({"nq": b, "ef": ef, "ms": ms, "qps": b / ms * 1e3, "recall@10": recall(di.cpu().numpy()) if b >= nt else None})
-    gx.close()
-    ivf = capi.Index(capi.INDEX_IVFFLAT, capi.METRIC_L2, a.dim, "ncentroids=%d,kmeans_iters=10" % a.nlist)
-    ivf.train(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
-    ivf.add(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
-    ivf.build()
-    for b in batches:
+            outs = {f: (torch.empty_like(di), torch.empty_like(dd)) for f in forms}
+            calls = [lambda f=f, ix=ix: ix.search_device(q.data_ptr(), b, k, outs[f][0].data_ptr(), outs[f][1].data_ptr(), ef=ef, stream=stream)
+                     for f, ix in forms.items()]
+            for f, ms in zip(forms, timed_all(calls)):
+                med = float(np.median(ms))
+                out["graph"].append({"bits": f, "nq": b, "ef": ef, "ms": med, "ms_min": min(ms), "ms_max": max(ms), "qps": b / med * 1e3,
+                                     "recall@10": recall(outs[f][0].cpu().numpy()) if b >= nt else None})
+    for ix in forms.values():
+        ix.close()
+    if 32 not in forms:
+        gx.close()
+    if a.nprobes:
+        ivf = capi.Index(capi.INDEX_IVFFLAT, capi.METRIC_L2, a.dim, "ncentroids=%d,kmeans_iters=10" % a.nlist)
+        ivf.train(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
+        ivf.add(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
+        ivf.build()
+    for b in batches if a.nprobes else ():
         for p in (int(v) for v in a.nprobes.split(",")):
             ms = timed(lambda: ivf.search_device(q.data_ptr(), b, k, p, di.data_ptr(), dd.data_ptr(), stream))
             out["ivfflat"].append({"nq": b, "nprobe": p, "ms": ms, "qps": b / ms * 1e3, "recall@10": recall(di.cpu().numpy()) if b >= nt else None})
