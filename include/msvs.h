@@ -524,7 +524,8 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
  *      key order; unfilled slots -1 and the neutral value.  Dead rows are traversed and occupy B; a selective filter wants a larger ef.
  *   k = 0 or nq = 0 is a no-op; before build / set_graph: MSVS_ERR_NOT_READY.
  *
- * build: deterministic (the same input gives the same bits) and O(n^2) -- every row is searched exactly over all rows.  K0 = 2R.
+ * build: deterministic (the same input gives the same bits).  K0 = 2R.  With create's join_iters = 0 (the default) it is O(n^2) --
+ *   every row is searched exactly over all rows; join_iters >= 1 replaces step 3 by 3a - 3c below, whose cost is linear in n.
  *   1. centroids: the IVFFLAT trainer over the store's rows (create's params: ncentroids, kmeans_iters, train_sample, seed).
  *   2. seed[l] = the label of the exact top-1 of centroid l, searched as a query of the index's metric over all rows; -1 if none.
  *   3. L_i[0 .. K0) = the exact top-(K0 + 1) of row i as such a query, by (distance, label), label i removed if present, else the
@@ -534,6 +535,21 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
  *   5. The incoming edges of j are (r, i) with F_i[r] = j; G_j = the i of the R/2 smallest (r, i), in that order.  N_j = the valid
  *      entries of F_j[0 .. R/2), then the G_j not yet present, then the F_j[R/2 .. R) not yet present, cut to R; the rest 0xFFFFFFFF.
  *   An empty row store: MSVS_ERR_INVALID_ARGUMENT.
+ *   Create's build parameters (integers): join_iters T, 0 .. 16, default 0; build_nprobe p >= 1, default 8; join_sample S, 1 .. 32,
+ *   default 8.  Out of range, or a join whose LDS image (the query, 5 KiB of beam, K0 (S + 2) + 16 words, a visited table of the
+ *   next power of two >= 2 (K0 (S + 1) + 1) words) exceeds 160 KiB: MSVS_ERR_INVALID_ARGUMENT.  p and S are read only when T >= 1.
+ *   With T >= 1 step 3 is:
+ *   3a. L^0_i: an IVFFLAT index of the index's metric (cosine: IP over the stored unit rows) is given the centroids of step 1
+ *       (msvs_index_set_centroids) and all n rows with labels 0 .. n-1; L^0_i is its msvs_index_search result for row i as a query
+ *       (cosine: normalised again) with nprobe = min(p, nlist) and k = K0 + 1, label i removed if present, else the last entry
+ *       dropped; -1 padded.  min(p, nlist) > MSVS_MAX_K is that search's MSVS_ERR_UNSUPPORTED_K.  With p >= nlist this is step 3.
+ *   3b. One join iteration t -> t + 1, for every node i from the OLD lists only: C_i = { L^t_i[a] >= 0 } united with
+ *       { L^t_j[b] : j = L^t_i[a] >= 0, b < S, L^t_j[b] >= 0 }, without i, duplicates counted once.  Every label of C_i is scored
+ *       against its stored row with the canonical scan arithmetic, row i being the query (cosine: normalised again); keys,
+ *       admission and NaN as in search step 2.  L^{t+1}_i = the K0 lowest keys of C_i in key order, -1 padded.  A set operation
+ *       over unique keys: no scoring order reaches the result.
+ *   3c. Stop after T iterations, or after an iteration in which no node's list changed; the final lists feed step 4.  Exact lists
+ *       are a fixed point: build_nprobe >= nlist gives the graph of join_iters = 0.
  * set_graph installs the caller's structure instead (host or device: mem); a non-finite centroid, a seed outside [-1, n) or an edge
  *   that is neither below n nor 0xFFFFFFFF is MSVS_ERR_INVALID_ARGUMENT.
  * memory_usage: device bytes of the graph, the centroids and the seeds.  export: any output may be NULL.

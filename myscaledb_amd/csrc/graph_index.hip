@@ -4,7 +4,8 @@
 // bit_size=8: the index keeps one 8-bit quantiser and a code row per label, made from the store by build / set_graph; the search
 // scores decoded rows and nothing but build / set_graph reads the store.
 // Reused as they are: the row store (refine.hip), the canonical scoring of refine_kernels.hpp's chain, the k-means trainer and the
-// canonical coarse top-P (coded_ivf.hpp: kmeans, flat_search_device), the exact FLAT search for the build's neighbour lists.
+// canonical coarse top-P (coded_ivf.hpp: kmeans, flat_search_device), the exact FLAT search for the build's neighbour lists -- or,
+// with join_iters >= 1, an IVFFLAT search of build_nprobe lists whose lists graph_join_kernel repairs across partition borders.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -22,6 +23,9 @@ struct msvs_graph_index
     int metric = MSVS_METRIC_L2;
     size_t dim = 0, n = 0, nlist = 0;
     uint32_t ld = 0, R = 32;
+    // the build (create's join_iters, build_nprobe, join_sample): 0 iterations is the exact O(n^2) build
+    size_t join_iters = 0, build_nprobe = 8;
+    uint32_t join_sample = 8;
     int device = 0;
     std::string params;
     const msvs_rows * rows = nullptr; // borrowed
@@ -104,6 +108,17 @@ void launch_graph_search(const GraphSearchParams & a, size_t nq, size_t lds, hip
         MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRAPH_LDS_MAX));
     });
     hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(BLOCK), lds, stream, a);
+}
+
+template <int METRIC>
+void launch_graph_join(const GraphJoinParams & a, size_t nodes, size_t lds, hipStream_t stream)
+{
+    constexpr auto kernel = &graph_join_kernel<METRIC>;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRAPH_LDS_MAX));
+    });
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nodes), dim3(BLOCK), lds, stream, a);
 }
 
 /// Everything on the device, enqueued on `stream`: queries padded (normalised for cosine), the canonical coarse top-P, one launch.
@@ -376,7 +391,26 @@ extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, con
         const long bits = param_int(p, "bit_size", 32);
         if (bits != 32 && bits != 8)
             fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index scores f32 rows (bit_size=32) or 8-bit codes (bit_size=8) (bit_size %ld)", bits);
+        const long join_iters = param_int(p, "join_iters", 0), build_nprobe = param_int(p, "build_nprobe", 8), join_sample = param_int(p, "join_sample", 8);
+        if (join_iters < 0 || join_iters > 16)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the graph build runs 0 to 16 join iterations (join_iters %ld)", join_iters);
+        if (join_iters && (build_nprobe < 1 || join_sample < 1 || join_sample > 32))
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the join needs build_nprobe >= 1 and 1 <= join_sample <= 32 (build_nprobe %ld, join_sample %ld)",
+                 build_nprobe, join_sample);
+        if (join_iters)
+        {
+            const uint32_t K0 = 2 * (uint32_t)degree, cap = K0 * ((uint32_t)join_sample + 1);
+            const size_t lds = graph_join_lds_bytes(rv.ld / 4, K0, cap, graph_join_table(cap));
+            if (lds > GRAPH_LDS_MAX)
+                fail(MSVS_ERR_INVALID_ARGUMENT, "the graph join's LDS image (%zu bytes) exceeds %zu", lds, GRAPH_LDS_MAX);
+        }
         std::unique_ptr<msvs_graph_index> ix(new msvs_graph_index);
+        if (join_iters)
+        {
+            ix->join_iters = (size_t)join_iters;
+            ix->build_nprobe = (size_t)build_nprobe;
+            ix->join_sample = (uint32_t)join_sample;
+        }
         ix->metric = metric;
         ix->dim = rv.dim;
         ix->ld = rv.ld;
@@ -439,7 +473,8 @@ extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float *
     });
 }
 
-/// Deterministic, from exact lists (include/msvs.h); O(n^2): every row is searched over all rows.
+/// Deterministic (include/msvs.h).  join_iters = 0: from exact lists, O(n^2) -- every row is searched over all rows.  join_iters >= 1:
+/// from the lists of an IVFFLAT search of build_nprobe lists, repaired across partition borders by graph_join_kernel.
 extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
 {
     return guarded([&] {
@@ -468,30 +503,70 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
                                       hipMemcpyDeviceToDevice, stream));
             MSVS_HIP(hipStreamSynchronize(stream));
         }
-        const size_t nlist = ix->nlist;
-        // the exact search: a temporary FLAT index over the same rows (cosine: inner product over the stored unit rows, the queries normalised here)
+        const size_t nlist = ix->nlist, T = ix->join_iters;
+        // the lists' search: a temporary index over the same rows (cosine: inner product over the stored unit rows, the queries
+        // normalised here) -- FLAT, or with join_iters >= 1 IVFFLAT over the centroids of step 1, probing build_nprobe lists
+        const int tmp_metric = ix->metric == MSVS_METRIC_L2 ? MSVS_METRIC_L2 : MSVS_METRIC_IP;
         msvs_index_t * raw = nullptr;
-        int rc = msvs_index_create(MSVS_INDEX_FLAT, ix->metric == MSVS_METRIC_L2 ? MSVS_METRIC_L2 : MSVS_METRIC_IP, dim, "", &raw);
-        const TmpIndex flat(raw, msvs_index_free);
+        int rc = msvs_index_create(T ? MSVS_INDEX_IVFFLAT : MSVS_INDEX_FLAT, tmp_metric, dim, "", &raw);
+        TmpIndex lists_index(raw, msvs_index_free);
+        if (rc == MSVS_OK && T)
+        {
+            DevBuf<float> cd(nlist * dim);
+            MSVS_HIP(hipMemcpy2DAsync(cd.p, dim * 4, ix->centroids.p, (size_t)ix->ld * 4, dim * 4, nlist, hipMemcpyDeviceToDevice, stream));
+            MSVS_HIP(hipStreamSynchronize(stream));
+            rc = msvs_index_set_centroids(raw, cd.p, nlist, MSVS_MEM_DEVICE);
+        }
         if (rc == MSVS_OK)
             rc = msvs_index_add(raw, dense.p, nullptr, n, MSVS_MEM_DEVICE);
         if (rc == MSVS_OK)
             rc = msvs_index_build(raw);
         if (rc != MSVS_OK)
             fail(rc, "%s", std::string(msvs_last_error()).c_str());
-        const size_t chunk = std::max(GRAPH_LIST_CHUNK, nlist);
+        const size_t chunk = std::max(GRAPH_LIST_CHUNK, nlist), lists_nprobe = T ? std::min(ix->build_nprobe, nlist) : 1;
         DevBuf<float> dq(chunk * dim), ddis(chunk * (K0 + 1));
         DevBuf<int64_t> dids(chunk * (K0 + 1));
-        auto exact = [&](const float * src, size_t src_ld, size_t cnt, uint32_t k) {
-            MSVS_HIP(hipMemcpy2DAsync(dq.p, dim * 4, src, src_ld * 4, dim * 4, cnt, hipMemcpyDeviceToDevice, stream));
+        auto as_queries = [&](const float * src, size_t src_ld, size_t cnt, float * dst, size_t dst_ld) {
+            if (dst_ld != dim)
+                MSVS_HIP(hipMemsetAsync(dst, 0, cnt * dst_ld * 4, stream));
+            MSVS_HIP(hipMemcpy2DAsync(dst, dst_ld * 4, src, src_ld * 4, dim * 4, cnt, hipMemcpyDeviceToDevice, stream));
             if (ix->metric == MSVS_METRIC_COSINE)
-                normalize_device_rows(dq.p, cnt, (uint32_t)dim, (uint32_t)dim, stream);
-            rc = msvs_index_search_device(raw, dq.p, cnt, (int)k, 1, nullptr, 0, dids.p, ddis.p, stream);
+                normalize_device_rows(dst, cnt, (uint32_t)dim, (uint32_t)dst_ld, stream);
+        };
+        auto exact = [&](const float * src, size_t src_ld, size_t cnt, uint32_t k) {
+            as_queries(src, src_ld, cnt, dq.p, dim);
+            rc = msvs_index_search_device(raw, dq.p, cnt, (int)k, (int)lists_nprobe, nullptr, 0, dids.p, ddis.p, stream);
             if (rc != MSVS_OK)
                 fail(rc, "%s", std::string(msvs_last_error()).c_str());
         };
-        // 2. seeds: the exact top-1 of every centroid
-        exact(ix->centroids.p, ix->ld, nlist, 1);
+        // the join's rows: a device table with the store's leading dimension -- the store's own when it is in HBM, else a padded copy
+        DevBuf<float> padded;
+        const float * table = rv.table;
+        if (T && rv.host)
+        {
+            table = dense.p;
+            if (ix->ld != dim)
+            {
+                padded.alloc(n * ix->ld);
+                upload_rows(padded.p, dense.p, n, (uint32_t)dim, ix->ld, MSVS_MEM_DEVICE, stream);
+                table = padded.p;
+            }
+        }
+        // 2. seeds: the exact top-1 of every centroid (join_iters >= 1: the canonical scan over the join's table, as the coarse step)
+        if (T)
+        {
+            DevBuf<float> cq(nlist * ix->ld);
+            as_queries(ix->centroids.p, ix->ld, nlist, cq.p, ix->ld);
+            Scratch & scr = scratch_for(stream);
+            scr.reserve(flat_scratch_bytes(n, nlist, 1, ix->ld) + 1024, stream);
+            MergeParams out{};
+            out.out_ids = dids.p;
+            out.out_dis = ddis.p;
+            flat_search_device(scr, scan_metric(ix->metric), table, nullptr, n, ix->ld, cq.p, nlist, 1, nullptr, 0, out, stream);
+            MSVS_HIP(hipStreamSynchronize(stream));
+        }
+        else
+            exact(ix->centroids.p, ix->ld, nlist, 1);
         std::vector<int64_t> top(nlist);
         MSVS_HIP(hipMemcpyAsync(top.data(), dids.p, nlist * 8, hipMemcpyDeviceToHost, stream));
         MSVS_HIP(hipStreamSynchronize(stream));
@@ -508,6 +583,50 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
                                K0, lists.p);
             MSVS_HIP(hipGetLastError());
         }
+        // 3b, 3c. the join: T iterations at most, old lists in, new lists out, until no list changes
+        const int32_t * final_lists = lists.p;
+        DevBuf<int32_t> other;
+        if (T)
+        {
+            other.alloc(n * K0);
+            DevBuf<uint32_t> changed(1);
+            DevBuf<float> jq(ix->metric == MSVS_METRIC_COSINE ? std::min(n, GRAPH_QUERY_CHUNK) * ix->ld : 0);
+            GraphJoinParams a{};
+            a.rows = reinterpret_cast<const float4 *>(table);
+            a.changed = changed.p;
+            a.n = (uint32_t)n;
+            a.ld4 = ix->ld / 4;
+            a.K0 = K0;
+            a.S = ix->join_sample;
+            a.cap = K0 * (ix->join_sample + 1);
+            a.tab = graph_join_table(a.cap);
+            const size_t lds = graph_join_lds_bytes(a.ld4, K0, a.cap, a.tab), step = jq.n ? GRAPH_QUERY_CHUNK : n;
+            int32_t * bufs[2] = {lists.p, other.p};
+            for (size_t t = 0; t < T; t++)
+            {
+                a.lists = bufs[t & 1];
+                a.next = bufs[(t + 1) & 1];
+                MSVS_HIP(hipMemsetAsync(changed.p, 0, 4, stream));
+                for (size_t i0 = 0; i0 < n; i0 += step) // (cosine: the nodes' rows normalised again, a chunk at a time)
+                {
+                    const size_t cnt = std::min(step, n - i0);
+                    if (jq.n)
+                        as_queries(table + i0 * ix->ld, ix->ld, cnt, jq.p, ix->ld);
+                    a.Q = reinterpret_cast<const float4 *>(jq.n ? jq.p : table + i0 * ix->ld);
+                    a.i0 = (uint32_t)i0;
+                    ProfileScope prof("graph_join", stream);
+                    with_int<M_IP, M_L2>(scan_metric(ix->metric), [&](auto mm) { launch_graph_join<decltype(mm)::value>(a, cnt, lds, stream); });
+                    MSVS_HIP(hipGetLastError());
+                }
+                uint32_t moved = 0;
+                MSVS_HIP(hipMemcpyAsync(&moved, changed.p, 4, hipMemcpyDeviceToHost, stream));
+                MSVS_HIP(hipStreamSynchronize(stream));
+                final_lists = a.next;
+                if (moved == 0)
+                    break;
+            }
+            lists_index.reset(); // (the stream is idle)
+        }
         // 4. prune by detours; 5. reverse edges: count, prefix sum, scatter, per-node selection and merge
         const size_t words = n * R;
         DevBuf<uint32_t> F(words), cnt(n);
@@ -518,7 +637,7 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
             MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&graph_prune_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)graph_prune_lds_bytes(128)));
         });
-        hipLaunchKernelGGL(graph_prune_kernel, dim3((unsigned)n), dim3(BLOCK), graph_prune_lds_bytes(K0), stream, lists.p, (uint32_t)n, K0, R, F.p);
+        hipLaunchKernelGGL(graph_prune_kernel, dim3((unsigned)n), dim3(BLOCK), graph_prune_lds_bytes(K0), stream, final_lists, (uint32_t)n, K0, R, F.p);
         MSVS_HIP(hipMemsetAsync(cnt.p, 0, n * 4, stream));
         const unsigned egrid = (unsigned)ceil_div(words, (size_t)256);
         hipLaunchKernelGGL(graph_count_kernel, dim3(egrid), dim3(256), 0, stream, F.p, words, cnt.p);

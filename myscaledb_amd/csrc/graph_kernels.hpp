@@ -31,6 +31,8 @@
 //   block, a whole width = 1 round in one go.  Longer rows: one row a group, chunks of GRAPH_SQ_LONG_UNITS units double buffered
 //   (the next chunk, or the next label's first, is on its way while this one is decoded), as sq_ivf_scan_kernel's wnext.
 //
+// graph_join_kernel: the sub-quadratic build's neighbours-of-neighbours join (create's join_iters >= 1), one block per node; it shares
+//   graph_visit, graph_wave_place and graph_merge with the search.  Its design stands at the kernel.
 // graph_prune_kernel, graph_count_kernel, graph_scan_kernel, graph_scatter_kernel, graph_reverse_kernel: the build, integers only.
 // The coded form's quantiser and codes are made by sq_ivf_kernels.hpp's sq_range_kernel / sq_encode_kernel<8> fed a zero centroid.
 #pragma once
@@ -87,10 +89,13 @@ struct GraphLds
     // ctl: 0 labels to score this round, 1 |V|, 2 beam entries, 3 newly admitted keys, 4 alive results; 8 .. 15 four 64-bit ballots
 };
 
+/// the slot of the visited table a label's probe sequence starts at
+__device__ __forceinline__ uint32_t graph_home(const uint32_t label, const uint32_t tab) { return __umulhi(label * 0x9E3779B1u, tab); }
+
 /// label -> true if this thread is the one that put it into the visited table
 __device__ __forceinline__ bool graph_visit(uint32_t * table, const uint32_t tab, const uint32_t label)
 {
-    uint32_t h = __umulhi(label * 0x9E3779B1u, tab);
+    uint32_t h = graph_home(label, tab);
     for (;;)
     {
         const uint32_t prev = atomicCAS(&table[h], GRAPH_EMPTY, label);
@@ -257,23 +262,11 @@ __device__ __forceinline__ void graph_score_codes(const GraphSearchParams & a, c
     }
 }
 
-/// One round: this thread's candidate label (GRAPH_EMPTY: none) is visited, the winners are scored and merged into the beam.
-/// Entered and left with every thread past a barrier and ctl[0] = ctl[3] = 0.
-template <int METRIC, int BITS>
-__device__ __forceinline__ void graph_round(const GraphSearchParams & a, const GraphLds & L, const uint32_t lab, const uint32_t tid)
+/// Merge by ranking: the m staged keys go into the sorted beam of cnt keys, cut to ef.  Entered with every thread past the barrier
+/// behind the last staged key; left past a barrier with ctl[2] the beam's new fill, ctl[1] grown by m and ctl[0] = ctl[3] = 0.
+__device__ __forceinline__ void graph_merge(const GraphLds & L, const uint32_t ef, const uint32_t m, const uint32_t cnt, const uint32_t tid)
 {
-    const uint32_t lane = tid & 63, grp = tid >> 4, g = tid & 15;
-    const bool won = lab != GRAPH_EMPTY && graph_visit(L.table, a.tab, lab);
-    const uint32_t place = graph_wave_place(&L.ctl[0], won, lane);
-    if (won)
-        L.slab[place] = lab;
-    __syncthreads();
-    const uint32_t m = L.ctl[0], cnt = L.ctl[2];
-    if constexpr (BITS == 8)
-        graph_score_codes<METRIC>(a, L, m, grp, g);
-    else
-        graph_score_rows<METRIC>(a, L, m, grp, g);
-    __syncthreads();
+    const uint32_t lane = tid & 63;
     const uint64_t old = tid < cnt ? L.beam[tid] : KEY_NONE, neu = tid < m ? L.stage[tid] : KEY_NONE;
     const uint32_t old_flag = tid < cnt ? L.flag[tid] : 0;
     uint32_t rank_old = tid, rank_new = 0;
@@ -298,12 +291,12 @@ __device__ __forceinline__ void graph_round(const GraphSearchParams & a, const G
     }
     (void)graph_wave_place(&L.ctl[3], neu != KEY_NONE, lane);
     __syncthreads(); // everybody has read the beam, the flags and the staged keys
-    if (old != KEY_NONE && rank_old < a.ef)
+    if (old != KEY_NONE && rank_old < ef)
     {
         L.beam[rank_old] = old;
         L.flag[rank_old] = old_flag;
     }
-    if (neu != KEY_NONE && rank_new < a.ef)
+    if (neu != KEY_NONE && rank_new < ef)
     {
         L.beam[rank_new] = neu;
         L.flag[rank_new] = 0;
@@ -312,12 +305,32 @@ __device__ __forceinline__ void graph_round(const GraphSearchParams & a, const G
     __syncthreads();
     if (tid == 0)
     {
-        L.ctl[2] = min(a.ef, cnt + admitted);
+        L.ctl[2] = min(ef, cnt + admitted);
         L.ctl[1] += m;
         L.ctl[0] = 0;
         L.ctl[3] = 0;
     }
     __syncthreads();
+}
+
+/// One round: this thread's candidate label (GRAPH_EMPTY: none) is visited, the winners are scored and merged into the beam.
+/// Entered and left with every thread past a barrier and ctl[0] = ctl[3] = 0.
+template <int METRIC, int BITS>
+__device__ __forceinline__ void graph_round(const GraphSearchParams & a, const GraphLds & L, const uint32_t lab, const uint32_t tid)
+{
+    const uint32_t lane = tid & 63, grp = tid >> 4, g = tid & 15;
+    const bool won = lab != GRAPH_EMPTY && graph_visit(L.table, a.tab, lab);
+    const uint32_t place = graph_wave_place(&L.ctl[0], won, lane);
+    if (won)
+        L.slab[place] = lab;
+    __syncthreads();
+    const uint32_t m = L.ctl[0], cnt = L.ctl[2];
+    if constexpr (BITS == 8)
+        graph_score_codes<METRIC>(a, L, m, grp, g);
+    else
+        graph_score_rows<METRIC>(a, L, m, grp, g);
+    __syncthreads();
+    graph_merge(L, a.ef, m, cnt, tid);
 }
 
 template <int METRIC, int BITS = 32>
@@ -452,6 +465,188 @@ static __global__ void graph_lists_kernel(const int64_t * ids, uint32_t cnt, uin
     for (uint32_t j = 0; j <= K0 && o < K0; j++)
         if (src[j] != (int64_t)(i0 + i))
             dst[o++] = (int32_t)src[j];
+}
+
+// ------------------------------------------------------------------------------------------- build: the join (join_iters >= 1)
+
+// float4 pieces of a row a lane requests ahead of their use.  From the compiler's resource report (gfx950): two sets of 8 take 120
+// VGPRs, the search's 4 waves per SIMD, no scratch; two sets of 12 (all of d = 768) take 169 VGPRs, 2 waves.  Not yet timed.
+constexpr uint32_t GRAPH_JOIN_HEAD = 8;
+constexpr uint32_t GRAPH_JOIN_FETCH = 4; // list words a thread requests before it visits the first of them
+
+struct GraphJoinParams
+{
+    const float4 * rows;    // n x ld4, zero padded, in HBM
+    const float4 * Q;       // the launch's nodes as queries: gridDim.x x ld4, zero padded (normalised again for cosine)
+    const int32_t * lists;  // n x K0: L^t, read only
+    int32_t * next;         // n x K0: L^{t+1}
+    uint32_t * changed;     // += 1 for every node whose list changed
+    uint32_t n, i0, ld4, K0, S, cap, tab; // i0: the launch's first node; cap = K0 (S + 1); tab: a power of two >= 2 (cap + 1)
+};
+
+inline uint32_t graph_join_table(uint32_t cap)
+{
+    uint32_t tab = 64;
+    while (tab < 2 * (cap + 1))
+        tab <<= 1;
+    return tab;
+}
+
+/// the query | beam, staged keys, flags (256 each) | the score list (cap) | the node's own list (K0) | control words | the visited table
+inline size_t graph_join_lds_bytes(uint32_t ld4, uint32_t K0, uint32_t cap, uint32_t tab)
+{
+    return (size_t)ld4 * 16 + GRAPH_ROUND * (8 + 8 + 4) + ((size_t)cap + K0 + GRAPH_CTL + tab) * 4;
+}
+
+/// One join iteration of include/msvs.h's build step 3b, one block of 256 threads per node i:
+///   C_i = L_i and the first S entries of the lists of L_i's members, without i and without duplicates; L'_i = its K0 lowest keys.
+/// The whole of C_i is known after two dependent loads and nothing in it waits for a merge, so the kernel
+///   1. gathers: L_i, then all K0 x S neighbour words, GRAPH_JOIN_FETCH requests a thread at a time; every word goes through the
+///      visited table (i sits there from the start) and the winners are compacted into ONE score list;
+///   2. scores the list as one stream: group grp takes its labels grp, grp + 16, ... with the NEXT label's first GRAPH_JOIN_HEAD
+///      pieces requested before this label's arithmetic (two named register sets, swapped by unrolling), and every 256 labels the
+///      staged keys go through graph_merge into a beam of K0 -- the requests of the next chunk's first rows are in flight across
+///      the merge and its barriers.  The arithmetic and its order are canonical_row_chain's, so a key is the search's;
+///   3. writes the beam's labels (-1 beyond its fill) to the other list buffer and counts the node if its list changed.
+template <int METRIC>
+static __global__ __launch_bounds__(BLOCK) void graph_join_kernel(const GraphJoinParams a)
+{
+    extern __shared__ __align__(16) unsigned char graph_lds[];
+    GraphLds L;
+    L.qs = reinterpret_cast<float4 *>(graph_lds);
+    L.vm = L.st = nullptr;
+    L.beam = reinterpret_cast<uint64_t *>(graph_lds + (size_t)a.ld4 * 16);
+    L.stage = L.beam + GRAPH_ROUND;
+    L.flag = reinterpret_cast<uint32_t *>(L.stage + GRAPH_ROUND);
+    L.slab = L.flag + GRAPH_ROUND;
+    int32_t * mine = reinterpret_cast<int32_t *>(L.slab + a.cap);
+    L.ctl = reinterpret_cast<uint32_t *>(mine + a.K0);
+    L.table = L.ctl + GRAPH_CTL;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, grp = tid >> 4, g = tid & 15, node = a.i0 + blockIdx.x, K0 = a.K0;
+    for (uint32_t i = tid; i < a.ld4; i += BLOCK)
+        L.qs[i] = a.Q[(size_t)blockIdx.x * a.ld4 + i];
+    const uint32_t home = graph_home(node, a.tab);
+    for (uint32_t i = tid; i < a.tab; i += BLOCK)
+        L.table[i] = i == home ? node : GRAPH_EMPTY; // the node is visited before anybody asks: it is never scored
+    if (tid < GRAPH_CTL)
+        L.ctl[tid] = 0;
+    if (tid < K0)
+    {
+        const int32_t v = a.lists[(size_t)node * K0 + tid];
+        mine[tid] = v >= 0 && (uint32_t)v < a.n ? v : -1;
+    }
+    __syncthreads();
+    // 1. gather and dedup: word e < K0 is L_i[e]; word K0 + x is entry x % S of the list of L_i[x / S]
+    for (uint32_t e0 = 0; e0 < a.cap; e0 += BLOCK * GRAPH_JOIN_FETCH)
+    {
+        uint32_t w[GRAPH_JOIN_FETCH];
+#pragma unroll
+        for (uint32_t u = 0; u < GRAPH_JOIN_FETCH; u++)
+        {
+            const uint32_t e = e0 + u * BLOCK + tid;
+            w[u] = GRAPH_EMPTY;
+            if (e < K0)
+                w[u] = (uint32_t)mine[e];
+            else if (e < a.cap)
+            {
+                const uint32_t x = e - K0;
+                const int32_t j = mine[x / a.S];
+                if (j >= 0)
+                {
+                    const int32_t v = a.lists[(size_t)j * K0 + x % a.S];
+                    w[u] = v >= 0 && (uint32_t)v < a.n ? (uint32_t)v : GRAPH_EMPTY;
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < GRAPH_JOIN_FETCH; u++)
+        {
+            const bool won = w[u] != GRAPH_EMPTY && graph_visit(L.table, a.tab, w[u]);
+            const uint32_t place = graph_wave_place(&L.ctl[0], won, lane);
+            if (won)
+                L.slab[place] = w[u];
+        }
+    }
+    __syncthreads();
+    // 2. score in one stream
+    const uint32_t total = L.ctl[0], jfull = a.ld4 >> 4, jtail = a.ld4 & 15;
+    const uint32_t np = jfull + (g < jtail ? 1u : 0u), nu = jfull + (jtail ? 1u : 0u); // pieces of this lane; of the longest lane
+    auto request = [&](float4(&y)[GRAPH_JOIN_HEAD], const uint32_t id) {
+        const float4 * row = a.rows + (size_t)id * a.ld4;
+#pragma unroll
+        for (uint32_t u = 0; u < GRAPH_JOIN_HEAD; u++)
+        {
+            y[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (u < nu) // (uniform; a lane without the tail piece asks for the row's first piece again and drops it)
+                y[u] = row[u < np ? u * 16 + g : 0];
+        }
+    };
+    auto score = [&](const float4(&y)[GRAPH_JOIN_HEAD], const uint32_t id) {
+        const float4 * yrow = a.rows + (size_t)id * a.ld4 + g;
+        const float4 * qrow = L.qs + g;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (uint32_t u = 0; u < GRAPH_JOIN_HEAD; u++)
+            if (u < np)
+                canonical_update<METRIC>(acc, qrow[u * 16], y[u]);
+        if (jfull >= GRAPH_JOIN_HEAD) // the rest of a long row, as canonical_row_chain walks it
+        {
+            uint32_t j = GRAPH_JOIN_HEAD;
+            for (; j + 4 <= jfull; j += 4)
+            {
+                const float4 y0 = yrow[j * 16], y1 = yrow[(j + 1) * 16], y2 = yrow[(j + 2) * 16], y3 = yrow[(j + 3) * 16];
+                canonical_update<METRIC>(acc, qrow[j * 16], y0);
+                canonical_update<METRIC>(acc, qrow[(j + 1) * 16], y1);
+                canonical_update<METRIC>(acc, qrow[(j + 2) * 16], y2);
+                canonical_update<METRIC>(acc, qrow[(j + 3) * 16], y3);
+            }
+            for (; j < jfull; j++)
+                canonical_update<METRIC>(acc, qrow[j * 16], yrow[j * 16]);
+            if (g < jtail)
+                canonical_update<METRIC>(acc, qrow[jfull * 16], yrow[jfull * 16]);
+        }
+        const float s = row16_tree_sum(__fadd_rn(__fadd_rn(acc.x, acc.y), __fadd_rn(acc.z, acc.w)));
+        return make_key<METRIC>(s, id);
+    };
+    float4 ya[GRAPH_JOIN_HEAD], yb[GRAPH_JOIN_HEAD];
+    if (grp < total)
+        request(ya, L.slab[grp]);
+    for (uint32_t base = 0; base < total; base += GRAPH_ROUND)
+    {
+        for (uint32_t c = base + grp; c < min(base + GRAPH_ROUND, total); c += 32) // two labels a trip: ya holds label c's head
+        {
+            const uint32_t ida = L.slab[c], idb = c + 16 < total ? L.slab[c + 16] : GRAPH_EMPTY;
+            if (idb != GRAPH_EMPTY)
+                request(yb, idb);
+            const uint64_t ka = score(ya, ida);
+            if (g == 0)
+                L.stage[c - base] = ka;
+            if (c + 32 < total) // (the trip's last label of a chunk asks for the next chunk's first)
+                request(ya, L.slab[c + 32]);
+            if (idb != GRAPH_EMPTY)
+            {
+                const uint64_t kb = score(yb, idb);
+                if (g == 0)
+                    L.stage[c + 16 - base] = kb;
+            }
+        }
+        __syncthreads();
+        graph_merge(L, K0, min(GRAPH_ROUND, total - base), L.ctl[2], tid);
+    }
+    // 3. the new list
+    const uint32_t cnt = L.ctl[2];
+    bool differs = false;
+    if (tid < K0)
+    {
+        const int32_t v = tid < cnt ? (int32_t)(uint32_t)L.beam[tid] : -1;
+        a.next[(size_t)node * K0 + tid] = v;
+        differs = v != mine[tid];
+    }
+    if (__ballot(differs) && lane == 0)
+        L.ctl[4] = 1;
+    __syncthreads();
+    if (tid == 0 && L.ctl[4])
+        atomicAdd(a.changed, 1u);
 }
 
 inline size_t graph_prune_lds_bytes(uint32_t K0) { return ((size_t)K0 * K0 + 2 * K0) * 4; }

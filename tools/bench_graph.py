@@ -1,7 +1,8 @@
 """The graph index on one GPU: --rows x --dim rows of one of bench.py's data models (--data mid | iid | blobs03) in a device row
 store, a built index of degree --degree, searched through the device entry on one stream.  Reports, gates nothing.
 
-  - the build's wall time (msvs_graph_index_build as a whole: trainer, exact lists, prune, reverse edges);
+  - the build's wall time (msvs_graph_index_build as a whole: trainer, lists, prune, reverse edges), printed as soon as it is known;
+    --join-iters T >= 1 selects the sub-quadratic build (IVF lists of --build-nprobe lists, T join iterations over --join-sample entries);
   - for nq in --batches and ef in --efs: recall@10 against an exact scan of the rows (torch, on the first 256 queries), the median
     time of --reps calls between HIP events after a warm-up call (and their spread, min .. max), queries/s;
   - --bits 32,8: the index is built once at 32 bits, exported, and the same structure is handed (set_graph) to a bit_size=8 index
@@ -11,7 +12,7 @@ store, a built index of degree --degree, searched through the device entry on on
 Writes one JSON file (default profiles/graph.json) and prints it.
 
     python -m tools.bench_graph [--rows N] [--dim D] [--data mid] [--degree 32] [--nlist 1024] [--batches 1,64,4096] [--efs 32,64,128,256]
-                                [--bits 32,8] [--nprobes 8,16,32,64] [--reps R] [--out FILE]
+                                [--bits 32,8] [--nprobes 8,16,32,64] [--join-iters T] [--build-nprobe P] [--join-sample S] [--reps R] [--out FILE]
 """
 import argparse
 import json
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--efs", default="32,64,128,256")
     ap.add_argument("--bits", default="32", help="forms of the graph index to search: 32, 8 or 32,8")
     ap.add_argument("--nprobes", default="8,16,32,64", help="of the IVFFLAT index beside it; empty: leave it out")
+    ap.add_argument("--join-iters", type=int, default=0, help="0: the exact O(n^2) build; >= 1: IVF lists repaired by the join kernel")
+    ap.add_argument("--build-nprobe", type=int, default=8)
+    ap.add_argument("--join-sample", type=int, default=8)
     ap.add_argument("--reps", type=int, default=11)
     ap.add_argument("--out", default=os.path.join("profiles", "graph.json"))
     a = ap.parse_args()
@@ -91,10 +95,12 @@ def main():
     out = {"data": what, "rows": a.rows, "dim": a.dim, "degree": a.degree, "nlist": a.nlist, "graph": [], "ivfflat": []}
     rows = capi.Rows(a.dim, a.rows)
     rows.append(x.data_ptr(), n=a.rows, mem=capi.MEM_DEVICE)
-    gx = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,ncentroids=%d,kmeans_iters=10" % (a.degree, a.nlist))
+    build = "join_iters=%d,build_nprobe=%d,join_sample=%d" % (a.join_iters, a.build_nprobe, a.join_sample)
+    gx = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,ncentroids=%d,kmeans_iters=10,%s" % (a.degree, a.nlist, build))
     t0 = time.perf_counter()
     gx.build()
-    out["build_s"] = time.perf_counter() - t0
+    out["build"], out["build_s"] = build, time.perf_counter() - t0
+    print("build (%s): %.2f s" % (build, out["build_s"]), flush=True)
     forms = {32: gx}
     bits = [int(v) for v in a.bits.split(",")]
     if 8 in bits:
