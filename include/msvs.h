@@ -581,8 +581,26 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
  *   File: header version 2, otherwise the same 64 bytes; the body is the centroids, the seeds, nbr, vmin, vmax and the codes as
  *     n x dim bytes in natural order, all under the body's checksum.  A 32-bit index writes and reads version 1 exactly as before.
  *     load_io takes a version-2 file with rows == NULL; a non-NULL store is checked for n alone.  Bounds that are not finite,
- *     vmax < vmin, an infinite span or a wrong size are MSVS_ERR_IO like any corruption.  A version-1 file keeps its rules. */
+ *     vmax < vmin, an infinite span or a wrong size are MSVS_ERR_IO like any corruption.  A version-1 file keeps its rules.
+ *
+ * Wide search: search_wide / search_wide_device, the argument lists of search / search_device.  The definition is search steps
+ * 1 - 6 above word for word (bit_size=8: against the decoded row), with three numbers changed:
+ *   ef 1 .. MSVS_MAX_K_ROUNDS, default max(k, 64) capped at MSVS_MAX_K_ROUNDS (MSVS_ERR_INVALID_ARGUMENT beyond);
+ *   k <= MSVS_MAX_K_ROUNDS and k <= ef (MSVS_ERR_UNSUPPORTED_K otherwise);
+ *   step 5 stops before an iteration if |V| + width * R > MSVS_GRAPH_WIDE_VISITED_MAX (262144 = 8192 x 32: the default iteration
+ *   count of ef = 4096 at R = 32).
+ *   min(nprobe, nlist) <= MSVS_MAX_K as above (the seeds are one round of at most 256 labels); width 1 .. 4 and the max_iters default
+ *   ceil(2 ef / width) + 8 are unchanged; scoring, keys, strict admission, NaN, the set-operation beam update, the filter of step 6,
+ *   cosine's fl(1 - ip), the no-ops and the not-ready and null-argument errors carry over unchanged.
+ *   The result is a function of the inputs alone.  For any parameters that search accepts and whose search does not end by its
+ *   MSVS_GRAPH_VISITED_MAX rule, search_wide returns search's result bit for bit.  A selective filter is what it is for: dead rows
+ *   occupy B, and ef = 4096 leaves room for k alive rows where ef = 256 does not.
+ *   The visited set lives in device memory (at most 2 MiB a resident query, 1 GiB of the stream's scratch arena in all); the LDS
+ *   image holds the query (bit_size=8: and vmin, step), ef x 9 bytes of beam and 3 KiB of round state; a parameter set whose image
+ *   exceeds 160 KiB is MSVS_ERR_INVALID_ARGUMENT.  dim = 8192 with bit_size=8 fits at ef = 4096.
+ *   The wide entries always run the wide kernel, also for ef <= MSVS_MAX_K; search / search_device keep every limit they have. */
 #define MSVS_GRAPH_VISITED_MAX 12288
+#define MSVS_GRAPH_WIDE_VISITED_MAX 262144
 typedef struct msvs_graph_index msvs_graph_index_t;
 MSVS_API int msvs_graph_index_create(int metric, const msvs_rows_t * rows, const char * params, msvs_graph_index_t ** out);
 MSVS_API void msvs_graph_index_free(msvs_graph_index_t * index);
@@ -602,6 +620,11 @@ MSVS_API int msvs_graph_index_search(const msvs_graph_index_t * index, const flo
 MSVS_API int msvs_graph_index_search_device(const msvs_graph_index_t * index, const float * d_queries, size_t nq, size_t k, size_t ef,
                                             size_t nprobe, size_t width, size_t max_iters, const uint64_t * d_alive_bits, size_t nbits,
                                             int64_t * d_ids, float * d_dis, void * hip_stream);
+MSVS_API int msvs_graph_index_search_wide(const msvs_graph_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
+                                          const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
+MSVS_API int msvs_graph_index_search_wide_device(const msvs_graph_index_t * index, const float * d_queries, size_t nq, size_t k, size_t ef,
+                                                 size_t nprobe, size_t width, size_t max_iters, const uint64_t * d_alive_bits,
+                                                 size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream);
 MSVS_API int msvs_graph_index_serialize_io(const msvs_graph_index_t * index, const struct msvs_io * io);
 MSVS_API int msvs_graph_index_load_io(const struct msvs_io * io, const msvs_rows_t * rows, msvs_graph_index_t ** out);
 

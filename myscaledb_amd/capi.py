@@ -67,6 +67,7 @@ SYMBOLS = [
     "msvs_graph_index_num_data", "msvs_graph_index_num_lists", "msvs_graph_index_degree", "msvs_graph_index_memory_usage",
     "msvs_graph_index_export", "msvs_graph_index_search", "msvs_graph_index_search_device", "msvs_graph_index_serialize_io",
     "msvs_graph_index_load_io", "msvs_graph_index_bit_size", "msvs_graph_index_export_codes",
+    "msvs_graph_index_search_wide", "msvs_graph_index_search_wide_device",
 ]
 
 
@@ -651,6 +652,7 @@ class Rows:
 
 
 GRAPH_VISITED_MAX = 12288  # MSVS_GRAPH_VISITED_MAX: labels one graph search scores at most
+GRAPH_WIDE_VISITED_MAX = 262144  # MSVS_GRAPH_WIDE_VISITED_MAX: ... of GraphIndex.search_wide
 GRAPH_NO_EDGE = 0xFFFFFFFF
 
 
@@ -689,11 +691,22 @@ class GraphIndex(_CodedIndex):
         """params: "ef=E,nprobe=P,width=W,max_iters=I" (any subset); alive: bool over labels."""
         return _CodedIndex.search(self, queries, k, params, alive, nbits)
 
-    def search_device(self, d_queries, nq, k, d_ids, d_dis, ef=0, nprobe=8, width=1, max_iters=0, stream=0, d_alive=0, nbits=0):
+    def search_device(self, d_queries, nq, k, d_ids, d_dis, ef=0, nprobe=8, width=1, max_iters=0, stream=0, d_alive=0, nbits=0,
+                      _entry="search_device"):
         """All buffers are raw device addresses (ints); ef / max_iters 0: the defaults; enqueues on `stream` and returns immediately."""
-        _check(lib().msvs_graph_index_search_device(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(ef),
-                                                    C.c_size_t(nprobe), C.c_size_t(width), C.c_size_t(max_iters), self._dev(d_alive),
-                                                    C.c_size_t(nbits), C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)), self._dev(stream)))
+        fn = self._fn(_entry)
+        fn.argtypes = [C.c_void_p, C.c_void_p] + [C.c_size_t] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(fn(self._h, C.c_void_p(int(d_queries)), C.c_size_t(nq), C.c_size_t(k), C.c_size_t(ef), C.c_size_t(nprobe), C.c_size_t(width),
+                  C.c_size_t(max_iters), self._dev(d_alive), C.c_size_t(nbits), C.c_void_p(int(d_ids)), C.c_void_p(int(d_dis)), self._dev(stream)))
+
+    def search_wide(self, queries, k, params="", alive=None, nbits=None):
+        """search with ef and k <= MAX_K_ROUNDS and a visited set of GRAPH_WIDE_VISITED_MAX labels (msvs_graph_index_search_wide): the
+        same definition, so the same result wherever search accepts the parameters and does not end by its visited limit."""
+        return _CodedIndex.search(self, queries, k, params, alive, nbits, _entry="search_wide")
+
+    def search_wide_device(self, d_queries, nq, k, d_ids, d_dis, ef=0, nprobe=8, width=1, max_iters=0, stream=0, d_alive=0, nbits=0):
+        """search_device with ef and k <= MAX_K_ROUNDS (msvs_graph_index_search_wide_device)."""
+        self.search_device(d_queries, nq, k, d_ids, d_dis, ef, nprobe, width, max_iters, stream, d_alive, nbits, _entry="search_wide_device")
 
     def export(self):
         """-> (centroids [nlist, dim], seeds [nlist] i32, nbr [n, degree] u32)"""

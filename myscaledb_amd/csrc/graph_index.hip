@@ -3,6 +3,7 @@
 // is a function of the inputs alone.  The kernels and their layout: graph_kernels.hpp.  DESIGN.md 4.14.
 // bit_size=8: the index keeps one 8-bit quantiser and a code row per label, made from the store by build / set_graph; the search
 // scores decoded rows and nothing but build / set_graph reads the store.
+// search_wide: the same definition with ef, k <= MSVS_MAX_K_ROUNDS, served by graph_wide_search_kernel on a fixed grid.
 // Reused as they are: the row store (refine.hip), the canonical scoring of refine_kernels.hpp's chain, the k-means trainer and the
 // canonical coarse top-P (coded_ivf.hpp: kmeans, flat_search_device), the exact FLAT search for the build's neighbour lists -- or,
 // with join_iters >= 1, an IVFFLAT search of build_nprobe lists whose lists graph_join_kernel repairs across partition borders.
@@ -73,21 +74,21 @@ struct GraphSearch // the search parameters, defaults filled in
     size_t ef = 0, nprobe = 8, width = 1, max_iters = 0;
 };
 
-/// ef 0: max(k, 64) capped at MSVS_MAX_K; max_iters 0: ceil(2 ef / width) + 8
-GraphSearch graph_defaults(size_t k, size_t ef, size_t nprobe, size_t width, size_t max_iters)
+/// ef 0: max(k, 64) capped at ef_max (MSVS_MAX_K; the wide search: MSVS_MAX_K_ROUNDS); max_iters 0: ceil(2 ef / width) + 8
+GraphSearch graph_defaults(size_t k, size_t ef, size_t nprobe, size_t width, size_t max_iters, size_t ef_max)
 {
     GraphSearch s;
-    s.ef = ef ? ef : std::min<size_t>(std::max<size_t>(k, 64), MSVS_MAX_K);
+    s.ef = ef ? ef : std::min<size_t>(std::max<size_t>(k, 64), ef_max);
     s.nprobe = nprobe;
     s.width = width;
-    if (s.ef > MSVS_MAX_K || width < 1 || width > 4 || nprobe < 1)
-        fail(MSVS_ERR_INVALID_ARGUMENT, "graph search needs 1 <= ef <= %d, 1 <= width <= 4 and nprobe >= 1 (ef %zu, width %zu, nprobe %zu)", MSVS_MAX_K,
+    if (s.ef > ef_max || width < 1 || width > 4 || nprobe < 1)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "graph search needs 1 <= ef <= %zu, 1 <= width <= 4 and nprobe >= 1 (ef %zu, width %zu, nprobe %zu)", ef_max,
              s.ef, width, nprobe);
     s.max_iters = max_iters ? max_iters : ceil_div(2 * s.ef, width) + 8;
     return s;
 }
 
-GraphSearch parse_graph_search(const char * params, size_t k)
+GraphSearch parse_graph_search(const char * params, size_t k, size_t ef_max)
 {
     const auto p = parse_params(params);
     for (const auto & kv : p)
@@ -96,7 +97,7 @@ GraphSearch parse_graph_search(const char * params, size_t k)
     const long ef = param_int(p, "ef", 0), nprobe = param_int(p, "nprobe", 8), width = param_int(p, "width", 1), it = param_int(p, "max_iters", 0);
     if ((p.count("ef") && ef < 1) || nprobe < 1 || width < 1 || (p.count("max_iters") && it < 1))
         fail(MSVS_ERR_INVALID_ARGUMENT, "ef, nprobe, width and max_iters must be >= 1");
-    return graph_defaults(k, (size_t)ef, (size_t)nprobe, (size_t)width, (size_t)it);
+    return graph_defaults(k, (size_t)ef, (size_t)nprobe, (size_t)width, (size_t)it, ef_max);
 }
 
 template <int METRIC, int BITS>
@@ -110,6 +111,31 @@ void launch_graph_search(const GraphSearchParams & a, size_t nq, size_t lds, hip
     hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(BLOCK), lds, stream, a);
 }
 
+// The wide search's grid is fixed: as many blocks as stay resident, each with a visited table of its own in the stream's arena.
+constexpr size_t GRAPH_WIDE_TABLE_BUDGET = (size_t)1 << 30; // bytes of visited tables of one launch at most
+constexpr size_t GRAPH_WIDE_CU_LDS = 160 * 1024;            // blocks per CU: the LDS images that fit a CU's 160 KiB ...
+constexpr size_t GRAPH_WIDE_CU_BLOCKS = 4;                  // ... and at most 4: a block is a wavefront per SIMD, the kernel takes 113 .. 150 VGPRs
+
+/// the beam entries a thread of the wide kernel holds: the kernel's E for this ef
+int graph_wide_entries(size_t ef)
+{
+    int e = 1;
+    while ((size_t)e * BLOCK < ef)
+        e *= 2;
+    return e;
+}
+
+template <int METRIC, int BITS, int E>
+void launch_graph_wide_search(const GraphWideParams & a, unsigned grid, size_t lds, hipStream_t stream)
+{
+    constexpr auto kernel = &graph_wide_search_kernel<METRIC, BITS, E>;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRAPH_LDS_MAX));
+    });
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, stream, a);
+}
+
 template <int METRIC>
 void launch_graph_join(const GraphJoinParams & a, size_t nodes, size_t lds, hipStream_t stream)
 {
@@ -121,11 +147,13 @@ void launch_graph_join(const GraphJoinParams & a, size_t nodes, size_t lds, hipS
     hipLaunchKernelGGL(kernel, dim3((unsigned)nodes), dim3(BLOCK), lds, stream, a);
 }
 
-/// Everything on the device, enqueued on `stream`: queries padded (normalised for cosine), the canonical coarse top-P, one launch.
-void graph_search_device(const msvs_graph_index & ix, const float * d_queries, size_t nq, size_t k, const GraphSearch & s, const uint64_t * d_alive,
-                         size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+/// Everything on the device, enqueued on `stream`: queries padded (normalised for cosine), the canonical coarse top-P, one launch a
+/// chunk of queries -- of graph_search_kernel (a block a query, the visited table in LDS), or with `wide` of graph_wide_search_kernel
+/// (a fixed grid, the visited tables in the stream's arena).
+void graph_search_chunks(const msvs_graph_index & ix, const float * d_queries, size_t nq, size_t k, const GraphSearch & s, const uint64_t * d_alive,
+                         size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream, bool wide)
 {
-    check_k(k);
+    check_k(k, wide ? MSVS_MAX_K_ROUNDS : MSVS_MAX_K);
     check_graph_ready(ix);
     if (k > s.ef)
         fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds ef = %zu, the beam of the graph search", k, s.ef);
@@ -133,10 +161,12 @@ void graph_search_device(const msvs_graph_index & ix, const float * d_queries, s
     if (P > MSVS_MAX_K)
         fail(MSVS_ERR_UNSUPPORTED_K, "min(nprobe, nlist) = %zu exceeds the coarse quantiser's top-k limit %d", P, MSVS_MAX_K);
     // the visited table: what the search can score at most, at load factor <= 0.5
-    const size_t iters = std::min<size_t>(s.max_iters, MSVS_GRAPH_VISITED_MAX), reach = std::min<size_t>(MSVS_GRAPH_VISITED_MAX, P + iters * fan);
-    const uint32_t tab = (uint32_t)(2 * std::max<size_t>(reach, 32)), ld4 = ix.ld / 4, lc4 = ix.ldc / 4;
+    const size_t cap = wide ? MSVS_GRAPH_WIDE_VISITED_MAX : MSVS_GRAPH_VISITED_MAX;
+    const size_t iters = std::min<size_t>(s.max_iters, cap), reach = std::min<size_t>(cap, P + iters * fan);
+    // (the wide kernel clears its table with 16-byte stores: a multiple of four words)
+    const uint32_t tab = (uint32_t)round_up(2 * std::max<size_t>(reach, 32), (size_t)(wide ? 4 : 1)), ld4 = ix.ld / 4, lc4 = ix.ldc / 4;
     const bool coded = ix.bits == 8;
-    const size_t lds = coded ? graph_sq_lds_bytes(lc4, tab) : graph_lds_bytes(ld4, tab);
+    const size_t lds = wide ? graph_wide_lds_bytes(coded ? 3 * lc4 : ld4, (uint32_t)s.ef) : coded ? graph_sq_lds_bytes(lc4, tab) : graph_lds_bytes(ld4, tab);
     if (lds > GRAPH_LDS_MAX)
         fail(MSVS_ERR_INVALID_ARGUMENT, "the graph search's LDS image (%zu bytes) exceeds %zu", lds, GRAPH_LDS_MAX);
     if (nq == 0 || k == 0)
@@ -153,10 +183,14 @@ void graph_search_device(const msvs_graph_index & ix, const float * d_queries, s
     }
     const int m = scan_metric(ix.metric);
     const size_t chunk = std::min(nq, GRAPH_QUERY_CHUNK);
+    // the wide grid: the blocks the device keeps resident, no more than there are queries or tables within the budget
+    const size_t per_cu = std::max<size_t>(1, std::min(GRAPH_WIDE_CU_LDS / lds, GRAPH_WIDE_CU_BLOCKS));
+    const size_t grid = wide ? std::max<size_t>(1, std::min({chunk, per_cu * device_cu_count(), GRAPH_WIDE_TABLE_BUDGET / ((size_t)tab * 4)})) : 0;
     Scratch & scr = scratch_for(stream);
-    scr.reserve(chunk * ((size_t)ix.ld * 4 + P * 4) + flat_scratch_bytes(ix.nlist, chunk, (uint32_t)P, ix.ld) + 8 * 256, stream);
+    scr.reserve(chunk * ((size_t)ix.ld * 4 + P * 4) + flat_scratch_bytes(ix.nlist, chunk, (uint32_t)P, ix.ld) + grid * tab * 4 + 9 * 256, stream);
     float * dq = scr.take<float>(chunk * ix.ld);
     int32_t * probes = scr.take<int32_t>(chunk * P);
+    uint32_t * tables = wide ? scr.take<uint32_t>(grid * tab) : nullptr;
     const size_t mark = scr.used;
     for (size_t q0 = 0; q0 < nq; q0 += chunk)
     {
@@ -169,7 +203,9 @@ void graph_search_device(const msvs_graph_index & ix, const float * d_queries, s
         co.mode = 1;
         co.out_probes = probes;
         flat_search_device(scr, m, ix.centroids.p, nullptr, ix.nlist, ix.ld, dq, nqc, (uint32_t)P, nullptr, 0, co, stream);
-        GraphSearchParams a{};
+        GraphWideParams a{};
+        a.tables = tables;
+        a.nq = (uint32_t)nqc;
         a.rows = reinterpret_cast<const float4 *>(table);
         a.codes = reinterpret_cast<const uint4 *>(ix.codes.p);
         a.vmin = reinterpret_cast<const float4 *>(ix.d_vmin.p);
@@ -194,15 +230,33 @@ void graph_search_device(const msvs_graph_index & ix, const float * d_queries, s
         a.P = (uint32_t)P;
         a.tab = tab;
         a.cosine = ix.metric == MSVS_METRIC_COSINE;
-        ProfileScope prof("graph_search", stream);
+        ProfileScope prof(wide ? "graph_wide_search" : "graph_search", stream);
         with_int<M_IP, M_L2>(m, [&](auto mm) {
-            if (coded)
-                launch_graph_search<decltype(mm)::value, 8>(a, nqc, lds, stream);
-            else
-                launch_graph_search<decltype(mm)::value, 32>(a, nqc, lds, stream);
+            with_int<8, 32>((int)ix.bits, [&](auto bb) {
+                constexpr int METRIC = decltype(mm)::value, BITS = decltype(bb)::value;
+                if (!wide)
+                    launch_graph_search<METRIC, BITS>(a, nqc, lds, stream);
+                else
+                    with_int<1, 2, 4, 8, 16>(graph_wide_entries(s.ef), [&](auto ee) {
+                        launch_graph_wide_search<METRIC, BITS, decltype(ee)::value>(a, (unsigned)std::min(grid, nqc), lds, stream);
+                    });
+            });
         });
         MSVS_HIP(hipGetLastError());
     }
+}
+
+void graph_search_device(const msvs_graph_index & ix, const float * d_queries, size_t nq, size_t k, const GraphSearch & s, const uint64_t * d_alive,
+                         size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+{
+    graph_search_chunks(ix, d_queries, nq, k, s, d_alive, nbits, d_ids, d_dis, stream, false);
+}
+
+/// the wide search (include/msvs.h): ef and k up to MSVS_MAX_K_ROUNDS, always graph_wide_search_kernel
+void graph_wide_search_device(const msvs_graph_index & ix, const float * d_queries, size_t nq, size_t k, const GraphSearch & s,
+                              const uint64_t * d_alive, size_t nbits, int64_t * d_ids, float * d_dis, hipStream_t stream)
+{
+    graph_search_chunks(ix, d_queries, nq, k, s, d_alive, nbits, d_ids, d_dis, stream, true);
 }
 
 /// centroids (nlist x dim, host), seeds and edges (host) -> the index's device buffers; the caller has validated them
@@ -657,26 +711,29 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
     });
 }
 
-extern "C" int msvs_graph_index_search_device(const msvs_graph_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t ef, size_t nprobe,
-                                              size_t width, size_t max_iters, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
-                                              float * d_dis, void * hip_stream)
+/// search_device / search_wide_device
+int graph_search_device_entry(const msvs_graph_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t ef, size_t nprobe, size_t width,
+                              size_t max_iters, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids, float * d_dis, void * hip_stream, bool wide)
 {
     return guarded([&] {
+        const size_t limit = wide ? MSVS_MAX_K_ROUNDS : MSVS_MAX_K;
         check_graph(ix);
-        check_k(k);
-        graph_search_device(*ix, d_queries, nq, k, graph_defaults(k, ef, nprobe, width, max_iters), d_alive_bits, nbits, d_ids, d_dis,
-                            as_stream(hip_stream));
+        check_k(k, limit);
+        (wide ? graph_wide_search_device : graph_search_device)(*ix, d_queries, nq, k, graph_defaults(k, ef, nprobe, width, max_iters, limit),
+                                                                 d_alive_bits, nbits, d_ids, d_dis, as_stream(hip_stream));
     });
 }
 
-extern "C" int msvs_graph_index_search(const msvs_graph_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
-                                       const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+/// search / search_wide: the queries and the filter staged in, the results staged out
+int graph_search_entry(const msvs_graph_index_t * ix, const float * queries, size_t nq, size_t k, const char * params, const uint64_t * alive_bits,
+                       size_t nbits, int64_t * ids, float * dis, bool wide)
 {
     return guarded([&] {
+        const size_t limit = wide ? MSVS_MAX_K_ROUNDS : MSVS_MAX_K;
         DeviceGuard on_device(ix ? ix->device : -1);
         check_graph(ix);
-        check_k(k);
-        const GraphSearch s = parse_graph_search(params, k);
+        check_k(k, limit);
+        const GraphSearch s = parse_graph_search(params, k, limit);
         check_graph_ready(*ix);
         if (k > s.ef)
             fail(MSVS_ERR_UNSUPPORTED_K, "k = %zu exceeds ef = %zu, the beam of the graph search", k, s.ef);
@@ -695,11 +752,37 @@ extern "C" int msvs_graph_index_search(const msvs_graph_index_t * ix, const floa
         MSVS_HIP(hipMemcpyAsync(dq, queries, nq * ix->dim * 4, hipMemcpyHostToDevice, stream));
         if (words)
             MSVS_HIP(hipMemcpyAsync(d_alive, alive_bits, words * 8, hipMemcpyHostToDevice, stream));
-        graph_search_device(*ix, dq, nq, k, s, d_alive, nbits, d_ids, d_dis, stream);
+        (wide ? graph_wide_search_device : graph_search_device)(*ix, dq, nq, k, s, d_alive, nbits, d_ids, d_dis, stream);
         MSVS_HIP(hipMemcpyAsync(ids, d_ids, nq * k * 8, hipMemcpyDeviceToHost, stream));
         MSVS_HIP(hipMemcpyAsync(dis, d_dis, nq * k * 4, hipMemcpyDeviceToHost, stream));
         MSVS_HIP(hipStreamSynchronize(stream));
     });
+}
+
+extern "C" int msvs_graph_index_search_device(const msvs_graph_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t ef, size_t nprobe,
+                                              size_t width, size_t max_iters, const uint64_t * d_alive_bits, size_t nbits, int64_t * d_ids,
+                                              float * d_dis, void * hip_stream)
+{
+    return graph_search_device_entry(ix, d_queries, nq, k, ef, nprobe, width, max_iters, d_alive_bits, nbits, d_ids, d_dis, hip_stream, false);
+}
+
+extern "C" int msvs_graph_index_search(const msvs_graph_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
+                                       const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return graph_search_entry(ix, queries, nq, k, params, alive_bits, nbits, ids, dis, false);
+}
+
+extern "C" int msvs_graph_index_search_wide_device(const msvs_graph_index_t * ix, const float * d_queries, size_t nq, size_t k, size_t ef,
+                                                   size_t nprobe, size_t width, size_t max_iters, const uint64_t * d_alive_bits, size_t nbits,
+                                                   int64_t * d_ids, float * d_dis, void * hip_stream)
+{
+    return graph_search_device_entry(ix, d_queries, nq, k, ef, nprobe, width, max_iters, d_alive_bits, nbits, d_ids, d_dis, hip_stream, true);
+}
+
+extern "C" int msvs_graph_index_search_wide(const msvs_graph_index_t * ix, const float * queries, size_t nq, size_t k, const char * params,
+                                            const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis)
+{
+    return graph_search_entry(ix, queries, nq, k, params, alive_bits, nbits, ids, dis, true);
 }
 
 // ------------------------------------------------------------------------------------------- export and files

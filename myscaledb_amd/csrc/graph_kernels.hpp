@@ -31,6 +31,8 @@
 //   block, a whole width = 1 round in one go.  Longer rows: one row a group, chunks of GRAPH_SQ_LONG_UNITS units double buffered
 //   (the next chunk, or the next label's first, is on its way while this one is decoded), as sq_ivf_scan_kernel's wnext.
 //
+// graph_wide_search_kernel<METRIC, BITS, E>: the same search with ef, k <= 4096 (search_wide): a fixed grid, E beam entries a thread,
+//   the visited table in global memory.  Its design stands at the kernel.
 // graph_join_kernel: the sub-quadratic build's neighbours-of-neighbours join (create's join_iters >= 1), one block per node; it shares
 //   graph_visit, graph_wave_place and graph_merge with the search.  Its design stands at the kernel.
 // graph_prune_kernel, graph_count_kernel, graph_scan_kernel, graph_scatter_kernel, graph_reverse_kernel: the build, integers only.
@@ -447,6 +449,278 @@ static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphS
         a.out_ids[o] = -1;
         const float v = key_value<METRIC>(KEY_NONE);
         a.out_dis[o] = a.cosine ? __fsub_rn(1.0f, v) : v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------- the wide search (ef, k <= 4096)
+
+// graph_wide_search_kernel<METRIC, BITS, E>: the search of include/msvs.h's definition with a beam of up to MSVS_MAX_K_ROUNDS entries
+// and a visited set of up to MSVS_GRAPH_WIDE_VISITED_MAX labels.  Visit, score and keys are the narrow search's functions; the rest:
+//   Work split: a FIXED grid (the launcher: what fits by LDS image x CUs, and by the table budget); block b serves queries b,
+//     b + gridDim.x, ...  BITS 8 stages vmin and step once per block, the query once per query.
+//   Visited table: a slice of `tab` words of GLOBAL memory per block, cleared at the start of every query with 16-byte stores; after
+//     a fence and a barrier it is touched through atomicCAS alone (graph_visit), so no cached line ever reaches a decision.
+//   LDS image (graph_wide_lds_bytes): the query (| vmin | step) | beam keys (ef x 8) | staged keys (256 x 8) | labels to score
+//     (256 x 4) | control words (32 x 4) | expanded flags (ef bytes).
+//   Merge by ranking, E = the beam entries a thread holds (entry e x 256 + tid; E x 256 >= ef):
+//     1. the m <= 256 staged keys rank among themselves (broadcast reads) and are rewritten in rank order, the admitted ones first;
+//     2. a thread's E old keys each count the staged keys below them: E independent branch-free binary searches of <= 9 steps;
+//        new rank = old position + that count;
+//     3. staged key t counts the beam keys below it (<= 13 steps); its rank = that count + t;
+//     4. after a barrier every entry with rank < ef writes itself and its flag -- an old entry only if its rank moved.
+//   Parent pick: ctl[4] is a cursor before which every beam entry is expanded.  The pick scans windows of 256 entries from it, one
+//     ballot per wavefront, until `width` clear flags are found or the fill ends; a merge lowers the cursor to the lowest rank a new
+//     key took.  The parents are the `width` lowest-key unexpanded entries, as in the narrow search.
+//   Epilogue: the beam in windows of 256 with a running count of alive entries; the first k are written, the rest padded.
+constexpr uint32_t GRAPH_WIDE_CTL = 32; // 0 labels to score, 1 |V|, 2 beam entries, 3 admitted keys, 4 cursor; 8 .. 15 ballots; 16 .. 19 parent slots
+
+struct GraphWideParams : GraphSearchParams
+{
+    uint32_t * tables; // gridDim.x slices of tab words (tab % 4 == 0)
+    uint32_t nq;
+};
+
+/// q4: the float4 of the query image (ld4; BITS 8: 3 lc4)
+inline size_t graph_wide_lds_bytes(uint32_t q4, uint32_t ef)
+{
+    return (size_t)q4 * 16 + (size_t)ef * 8 + GRAPH_ROUND * (8 + 4) + GRAPH_WIDE_CTL * 4 + (((size_t)ef + 15) & ~(size_t)15);
+}
+
+/// sorted keys[0 .. n) -> how many are below key; p2: the largest power of two <= n (0 for n = 0).  No branch: chains interleave.
+__device__ __forceinline__ uint32_t graph_count_below(const uint64_t * keys, const uint32_t n, const uint32_t p2, const uint64_t key)
+{
+    uint32_t pos = 0;
+    for (uint32_t s = p2; s; s >>= 1)
+        pos += pos + s <= n && keys[pos + s - 1] < key ? s : 0u;
+    return pos;
+}
+
+__device__ __forceinline__ uint32_t graph_floor_pow2(const uint32_t n) { return n ? 1u << (31 - __builtin_clz(n)) : 0u; }
+
+/// The wide merge (the header's steps 1 - 4).  Entered and left as graph_merge; ctl[4] is lowered to the lowest rank a new key took.
+template <int E>
+__device__ __forceinline__ void graph_wide_merge(const GraphLds & L, uint8_t * flag, const uint32_t ef, const uint32_t m, const uint32_t cnt,
+                                                 const uint32_t tid)
+{
+    const uint32_t lane = tid & 63;
+    // 1. the staged keys in rank order (KEY_NONE: not admitted, behind every key)
+    uint64_t neu = tid < m ? L.stage[tid] : KEY_NONE;
+    uint32_t rank_new = 0;
+    for (uint32_t j = 0; j < m; j++)
+        rank_new += L.stage[j] < neu ? 1u : 0u; // one address for the whole block: a broadcast read
+    (void)graph_wave_place(&L.ctl[3], neu != KEY_NONE, lane);
+    __syncthreads();
+    if (neu != KEY_NONE)
+        L.stage[rank_new] = neu;
+    __syncthreads();
+    const uint32_t ma = L.ctl[3], pa = graph_floor_pow2(ma), pc = graph_floor_pow2(cnt);
+    // 2. the old keys: position + staged keys below
+    uint64_t old[E];
+    uint32_t rank_old[E];
+    uint8_t old_flag[E];
+#pragma unroll
+    for (int e = 0; e < E; e++)
+    {
+        const uint32_t i = (uint32_t)e * BLOCK + tid;
+        old[e] = i < cnt ? L.beam[i] : KEY_NONE;
+        old_flag[e] = i < cnt ? flag[i] : (uint8_t)0;
+        rank_old[e] = 0;
+    }
+    for (uint32_t s = pa; s; s >>= 1)
+#pragma unroll
+        for (int e = 0; e < E; e++)
+            rank_old[e] += rank_old[e] + s <= ma && L.stage[rank_old[e] + s - 1] < old[e] ? s : 0u;
+    // 3. the new keys: beam keys below + staged rank
+    neu = tid < ma ? L.stage[tid] : KEY_NONE;
+    rank_new = tid < ma ? graph_count_below(L.beam, cnt, pc, neu) + tid : ef;
+    uint32_t low = rank_new;
+    for (int d = 32; d; d >>= 1)
+        low = min(low, (uint32_t)__shfl_xor((int)low, d));
+    __syncthreads(); // everybody has read the beam, the flags and the staged keys
+    // 4. every survivor writes itself
+#pragma unroll
+    for (int e = 0; e < E; e++)
+    {
+        const uint32_t i = (uint32_t)e * BLOCK + tid, r = i + rank_old[e];
+        if (old[e] != KEY_NONE && r != i && r < ef)
+        {
+            L.beam[r] = old[e];
+            flag[r] = old_flag[e];
+        }
+    }
+    if (rank_new < ef)
+    {
+        L.beam[rank_new] = neu;
+        flag[rank_new] = 0;
+    }
+    if (lane == 0 && low < ef)
+        atomicMin(&L.ctl[4], low);
+    __syncthreads();
+    if (tid == 0)
+    {
+        L.ctl[2] = min(ef, cnt + ma);
+        L.ctl[1] += m;
+        L.ctl[0] = 0;
+        L.ctl[3] = 0;
+    }
+    __syncthreads();
+}
+
+/// graph_round with the visited table in global memory and the wide merge
+template <int METRIC, int BITS, int E>
+__device__ __forceinline__ void graph_wide_round(const GraphWideParams & a, const GraphLds & L, uint8_t * flag, const uint32_t lab, const uint32_t tid)
+{
+    const uint32_t lane = tid & 63, grp = tid >> 4, g = tid & 15;
+    const bool won = lab != GRAPH_EMPTY && graph_visit(L.table, a.tab, lab);
+    const uint32_t place = graph_wave_place(&L.ctl[0], won, lane);
+    if (won)
+        L.slab[place] = lab;
+    __syncthreads();
+    const uint32_t m = L.ctl[0], cnt = L.ctl[2];
+    if constexpr (BITS == 8)
+        graph_score_codes<METRIC>(a, L, m, grp, g);
+    else
+        graph_score_rows<METRIC>(a, L, m, grp, g);
+    __syncthreads();
+    graph_wide_merge<E>(L, flag, a.ef, m, cnt, tid);
+}
+
+template <int METRIC, int BITS, int E>
+static __global__ __launch_bounds__(BLOCK) void graph_wide_search_kernel(const GraphWideParams a)
+{
+    static_assert(BITS == 32 || BITS == 8, "f32 rows of a row store, or 8-bit codes");
+    static_assert(E * BLOCK <= MSVS_MAX_K_ROUNDS, "the beam's entries a thread holds");
+    extern __shared__ __align__(16) unsigned char graph_lds[];
+    GraphLds L;
+    L.qs = reinterpret_cast<float4 *>(graph_lds);
+    L.vm = L.qs + a.lc4;
+    L.st = L.vm + a.lc4;
+    L.beam = reinterpret_cast<uint64_t *>(graph_lds + (BITS == 8 ? (size_t)a.lc4 * 48 : (size_t)a.ld4 * 16));
+    L.stage = L.beam + a.ef;
+    L.flag = nullptr; // (the wide beam's flags are bytes)
+    L.slab = reinterpret_cast<uint32_t *>(L.stage + GRAPH_ROUND);
+    L.ctl = L.slab + GRAPH_ROUND;
+    L.table = a.tables + (size_t)blockIdx.x * a.tab;
+    uint8_t * flag = reinterpret_cast<uint8_t *>(L.ctl + GRAPH_WIDE_CTL);
+    uint64_t * ballots = reinterpret_cast<uint64_t *>(L.ctl + 8);
+    uint32_t * parents = L.ctl + 16;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fan = a.width << a.lgR;
+    if constexpr (BITS == 8)
+        for (uint32_t i = tid; i < a.lc4; i += BLOCK)
+        {
+            L.vm[i] = a.vmin[i];
+            L.st[i] = a.step[i];
+        }
+    for (uint32_t q = blockIdx.x; q < a.nq; q += gridDim.x)
+    {
+        __syncthreads(); // the previous query's last reader is done
+        const uint32_t q4 = BITS == 8 ? a.lc4 : a.ld4;
+        for (uint32_t i = tid; i < q4; i += BLOCK)
+            L.qs[i] = i < a.ld4 ? a.Q[(size_t)q * a.ld4 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        uint4 * clear = reinterpret_cast<uint4 *>(L.table);
+        for (uint32_t i = tid; i < a.tab / 4; i += BLOCK)
+            clear[i] = make_uint4(GRAPH_EMPTY, GRAPH_EMPTY, GRAPH_EMPTY, GRAPH_EMPTY);
+        if (tid < GRAPH_WIDE_CTL)
+            L.ctl[tid] = 0;
+        __threadfence(); // the clear is in memory before the first atomic asks
+        __syncthreads();
+        // the seeds of the probed lists
+        uint32_t lab = GRAPH_EMPTY;
+        if (tid < a.P)
+        {
+            const int32_t l = a.probes[(size_t)q * a.P + tid];
+            const int32_t s = l >= 0 ? a.seed[l] : -1;
+            if (s >= 0 && (uint32_t)s < a.n)
+                lab = (uint32_t)s;
+        }
+        graph_wide_round<METRIC, BITS, E>(a, L, flag, lab, tid);
+        for (uint32_t it = 0; it < a.max_iters; it++)
+        {
+            const uint32_t cnt = L.ctl[2];
+            if (L.ctl[1] + fan > MSVS_GRAPH_WIDE_VISITED_MAX)
+                break;
+            // the first `width` clear flags from the cursor on
+            uint32_t found = 0;
+            for (uint32_t base = L.ctl[4]; found < a.width && base < cnt; base += BLOCK)
+            {
+                const uint32_t i = base + tid;
+                const bool open = i < cnt && flag[i] == 0;
+                const uint64_t b = __ballot(open);
+                if (lane == 0)
+                    ballots[wave] = b;
+                __syncthreads();
+                uint32_t before = 0, total = 0;
+                for (uint32_t w = 0; w < 4; w++)
+                {
+                    const uint32_t c = (uint32_t)__popcll(ballots[w]);
+                    before += w < wave ? c : 0;
+                    total += c;
+                }
+                const uint32_t at = found + before + (uint32_t)__popcll(b & ((1ull << lane) - 1));
+                if (open && at < a.width)
+                {
+                    parents[at] = i;
+                    flag[i] = 1;
+                    atomicMax(&L.ctl[4], i + 1); // everything up to a parent is expanded now
+                }
+                found += total;
+                __syncthreads(); // (the next window's ballots must not overtake a reader)
+            }
+            if (found == 0)
+                break;
+            found = min(found, a.width);
+            lab = GRAPH_EMPTY;
+            const uint32_t p = tid >> a.lgR;
+            if (tid < fan && p < found)
+            {
+                const uint32_t parent = (uint32_t)L.beam[parents[p]];
+                const uint32_t e = a.nbr[(size_t)parent * a.R + (tid & (a.R - 1))];
+                lab = e < a.n ? e : GRAPH_EMPTY;
+            }
+            graph_wide_round<METRIC, BITS, E>(a, L, flag, lab, tid);
+        }
+        // the first k alive entries of the beam
+        const uint32_t cnt = L.ctl[2];
+        uint32_t alive = 0;
+        for (uint32_t base = 0; base < cnt && alive < a.k; base += BLOCK)
+        {
+            const uint32_t i = base + tid;
+            const uint64_t key = i < cnt ? L.beam[i] : KEY_NONE;
+            bool ok = key != KEY_NONE;
+            if (ok && a.alive)
+            {
+                const uint32_t id = (uint32_t)key;
+                ok = id < a.nbits && ((a.alive[id >> 6] >> (id & 63)) & 1);
+            }
+            const uint64_t bo = __ballot(ok);
+            if (lane == 0)
+                ballots[wave] = bo;
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+            for (uint32_t w = 0; w < 4; w++)
+            {
+                const uint32_t c = (uint32_t)__popcll(ballots[w]);
+                before += w < wave ? c : 0;
+                total += c;
+            }
+            const uint32_t rank = alive + before + (uint32_t)__popcll(bo & ((1ull << lane) - 1));
+            if (ok && rank < a.k)
+            {
+                const size_t o = (size_t)q * a.k + rank;
+                a.out_ids[o] = (int64_t)(uint32_t)key;
+                const float v = key_value<METRIC>(key);
+                a.out_dis[o] = a.cosine ? __fsub_rn(1.0f, v) : v;
+            }
+            alive += total;
+            __syncthreads();
+        }
+        for (size_t i = (size_t)alive + tid; i < a.k; i += BLOCK)
+        {
+            const size_t o = (size_t)q * a.k + i;
+            a.out_ids[o] = -1;
+            const float v = key_value<METRIC>(KEY_NONE);
+            a.out_dis[o] = a.cosine ? __fsub_rn(1.0f, v) : v;
+        }
     }
 }
 

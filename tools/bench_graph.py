@@ -7,7 +7,9 @@ store, a built index of degree --degree, searched through the device entry on on
     time of --reps calls between HIP events after a warm-up call (and their spread, min .. max), queries/s;
   - --bits 32,8: the index is built once at 32 bits, exported, and the same structure is handed (set_graph) to a bit_size=8 index
     over the same store, so both forms search one graph; their repetitions alternate inside one process, shape by shape;
-  - beside them the IVFFLAT index of the same rows (nlist --nlist) at --nprobes, the same way, to read the nprobe of equal recall off.
+  - beside them the IVFFLAT index of the same rows (nlist --nlist) at --nprobes, the same way, to read the nprobe of equal recall off;
+  - --wide: the wide search (search_wide_device) against search_device at ef 64 and 256, its own range (--wide-efs) and filtered
+    searches with --alive of the rows alive (wide_section).
 
 Writes one JSON file (default profiles/graph.json) and prints it.
 
@@ -28,9 +30,69 @@ import bench  # noqa: E402
 import myscaledb_amd.capi as capi  # noqa: E402
 
 
+def wide_section(a, gx, x, q, batches, timed_all, stream):
+    """--wide: search_wide_device beside search_device on the 32-bit index (repetitions alternating), the range only it reaches
+    (--wide-efs at the batches >= 64: recall@10, and recall@1000 with k = 1000), and filtered searches (--alive fractions, k = 10)."""
+    import torch
+    dev, nt = x.device, min(256, len(q))
+
+    def exact(k, alive=None):
+        best = torch.full((nt, k), float("inf"), device=dev)
+        best_i = torch.full((nt, k), -1, device=dev, dtype=torch.int64)
+        for r0 in range(0, a.rows, 1 << 16):
+            d2 = (torch.cdist(q[:nt].double(), x[r0:r0 + (1 << 16)].double()) ** 2).float()
+            if alive is not None:
+                d2[:, ~alive[r0:r0 + (1 << 16)]] = float("inf")
+            cat_i = torch.cat([best_i, torch.arange(r0, r0 + d2.shape[1], device=dev).expand(nt, -1)], 1)
+            best, sel = torch.topk(torch.cat([best, d2], 1), k, dim=1, largest=False)
+            best_i = torch.gather(cat_i, 1, sel)
+        return [set(r[np.isfinite(d)].tolist()) for r, d in zip(best_i.cpu().numpy(), best.cpu().numpy())]
+
+    def recall(truth, ids):
+        return float(np.mean([len(t & set(g.tolist())) / max(len(t), 1) for t, g in zip(truth, ids[:nt])]))
+
+    def run(fn, b, k, ef, **kw):
+        di = torch.empty((b, k), device=dev, dtype=torch.int64)
+        dd = torch.empty((b, k), device=dev, dtype=torch.float32)
+        return di, lambda: fn(q.data_ptr(), b, k, di.data_ptr(), dd.data_ptr(), ef=ef, stream=stream, **kw)
+
+    def row(name, b, k, ef, ms, **more):
+        med = float(np.median(ms))
+        return dict({"entry": name, "nq": b, "k": k, "ef": ef, "ms": med, "ms_min": min(ms), "ms_max": max(ms), "qps": b / med * 1e3}, **more)
+
+    res, truth = {"cost": [], "range": [], "filtered": []}, {10: exact(10), 1000: exact(1000)}
+    for b in batches:
+        for ef in (64, 256):
+            (dn, narrow), (dw, wide) = run(gx.search_device, b, 10, ef), run(gx.search_wide_device, b, 10, ef)
+            ms = timed_all([narrow, wide])
+            same = bool((dn == dw).all())
+            res["cost"] += [row("search", b, 10, ef, ms[0]), row("search_wide", b, 10, ef, ms[1], equal_ids=same)]
+    for b in (b for b in batches if b >= 64):
+        for ef in (int(v) for v in a.wide_efs.split(",")):
+            for k in (10, 1000):
+                if k <= ef:
+                    di, call = run(gx.search_wide_device, b, k, ef)
+                    ms = timed_all([call])[0]
+                    res["range"].append(row("search_wide", b, k, ef, ms, recall=recall(truth[k], di.cpu().numpy()) if b >= nt else None))
+    b = max(batches)
+    for frac in (float(v) for v in a.alive.split(",")):
+        alive = torch.rand(a.rows, device=dev, generator=torch.Generator(dev).manual_seed(7)) < frac
+        bits = torch.from_numpy(capi.pack_bits(alive.cpu().numpy()).view(np.int64)).to(dev)
+        t = exact(10, alive)
+        for name, fn, ef in [("search", gx.search_device, 256)] + [("search_wide", gx.search_wide_device, int(v)) for v in a.wide_efs.split(",")]:
+            di, call = run(fn, b, 10, ef, d_alive=bits.data_ptr(), nbits=a.rows)
+            ms = timed_all([call])[0]
+            ids = di.cpu().numpy()
+            res["filtered"].append(row(name, b, 10, ef, ms, alive=frac, filled=float((ids >= 0).mean()), recall=recall(t, ids) if b >= nt else None))
+    return res
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
+    ap.add_argument("--wide", action="store_true", help="also measure search_wide_device (the 32-bit index): see wide_section")
+    ap.add_argument("--wide-efs", default="512,1024,4096")
+    ap.add_argument("--alive", default="0.05,0.01", help="--wide: the alive fractions of its filtered searches")
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--data", default="mid", choices=("mid", "iid", "blobs03"))
@@ -120,6 +182,8 @@ def main():
                 med = float(np.median(ms))
                 out["graph"].append({"bits": f, "nq": b, "ef": ef, "ms": med, "ms_min": min(ms), "ms_max": max(ms), "qps": b / med * 1e3,
                                      "recall@10": recall(outs[f][0].cpu().numpy()) if b >= nt else None})
+    if a.wide:
+        out["wide"] = wide_section(a, gx, x, q, batches, timed_all, stream)
     for ix in forms.values():
         ix.close()
     if 32 not in forms:
