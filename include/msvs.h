@@ -583,6 +583,45 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
  *     load_io takes a version-2 file with rows == NULL; a non-NULL store is checked for n alone.  Bounds that are not finite,
  *     vmax < vmin, an infinite span or a wrong size are MSVS_ERR_IO like any corruption.  A version-1 file keeps its rules.
  *
+ * Product-quantised rows: create's parameter pq_m=M (default 0: off, and everything above holds unchanged).  With M >= 1 bit_size is
+ * the width of a code, 8 (the default then) or 4: the index keeps M sub-codebooks of ksub = 1 << bit_size entries of dsub = dim / M
+ * floats and n rows of M codes, and the search scores a label by M table look-ups.  M must divide dim, 1 <= M <= 128 at 8 bits and
+ * 1 <= M <= 256 at 4 bits, and the smallest narrow search's LDS image (below) must fit 160 KiB; that, or any other bit_size (32
+ * included), is MSVS_ERR_INVALID_ARGUMENT.  All arithmetic is f32 with separately rounded operations and no fma.
+ *   Stored row: the row as fed (the normalised row for cosine).  There is no centroid residual: a graph row belongs to no list.
+ *   Decoded row: x^[s * dsub + t] = cb[s][code[s]][t].
+ *   Encode (every metric): code[s] = the j with the smallest L2 sub-score of the row's sub-vector against cb[s][j], the sequential
+ *     sum from +0, t ascending, of fl(fl(x_t - cb_t)^2); ties to the lowest j; a NaN score never wins, all NaN is code 0 (the
+ *     msvs_pq_index rule).
+ *   Codebooks: msvs_graph_index_set_pq_codebooks hands them in ([s][j][t], M * ksub * dsub floats, host or device: mem) BEFORE
+ *     build / set_graph, which then only encode; a non-finite entry is MSVS_ERR_INVALID_ARGUMENT and leaves the index without
+ *     codebooks; on an index without pq_m, or on one that is ready, MSVS_ERR_INVALID_ARGUMENT.  Otherwise build / set_graph train
+ *     them: the msvs_pq_index codebook step over the stored rows themselves -- at most 262144 rows, row floor(i * n / cap); per
+ *     sub-space the IVFFLAT k-means (L2, ksub centroids, create's kmeans_iters and seed).  n < ksub, or a non-finite entry coming
+ *     out, is MSVS_ERR_INVALID_ARGUMENT and the index is left not ready.  The same input gives the same bits.
+ *   Query table, per query q (normalised first for cosine): T[s][j] = the sequential sum from +0, t ascending, of
+ *     fl(fl(q_t - cb[s][j][t])^2) (L2) or fl(q_t * cb[s][j][t]) (IP, cosine), q_t = q[s * dsub + t].
+ *   Row score: c = ceil(M / 16); p_g = +0 (g = 0 .. 15), then p_g = fl(p_g + T[s][code[s]]) for s = g c .. min(M, (g + 1) c) - 1
+ *     ascending (an empty run leaves +0); the score is the adjacent-pairwise tree ((p0 + p1) + (p2 + p3)) + ... of p_0 .. p_15.
+ *   Search: steps 1 - 6 above word for word with "scored against its stored row with the canonical scan arithmetic" read as "scored
+ *     as above"; seeds, V, keys, strict admission, NaN, the set-operation beam update, the stopping rules, the filter, cosine's
+ *     fl(1 - score), the limits, the no-ops and the errors are unchanged, for search, search_device, search_wide and
+ *     search_wide_device alike.  LDS image: 4 * ksub * M bytes of tables + 6 KiB of beam + 64 bytes + the visited table (4 bytes x 2 x
+ *     max(32, min(MSVS_GRAPH_VISITED_MAX, min(nprobe, nlist) + max_iters * width * R))); the wide search: 4 * ksub * M + ef x 9 bytes
+ *     (ef rounded up to 16 for the flags) + 3 KiB + 128 bytes.  The query has no image.  Beyond 160 KiB: MSVS_ERR_INVALID_ARGUMENT
+ *     (M = 96 at 8 bits and the default ef = 64, R = 32: about 136 KiB; M = 128 wants ef <= 40 or so at R = 32).
+ *   The row store is read by build and set_graph only, exactly as for bit_size=8.
+ *   pq_m: M, or 0 for an index without the form and for NULL.  bit_size: 8 or 4.  export_pq: the codebooks [s][j][t] and n x M codes,
+ *     one code a byte in natural order for both widths; either output may be NULL; MSVS_ERR_INVALID_ARGUMENT on an index without
+ *     the form, MSVS_ERR_NOT_READY before build / set_graph.  export_codes stays MSVS_ERR_INVALID_ARGUMENT: there is no vmin / vmax.
+ *   memory_usage grows by n x the stored row's bytes plus the device codebooks (4 * ksub * dim).  A stored row is 16 lane slots of
+ *     4 bytes when ceil(M / 16) * bit_size <= 32, else of 8 bytes: 64 or 128 bytes.
+ *   File: header version 3, otherwise the same 64 bytes; the body is the centroids, the seeds, nbr, then u64 M, u64 bit_size, the
+ *     codebooks [s][j][t] and the codes: n x M bytes at 8 bits, n x ceil(M / 2) bytes at 4 bits (the even s in the low nibble, the
+ *     pad nibble of an odd M 0), all under the body's checksum.  load_io takes it with rows == NULL; a non-NULL store is checked
+ *     for n alone.  A wrong M or bit_size, a non-finite codebook entry, a non-zero pad nibble or a wrong size is MSVS_ERR_IO.
+ *     (A code is a byte or a nibble, so none can reach ksub.)  Versions 1 and 2 are written and read exactly as before.
+ *
  * Wide search: search_wide / search_wide_device, the argument lists of search / search_device.  The definition is search steps
  * 1 - 6 above word for word (bit_size=8: against the decoded row), with three numbers changed:
  *   ef 1 .. MSVS_MAX_K_ROUNDS, default max(k, 64) capped at MSVS_MAX_K_ROUNDS (MSVS_ERR_INVALID_ARGUMENT beyond);
@@ -615,6 +654,9 @@ MSVS_API size_t msvs_graph_index_memory_usage(const msvs_graph_index_t * index);
 MSVS_API int msvs_graph_index_export(const msvs_graph_index_t * index, float * centroids, int32_t * seeds, uint32_t * nbr);
 MSVS_API size_t msvs_graph_index_bit_size(const msvs_graph_index_t * index);
 MSVS_API int msvs_graph_index_export_codes(const msvs_graph_index_t * index, float * vmin, float * vmax, uint8_t * codes);
+MSVS_API size_t msvs_graph_index_pq_m(const msvs_graph_index_t * index);
+MSVS_API int msvs_graph_index_set_pq_codebooks(msvs_graph_index_t * index, const float * codebooks, int mem);
+MSVS_API int msvs_graph_index_export_pq(const msvs_graph_index_t * index, float * codebooks, uint8_t * codes);
 MSVS_API int msvs_graph_index_search(const msvs_graph_index_t * index, const float * queries, size_t nq, size_t k, const char * params,
                                      const uint64_t * alive_bits, size_t nbits, int64_t * ids, float * dis);
 MSVS_API int msvs_graph_index_search_device(const msvs_graph_index_t * index, const float * d_queries, size_t nq, size_t k, size_t ef,

@@ -68,6 +68,7 @@ SYMBOLS = [
     "msvs_graph_index_export", "msvs_graph_index_search", "msvs_graph_index_search_device", "msvs_graph_index_serialize_io",
     "msvs_graph_index_load_io", "msvs_graph_index_bit_size", "msvs_graph_index_export_codes",
     "msvs_graph_index_search_wide", "msvs_graph_index_search_wide_device",
+    "msvs_graph_index_pq_m", "msvs_graph_index_set_pq_codebooks", "msvs_graph_index_export_pq",
 ]
 
 
@@ -662,7 +663,11 @@ class GraphIndex(_CodedIndex):
     "degree=16|32|64", "bit_size=32|8" and the IVFFLAT trainer's keys ("ncentroids=N,kmeans_iters=I,...").
     bit_size=8: build / set_graph also make one 8-bit quantiser and a code row per label from the store; the search scores the decoded
     rows, so its results are those of a 32-bit index over a store holding them, and after the last build / set_graph nothing reads
-    `rows` any more: it may be closed, and load_io needs none."""
+    `rows` any more: it may be closed, and load_io needs none.
+    pq_m=M: product-quantised rows instead -- M sub-codebooks of 1 << bit_size entries (bit_size=8, the default then, or 4), trained
+    by build / set_graph over the stored rows or handed in before with set_pq_codebooks, and M codes a label; the search scores a
+    label by M look-ups into a per-query table.  The store is free afterwards as for bit_size=8; search(k = 100) + capi.refine over a
+    store is the two-stage search."""
     _c = "msvs_graph_index"
 
     def __init__(self, metric, rows, params="", _handle=None, _dim=None):
@@ -727,6 +732,25 @@ class GraphIndex(_CodedIndex):
         codes = np.empty((self.num_data, self.dim), np.uint8)
         _check(lib().msvs_graph_index_export_codes(self._h, _p(vmin, C.c_float), _p(vmax, C.c_float), _p(codes, C.c_uint8)))
         return vmin, vmax, codes
+
+    @property
+    def pq_m(self):
+        """the sub-quantisers of a product-quantised index (bit_size is then the width of a code), else 0"""
+        return self._size("pq_m")
+
+    def set_pq_codebooks(self, codebooks):
+        """codebooks [pq_m, 1 << bit_size, dim / pq_m] f32, before build / set_graph: they then only encode"""
+        cb = _f32(codebooks).ravel()
+        assert not self.pq_m or cb.size == self.dim << self.bit_size
+        _check(lib().msvs_graph_index_set_pq_codebooks(self._h, _p(cb, C.c_float), MEM_HOST))
+
+    def export_pq(self):
+        """pq_m=M -> (codebooks [M, ksub, dsub], codes [n, M] u8, one code a byte in natural order)"""
+        m = self.pq_m
+        cb = np.empty((m, 1 << self.bit_size, self.dim // max(m, 1)), np.float32)
+        codes = np.empty((self.num_data, m), np.uint8)
+        _check(lib().msvs_graph_index_export_pq(self._h, _p(cb, C.c_float), _p(codes, C.c_uint8)))
+        return cb, codes
 
     @classmethod
     def load_io(cls, store, rows=None):

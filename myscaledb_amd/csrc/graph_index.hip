@@ -3,6 +3,8 @@
 // is a function of the inputs alone.  The kernels and their layout: graph_kernels.hpp.  DESIGN.md 4.14.
 // bit_size=8: the index keeps one 8-bit quantiser and a code row per label, made from the store by build / set_graph; the search
 // scores decoded rows and nothing but build / set_graph reads the store.
+// pq_m=M: the index keeps M sub-codebooks (trained over the store by the IVFPQ index's codebook step, or handed in) and M codes a
+// label in GraphPqLayout's order; the search scores a label by M look-ups into a per-query table; file version 3.
 // search_wide: the same definition with ef, k <= MSVS_MAX_K_ROUNDS, served by graph_wide_search_kernel on a fixed grid.
 // Reused as they are: the row store (refine.hip), the canonical scoring of refine_kernels.hpp's chain, the k-means trainer and the
 // canonical coarse top-P (coded_ivf.hpp: kmeans, flat_search_device), the exact FLAT search for the build's neighbour lists -- or,
@@ -38,7 +40,16 @@ struct msvs_graph_index
     std::vector<float> h_vmin, h_vmax; // dim
     DevBuf<float> d_vmin, d_step;      // ldc, zero padded
     DevBuf<uint8_t> codes;             // n x ldc
+    // pq_m=M (bits is then the width of a code, 8 or 4; no quantiser, ldc unused): codes holds n rows of GraphPqLayout
+    size_t pq_m = 0;
+    bool cb_handed = false;  // h_cb came through set_pq_codebooks: build / set_graph encode only
+    std::vector<float> h_cb; // [m][ksub][dsub]
+    DevBuf<float> cbT;       // the same in pq_cb_index's order
     bool ready = false;
+    bool sq() const { return bits == 8 && !pq_m; }
+    bool coded() const { return bits == 8 || pq_m; } // the search reads the index's own rows, never the store
+    size_t ksub() const { return (size_t)1 << bits; }
+    GraphPqLayout pq_layout() const { return GraphPqLayout((uint32_t)pq_m, bits); }
 };
 
 namespace
@@ -48,6 +59,7 @@ constexpr size_t GRAPH_LDS_MAX = 160 * 1024;
 constexpr size_t GRAPH_QUERY_CHUNK = 16384; // queries of one coarse step + launch
 constexpr size_t GRAPH_LIST_CHUNK = 4096;   // rows whose exact lists one FLAT search of the build returns
 constexpr size_t GRAPH_CODE_CHUNK = (size_t)1 << 27; // codes one launch of the encoder writes
+constexpr size_t GRAPH_PQ_TRAIN_ROWS = 262144;       // stored rows the sub-codebooks are trained on at most (the IVFPQ index's number)
 
 uint32_t log2_of(uint32_t v)
 {
@@ -165,8 +177,10 @@ void graph_search_chunks(const msvs_graph_index & ix, const float * d_queries, s
     const size_t iters = std::min<size_t>(s.max_iters, cap), reach = std::min<size_t>(cap, P + iters * fan);
     // (the wide kernel clears its table with 16-byte stores: a multiple of four words)
     const uint32_t tab = (uint32_t)round_up(2 * std::max<size_t>(reach, 32), (size_t)(wide ? 4 : 1)), ld4 = ix.ld / 4, lc4 = ix.ldc / 4;
-    const bool coded = ix.bits == 8;
-    const size_t lds = wide ? graph_wide_lds_bytes(coded ? 3 * lc4 : ld4, (uint32_t)s.ef) : coded ? graph_sq_lds_bytes(lc4, tab) : graph_lds_bytes(ld4, tab);
+    const bool coded = ix.coded();
+    // the float4 before the beam: the query, or query | vmin | step, or the product-quantised tables
+    const uint32_t head4 = ix.pq_m ? (uint32_t)(ix.pq_m * ix.ksub() / 4) : ix.sq() ? 3 * lc4 : ld4;
+    const size_t lds = wide ? graph_wide_lds_bytes(head4, (uint32_t)s.ef) : graph_lds_bytes(head4, tab);
     if (lds > GRAPH_LDS_MAX)
         fail(MSVS_ERR_INVALID_ARGUMENT, "the graph search's LDS image (%zu bytes) exceeds %zu", lds, GRAPH_LDS_MAX);
     if (nq == 0 || k == 0)
@@ -211,7 +225,16 @@ void graph_search_chunks(const msvs_graph_index & ix, const float * d_queries, s
         a.vmin = reinterpret_cast<const float4 *>(ix.d_vmin.p);
         a.step = reinterpret_cast<const float4 *>(ix.d_step.p);
         a.lc4 = lc4;
-        a.Q = reinterpret_cast<const float4 *>(dq);
+        if (ix.pq_m)
+        {
+            const GraphPqLayout lay = ix.pq_layout();
+            a.pq_cb = ix.cbT.p;
+            a.pq_m = lay.m;
+            a.pq_dsub = (uint32_t)(ix.dim / ix.pq_m);
+            a.pq_c = lay.c;
+            a.pq_w = lay.w;
+        }
+        a.Q =reinterpret_cast<const float4 *>(dq);
         a.nbr = ix.nbr.p;
         a.seed = ix.seeds.p;
         a.probes = probes;
@@ -232,7 +255,7 @@ void graph_search_chunks(const msvs_graph_index & ix, const float * d_queries, s
         a.cosine = ix.metric == MSVS_METRIC_COSINE;
         ProfileScope prof(wide ? "graph_wide_search" : "graph_search", stream);
         with_int<M_IP, M_L2>(m, [&](auto mm) {
-            with_int<8, 32>((int)ix.bits, [&](auto bb) {
+            with_int<8, 32, GRAPH_PQ8, GRAPH_PQ4>(ix.pq_m ? (ix.bits == 8 ? GRAPH_PQ8 : GRAPH_PQ4) : (int)ix.bits, [&](auto bb) {
                 constexpr int METRIC = decltype(mm)::value, BITS = decltype(bb)::value;
                 if (!wide)
                     launch_graph_search<METRIC, BITS>(a, nqc, lds, stream);
@@ -375,8 +398,161 @@ std::vector<uint8_t> host_codes(const msvs_graph_index & ix, hipStream_t stream)
 
 void check_graph_coded(const msvs_graph_index & ix)
 {
-    if (ix.bits != 8)
-        fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index keeps f32 rows of its row store (bit_size=32): it has no codes");
+    if (!ix.sq())
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index keeps %s: it has no quantiser bounds and scalar codes",
+             ix.pq_m ? "product-quantised codes (pq_m)" : "f32 rows of its row store (bit_size=32)");
+}
+
+void check_graph_pq(const msvs_graph_index & ix)
+{
+    if (!ix.pq_m)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index was created without pq_m: it has no product-quantised form");
+}
+
+// ------------------------------------------------------------------------------------------- product-quantised rows (pq_m)
+
+/// codebooks [m][ksub][dsub] on the host, all finite -> the index's host and device copies (pq_cb_index's order); synchronises
+void set_graph_codebooks(msvs_graph_index & ix, const float * cb, hipStream_t stream)
+{
+    const size_t m = ix.pq_m, ksub = ix.ksub(), dsub = ix.dim / m;
+    ix.h_cb.assign(cb, cb + ksub * ix.dim);
+    std::vector<float> t(ksub * ix.dim);
+    with_int<8, 4>((int)ix.bits, [&](auto b) {
+        for (uint32_t s = 0; s < m; s++)
+            for (uint32_t j = 0; j < ksub; j++)
+                for (uint32_t u = 0; u < dsub; u++)
+                    t[pq_cb_index<decltype(b)::value>(s, u, j, (uint32_t)m, (uint32_t)dsub)] = cb[((size_t)s * ksub + j) * dsub + u];
+    });
+    ix.cbT.alloc(t.size());
+    MSVS_HIP(hipMemcpyAsync(ix.cbT.p, t.data(), t.size() * 4, hipMemcpyHostToDevice, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+}
+
+/// the index of the first non-finite float of cb[0 .. count), or count
+size_t first_non_finite(const float * cb, size_t count)
+{
+    for (size_t i = 0; i < count; i++)
+        if (!std::isfinite(cb[i]))
+            return i;
+    return count;
+}
+
+/// The IVFPQ index's codebook step over the stored rows themselves (include/msvs.h): the evenly spaced rows floor(i n / cap),
+/// then per sub-space the IVFFLAT k-means with create's kmeans_iters and seed.  The sample keeps the store's leading dimension
+/// (pq_pick_rows_kernel copies whole padded rows), so a sub-space is a strided view of it.
+void train_graph_codebooks(msvs_graph_index & ix, const RowsView & rv, hipStream_t stream)
+{
+    const size_t n = ix.n, m = ix.pq_m, ksub = ix.ksub(), dsub = ix.dim / m, ld = rv.ld;
+    if (n < ksub)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "pq_m with bit_size=%u needs at least %zu stored rows to train on (%zu)", ix.bits, ksub, n);
+    const size_t cap = std::min(n, GRAPH_PQ_TRAIN_ROWS);
+    DevBuf<float> sample(cap * ld), sub(cap * dsub);
+    hipLaunchKernelGGL(pq_pick_rows_kernel, dim3((unsigned)ceil_div(cap * ld, (size_t)256)), dim3(256), 0, stream, rv.table, n, cap, (size_t)0, cap,
+                       (uint32_t)ld, sample.p);
+    MSVS_HIP(hipGetLastError());
+    std::string sub_params;
+    for (const auto & kv : parse_params(ix.params.c_str()))
+        if (kv.first == "kmeans_iters" || kv.first == "seed")
+            sub_params += kv.first + "=" + kv.second + ",";
+    sub_params += "ncentroids=" + std::to_string(ksub);
+    std::vector<float> cb(ksub * ix.dim);
+    for (size_t s = 0; s < m; s++)
+    {
+        MSVS_HIP(hipMemcpy2DAsync(sub.p, dsub * 4, sample.p + s * dsub, ld * 4, dsub * 4, cap, hipMemcpyDeviceToDevice, stream));
+        MSVS_HIP(hipStreamSynchronize(stream));
+        const TmpIndex tmp = kmeans(MSVS_METRIC_L2, dsub, sub_params, sub.p, cap, MSVS_MEM_DEVICE);
+        if (tmp->nlist != ksub)
+            fail(MSVS_ERR_DEVICE, "internal: sub-quantiser %zu came out with %zu centroids", s, tmp->nlist);
+        MSVS_HIP(hipMemcpy2D(cb.data() + s * ksub * dsub, dsub * 4, tmp->centroids.p, (size_t)tmp->ld * 4, dsub * 4, ksub, hipMemcpyDeviceToHost));
+    }
+    const size_t bad = first_non_finite(cb.data(), cb.size());
+    if (bad < cb.size())
+        fail(MSVS_ERR_INVALID_ARGUMENT, "codebook entry %zu of sub-quantiser %zu came out not finite: a stored row is NaN, infinite or overflows",
+             (bad / dsub) % ksub, bad / (ksub * dsub));
+    set_graph_codebooks(ix, cb.data(), stream);
+}
+
+/// pq_m, after build / set_graph (ix.n is set): the codebooks unless they were handed in, then the codes.  As encode_store, the
+/// rows are read where they are by the IVFPQ index's encoders against ONE all-zero centroid -- fl(0 + cb) = cb in value, so the
+/// sub-score is the row's against the entry itself -- a chunk at a time, and graph_pq_repack_kernel puts each chunk into the
+/// search's stored order.
+void encode_pq_store(msvs_graph_index & ix, hipStream_t stream)
+{
+    const RowsView rv = rows_view(ix.rows);
+    const size_t n = ix.n, m = ix.pq_m, dsub = ix.dim / m;
+    if (rv.n < n)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the row store holds %zu rows, the graph was made over %zu", rv.n, n);
+    if (!ix.cb_handed)
+        train_graph_codebooks(ix, rv, stream);
+    const GraphPqLayout lay = ix.pq_layout();
+    const uint32_t mp = (uint32_t)ceil_div(m * ix.bits, (size_t)8);
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::max<size_t>(n, 1), GRAPH_CODE_CHUNK / mp));
+    DevBuf<float> zero(rv.ld);
+    DevBuf<int32_t> list(chunk);
+    DevBuf<uint8_t> natural(chunk * mp);
+    MSVS_HIP(hipMemsetAsync(zero.p, 0, (size_t)rv.ld * 4, stream));
+    MSVS_HIP(hipMemsetAsync(list.p, 0, chunk * 4, stream));
+    ix.codes.alloc(std::max<size_t>(n * lay.row_bytes(), 1));
+    static std::once_flag once; // the 8-bit encoder stages a row and its centroid: 64 KiB at dim = 8192, beside its static bytes
+    std::call_once(once, [] {
+        MSVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_encode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8192 * 4));
+    });
+    for (size_t r0 = 0; r0 < n; r0 += chunk)
+    {
+        const size_t cnt = std::min(chunk, n - r0);
+        const float * x = rv.table + r0 * rv.ld;
+        if (ix.bits == 4)
+            hipLaunchKernelGGL(pq4_encode_kernel, dim3((unsigned)ceil_div(cnt, (size_t)16)), dim3(BLOCK), 0, stream, x, list.p, zero.p, ix.cbT.p, cnt,
+                               rv.ld, (uint32_t)m, (uint32_t)dsub, mp, natural.p);
+        else
+            hipLaunchKernelGGL(pq_encode_kernel, dim3((unsigned)ceil_div(cnt, (size_t)8)), dim3(BLOCK), 2 * ix.dim * 4, stream, x, list.p, zero.p,
+                               ix.cbT.p, cnt, (uint32_t)ix.dim, rv.ld, (uint32_t)m, (uint32_t)dsub, mp, 8u, natural.p);
+        hipLaunchKernelGGL(graph_pq_repack_kernel, dim3((unsigned)ceil_div(cnt * lay.row_bytes(), (size_t)256)), dim3(256), 0, stream, natural.p, cnt,
+                           lay.m, lay.bits, mp, ix.codes.p + r0 * lay.row_bytes());
+        MSVS_HIP(hipGetLastError());
+    }
+    MSVS_HIP(hipStreamSynchronize(stream));
+    MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
+}
+
+/// stored rows (GraphPqLayout) <-> n x m codes, a code a byte in natural order
+void pq_unpack_rows(const GraphPqLayout & lay, const uint8_t * stored, size_t n, uint8_t * out)
+{
+    for (size_t r = 0; r < n; r++)
+        for (uint32_t s = 0; s < lay.m; s++)
+            out[r * lay.m + s] = (uint8_t)((stored[r * lay.row_bytes() + lay.pos(s)] >> lay.shift(s)) & ((1u << lay.bits) - 1));
+}
+
+void pq_pack_rows(const GraphPqLayout & lay, const uint8_t * codes, size_t n, uint8_t * stored)
+{
+    for (size_t r = 0; r < n; r++)
+        for (uint32_t s = 0; s < lay.m; s++)
+            stored[r * lay.row_bytes() + lay.pos(s)] |= (uint8_t)(codes[r * lay.m + s] << lay.shift(s));
+}
+
+/// the product-quantised codes of the index, n x m in natural order
+std::vector<uint8_t> host_pq_codes(const msvs_graph_index & ix, hipStream_t stream)
+{
+    const GraphPqLayout lay = ix.pq_layout();
+    std::vector<uint8_t> stored(ix.n * lay.row_bytes()), out(ix.n * ix.pq_m);
+    if (!stored.empty())
+        MSVS_HIP(hipMemcpyAsync(stored.data(), ix.codes.p, stored.size(), hipMemcpyDeviceToHost, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    pq_unpack_rows(lay, stored.data(), ix.n, out.data());
+    return out;
+}
+
+/// the file's rows: a code a byte at 8 bits; at 4 bits ceil(m / 2) bytes, the even s in the low nibble, the pad nibble 0
+std::vector<uint8_t> pq_file_rows(const std::vector<uint8_t> & codes, size_t n, size_t m, uint32_t bits)
+{
+    if (bits == 8)
+        return codes;
+    const size_t rb = ceil_div(m, (size_t)2);
+    std::vector<uint8_t> out(n * rb, 0);
+    for (size_t r = 0; r < n; r++)
+        for (size_t s = 0; s < m; s++)
+            out[r * rb + s / 2] |= (uint8_t)(codes[r * m + s] << ((s & 1) * 4));
+    return out;
 }
 
 /// what a caller's or a file's structure must satisfy -> nullptr, or what is wrong with it
@@ -425,6 +601,15 @@ uint64_t graph_body_check2(const std::vector<float> & c, const std::vector<int32
                            fnv1a(lo.data(), lo.size() * 4), fnv1a(hi.data(), hi.size() * 4), fnv1a(codes.data(), codes.size())};
     return fnv1a(h, sizeof(h));
 }
+
+/// version 3: the centroids, the seeds, the edges, (m, bits), the codebooks and the file's code rows
+uint64_t graph_body_check3(const std::vector<float> & c, const std::vector<int32_t> & s, const std::vector<uint32_t> & e, const uint64_t (&geometry)[2],
+                           const std::vector<float> & cb, const std::vector<uint8_t> & codes)
+{
+    const uint64_t h[6] = {fnv1a(c.data(), c.size() * 4), fnv1a(s.data(), s.size() * 4), fnv1a(e.data(), e.size() * 4),
+                           fnv1a(geometry, sizeof(geometry)), fnv1a(cb.data(), cb.size() * 4), fnv1a(codes.data(), codes.size())};
+    return fnv1a(h, sizeof(h));
+}
 }
 
 extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, const char * params, msvs_graph_index_t ** out)
@@ -442,9 +627,23 @@ extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, con
         const long degree = param_int(p, "degree", 32);
         if (degree != 16 && degree != 32 && degree != 64)
             fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index has degree 16, 32 or 64 (degree %ld)", degree);
-        const long bits = param_int(p, "bit_size", 32);
-        if (bits != 32 && bits != 8)
+        const long pq_m = param_int(p, "pq_m", 0);
+        if (pq_m < 0)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "pq_m is 0 (off) or the number of sub-quantisers (pq_m %ld)", pq_m);
+        const long bits = param_int(p, "bit_size", pq_m ? 8 : 32);
+        if (!pq_m && bits != 32 && bits != 8)
             fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index scores f32 rows (bit_size=32) or 8-bit codes (bit_size=8) (bit_size %ld)", bits);
+        if (pq_m)
+        {
+            // (the smallest narrow search: ef = nprobe = width = max_iters = 1 reaches 1 + degree labels)
+            const uint32_t tab = 2 * std::max<uint32_t>(1 + (uint32_t)degree, 32);
+            if ((bits != 8 && bits != 4) || pq_m > 1024 / bits || rv.dim % (size_t)pq_m != 0
+                || graph_pq_lds_bytes((uint32_t)pq_m, (uint32_t)bits, tab) > GRAPH_LDS_MAX)
+                fail(MSVS_ERR_INVALID_ARGUMENT,
+                     "a product-quantised graph index needs bit_size 8 or 4, 1 <= pq_m <= 128 (256 at bit_size=4) dividing dim, and tables "
+                     "of pq_m KiB (pq_m / 16 KiB) + 7 KiB within 160 KiB (dim %zu, pq_m %ld, bit_size %ld)",
+                     rv.dim, pq_m, bits);
+        }
         const long join_iters = param_int(p, "join_iters", 0), build_nprobe = param_int(p, "build_nprobe", 8), join_sample = param_int(p, "join_sample", 8);
         if (join_iters < 0 || join_iters > 16)
             fail(MSVS_ERR_INVALID_ARGUMENT, "the graph build runs 0 to 16 join iterations (join_iters %ld)", join_iters);
@@ -469,7 +668,8 @@ extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, con
         ix->dim = rv.dim;
         ix->ld = rv.ld;
         ix->bits = (uint32_t)bits;
-        ix->ldc = (uint32_t)round_up(rv.dim, (size_t)16);
+        ix->pq_m = (size_t)pq_m;
+        ix->ldc =(uint32_t)round_up(rv.dim, (size_t)16);
         ix->R = (uint32_t)degree;
         ix->rows = rows;
         ix->device = rv.device;
@@ -488,8 +688,38 @@ extern "C" size_t msvs_graph_index_memory_usage(const msvs_graph_index_t * ix)
 {
     if (!ix)
         return 0;
-    const size_t coded = ix->bits == 8 && ix->ready ? ix->n * ix->ldc + ix->d_vmin.bytes() + ix->d_step.bytes() : 0;
+    size_t coded = ix->sq() && ix->ready ? ix->n * ix->ldc + ix->d_vmin.bytes() + ix->d_step.bytes() : 0;
+    if (ix->pq_m && ix->ready)
+        coded = ix->n * ix->pq_layout().row_bytes() + ix->cbT.bytes();
     return ix->nbr.bytes() + ix->centroids.bytes() + ix->seeds.bytes() + coded;
+}
+extern "C" size_t msvs_graph_index_pq_m(const msvs_graph_index_t * ix) { return ix ? ix->pq_m : 0; }
+
+extern "C" int msvs_graph_index_set_pq_codebooks(msvs_graph_index_t * ix, const float * codebooks, int mem)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        check_graph_pq(*ix);
+        if (!codebooks)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null codebooks");
+        if (ix->ready)
+            fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index has its codes already: codebooks are handed in before build / set_graph");
+        std::vector<float> cb(ix->ksub() * ix->dim);
+        if (mem == MSVS_MEM_DEVICE)
+            MSVS_HIP(hipMemcpy(cb.data(), codebooks, cb.size() * 4, hipMemcpyDeviceToHost));
+        else
+            memcpy(cb.data(), codebooks, cb.size() * 4);
+        ix->cb_handed = false; // (a refused set leaves the index without codebooks)
+        ix->h_cb.clear();
+        ix->cbT.release();
+        const size_t bad = first_non_finite(cb.data(), cb.size()), dsub = ix->dim / ix->pq_m;
+        if (bad < cb.size())
+            fail(MSVS_ERR_INVALID_ARGUMENT, "codebook entry %zu of sub-quantiser %zu is not finite", (bad / dsub) % ix->ksub(),
+                 bad / (ix->ksub() * dsub));
+        set_graph_codebooks(*ix, cb.data(), thread_stream());
+        ix->cb_handed = true;
+    });
 }
 
 extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float * centroids, size_t nlist, const int32_t * seeds, const uint32_t * nbr,
@@ -521,7 +751,9 @@ extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float *
         ix->ready = false;
         ix->n = n;
         install_graph(*ix, c.data(), nlist, s.data(), e.data(), thread_stream());
-        if (ix->bits == 8)
+        if (ix->pq_m)
+            encode_pq_store(*ix, thread_stream());
+        else if (ix->bits == 8)
             encode_store(*ix, thread_stream());
         ix->ready = true;
     });
@@ -705,7 +937,9 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
         MSVS_HIP(hipStreamSynchronize(stream));
         MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
         ix->n = n;
-        if (ix->bits == 8)
+        if (ix->pq_m)
+            encode_pq_store(*ix, stream);
+        else if (ix->bits == 8)
             encode_store(*ix, stream);
         ix->ready = true;
     });
@@ -826,6 +1060,23 @@ extern "C" int msvs_graph_index_export_codes(const msvs_graph_index_t * ix, floa
     });
 }
 
+extern "C" int msvs_graph_index_export_pq(const msvs_graph_index_t * ix, float * codebooks, uint8_t * codes)
+{
+    return guarded([&] {
+        DeviceGuard on_device(ix ? ix->device : -1);
+        check_graph(ix);
+        check_graph_pq(*ix);
+        check_graph_ready(*ix);
+        if (codebooks)
+            memcpy(codebooks, ix->h_cb.data(), ix->h_cb.size() * 4);
+        if (codes)
+        {
+            const std::vector<uint8_t> c = host_pq_codes(*ix, thread_stream());
+            memcpy(codes, c.data(), c.size());
+        }
+    });
+}
+
 extern "C" int msvs_graph_index_serialize_io(const msvs_graph_index_t * ix, const msvs_io_t * io)
 {
     return guarded([&] {
@@ -839,24 +1090,36 @@ extern "C" int msvs_graph_index_serialize_io(const msvs_graph_index_t * ix, cons
         MSVS_HIP(hipMemcpy(s.data(), ix->seeds.p, s.size() * 4, hipMemcpyDeviceToHost));
         if (!e.empty())
             MSVS_HIP(hipMemcpy(e.data(), ix->nbr.p, e.size() * 4, hipMemcpyDeviceToHost));
-        const bool coded = ix->bits == 8;
-        const std::vector<uint8_t> codes = coded ? host_codes(*ix, stream) : std::vector<uint8_t>();
+        const bool coded = ix->sq(), pq = ix->pq_m != 0;
+        const std::vector<uint8_t> codes = coded ? host_codes(*ix, stream)
+                                           : pq  ? pq_file_rows(host_pq_codes(*ix, stream), ix->n, ix->pq_m, ix->bits)
+                                                 : std::vector<uint8_t>();
+        const uint64_t geometry[2] = {ix->pq_m, ix->bits};
         IoStream f(io, "graph_data", 1);
         GraphHeader h{};
         memcpy(h.magic, "MSVSGR01", 8);
-        h.version = coded ? 2 : 1;
+        h.version = pq ? 3 : coded ? 2 : 1;
         h.metric = ix->metric;
         h.dim = ix->dim;
         h.nlist = ix->nlist;
         h.n = ix->n;
         h.degree = ix->R;
-        h.body = coded ? graph_body_check2(c, s, e, ix->h_vmin, ix->h_vmax, codes) : graph_body_check(c, s, e);
+        h.body = pq      ? graph_body_check3(c, s, e, geometry, ix->h_cb, codes)
+                 : coded ? graph_body_check2(c, s, e, ix->h_vmin, ix->h_vmax, codes)
+                         : graph_body_check(c, s, e);
         h.check = fnv1a(&h, offsetof(GraphHeader, check));
         f.write(&h, sizeof(h));
         f.write(c.data(), c.size() * 4);
         f.write(s.data(), s.size() * 4);
         if (!e.empty())
             f.write(e.data(), e.size() * 4);
+        if (pq)
+        {
+            f.write(geometry, sizeof(geometry));
+            f.write(ix->h_cb.data(), ix->h_cb.size() * 4);
+            if (!codes.empty())
+                f.write(codes.data(), codes.size());
+        }
         if (coded)
         {
             f.write(ix->h_vmin.data(), ix->dim * 4);
@@ -886,12 +1149,12 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
         IoStream f(io, "graph_data", 0);
         GraphHeader h{};
         f.read(&h, sizeof(h));
-        if (memcmp(h.magic, "MSVSGR01", 8) != 0 || (h.version != 1 && h.version != 2) || h.check != fnv1a(&h, offsetof(GraphHeader, check))
+        if (memcmp(h.magic, "MSVSGR01", 8) != 0 || h.version < 1 || h.version > 3 || h.check != fnv1a(&h, offsetof(GraphHeader, check))
             || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || (h.degree != 16 && h.degree != 32 && h.degree != 64))
             fail(MSVS_ERR_IO, "corrupt msvs graph index header");
-        const bool coded = h.version == 2;
+        const bool pq = h.version == 3, coded = h.version >= 2; // (coded: the file carries what the search reads)
         if (!coded && !rows)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store: only a file of a bit_size=8 index carries what its search reads");
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store: only a file of a bit_size=8 or pq_m index carries what its search reads");
         if (coded && h.dim == 0)
             fail(MSVS_ERR_IO, "corrupt msvs graph index header");
         if (coded ? (rows && h.n != rv.n) : (h.n != rv.n || h.dim != rv.dim || (h.metric == MSVS_METRIC_COSINE) != (rv.normalize != 0)))
@@ -900,25 +1163,44 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
         read_grow(f, c, (size_t)(h.nlist * h.dim));
         read_grow(f, s, (size_t)h.nlist);
         read_grow(f, e, (size_t)(h.n * h.degree));
-        if (coded)
+        uint64_t geometry[2] = {0, 0}; // version 3: m, bits
+        std::vector<float> cb;
+        if (pq)
+        {
+            f.read(geometry, sizeof(geometry));
+            const uint64_t m = geometry[0], bits = geometry[1];
+            if ((bits != 8 && bits != 4) || m < 1 || m > 1024 / bits || h.dim % m != 0)
+                fail(MSVS_ERR_IO, "corrupt msvs graph index: %llu sub-quantisers of %llu bits over dim %llu", (unsigned long long)m,
+                     (unsigned long long)bits, (unsigned long long)h.dim);
+            read_grow(f, cb, (size_t)(h.dim << bits));
+            read_grow(f, codes, (size_t)(h.n * ceil_div(m * bits, (uint64_t)8)));
+        }
+        else if (coded)
         {
             read_grow(f, lo, (size_t)h.dim);
             read_grow(f, hi, (size_t)h.dim);
             read_grow(f, codes, (size_t)(h.n * h.dim));
         }
         expect_end(f);
-        if (h.body != (coded ? graph_body_check2(c, s, e, lo, hi, codes) : graph_body_check(c, s, e)))
+        if (h.body != (pq ? graph_body_check3(c, s, e, geometry, cb, codes) : coded ? graph_body_check2(c, s, e, lo, hi, codes) : graph_body_check(c, s, e)))
             fail(MSVS_ERR_IO, "corrupt msvs graph index: the body's checksum does not match");
+        if (pq && first_non_finite(cb.data(), cb.size()) < cb.size())
+            fail(MSVS_ERR_IO, "corrupt msvs graph index: a codebook entry is not finite");
+        if (pq && geometry[1] == 4 && (geometry[0] & 1)) // (a code is a nibble or a byte: none can reach ksub; the pad nibble can be set)
+            for (size_t r = 0, rb = (size_t)(geometry[0] + 1) / 2; r < h.n; r++)
+                if (codes[r * rb + rb - 1] >> 4)
+                    fail(MSVS_ERR_IO, "corrupt msvs graph index: the pad nibble of row %zu is not 0", r);
         if (const char * bad = graph_structure_error(c.data(), (size_t)h.nlist, (size_t)h.dim, s.data(), e.data(), (size_t)h.n, (uint32_t)h.degree))
             fail(MSVS_ERR_IO, "corrupt msvs graph index: %s", bad);
-        if (coded)
+        if (coded && !pq)
             for (size_t j = 0; j < h.dim; j++)
                 if (graph_unusable_dimension(&lo[j], &hi[j], 1) == 0 || hi[j] < lo[j])
                     fail(MSVS_ERR_IO, "corrupt msvs graph index: the quantiser bounds of dimension %zu are not finite, vmax < vmin or their span is infinite", j);
         ix->metric = h.metric;
         ix->dim = (size_t)h.dim;
         ix->ld = padded_dim((size_t)h.dim);
-        ix->bits = coded ? 8 : 32;
+        ix->bits = pq ? (uint32_t)geometry[1] : coded ? 8 : 32;
+        ix->pq_m = (size_t)geometry[0];
         ix->ldc = (uint32_t)round_up((size_t)h.dim, (size_t)16);
         ix->R = (uint32_t)h.degree;
         // (a version-2 file is checked against a store for n alone; build / set_graph need one of the index's own shape)
@@ -927,7 +1209,21 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
         ix->n = (size_t)h.n;
         hipStream_t stream = thread_stream();
         install_graph(*ix, c.data(), (size_t)h.nlist, s.data(), e.data(), stream);
-        if (coded)
+        if (pq)
+        {
+            set_graph_codebooks(*ix, cb.data(), stream);
+            ix->cb_handed = true; // (a later set_graph over a store encodes with the file's codebooks)
+            const GraphPqLayout lay = ix->pq_layout();
+            std::vector<uint8_t> natural(ix->n * ix->pq_m), stored(std::max<size_t>(ix->n * lay.row_bytes(), 1), 0);
+            const size_t rb = codes.size() / std::max<size_t>(ix->n, 1);
+            for (size_t r = 0; r < ix->n; r++)
+                for (size_t s = 0; s < ix->pq_m; s++)
+                    natural[r * ix->pq_m + s] = ix->bits == 8 ? codes[r * rb + s] : (codes[r * rb + s / 2] >> ((s & 1) * 4)) & 15;
+            pq_pack_rows(lay, natural.data(), ix->n, stored.data());
+            ix->codes.alloc(stored.size());
+            MSVS_HIP(hipMemcpy(ix->codes.p, stored.data(), stored.size(), hipMemcpyHostToDevice));
+        }
+        else if (coded)
         {
             set_graph_quantiser(*ix, lo.data(), hi.data(), stream);
             std::vector<uint8_t> stored(std::max<size_t>(ix->n * ix->ldc, 1), 0); // natural order -> the stored order, pad bytes 0

@@ -31,6 +31,19 @@
 //   block, a whole width = 1 round in one go.  Longer rows: one row a group, chunks of GRAPH_SQ_LONG_UNITS units double buffered
 //   (the next chunk, or the next label's first, is on its way while this one is decoded), as sq_ivf_scan_kernel's wnext.
 //
+// graph_search_kernel<METRIC, GRAPH_PQ8 | GRAPH_PQ4>: the same search over product-quantised codes (create's pq_m=M) -- a label is
+//   scored by M look-ups into a per-query table T[s][j] (include/msvs.h: "Product-quantised rows").  Visit, merge, parent pick and
+//   epilogue are the code above; the table build, the score step, the stored row and the LDS image are its own:
+//   LDS image (graph_pq_lds_bytes): T (4 x ksub x M bytes, built once per query by graph_pq_build_tables) | the 6 KiB of beam /
+//   stage / flags / labels | control words | the visited table.  The query is read from global memory by the table build alone
+//   (one address for the whole block: a scalar load) and has no LDS image.
+//   Stored row (GraphPqLayout): sixteen lane slots of W = 4 or 8 bytes, row-major, 64 or 128 bytes a row.  Slot g holds the codes of
+//   the sub-spaces g c .. g c + c - 1, c = ceil(M / 16), in ascending order from bit 0 (4 bits: two a byte, a slot starts a byte),
+//   zero padded.  One label's codes are ONE aligned 4- or 8-byte load a lane, 64 or 128 contiguous bytes a 16-lane group, and the
+//   lane's run -- the partial sum p_g of the definition -- is contiguous in what it loaded.
+//   score: a group takes its labels c0, c0 + 16, c0 + 32, c0 + 48 of the round at once and requests all four rows before the first
+//   look-up (64 rows in flight a block: a whole width = 1 round of R <= 64); then c look-ups a lane, row16_tree_sum, make_key.
+//
 // graph_wide_search_kernel<METRIC, BITS, E>: the same search with ef, k <= 4096 (search_wide): a fixed grid, E beam entries a thread,
 //   the visited table in global memory.  Its design stands at the kernel.
 // graph_join_kernel: the sub-quadratic build's neighbours-of-neighbours join (create's join_iters >= 1), one block per node; it shares
@@ -40,6 +53,7 @@
 #pragma once
 
 #include "mfma_scan_kernels.hpp"
+#include "pq_ivf_kernels.hpp"
 #include "scan_kernels.hpp"
 #include "sq_ivf_kernels.hpp"
 
@@ -57,6 +71,10 @@ constexpr uint32_t GRAPH_CTL = 16;            // control words
 constexpr uint32_t GRAPH_SQ_MULTI_UNITS = 4; // rows of up to 4 units (dim <= 1024): four labels a group at once
 constexpr uint32_t GRAPH_SQ_LONG_UNITS = 4;  // longer rows: units of a double-buffered chunk
 
+// The kernels' BITS axis: 32 (f32 rows), 8 (scalar-quantised codes), and the two product-quantised forms
+constexpr int GRAPH_PQ8 = 0x108, GRAPH_PQ4 = 0x104;
+constexpr bool graph_is_pq(int bits) { return bits == GRAPH_PQ8 || bits == GRAPH_PQ4; }
+
 struct GraphSearchParams
 {
     const float4 * rows;    // n x ld4 at least, zero padded; HBM or mapped pinned host memory
@@ -73,6 +91,10 @@ struct GraphSearchParams
     const uint4 * codes;         // n x lc4 / 4 16-byte words, stored order (sq_layout.hpp)
     const float4 * vmin, * step; // lc4, zero padded
     uint32_t lc4;                // round_up(dim, 16) / 4 >= ld4
+    // BITS GRAPH_PQ8 / GRAPH_PQ4 (rows is not read; codes: n rows of GraphPqLayout, 16 x pq_w bytes each):
+    const float * pq_cb;          // the codebooks in pq_cb_index's order
+    uint32_t pq_m, pq_dsub, pq_c; // sub-spaces, floats of one, sub-spaces a lane: ceil(pq_m / 16)
+    uint32_t pq_w;                // bytes of a lane slot: 4 or 8
 };
 
 inline size_t graph_lds_bytes(uint32_t ld4, uint32_t tab)
@@ -83,9 +105,23 @@ inline size_t graph_lds_bytes(uint32_t ld4, uint32_t tab)
 /// the coded image: vmin and step beside the query, all three of lc4 float4
 inline size_t graph_sq_lds_bytes(uint32_t lc4, uint32_t tab) { return graph_lds_bytes(lc4, tab) + (size_t)lc4 * 32; }
 
+/// The product-quantised stored row: sixteen lane slots of w bytes; slot g holds the codes of the sub-spaces g c .. g c + c - 1
+/// from bit 0 up.  pos(s): the byte of a row code s lives in (4 bits: its nibble is (s % c) & 1); row_bytes = 16 w <= 128.
+struct GraphPqLayout
+{
+    uint32_t m, bits, c, w;
+    __host__ __device__ GraphPqLayout(uint32_t m_, uint32_t bits_) : m(m_), bits(bits_), c((m_ + 15) / 16), w(((m_ + 15) / 16) * bits_ > 32 ? 8 : 4) {}
+    __host__ __device__ uint32_t row_bytes() const { return 16 * w; }
+    __host__ __device__ uint32_t pos(uint32_t s) const { return (s / c) * w + (s % c) * bits / 8; }
+    __host__ __device__ uint32_t shift(uint32_t s) const { return bits == 4 ? ((s % c) & 1) * 4 : 0; }
+};
+
+/// the product-quantised image: the tables where the other forms keep the query
+inline size_t graph_pq_lds_bytes(uint32_t m, uint32_t bits, uint32_t tab) { return graph_lds_bytes(m << (bits - 2), tab); }
+
 struct GraphLds
 {
-    float4 * qs, * vm, * st; // (vm, st: BITS 8)
+    float4 * qs, * vm, * st; // (vm, st: BITS 8; the product-quantised forms: qs is the tables T[s][j], ksub x m floats)
     uint64_t * beam, * stage;
     uint32_t * flag, * slab, * ctl, * table;
     // ctl: 0 labels to score this round, 1 |V|, 2 beam entries, 3 newly admitted keys, 4 alive results; 8 .. 15 four 64-bit ballots
@@ -264,6 +300,142 @@ __device__ __forceinline__ void graph_score_codes(const GraphSearchParams & a, c
     }
 }
 
+// ------------------------------------------------------------------------------------------- product-quantised rows
+
+/// T[s][j] of include/msvs.h for the query q (dim floats in global memory, normalised for cosine), into LDS; the caller's barrier
+/// follows.  8 bits: thread j owns entry j of every sub-space, so a wavefront's codebook loads are 256 contiguous bytes and q's
+/// element is one address for the block.  4 bits: a wavefront is (4 consecutive sub-spaces) x (16 entries), pq_cb_index's grouped
+/// order; the block takes 16 sub-spaces a pass.
+template <int METRIC, int BITS>
+__device__ __forceinline__ void graph_pq_build_tables(const GraphSearchParams & a, float * lut, const float * q, const uint32_t tid)
+{
+    const uint32_t m = a.pq_m, dsub = a.pq_dsub;
+    auto term = [](const float qv, const float v) {
+        if constexpr (METRIC == M_L2)
+        {
+            const float df = __fsub_rn(qv, v);
+            return __fmul_rn(df, df);
+        }
+        else
+            return __fmul_rn(qv, v);
+    };
+    if constexpr (BITS == GRAPH_PQ8)
+    {
+        // pq_cb_index<8>(s, t, tid, ...) = (s dsub + t) 256 + tid: the columns i = s dsub + t are one run of dim loads, taken eight
+        // at a time so that eight requests a thread are in flight; a table entry is closed whenever its dsub terms are in
+        const float * cb = a.pq_cb + tid;
+        const uint32_t dim = m * dsub;
+        uint32_t s = 0, t = 0;
+        float e = 0.f;
+        for (uint32_t i0 = 0; i0 < dim; i0 += 8)
+        {
+            float v[8];
+#pragma unroll
+            for (uint32_t u = 0; u < 8; u++)
+                v[u] = i0 + u < dim ? cb[(size_t)(i0 + u) * 256] : 0.f;
+#pragma unroll
+            for (uint32_t u = 0; u < 8; u++)
+                if (i0 + u < dim)
+                {
+                    e = __fadd_rn(e, term(q[i0 + u], v[u]));
+                    if (++t == dsub)
+                    {
+                        lut[s * 256 + tid] = e;
+                        e = 0.f;
+                        t = 0;
+                        s++;
+                    }
+                }
+        }
+    }
+    else
+    {
+        const uint32_t j = tid & 15;
+        for (uint32_t s = tid >> 4; s < m; s += 16)
+        {
+            const float * cb = a.pq_cb + pq_cb_index<4>(s, 0, j, m, dsub);
+            const uint32_t gw = pq_cb_stride<4>(s, m);
+            const float * qs = q + s * dsub;
+            float e = 0.f;
+            for (uint32_t t = 0; t < dsub; t++)
+                e = __fadd_rn(e, term(qs[t], cb[(size_t)t * gw]));
+            lut[s * 16 + j] = e;
+        }
+    }
+}
+
+/// score, product-quantised codes: lane g of the group that owns a label adds its run's table entries in ascending order (the
+/// definition's p_g); the sixteen partials fold with row16_tree_sum.  The loads of the group's four labels leave before the first
+/// look-up.  w64: the lane's slot, codes from bit 0 up.
+template <int METRIC, int BITS>
+__device__ __forceinline__ void graph_score_pq(const GraphSearchParams & a, const GraphLds & L, const uint32_t m, const uint32_t grp, const uint32_t g)
+{
+    constexpr uint32_t CB = BITS == GRAPH_PQ8 ? 8 : 4, KSUB = 1u << CB;
+    const float * lut = reinterpret_cast<const float *>(L.qs);
+    const uint32_t c = a.pq_c, s0 = g * c, run = s0 < a.pq_m ? min(c, a.pq_m - s0) : 0u, words = a.pq_w >> 2;
+    const uint32_t * codes = reinterpret_cast<const uint32_t *>(a.codes);
+    for (uint32_t c0 = grp; c0 < m; c0 += 64)
+    {
+        uint64_t w[4];
+        uint32_t id[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+        {
+            const uint32_t cc = c0 + 16 * r;
+            id[r] = cc < m ? L.slab[cc] : GRAPH_EMPTY;
+            w[r] = 0;
+            if (id[r] != GRAPH_EMPTY)
+            {
+                const uint32_t * slot = codes + ((size_t)id[r] * 16 + g) * words;
+                if (words == 2)
+                {
+                    const uint2 v = *reinterpret_cast<const uint2 *>(slot);
+                    w[r] = (uint64_t)v.y << 32 | v.x;
+                }
+                else
+                    w[r] = *slot;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            if (id[r] != GRAPH_EMPTY) // (uniform over the group)
+            {
+                // c steps for every lane, so the group stays in step up to the lane sum; a step past the lane's run reads the
+                // last table (a pad code is 0) and is dropped by a select
+                float p = 0.f;
+                uint64_t v = w[r];
+                for (uint32_t i = 0; i < c; i++, v >>= CB)
+                {
+                    const float e = lut[min(s0 + i, a.pq_m - 1) * KSUB + ((uint32_t)v & (KSUB - 1))];
+                    p = i < run ? __fadd_rn(p, e) : p;
+                }
+                p = row16_tree_sum(p);
+                if (g == 0)
+                    L.stage[c0 + 16 * r] = make_key<METRIC>(p, id[r]);
+            }
+    }
+}
+
+/// the encoders' rows (pq_encode_kernel: a code a byte; pq4_encode_kernel: two a byte; rows of mp bytes) -> the stored rows of
+/// GraphPqLayout, a thread a stored byte, pad bits 0
+static __global__ void graph_pq_repack_kernel(const uint8_t * src, size_t n, uint32_t m, uint32_t bits, uint32_t mp, uint8_t * dst)
+{
+    const GraphPqLayout lay(m, bits);
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * lay.row_bytes())
+        return;
+    const size_t r = e / lay.row_bytes();
+    const uint32_t b = (uint32_t)(e - r * lay.row_bytes()), g = b / lay.w, o = b % lay.w;
+    uint32_t out = 0;
+    for (uint32_t h = 0; h < 8 / bits; h++) // the codes of this byte
+    {
+        const uint32_t i = o * (8 / bits) + h, s = g * lay.c + i;
+        if (i < lay.c && s < m)
+            out |= (bits == 8 ? src[r * mp + s] : (src[r * mp + (s >> 1)] >> ((s & 1) * 4)) & 15u) << (h * bits);
+    }
+    dst[e] = (uint8_t)out;
+}
+
 /// Merge by ranking: the m staged keys go into the sorted beam of cnt keys, cut to ef.  Entered with every thread past the barrier
 /// behind the last staged key; left past a barrier with ctl[2] the beam's new fill, ctl[1] grown by m and ctl[0] = ctl[3] = 0.
 __device__ __forceinline__ void graph_merge(const GraphLds & L, const uint32_t ef, const uint32_t m, const uint32_t cnt, const uint32_t tid)
@@ -329,22 +501,33 @@ __device__ __forceinline__ void graph_round(const GraphSearchParams & a, const G
     const uint32_t m = L.ctl[0], cnt = L.ctl[2];
     if constexpr (BITS == 8)
         graph_score_codes<METRIC>(a, L, m, grp, g);
+    else if constexpr (graph_is_pq(BITS))
+        graph_score_pq<METRIC, BITS>(a, L, m, grp, g);
     else
         graph_score_rows<METRIC>(a, L, m, grp, g);
     __syncthreads();
     graph_merge(L, a.ef, m, cnt, tid);
 }
 
+/// bytes of the image before the beam: the query (| vmin | step), or the product-quantised tables
+template <int BITS>
+__device__ __forceinline__ size_t graph_head_bytes(const GraphSearchParams & a)
+{
+    if constexpr (graph_is_pq(BITS))
+        return (size_t)a.pq_m * 4 << (BITS & 15);
+    return BITS == 8 ? (size_t)a.lc4 * 48 : (size_t)a.ld4 * 16;
+}
+
 template <int METRIC, int BITS = 32>
 static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphSearchParams a)
 {
-    static_assert(BITS == 32 || BITS == 8, "f32 rows of a row store, or 8-bit codes");
+    static_assert(BITS == 32 || BITS == 8 || graph_is_pq(BITS), "f32 rows of a row store, 8-bit codes, or product-quantised codes");
     extern __shared__ __align__(16) unsigned char graph_lds[];
     GraphLds L;
     L.qs = reinterpret_cast<float4 *>(graph_lds);
     L.vm = L.qs + a.lc4;
     L.st = L.vm + a.lc4;
-    L.beam = reinterpret_cast<uint64_t *>(graph_lds + (BITS == 8 ? (size_t)a.lc4 * 48 : (size_t)a.ld4 * 16));
+    L.beam = reinterpret_cast<uint64_t *>(graph_lds + graph_head_bytes<BITS>(a));
     L.stage = L.beam + GRAPH_ROUND;
     L.flag = reinterpret_cast<uint32_t *>(L.stage + GRAPH_ROUND);
     L.slab = L.flag + GRAPH_ROUND;
@@ -358,6 +541,8 @@ static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphS
             L.vm[i] = a.vmin[i];
             L.st[i] = a.step[i];
         }
+    else if constexpr (graph_is_pq(BITS))
+        graph_pq_build_tables<METRIC, BITS>(a, reinterpret_cast<float *>(L.qs), reinterpret_cast<const float *>(a.Q + (size_t)q * a.ld4), tid);
     else
         for (uint32_t i = tid; i < a.ld4; i += BLOCK)
             L.qs[i] = a.Q[(size_t)q * a.ld4 + i];
@@ -579,6 +764,8 @@ __device__ __forceinline__ void graph_wide_round(const GraphWideParams & a, cons
     const uint32_t m = L.ctl[0], cnt = L.ctl[2];
     if constexpr (BITS == 8)
         graph_score_codes<METRIC>(a, L, m, grp, g);
+    else if constexpr (graph_is_pq(BITS))
+        graph_score_pq<METRIC, BITS>(a, L, m, grp, g);
     else
         graph_score_rows<METRIC>(a, L, m, grp, g);
     __syncthreads();
@@ -588,14 +775,14 @@ __device__ __forceinline__ void graph_wide_round(const GraphWideParams & a, cons
 template <int METRIC, int BITS, int E>
 static __global__ __launch_bounds__(BLOCK) void graph_wide_search_kernel(const GraphWideParams a)
 {
-    static_assert(BITS == 32 || BITS == 8, "f32 rows of a row store, or 8-bit codes");
+    static_assert(BITS == 32 || BITS == 8 || graph_is_pq(BITS), "f32 rows of a row store, 8-bit codes, or product-quantised codes");
     static_assert(E * BLOCK <= MSVS_MAX_K_ROUNDS, "the beam's entries a thread holds");
     extern __shared__ __align__(16) unsigned char graph_lds[];
     GraphLds L;
     L.qs = reinterpret_cast<float4 *>(graph_lds);
     L.vm = L.qs + a.lc4;
     L.st = L.vm + a.lc4;
-    L.beam = reinterpret_cast<uint64_t *>(graph_lds + (BITS == 8 ? (size_t)a.lc4 * 48 : (size_t)a.ld4 * 16));
+    L.beam = reinterpret_cast<uint64_t *>(graph_lds + graph_head_bytes<BITS>(a));
     L.stage = L.beam + a.ef;
     L.flag = nullptr; // (the wide beam's flags are bytes)
     L.slab = reinterpret_cast<uint32_t *>(L.stage + GRAPH_ROUND);
@@ -614,9 +801,14 @@ static __global__ __launch_bounds__(BLOCK) void graph_wide_search_kernel(const G
     for (uint32_t q = blockIdx.x; q < a.nq; q += gridDim.x)
     {
         __syncthreads(); // the previous query's last reader is done
-        const uint32_t q4 = BITS == 8 ? a.lc4 : a.ld4;
-        for (uint32_t i = tid; i < q4; i += BLOCK)
-            L.qs[i] = i < a.ld4 ? a.Q[(size_t)q * a.ld4 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (graph_is_pq(BITS))
+            graph_pq_build_tables<METRIC, BITS>(a, reinterpret_cast<float *>(L.qs), reinterpret_cast<const float *>(a.Q + (size_t)q * a.ld4), tid);
+        else
+        {
+            const uint32_t q4 = BITS == 8 ? a.lc4 : a.ld4;
+            for (uint32_t i = tid; i < q4; i += BLOCK)
+                L.qs[i] = i < a.ld4 ? a.Q[(size_t)q * a.ld4 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         uint4 * clear = reinterpret_cast<uint4 *>(L.table);
         for (uint32_t i = tid; i < a.tab / 4; i += BLOCK)
             clear[i] = make_uint4(GRAPH_EMPTY, GRAPH_EMPTY, GRAPH_EMPTY, GRAPH_EMPTY);

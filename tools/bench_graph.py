@@ -7,6 +7,8 @@ store, a built index of degree --degree, searched through the device entry on on
     time of --reps calls between HIP events after a warm-up call (and their spread, min .. max), queries/s;
   - --bits 32,8: the index is built once at 32 bits, exported, and the same structure is handed (set_graph) to a bit_size=8 index
     over the same store, so both forms search one graph; their repetitions alternate inside one process, shape by shape;
+    pq8:M / pq4:M add product-quantised forms (pq_m=M, 8- or 4-bit codes) over the same graph, and for each the recall@10 of
+    search(k = 100) + refine against the store and the time of a max_iters=1 search beside the whole one (the table build's share);
   - beside them the IVFFLAT index of the same rows (nlist --nlist) at --nprobes, the same way, to read the nprobe of equal recall off;
   - --wide: the wide search (search_wide_device) against search_device at ef 64 and 256, its own range (--wide-efs) and filtered
     searches with --alive of the rows alive (wide_section).
@@ -100,7 +102,8 @@ def main():
     ap.add_argument("--nlist", type=int, default=1024)
     ap.add_argument("--batches", default="1,64,4096")
     ap.add_argument("--efs", default="32,64,128,256")
-    ap.add_argument("--bits", default="32", help="forms of the graph index to search: 32, 8 or 32,8")
+    ap.add_argument("--bits", default="32", help="forms of the graph index to search: 32, 8, pq8:M, pq4:M (product-quantised, M sub-quantisers)")
+    ap.add_argument("--pq-iters", type=int, default=10, help="k-means iterations of the product-quantised forms' codebooks")
     ap.add_argument("--nprobes", default="8,16,32,64", help="of the IVFFLAT index beside it; empty: leave it out")
     ap.add_argument("--join-iters", type=int, default=0, help="0: the exact O(n^2) build; >= 1: IVF lists repaired by the join kernel")
     ap.add_argument("--build-nprobe", type=int, default=8)
@@ -164,21 +167,53 @@ def main():
     out["build"], out["build_s"] = build, time.perf_counter() - t0
     print("build (%s): %.2f s" % (build, out["build_s"]), flush=True)
     forms = {32: gx}
-    bits = [int(v) for v in a.bits.split(",")]
+    bits = [int(v) if v.isdigit() else v for v in a.bits.split(",")]
     if 8 in bits:
         t0 = time.perf_counter()
         forms[8] = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,bit_size=8" % a.degree)
         forms[8].set_graph(*gx.export())
         out["encode_s"] = time.perf_counter() - t0  # (with the structure's round trip through the host)
+    for f in (f for f in bits if isinstance(f, str)):  # pq8:M / pq4:M: codebooks trained over the store, codes, the same graph
+        width, m = f[2:].split(":")
+        t0 = time.perf_counter()
+        forms[f] = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,pq_m=%s,bit_size=%s,kmeans_iters=%d" % (a.degree, m, width, a.pq_iters))
+        forms[f].set_graph(*gx.export())
+        out.setdefault("pq_encode_s", {})[f] = time.perf_counter() - t0
     forms = {b: forms[b] for b in bits}
     out["graph_bytes"] = {str(b): ix.memory_usage for b, ix in forms.items()}
     out["row_bytes"] = {str(b): rows.memory_usage if b == 32 else 0 for b in forms}  # what the search needs resident besides
+    out["pq"] = []
+    for f, ix in ((f, ix) for f, ix in forms.items() if isinstance(f, str)):
+        # the two-stage search: search(k = 100) + refine against the store, recall@10; and the table build's share of the kernel:
+        # max_iters = 1 (tables, seeds, one expansion) against the whole search at ef = 64
+        d100 = torch.empty((nt, 100), device=dev, dtype=torch.int64)
+        s100 = torch.empty((nt, 100), device=dev, dtype=torch.float32)
+        for ef in (int(v) for v in a.efs.split(",")):
+            try:
+                ix.search_device(q.data_ptr(), nt, 100, d100.data_ptr(), s100.data_ptr(), ef=max(ef, 100), stream=stream)
+            except capi.MsvsError as e:
+                out["pq"].append({"bits": f, "ef": max(ef, 100), "refused": str(e)})
+                continue
+            capi.refine_device(rows, capi.METRIC_L2, q.data_ptr(), nt, d100.data_ptr(), 100, k, di.data_ptr(), dd.data_ptr(), stream)
+            torch.cuda.synchronize()
+            out["pq"].append({"bits": f, "ef": max(ef, 100), "refined_recall@10": recall(di[:nt].cpu().numpy())})
+        b = max(batches)
+        one, full = timed_all([lambda: ix.search_device(q.data_ptr(), b, k, di.data_ptr(), dd.data_ptr(), ef=64, max_iters=1, stream=stream),
+                               lambda: ix.search_device(q.data_ptr(), b, k, di.data_ptr(), dd.data_ptr(), ef=64, stream=stream)])
+        out["pq"].append({"bits": f, "nq": b, "ef": 64, "ms_max_iters_1": float(np.median(one)), "ms": float(np.median(full)),
+                          "table_share_at_most": float(np.median(one) / np.median(full))})
     for b in batches:
         for ef in (int(v) for v in a.efs.split(",")):
             outs = {f: (torch.empty_like(di), torch.empty_like(dd)) for f in forms}
-            calls = [lambda f=f, ix=ix: ix.search_device(q.data_ptr(), b, k, outs[f][0].data_ptr(), outs[f][1].data_ptr(), ef=ef, stream=stream)
-                     for f, ix in forms.items()]
-            for f, ms in zip(forms, timed_all(calls)):
+            calls = {f: (lambda f=f, ix=ix: ix.search_device(q.data_ptr(), b, k, outs[f][0].data_ptr(), outs[f][1].data_ptr(), ef=ef, stream=stream))
+                     for f, ix in forms.items()}
+            for f in list(calls):  # a form whose LDS image does not fit this ef (pq8:96 at ef = 128) is reported as refused
+                try:
+                    calls[f]()
+                except capi.MsvsError as e:
+                    out["graph"].append({"bits": f, "nq": b, "ef": ef, "refused": str(e)})
+                    del calls[f]
+            for f, ms in zip(calls, timed_all(list(calls.values()))):
                 med = float(np.median(ms))
                 out["graph"].append({"bits": f, "nq": b, "ef": ef, "ms": med, "ms_min": min(ms), "ms_max": max(ms), "qps": b / med * 1e3,
                                      "recall@10": recall(outs[f][0].cpu().numpy()) if b >= nt else None})
