@@ -558,8 +558,8 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
  *   corrupt is MSVS_ERR_IO.
  *
  * Coded rows: create's parameter bit_size.  32 (the default) is the index above.  8: the index also keeps ONE quantiser and n rows
- * of 8-bit codes, and the search scores decoded rows; anything else is MSVS_ERR_INVALID_ARGUMENT.  All arithmetic is f32 with
- * separately rounded operations and no fma.
+ * of 8-bit codes, and the search scores decoded rows; 16: n binary16 rows (below); anything else is MSVS_ERR_INVALID_ARGUMENT.
+ * All arithmetic is f32 with separately rounded operations and no fma.
  *   Quantiser: vmin[j] / vmax[j] = the exact minimum / maximum of column j over all n stored rows (the normalised rows for cosine),
  *     NaN ignored, a column with no non-NaN value 0 .. 0 (as msvs_sq_index_train); step[j] = fl(fl(vmax[j] - vmin[j]) / 255).
  *     A range whose span is not finite (any +-inf element in the store) is refused by build / set_graph with
@@ -575,13 +575,27 @@ MSVS_API int msvs_pq_index_search_refine_rounds_device(const msvs_pq_index_t * i
  *     the caller's structure as above, then the quantiser and the codes from the store.
  *   The row store is read by build and set_graph only: search, export, serialize and memory_usage never touch it, and once the last
  *     build / set_graph has returned the caller may free it.
- *   bit_size: 32 or 8 (0 for NULL).  export_codes: vmin[dim], vmax[dim] and n x dim codes in natural column order, any output may
+ *   bit_size: 32, 16 or 8 (0 for NULL).  export_codes: vmin[dim], vmax[dim] and n x dim codes in natural column order, any output may
  *     be NULL; MSVS_ERR_INVALID_ARGUMENT on a 32-bit index.  memory_usage grows by n x round_up(dim, 16) plus the device bytes of
  *     vmin and step (2 x round_up(dim, 16) x 4).
  *   File: header version 2, otherwise the same 64 bytes; the body is the centroids, the seeds, nbr, vmin, vmax and the codes as
  *     n x dim bytes in natural order, all under the body's checksum.  A 32-bit index writes and reads version 1 exactly as before.
  *     load_io takes a version-2 file with rows == NULL; a non-NULL store is checked for n alone.  Bounds that are not finite,
  *     vmax < vmin, an infinite span or a wrong size are MSVS_ERR_IO like any corruption.  A version-1 file keeps its rules.
+ *   bit_size=16 (without pq_m; pq_m with bit_size=16 stays MSVS_ERR_INVALID_ARGUMENT): the index keeps n rows of IEEE binary16
+ *     values instead of codes; half of the f32 bytes, no quantiser.
+ *     Encode: h_j = the binary16 value nearest to the stored element x_j (the normalised row for cosine), round to nearest even,
+ *       binary16 subnormals kept, overflow to +-inf, NaN stays NaN.  No centroid, no vmin / vmax, no clamping; no value is refused.
+ *     Decode: x^_j = float(h_j), exact.
+ *     Search: as for bit_size=8 -- steps 1 - 6 word for word against the decoded row, search, search_device, search_wide and
+ *       search_wide_device alike, so the result equals the 32-bit search over a row store holding x^, bit for bit, rows that decode
+ *       to +-inf or NaN included.  The LDS images are the 32-bit index's: the query and nothing beside it.
+ *     build / set_graph: the graph from the f32 rows, then the binary16 rows; the row store is read by these two only and may be
+ *       freed afterwards.  bit_size: 16.  export_codes stays MSVS_ERR_INVALID_ARGUMENT: there is no range to return.
+ *     memory_usage grows by n x 2 x round_up(dim, 16).
+ *     File: header version 4, otherwise the same 64 bytes; the body is the centroids, the seeds, nbr, then n x dim little-endian
+ *       binary16 values in natural order, all under the body's checksum.  load_io takes it with rows == NULL; a non-NULL store is
+ *       checked for n alone; a wrong size is MSVS_ERR_IO.  Versions 1 - 3 are written and read exactly as before.
  *
  * Product-quantised rows: create's parameter pq_m=M (default 0: off, and everything above holds unchanged).  With M >= 1 bit_size is
  * the width of a code, 8 (the default then) or 4: the index keeps M sub-codebooks of ksub = 1 << bit_size entries of dsub = dim / M

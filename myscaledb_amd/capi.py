@@ -660,7 +660,10 @@ GRAPH_NO_EDGE = 0xFFFFFFFF
 class GraphIndex(_CodedIndex):
     """msvs_graph_index_t: coarse centroids, a seed label per centroid and a fixed-degree neighbour graph over the rows of `rows` (a
     Rows the caller keeps alive and no longer appends to), searched by the seeded beam search include/msvs.h defines.  params:
-    "degree=16|32|64", "bit_size=32|8" and the IVFFLAT trainer's keys ("ncentroids=N,kmeans_iters=I,...").
+    "degree=16|32|64", "bit_size=32|16|8" and the IVFFLAT trainer's keys ("ncentroids=N,kmeans_iters=I,...").
+    bit_size=16: build / set_graph keep one IEEE binary16 row per label (round to nearest even, overflow to +-inf, no quantiser: no
+    value is refused and export_codes has nothing to return); the search scores the exactly decoded rows, half of f32's bytes, and the
+    store is free afterwards as for bit_size=8 below.
     bit_size=8: build / set_graph also make one 8-bit quantiser and a code row per label from the store; the search scores the decoded
     rows, so its results are those of a 32-bit index over a store holding them, and after the last build / set_graph nothing reads
     `rows` any more: it may be closed, and load_io needs none.

@@ -3,6 +3,8 @@
 // is a function of the inputs alone.  The kernels and their layout: graph_kernels.hpp.  DESIGN.md 4.14.
 // bit_size=8: the index keeps one 8-bit quantiser and a code row per label, made from the store by build / set_graph; the search
 // scores decoded rows and nothing but build / set_graph reads the store.
+// bit_size=16: the index keeps one binary16 row per label (graph_h16_encode_kernel, graph_h16_slot's order), no quantiser; the search
+// scores the exactly decoded rows with the f32 search's LDS image; file version 4.
 // pq_m=M: the index keeps M sub-codebooks (trained over the store by the IVFPQ index's codebook step, or handed in) and M codes a
 // label in GraphPqLayout's order; the search scores a label by M look-ups into a per-query table; file version 3.
 // search_wide: the same definition with ef, k <= MSVS_MAX_K_ROUNDS, served by graph_wide_search_kernel on a fixed grid.
@@ -40,6 +42,7 @@ struct msvs_graph_index
     std::vector<float> h_vmin, h_vmax; // dim
     DevBuf<float> d_vmin, d_step;      // ldc, zero padded
     DevBuf<uint8_t> codes;             // n x ldc
+    // bit_size=16: codes holds n x ldc binary16 values in graph_h16_slot's order; no quantiser
     // pq_m=M (bits is then the width of a code, 8 or 4; no quantiser, ldc unused): codes holds n rows of GraphPqLayout
     size_t pq_m = 0;
     bool cb_handed = false;  // h_cb came through set_pq_codebooks: build / set_graph encode only
@@ -47,7 +50,8 @@ struct msvs_graph_index
     DevBuf<float> cbT;       // the same in pq_cb_index's order
     bool ready = false;
     bool sq() const { return bits == 8 && !pq_m; }
-    bool coded() const { return bits == 8 || pq_m; } // the search reads the index's own rows, never the store
+    bool h16() const { return bits == 16 && !pq_m; }
+    bool coded() const { return bits != 32 || pq_m; } // the search reads the index's own rows, never the store
     size_t ksub() const { return (size_t)1 << bits; }
     GraphPqLayout pq_layout() const { return GraphPqLayout((uint32_t)pq_m, bits); }
 };
@@ -255,7 +259,7 @@ void graph_search_chunks(const msvs_graph_index & ix, const float * d_queries, s
         a.cosine = ix.metric == MSVS_METRIC_COSINE;
         ProfileScope prof(wide ? "graph_wide_search" : "graph_search", stream);
         with_int<M_IP, M_L2>(m, [&](auto mm) {
-            with_int<8, 32, GRAPH_PQ8, GRAPH_PQ4>(ix.pq_m ? (ix.bits == 8 ? GRAPH_PQ8 : GRAPH_PQ4) : (int)ix.bits, [&](auto bb) {
+            with_int<8, 32, 16, GRAPH_PQ8, GRAPH_PQ4>(ix.pq_m ? (ix.bits == 8 ? GRAPH_PQ8 : GRAPH_PQ4) : (int)ix.bits, [&](auto bb) {
                 constexpr int METRIC = decltype(mm)::value, BITS = decltype(bb)::value;
                 if (!wide)
                     launch_graph_search<METRIC, BITS>(a, nqc, lds, stream);
@@ -396,11 +400,51 @@ std::vector<uint8_t> host_codes(const msvs_graph_index & ix, hipStream_t stream)
     return out;
 }
 
+/// bit_size=16, after build / set_graph (ix.n is set): the store's n rows as binary16 in the search's stored order.  The rows are
+/// read where they are (HBM or mapped pinned host memory), GRAPH_CODE_CHUNK halves a launch.
+void encode_h16_store(msvs_graph_index & ix, hipStream_t stream)
+{
+    const RowsView rv = rows_view(ix.rows);
+    const size_t n = ix.n, lc4 = ix.ldc / 4;
+    if (rv.n < n)
+        fail(MSVS_ERR_INVALID_ARGUMENT, "the row store holds %zu rows, the graph was made over %zu", rv.n, n);
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::max<size_t>(n, 1), GRAPH_CODE_CHUNK / ix.ldc));
+    ix.codes.alloc(std::max<size_t>(n * ix.ldc * 2, 1));
+    for (size_t r0 = 0; r0 < n; r0 += chunk)
+    {
+        const size_t m = std::min(chunk, n - r0);
+        hipLaunchKernelGGL(graph_h16_encode_kernel, dim3((unsigned)ceil_div(m * lc4, (size_t)BLOCK)), dim3(BLOCK), 0, stream,
+                           reinterpret_cast<const float4 *>(rv.table + r0 * rv.ld), m, rv.ld / 4, (uint32_t)lc4,
+                           reinterpret_cast<uint2 *>(ix.codes.p) + r0 * lc4);
+        MSVS_HIP(hipGetLastError());
+    }
+    MSVS_HIP(hipStreamSynchronize(stream));
+    MSVS_HIP(hipDeviceSynchronize()); // searches run on other streams
+}
+
+/// half j of a binary16 stored row of ldc halves
+inline size_t h16_stored_pos(size_t j, uint32_t ldc) { return 4 * (size_t)graph_h16_slot((uint32_t)(j / 4), ldc / 4) + j % 4; }
+
+/// the binary16 rows of the index, n x dim in natural column order (the file)
+std::vector<uint16_t> host_h16_rows(const msvs_graph_index & ix, hipStream_t stream)
+{
+    std::vector<uint16_t> stored(ix.n * ix.ldc), out(ix.n * ix.dim);
+    if (!stored.empty())
+        MSVS_HIP(hipMemcpyAsync(stored.data(), ix.codes.p, stored.size() * 2, hipMemcpyDeviceToHost, stream));
+    MSVS_HIP(hipStreamSynchronize(stream));
+    for (size_t r = 0; r < ix.n; r++)
+        for (size_t j = 0; j < ix.dim; j++)
+            out[r * ix.dim + j] = stored[r * ix.ldc + h16_stored_pos(j, ix.ldc)];
+    return out;
+}
+
 void check_graph_coded(const msvs_graph_index & ix)
 {
     if (!ix.sq())
         fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index keeps %s: it has no quantiser bounds and scalar codes",
-             ix.pq_m ? "product-quantised codes (pq_m)" : "f32 rows of its row store (bit_size=32)");
+             ix.pq_m     ? "product-quantised codes (pq_m)"
+             : ix.h16() ? "binary16 rows (bit_size=16)"
+                         : "f32 rows of its row store (bit_size=32)");
 }
 
 void check_graph_pq(const msvs_graph_index & ix)
@@ -581,7 +625,8 @@ std::vector<float> host_centroids(const msvs_graph_index & ix, hipStream_t strea
 struct GraphHeader // 64 bytes, little endian
 {
     char magic[8]; // "MSVSGR01"
-    uint32_t version; // 1: f32 rows of the store; 2: bit_size=8, the body continues with vmin, vmax and n x dim codes
+    uint32_t version; // 1: f32 rows of the store; 2: bit_size=8, the body continues with vmin, vmax and n x dim codes; 3: pq_m; 4: bit_size=16,
+                      // the body continues with n x dim binary16 values
     int32_t metric;
     uint64_t dim, nlist, n, degree;
     uint64_t body; // FNV-1a of the centroids, the seeds and the edges (version 2: and vmin, vmax, the codes)
@@ -610,6 +655,13 @@ uint64_t graph_body_check3(const std::vector<float> & c, const std::vector<int32
                            fnv1a(geometry, sizeof(geometry)), fnv1a(cb.data(), cb.size() * 4), fnv1a(codes.data(), codes.size())};
     return fnv1a(h, sizeof(h));
 }
+
+/// version 4: the centroids, the seeds, the edges and the binary16 rows
+uint64_t graph_body_check4(const std::vector<float> & c, const std::vector<int32_t> & s, const std::vector<uint32_t> & e, const std::vector<uint16_t> & rows)
+{
+    const uint64_t h[4] = {fnv1a(c.data(), c.size() * 4), fnv1a(s.data(), s.size() * 4), fnv1a(e.data(), e.size() * 4), fnv1a(rows.data(), rows.size() * 2)};
+    return fnv1a(h, sizeof(h));
+}
 }
 
 extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, const char * params, msvs_graph_index_t ** out)
@@ -631,8 +683,9 @@ extern "C" int msvs_graph_index_create(int metric, const msvs_rows_t * rows, con
         if (pq_m < 0)
             fail(MSVS_ERR_INVALID_ARGUMENT, "pq_m is 0 (off) or the number of sub-quantisers (pq_m %ld)", pq_m);
         const long bits = param_int(p, "bit_size", pq_m ? 8 : 32);
-        if (!pq_m && bits != 32 && bits != 8)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "the graph index scores f32 rows (bit_size=32) or 8-bit codes (bit_size=8) (bit_size %ld)", bits);
+        if (!pq_m && bits != 32 && bits != 16 && bits != 8)
+            fail(MSVS_ERR_INVALID_ARGUMENT,
+                 "the graph index scores f32 rows (bit_size=32), binary16 rows (bit_size=16) or 8-bit codes (bit_size=8) (bit_size %ld)", bits);
         if (pq_m)
         {
             // (the smallest narrow search: ef = nprobe = width = max_iters = 1 reaches 1 + degree labels)
@@ -691,6 +744,8 @@ extern "C" size_t msvs_graph_index_memory_usage(const msvs_graph_index_t * ix)
     size_t coded = ix->sq() && ix->ready ? ix->n * ix->ldc + ix->d_vmin.bytes() + ix->d_step.bytes() : 0;
     if (ix->pq_m && ix->ready)
         coded = ix->n * ix->pq_layout().row_bytes() + ix->cbT.bytes();
+    if (ix->h16() && ix->ready)
+        coded = ix->n * ix->ldc * 2;
     return ix->nbr.bytes() + ix->centroids.bytes() + ix->seeds.bytes() + coded;
 }
 extern "C" size_t msvs_graph_index_pq_m(const msvs_graph_index_t * ix) { return ix ? ix->pq_m : 0; }
@@ -755,6 +810,8 @@ extern "C" int msvs_graph_index_set_graph(msvs_graph_index_t * ix, const float *
             encode_pq_store(*ix, thread_stream());
         else if (ix->bits == 8)
             encode_store(*ix, thread_stream());
+        else if (ix->bits == 16)
+            encode_h16_store(*ix, thread_stream());
         ix->ready = true;
     });
 }
@@ -941,6 +998,8 @@ extern "C" int msvs_graph_index_build(msvs_graph_index_t * ix)
             encode_pq_store(*ix, stream);
         else if (ix->bits == 8)
             encode_store(*ix, stream);
+        else if (ix->bits == 16)
+            encode_h16_store(*ix, stream);
         ix->ready = true;
     });
 }
@@ -1094,17 +1153,20 @@ extern "C" int msvs_graph_index_serialize_io(const msvs_graph_index_t * ix, cons
         const std::vector<uint8_t> codes = coded ? host_codes(*ix, stream)
                                            : pq  ? pq_file_rows(host_pq_codes(*ix, stream), ix->n, ix->pq_m, ix->bits)
                                                  : std::vector<uint8_t>();
+        const bool h16 = ix->h16();
+        const std::vector<uint16_t> halves = h16 ? host_h16_rows(*ix, stream) : std::vector<uint16_t>();
         const uint64_t geometry[2] = {ix->pq_m, ix->bits};
         IoStream f(io, "graph_data", 1);
         GraphHeader h{};
         memcpy(h.magic, "MSVSGR01", 8);
-        h.version = pq ? 3 : coded ? 2 : 1;
+        h.version = h16 ? 4 : pq ? 3 : coded ? 2 : 1;
         h.metric = ix->metric;
         h.dim = ix->dim;
         h.nlist = ix->nlist;
         h.n = ix->n;
         h.degree = ix->R;
-        h.body = pq      ? graph_body_check3(c, s, e, geometry, ix->h_cb, codes)
+        h.body = h16     ? graph_body_check4(c, s, e, halves)
+                 : pq    ? graph_body_check3(c, s, e, geometry, ix->h_cb, codes)
                  : coded ? graph_body_check2(c, s, e, ix->h_vmin, ix->h_vmax, codes)
                          : graph_body_check(c, s, e);
         h.check = fnv1a(&h, offsetof(GraphHeader, check));
@@ -1113,6 +1175,8 @@ extern "C" int msvs_graph_index_serialize_io(const msvs_graph_index_t * ix, cons
         f.write(s.data(), s.size() * 4);
         if (!e.empty())
             f.write(e.data(), e.size() * 4);
+        if (h16 && !halves.empty())
+            f.write(halves.data(), halves.size() * 2);
         if (pq)
         {
             f.write(geometry, sizeof(geometry));
@@ -1149,12 +1213,12 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
         IoStream f(io, "graph_data", 0);
         GraphHeader h{};
         f.read(&h, sizeof(h));
-        if (memcmp(h.magic, "MSVSGR01", 8) != 0 || h.version < 1 || h.version > 3 || h.check != fnv1a(&h, offsetof(GraphHeader, check))
+        if (memcmp(h.magic, "MSVSGR01", 8) != 0 || h.version < 1 || h.version > 4 || h.check != fnv1a(&h, offsetof(GraphHeader, check))
             || !header_ranges_ok(h.metric, h.dim, h.nlist, h.n) || (h.degree != 16 && h.degree != 32 && h.degree != 64))
             fail(MSVS_ERR_IO, "corrupt msvs graph index header");
-        const bool pq = h.version == 3, coded = h.version >= 2; // (coded: the file carries what the search reads)
+        const bool pq = h.version == 3, h16 = h.version == 4, coded = h.version >= 2; // (coded: the file carries what the search reads)
         if (!coded && !rows)
-            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store: only a file of a bit_size=8 or pq_m index carries what its search reads");
+            fail(MSVS_ERR_INVALID_ARGUMENT, "null row store: only a file of a bit_size=8, bit_size=16 or pq_m index carries what its search reads");
         if (coded && h.dim == 0)
             fail(MSVS_ERR_IO, "corrupt msvs graph index header");
         if (coded ? (rows && h.n != rv.n) : (h.n != rv.n || h.dim != rv.dim || (h.metric == MSVS_METRIC_COSINE) != (rv.normalize != 0)))
@@ -1165,7 +1229,10 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
         read_grow(f, e, (size_t)(h.n * h.degree));
         uint64_t geometry[2] = {0, 0}; // version 3: m, bits
         std::vector<float> cb;
-        if (pq)
+        std::vector<uint16_t> halves; // version 4
+        if (h16)
+            read_grow(f, halves, (size_t)(h.n * h.dim));
+        else if (pq)
         {
             f.read(geometry, sizeof(geometry));
             const uint64_t m = geometry[0], bits = geometry[1];
@@ -1182,7 +1249,7 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
             read_grow(f, codes, (size_t)(h.n * h.dim));
         }
         expect_end(f);
-        if (h.body != (pq ? graph_body_check3(c, s, e, geometry, cb, codes) : coded ? graph_body_check2(c, s, e, lo, hi, codes) : graph_body_check(c, s, e)))
+        if (h.body != (h16 ? graph_body_check4(c, s, e, halves) : pq ? graph_body_check3(c, s, e, geometry, cb, codes) : coded ? graph_body_check2(c, s, e, lo, hi, codes) : graph_body_check(c, s, e)))
             fail(MSVS_ERR_IO, "corrupt msvs graph index: the body's checksum does not match");
         if (pq && first_non_finite(cb.data(), cb.size()) < cb.size())
             fail(MSVS_ERR_IO, "corrupt msvs graph index: a codebook entry is not finite");
@@ -1192,14 +1259,14 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
                     fail(MSVS_ERR_IO, "corrupt msvs graph index: the pad nibble of row %zu is not 0", r);
         if (const char * bad = graph_structure_error(c.data(), (size_t)h.nlist, (size_t)h.dim, s.data(), e.data(), (size_t)h.n, (uint32_t)h.degree))
             fail(MSVS_ERR_IO, "corrupt msvs graph index: %s", bad);
-        if (coded && !pq)
+        if (coded && !pq && !h16)
             for (size_t j = 0; j < h.dim; j++)
                 if (graph_unusable_dimension(&lo[j], &hi[j], 1) == 0 || hi[j] < lo[j])
                     fail(MSVS_ERR_IO, "corrupt msvs graph index: the quantiser bounds of dimension %zu are not finite, vmax < vmin or their span is infinite", j);
         ix->metric = h.metric;
         ix->dim = (size_t)h.dim;
         ix->ld = padded_dim((size_t)h.dim);
-        ix->bits = pq ? (uint32_t)geometry[1] : coded ? 8 : 32;
+        ix->bits = pq ? (uint32_t)geometry[1] : h16 ? 16 : coded ? 8 : 32;
         ix->pq_m = (size_t)geometry[0];
         ix->ldc = (uint32_t)round_up((size_t)h.dim, (size_t)16);
         ix->R = (uint32_t)h.degree;
@@ -1222,6 +1289,15 @@ extern "C" int msvs_graph_index_load_io(const msvs_io_t * io, const msvs_rows_t 
             pq_pack_rows(lay, natural.data(), ix->n, stored.data());
             ix->codes.alloc(stored.size());
             MSVS_HIP(hipMemcpy(ix->codes.p, stored.data(), stored.size(), hipMemcpyHostToDevice));
+        }
+        else if (h16)
+        {
+            std::vector<uint16_t> stored(std::max<size_t>(ix->n * ix->ldc, 1), 0); // natural order -> the stored order, pad halves 0
+            for (size_t r = 0; r < ix->n; r++)
+                for (size_t j = 0; j < ix->dim; j++)
+                    stored[r * ix->ldc + h16_stored_pos(j, ix->ldc)] = halves[r * ix->dim + j];
+            ix->codes.alloc(stored.size() * 2);
+            MSVS_HIP(hipMemcpy(ix->codes.p, stored.data(), stored.size() * 2, hipMemcpyHostToDevice));
         }
         else if (coded)
         {

@@ -31,6 +31,17 @@
 //   block, a whole width = 1 round in one go.  Longer rows: one row a group, chunks of GRAPH_SQ_LONG_UNITS units double buffered
 //   (the next chunk, or the next label's first, is on its way while this one is decoded), as sq_ivf_scan_kernel's wnext.
 //
+// graph_search_kernel<METRIC, 16>: the same search over binary16 rows (create's bit_size=16) -- a label is scored against x^ = float(h),
+//   an exact conversion, so there is no quantiser and the LDS image is the f32 kernel's (graph_lds_bytes(ld4, tab)): the query alone.
+//   Stored row (graph_h16_slot): lc4 = round_up(dim, 16) / 4 float4 columns of four halves, 8 bytes each.  Inside a whole block of 32
+//   columns (256 bytes) column 32 b + g sits beside column 32 b + g + 16, so ONE 16-byte load of lane g is its two columns of the
+//   block (a "unit") and a group's request is 256 contiguous bytes; the tail (< 32 columns) stays in natural order and is one more
+//   unit of two 8-byte words.  The lane's columns come out ascending: the sums are canonical_row_chain + row16_tree_sum's.
+//   score (graph_score_h16): rows of at most 4 units (dim <= 512): four labels c, c + 16, c + 32, c + 48 of a group at once, every
+//   request out before the first v_cvt_f32_f16; at most 8 units (dim <= 1024): two labels at once -- a whole width = 1 round of R = 32;
+//   longer rows: one row a group, chunks of GRAPH_H16_LONG_UNITS units double buffered, as the 8-bit form's.  Nothing but the query
+//   is read from LDS, and only its ld4 columns: the pad columns of a stored row (zero halves) are skipped, not multiplied.
+//
 // graph_search_kernel<METRIC, GRAPH_PQ8 | GRAPH_PQ4>: the same search over product-quantised codes (create's pq_m=M) -- a label is
 //   scored by M look-ups into a per-query table T[s][j] (include/msvs.h: "Product-quantised rows").  Visit, merge, parent pick and
 //   epilogue are the code above; the table build, the score step, the stored row and the LDS image are its own:
@@ -71,7 +82,7 @@ constexpr uint32_t GRAPH_CTL = 16;            // control words
 constexpr uint32_t GRAPH_SQ_MULTI_UNITS = 4; // rows of up to 4 units (dim <= 1024): four labels a group at once
 constexpr uint32_t GRAPH_SQ_LONG_UNITS = 4;  // longer rows: units of a double-buffered chunk
 
-// The kernels' BITS axis: 32 (f32 rows), 8 (scalar-quantised codes), and the two product-quantised forms
+// The kernels' BITS axis: 32 (f32 rows), 16 (binary16 rows), 8 (scalar-quantised codes), and the two product-quantised forms
 constexpr int GRAPH_PQ8 = 0x108, GRAPH_PQ4 = 0x104;
 constexpr bool graph_is_pq(int bits) { return bits == GRAPH_PQ8 || bits == GRAPH_PQ4; }
 
@@ -91,6 +102,7 @@ struct GraphSearchParams
     const uint4 * codes;         // n x lc4 / 4 16-byte words, stored order (sq_layout.hpp)
     const float4 * vmin, * step; // lc4, zero padded
     uint32_t lc4;                // round_up(dim, 16) / 4 >= ld4
+    // BITS 16 (rows, vmin and step are not read): codes is n x lc4 / 2 16-byte words in graph_h16_slot's order
     // BITS GRAPH_PQ8 / GRAPH_PQ4 (rows is not read; codes: n rows of GraphPqLayout, 16 x pq_w bytes each):
     const float * pq_cb;          // the codebooks in pq_cb_index's order
     uint32_t pq_m, pq_dsub, pq_c; // sub-spaces, floats of one, sub-spaces a lane: ceil(pq_m / 16)
@@ -300,6 +312,163 @@ __device__ __forceinline__ void graph_score_codes(const GraphSearchParams & a, c
     }
 }
 
+// ------------------------------------------------------------------------------------------- binary16 rows
+
+// The score step's forms, from the compiler's resource report (gfx950): ROWS x UNITS 16-byte words are held while a
+// group's rows are scored -- 4 x 4 and 2 x 8 are 64 VGPRs of halves; the long form holds two chunks of GRAPH_H16_LONG_UNITS.  The
+// narrow kernel takes 111 VGPRs, the wide one 126 / 128 at E = 1 / 2: 4 waves per SIMD, no scratch.  At E = 4 / 8 the wide kernel
+// with 64 VGPRs of halves took 130 / 134 (3 waves); LIGHT halves the rows at once (2 x 4, 1 x 8): 102 / 106.  E = 16: 146, as f32's 149.
+constexpr uint32_t GRAPH_H16_LONG_UNITS = 4;
+
+/// The binary16 stored row of lc4 float4 columns (four halves, 8 bytes each): slot(c) = the 8-byte word of natural column c, col(s)
+/// its inverse.  Inside a whole block of 32 columns the words of columns 32 b + g and 32 b + g + 16 are adjacent (2 g, 2 g + 1);
+/// the tail keeps its order.  Half j of a row lives at half 4 slot(j / 4) + j % 4 (sq_layout.hpp's sq16_stored_pos).
+__host__ __device__ inline uint32_t graph_h16_slot(const uint32_t c, const uint32_t lc4)
+{
+    return c >= (lc4 & ~31u) ? c : (c & ~31u) + ((c & 15u) << 1) + ((c >> 4) & 1u);
+}
+__host__ __device__ inline uint32_t graph_h16_col(const uint32_t s, const uint32_t lc4)
+{
+    return s >= (lc4 & ~31u) ? s : (s & ~31u) + ((s & 31u) >> 1) + ((s & 1u) << 4);
+}
+
+/// X: n rows of ld4 float4 (zero padded; HBM or mapped pinned host memory) -> n stored binary16 rows; a thread an 8-byte word.
+/// (_Float16)x is v_cvt_f16_f32 in the default modes: to nearest even, subnormals kept, overflow to +-inf, NaN stays NaN.
+static __global__ __launch_bounds__(BLOCK) void graph_h16_encode_kernel(const float4 * X, size_t n, uint32_t ld4, uint32_t lc4, uint2 * out)
+{
+    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n * lc4)
+        return;
+    const size_t r = i / lc4;
+    const uint32_t c = graph_h16_col((uint32_t)(i - r * lc4), lc4);
+    const float4 x = c < ld4 ? X[r * ld4 + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    half2v lo, hi;
+    lo[0] = (_Float16)x.x;
+    lo[1] = (_Float16)x.y;
+    hi[0] = (_Float16)x.z;
+    hi[1] = (_Float16)x.w;
+    out[i] = make_uint2(__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi));
+}
+
+/// unit u of a stored row of nb whole blocks and tc tail columns: the lane's columns 32 u + g (x, y) and 32 u + g + 16 (z, w); a block
+/// is one 16-byte load, the tail one 8-byte word per column the lane owns there (0 beyond the row)
+__device__ __forceinline__ uint4 graph_h16_load_unit(const uint4 * row, const uint32_t u, const uint32_t nb, const uint32_t tc, const uint32_t g)
+{
+    if (u < nb)
+        return row[u * 16 + g];
+    const uint2 * tail = reinterpret_cast<const uint2 *>(row) + nb * 32;
+    const uint2 zero = make_uint2(0u, 0u), a = g < tc ? tail[g] : zero, b = g + 16 < tc ? tail[g + 16] : zero;
+    return make_uint4(a.x, a.y, b.x, b.y);
+}
+
+/// four halves (one float4 column) -> the decoded column, exactly: two packed pairs, four v_cvt_f32_f16
+__device__ __forceinline__ float4 graph_h16_decode(const uint32_t w0, const uint32_t w1)
+{
+    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+    const half2v lo = __builtin_bit_cast(half2v, w0), hi = __builtin_bit_cast(half2v, w1);
+    return make_float4((float)lo[0], (float)lo[1], (float)hi[0], (float)hi[1]);
+}
+
+/// the lane's two columns of unit u, decoded and accumulated in ascending order; the query has ld4 columns, a row's pad columns none
+template <int METRIC>
+__device__ __forceinline__ void graph_h16_score_unit(float4 & acc, const float4 * qs, const uint4 w, const uint32_t u, const uint32_t ld4, const uint32_t g)
+{
+    const uint32_t col = u * 32 + g;
+    if (col < ld4)
+        canonical_update<METRIC>(acc, qs[col], graph_h16_decode(w.x, w.y));
+    if (col + 16 < ld4)
+        canonical_update<METRIC>(acc, qs[col + 16], graph_h16_decode(w.z, w.w));
+}
+
+/// rows of at most UNITS units: a group takes ROWS labels c0, c0 + 16, ... of the round at once; every request leaves before the
+/// first convert, then row after row
+template <int METRIC, int ROWS, int UNITS>
+__device__ __forceinline__ void graph_h16_score_multi(const GraphSearchParams & a, const GraphLds & L, const uint32_t m, const uint32_t grp, const uint32_t g,
+                                                      const uint32_t nb, const uint32_t tc, const uint32_t nu)
+{
+    const uint32_t ld16 = a.lc4 >> 1;
+    for (uint32_t c0 = grp; c0 < m; c0 += 16 * ROWS)
+    {
+        uint4 w[ROWS][UNITS];
+        uint32_t id[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; r++)
+        {
+            const uint32_t c = c0 + 16 * r;
+            id[r] = c < m ? L.slab[c] : GRAPH_EMPTY;
+            const uint4 * row = a.codes + (size_t)id[r] * ld16;
+#pragma unroll
+            for (uint32_t u = 0; u < UNITS; u++)
+            {
+                w[r][u] = make_uint4(0, 0, 0, 0);
+                if (id[r] != GRAPH_EMPTY && u < nu)
+                    w[r][u] = graph_h16_load_unit(row, u, nb, tc, g);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS; r++)
+            if (id[r] != GRAPH_EMPTY) // (uniform over the group)
+            {
+                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (uint32_t u = 0; u < UNITS; u++)
+                    if (u < nu)
+                        graph_h16_score_unit<METRIC>(acc, L.qs, w[r][u], u, a.ld4, g);
+                const uint64_t key = graph_sq_key<METRIC>(acc, id[r]);
+                if (g == 0)
+                    L.stage[c0 + 16 * r] = key;
+            }
+    }
+}
+
+/// score, binary16 rows: the list's labels against their decoded rows (the header's three forms; nu is uniform over the block)
+template <int METRIC, bool LIGHT = false>
+__device__ __forceinline__ void graph_score_h16(const GraphSearchParams & a, const GraphLds & L, const uint32_t m, const uint32_t grp, const uint32_t g)
+{
+    const uint32_t nb = a.lc4 >> 5, tc = a.lc4 & 31, nu = nb + (tc ? 1 : 0), ld16 = a.lc4 >> 1;
+    if (nu <= 4)
+        return graph_h16_score_multi<METRIC, LIGHT ? 2 : 4, 4>(a, L, m, grp, g, nb, tc, nu);
+    if (nu <= 8)
+        return graph_h16_score_multi<METRIC, LIGHT ? 1 : 2, 8>(a, L, m, grp, g, nb, tc, nu);
+    uint4 next[GRAPH_H16_LONG_UNITS];
+    auto load_chunk = [&](const uint32_t id, const uint32_t u0) {
+        const uint4 * row = a.codes + (size_t)id * ld16;
+#pragma unroll
+        for (uint32_t e = 0; e < GRAPH_H16_LONG_UNITS; e++)
+        {
+            next[e] = make_uint4(0, 0, 0, 0);
+            if (u0 + e < nu)
+                next[e] = graph_h16_load_unit(row, u0 + e, nb, tc, g);
+        }
+    };
+    if (grp < m)
+        load_chunk(L.slab[grp], 0);
+    for (uint32_t c = grp; c < m; c += 16)
+    {
+        const uint32_t id = L.slab[c];
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (uint32_t u0 = 0; u0 < nu; u0 += GRAPH_H16_LONG_UNITS)
+        {
+            uint4 cur[GRAPH_H16_LONG_UNITS];
+#pragma unroll
+            for (uint32_t e = 0; e < GRAPH_H16_LONG_UNITS; e++)
+                cur[e] = next[e];
+            if (u0 + GRAPH_H16_LONG_UNITS < nu) // the next chunk, or the next label's first, is on its way during the converts
+                load_chunk(id, u0 + GRAPH_H16_LONG_UNITS);
+            else if (c + 16 < m)
+                load_chunk(L.slab[c + 16], 0);
+#pragma unroll
+            for (uint32_t e = 0; e < GRAPH_H16_LONG_UNITS; e++)
+                if (u0 + e < nu)
+                    graph_h16_score_unit<METRIC>(acc, L.qs, cur[e], u0 + e, a.ld4, g);
+        }
+        const uint64_t key = graph_sq_key<METRIC>(acc, id);
+        if (g == 0)
+            L.stage[c] = key;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- product-quantised rows
 
 /// T[s][j] of include/msvs.h for the query q (dim floats in global memory, normalised for cosine), into LDS; the caller's barrier
@@ -501,6 +670,8 @@ __device__ __forceinline__ void graph_round(const GraphSearchParams & a, const G
     const uint32_t m = L.ctl[0], cnt = L.ctl[2];
     if constexpr (BITS == 8)
         graph_score_codes<METRIC>(a, L, m, grp, g);
+    else if constexpr (BITS == 16)
+        graph_score_h16<METRIC>(a, L, m, grp, g);
     else if constexpr (graph_is_pq(BITS))
         graph_score_pq<METRIC, BITS>(a, L, m, grp, g);
     else
@@ -521,7 +692,7 @@ __device__ __forceinline__ size_t graph_head_bytes(const GraphSearchParams & a)
 template <int METRIC, int BITS = 32>
 static __global__ __launch_bounds__(BLOCK) void graph_search_kernel(const GraphSearchParams a)
 {
-    static_assert(BITS == 32 || BITS == 8 || graph_is_pq(BITS), "f32 rows of a row store, 8-bit codes, or product-quantised codes");
+    static_assert(BITS == 32 || BITS == 16 || BITS == 8 || graph_is_pq(BITS), "f32 rows of a row store, binary16 rows, 8-bit codes, or product-quantised codes");
     extern __shared__ __align__(16) unsigned char graph_lds[];
     GraphLds L;
     L.qs = reinterpret_cast<float4 *>(graph_lds);
@@ -764,6 +935,8 @@ __device__ __forceinline__ void graph_wide_round(const GraphWideParams & a, cons
     const uint32_t m = L.ctl[0], cnt = L.ctl[2];
     if constexpr (BITS == 8)
         graph_score_codes<METRIC>(a, L, m, grp, g);
+    else if constexpr (BITS == 16)
+        graph_score_h16<METRIC, (E >= 4)>(a, L, m, grp, g);
     else if constexpr (graph_is_pq(BITS))
         graph_score_pq<METRIC, BITS>(a, L, m, grp, g);
     else
@@ -775,7 +948,7 @@ __device__ __forceinline__ void graph_wide_round(const GraphWideParams & a, cons
 template <int METRIC, int BITS, int E>
 static __global__ __launch_bounds__(BLOCK) void graph_wide_search_kernel(const GraphWideParams a)
 {
-    static_assert(BITS == 32 || BITS == 8 || graph_is_pq(BITS), "f32 rows of a row store, 8-bit codes, or product-quantised codes");
+    static_assert(BITS == 32 || BITS == 16 || BITS == 8 || graph_is_pq(BITS), "f32 rows of a row store, binary16 rows, 8-bit codes, or product-quantised codes");
     static_assert(E * BLOCK <= MSVS_MAX_K_ROUNDS, "the beam's entries a thread holds");
     extern __shared__ __align__(16) unsigned char graph_lds[];
     GraphLds L;

@@ -5,8 +5,8 @@ store, a built index of degree --degree, searched through the device entry on on
     --join-iters T >= 1 selects the sub-quadratic build (IVF lists of --build-nprobe lists, T join iterations over --join-sample entries);
   - for nq in --batches and ef in --efs: recall@10 against an exact scan of the rows (torch, on the first 256 queries), the median
     time of --reps calls between HIP events after a warm-up call (and their spread, min .. max), queries/s;
-  - --bits 32,8: the index is built once at 32 bits, exported, and the same structure is handed (set_graph) to a bit_size=8 index
-    over the same store, so both forms search one graph; their repetitions alternate inside one process, shape by shape;
+  - --bits 32,8,16: the index is built once at 32 bits, exported, and the same structure is handed (set_graph) to a bit_size=8 and a
+    bit_size=16 index over the same store, so all forms search one graph; their repetitions alternate inside one process, shape by shape;
     pq8:M / pq4:M add product-quantised forms (pq_m=M, 8- or 4-bit codes) over the same graph, and for each the recall@10 of
     search(k = 100) + refine against the store and the time of a max_iters=1 search beside the whole one (the table build's share);
   - beside them the IVFFLAT index of the same rows (nlist --nlist) at --nprobes, the same way, to read the nprobe of equal recall off;
@@ -16,7 +16,7 @@ store, a built index of degree --degree, searched through the device entry on on
 Writes one JSON file (default profiles/graph.json) and prints it.
 
     python -m tools.bench_graph [--rows N] [--dim D] [--data mid] [--degree 32] [--nlist 1024] [--batches 1,64,4096] [--efs 32,64,128,256]
-                                [--bits 32,8] [--nprobes 8,16,32,64] [--join-iters T] [--build-nprobe P] [--join-sample S] [--reps R] [--out FILE]
+                                [--bits 32,8,16] [--nprobes 8,16,32,64] [--join-iters T] [--build-nprobe P] [--join-sample S] [--reps R] [--out FILE]
 """
 import argparse
 import json
@@ -102,7 +102,7 @@ def main():
     ap.add_argument("--nlist", type=int, default=1024)
     ap.add_argument("--batches", default="1,64,4096")
     ap.add_argument("--efs", default="32,64,128,256")
-    ap.add_argument("--bits", default="32", help="forms of the graph index to search: 32, 8, pq8:M, pq4:M (product-quantised, M sub-quantisers)")
+    ap.add_argument("--bits", default="32", help="forms of the graph index to search: 32, 16, 8, pq8:M, pq4:M (product-quantised, M sub-quantisers)")
     ap.add_argument("--pq-iters", type=int, default=10, help="k-means iterations of the product-quantised forms' codebooks")
     ap.add_argument("--nprobes", default="8,16,32,64", help="of the IVFFLAT index beside it; empty: leave it out")
     ap.add_argument("--join-iters", type=int, default=0, help="0: the exact O(n^2) build; >= 1: IVF lists repaired by the join kernel")
@@ -168,11 +168,11 @@ def main():
     print("build (%s): %.2f s" % (build, out["build_s"]), flush=True)
     forms = {32: gx}
     bits = [int(v) if v.isdigit() else v for v in a.bits.split(",")]
-    if 8 in bits:
+    for b in (b for b in (8, 16) if b in bits):
         t0 = time.perf_counter()
-        forms[8] = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,bit_size=8" % a.degree)
-        forms[8].set_graph(*gx.export())
-        out["encode_s"] = time.perf_counter() - t0  # (with the structure's round trip through the host)
+        forms[b] = capi.GraphIndex(capi.METRIC_L2, rows, "degree=%d,bit_size=%d" % (a.degree, b))
+        forms[b].set_graph(*gx.export())
+        out["encode_s" if b == 8 else "encode_h16_s"] = time.perf_counter() - t0  # (with the structure's round trip through the host)
     for f in (f for f in bits if isinstance(f, str)):  # pq8:M / pq4:M: codebooks trained over the store, codes, the same graph
         width, m = f[2:].split(":")
         t0 = time.perf_counter()
